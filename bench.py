@@ -2,7 +2,12 @@
 """Headline benchmark: rendered img/s of ``G.synthesis`` (seg2cat, 512^2 output, 128^2 rays x 128 depth samples).
 
     python bench.py --gpus N --steps K --warmup W           (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W --full    (the same line plus every extra object described below)
     python bench.py --gpus N --train-step                   (BASELINE config 3 instead: one training iteration per step)
+    python bench.py ... --dump-outputs DIR                  (also write the last timed step's outputs as DIR/<name>.npy, float32)
+
+A plain run (no --full) does only what the headline needs: set up, warm up, time K steps, print the line (metric, value, unit,
+ms_per_step, dtype, ...).  Everything else below is measured only with --full.
 
 A "step" is one pass of the hot path — StyleGAN2 tri-plane backbone -> fused tri-plane ray-marcher -> two
 super-resolution heads — over one batch of synthetic inputs already resident in HBM (random-init weights of the
@@ -61,7 +66,14 @@ def parse():
     p.add_argument('--no-exact-fp32', action='store_true', help='skip the second timed loop with the bf16x3 switches off')
     p.add_argument('--no-configs', action='store_true', help="skip the short timed loops of BASELINE.json's other single-GPU configurations")
     p.add_argument('--train-nrr', type=int, default=128, help='neural rendering resolution of the training passes (train.py: 128 for the 512^2 configs)')
-    return p.parse_args()
+    p.add_argument('--full', action='store_true', help='besides the headline: the per-stage / per-kernel eager pass and roofline, the CPU baseline, the exact-fp32 leg, '
+                                                       "BASELINE.json's other configurations, the short training iteration and (N > 1) the collective's own timing")
+    p.add_argument('--dump-outputs', metavar='DIR', default=None, help="after the timed steps, write what the last one computed (G.synthesis's output dict) as "
+                                                                       'DIR/<name>.npy in float32 (a fixed, seeded sample of each array if the total exceeds 64 MB)')
+    args = p.parse_args()
+    if args.dump_outputs and args.train_step:
+        p.error('--dump-outputs applies to the inference step, not to --train-step')
+    return args
 
 
 def build(args, device):
@@ -169,6 +181,25 @@ def pmc_record(args, nrr, exact=False):
     except (OSError, KeyError, ValueError):
         pass
     return None
+
+
+DUMP_BYTES = 60 << 20             # --dump-outputs: at most this many bytes of array data in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(outputs, path):
+    """Write every tensor of ``outputs`` as ``path/<name>.npy`` in float32.  If they hold more than DUMP_BYTES together, each array is
+    replaced by the same share of its elements, flat, at sorted indices drawn by a generator seeded with 0 (names in sorted order): the
+    same shapes give the same sample on every run, so two builds compare element for element."""
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in outputs.items() if torch.is_tensor(v)}
+    total = sum(a.nbytes for a in arrays.values())
+    rng = np.random.default_rng(0)
+    os.makedirs(path, exist_ok=True)
+    for k in sorted(arrays):
+        a = arrays[k]
+        if total > DUMP_BYTES:
+            n = max(1, a.size * DUMP_BYTES // total)
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, n, replace=False))]
+        np.save(os.path.join(path, k + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
 
 
 FUSED_ADAM = os.environ.get('P3D_BENCH_FUSED_ADAM', '1') != '0'
@@ -480,7 +511,7 @@ def main():
     torch.backends.cudnn.benchmark = bool(args.miopen_find)         # training_loop.py:280 sets True; find-mode costs ~100 s of warm-up per fresh box
 
     rccl = None
-    if world > 1:
+    if world > 1 and (args.full or args.train_step):
         # the training exchange must run over xGMI (strict: refuses NCCL_P2P_DISABLE); the inference line has no data-path collective, so there the switch is
         # recorded (rccl.p2p_disabled) instead of refused, and nothing in this object may cost the line itself
         if args.train_step:
@@ -507,7 +538,7 @@ def main():
 
     G_cpu, kw, info, ws_cpu, c_cpu = build(args, device)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, G_cpu, kw, info, ws_cpu, c_cpu)
     G = G_cpu.to(device)
     ws, c = ws_cpu.to(device), c_cpu.to(device)
@@ -522,9 +553,10 @@ def main():
         return step_
     step = make_step(G, ws, c, syn_kw)
 
-    def measure(settle_s, step=step, G=G, batch=args.batch, res=info['res']):
-        """Warm up, capture the step as one hipGraph, settle, time K steps (barrier + synchronize on both sides, MAX over ranks); then an
-        eager pass of the same steps with HIP events around the stages and the instrumented kernels."""
+    def measure(settle_s, step=step, G=G, batch=args.batch, res=info['res'], profile=True, keep_outputs=False):
+        """Warm up, capture the step as one hipGraph, settle, time K steps (barrier + synchronize on both sides, MAX over ranks); then
+        (``profile``) an eager pass of the same steps with HIP events around the stages and the instrumented kernels.  ``keep_outputs``: a
+        host copy of what the last timed step returned, under 'outputs'."""
         for _ in range(max(args.warmup, 1)):
             out = step()
         torch.cuda.synchronize()
@@ -567,12 +599,15 @@ def main():
             spent = time.perf_counter() - t_start
             if spent > settle_s or (spent > min(1.5, settle_s) and len(chunks) >= 3 and max(chunks[-3:]) < 1.015 * min(chunks[-3:])):
                 break
+        # the renderer's uniform draws come from the device generator: restart it here, so that the timed steps (and the outputs of the last one)
+        # do not depend on how many untimed steps the settling took
+        torch.cuda.manual_seed(1234 + rank)
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            run()
+            last = run()
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
@@ -582,7 +617,12 @@ def main():
             t = torch.tensor([elapsed], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+        outputs = None
+        if keep_outputs:                                                 # a replay returns nothing: its outputs are the captured step's tensors
+            outputs = {k: v.detach().float().cpu() for k, v in (out if graph is not None else last).items() if torch.is_tensor(v)}
         del graph
+        if not profile:
+            return dict(elapsed=elapsed, launch=launch, outputs=outputs)
         # per-kernel / per-stage HIP-event timing: a second, eager pass over the same steps (events cannot be read back from inside a
         # captured graph); the ray-marcher is one launch per step, so its event pair IS its launch duration.  Events are recorded on
         # torch's current stream == the stream every kernel of the step is launched on.
@@ -621,7 +661,7 @@ def main():
         mfma_conv = {k: {'ms_per_step': round(conv_ms[k], 3), 'tflops': round(conv_fl[k] / (conv_ms[k] * 1e-3) / 1e12, 1) if conv_ms[k] > 0 else None,
                          'frac_of_peak': round(conv_fl[k] * mults.get(k, 1.0) / (conv_ms[k] * 1e-3) / 1e12 / (157.3 if k == 'conv_f32' else 2500.0), 3) if conv_ms[k] > 0 else None}
                      for k in conv_keys}
-        return dict(elapsed=elapsed, launch=launch, render_kernel_ms=render_kernel_ms, n_render=len(kern), stage_ms=stage_ms, mfma_conv=mfma_conv)
+        return dict(elapsed=elapsed, launch=launch, outputs=outputs, render_kernel_ms=render_kernel_ms, n_render=len(kern), stage_ms=stage_ms, mfma_conv=mfma_conv)
 
     def roofline(m, mlp_bf3):
         """The ray-marcher's roofline object from its live launch duration + the committed counter passes of this kernel build."""
@@ -654,9 +694,11 @@ def main():
                   'ms_per_launch': round(m['render_kernel_ms'], 4), 'launches_timed': m['n_render'], 'units_per_launch': samples_per_launch})
         return r
 
-    main_m = measure(8.0)
+    main_m = measure(8.0, profile=args.full, keep_outputs=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(main_m['outputs'], args.dump_outputs)
     exact = None
-    if not args.no_exact_fp32:                                       # the same loop with every bf16x3 switch off: exact fp32 MFMA in the backbone and the decoder
+    if args.full and not args.no_exact_fp32:                         # the same loop with every bf16x3 switch off: exact fp32 MFMA in the backbone and the decoder
         prev = (_mc.split_bf16, rmod.mlp_bf16x3, _mc.f32_x6)
         _mc.split_bf16, rmod.mlp_bf16x3, _mc.f32_x6 = False, False, False
         try:
@@ -693,7 +735,7 @@ def main():
     # samples, configs[3]'s per-GPU share (edge2car, batch 16 over 2 GPUs: train.py:451-461) and configs[4]'s (seg2face, batch 8 over 4 GPUs:
     # train.py:425-437).  configs[0] is the reference's CPU case (cpu_baseline), configs[2] the training iteration (train_step).
     other = None
-    if not args.no_configs and world == 1 and args.dataset == 'seg2cat' and args.batch == 4 and args.depth == 128 and not args.force_fp32:      # (N > 1: the scaling run times configs[1]'s headline shape only)
+    if args.full and not args.no_configs and world == 1 and args.dataset == 'seg2cat' and args.batch == 4 and args.depth == 128 and not args.force_fp32:      # (N > 1: the scaling run times configs[1]'s headline shape only)
         import copy as _copy
         other = {}
         G = G.cpu()
@@ -721,7 +763,7 @@ def main():
         G = G.to(device)
 
     train = None
-    if not args.no_train_step:                                       # short: 2 warm-up + 3 timed iterations
+    if args.full and not args.no_train_step:                                       # short: 2 warm-up + 3 timed iterations
         G = G.cpu()
         torch.cuda.empty_cache()
         try:
@@ -754,19 +796,13 @@ def main():
                 _mc.f32_x6 = prev6
 
     if rank == 0:
-        ceiling = mfma_real_data_ceiling()
-        if ceiling:                                                  # the same classes against what the pipe can do on real data at the clock it then holds
-            ceiling['frac_of_it'] = {k: (round(v['tflops'] * {'conv_bf16x3': 3.0, 'conv_bf16x6': 6.0}.get(k, 1.0) / ceiling['tflops'], 3) if v.get('tflops') else None)
-                                     for k, v in main_m['mfma_conv'].items() if k != 'conv_f32'}
         bb = ('f32 tensors + f32 accumulation; the backbone convolutions (3x3 and the 1x1 ToRGB) form each product as 3 bf16 MFMAs of (hi, lo) splits ("bf16x3", <= 5e-6 of the '
               'output range vs fp64 per layer; P3D_BF16X3=0 = exact f32 MFMA, timed as `exact_fp32`)') if _mc.split_bf16 else 'f32 (exact f32 MFMA)'
         rm = 'f32 gather / sampling / compositing, decoder MLPs as bf16x3 (P3D_MLP_BF16X3=0 = exact f32 MFMA)' if rmod.mlp_bf16x3 else 'f32'
         dtype_desc = f'backbone: {bb}; ray-marcher: {rm}; super-resolution: ' + ('f32' if args.force_fp32 else 'f16 storage / f32 accumulation (the reference GPU config)')
-        elapsed, stage_ms = main_m['elapsed'], main_m['stage_ms']
+        elapsed = main_m['elapsed']
         ms_per_step = elapsed / args.steps * 1e3
         imgs = args.batch * world * args.steps
-        samples_per_launch = args.batch * nrr * nrr * args.depth
-        render_s = main_m['render_kernel_ms'] * 1e-3
         line = {
             'metric': f'rendered img/s ({info["res"]}^2, {args.depth} depth)',
             'value': round(imgs / elapsed, 3), 'unit': 'img/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -775,18 +811,28 @@ def main():
             'data': 'synthetic',
             'config': {'workload': f'{args.dataset} G.synthesis: batch {args.batch}/GPU, 256^2x96 tri-planes, {nrr}^2 rays x {args.depth // 2}+{args.depth // 2} samples, '
                                    f'two {info["sr"]} SR heads -> {info["res"]}^2 image + label map', 'launch': main_m['launch'], 'parallelism': f'replicas x{world} (images sharded, no collective)'},
-            'ray_samples_per_s': round(samples_per_launch / render_s, 1) if render_s > 0 else None,
-            'stage_ms': {k: round(v, 3) for k, v in stage_ms.items()},
-            'conv_tflops': round(FLOP_PER_IMG * args.batch / ((stage_ms['backbone'] + stage_ms['sr']) * 1e-3) / 1e12, 2) if stage_ms['backbone'] + stage_ms['sr'] > 0 else None,
-            'roofline': roofline(main_m, bool(rmod.mlp_bf16x3)),
-            'mfma_conv': main_m['mfma_conv'],
-            'mfma_real_data_ceiling': ceiling,
-            'exact_fp32': exact,
-            'configs': other,
-            'cpu_baseline': cpu,
-            'train_step': train,
-            'rccl': rccl,
         }
+        if args.full:
+            ceiling = mfma_real_data_ceiling()
+            if ceiling:                                              # the same classes against what the pipe can do on real data at the clock it then holds
+                ceiling['frac_of_it'] = {k: (round(v['tflops'] * {'conv_bf16x3': 3.0, 'conv_bf16x6': 6.0}.get(k, 1.0) / ceiling['tflops'], 3) if v.get('tflops') else None)
+                                         for k, v in main_m['mfma_conv'].items() if k != 'conv_f32'}
+            stage_ms = main_m['stage_ms']
+            samples_per_launch = args.batch * nrr * nrr * args.depth
+            render_s = main_m['render_kernel_ms'] * 1e-3
+            line.update({
+                'ray_samples_per_s': round(samples_per_launch / render_s, 1) if render_s > 0 else None,
+                'stage_ms': {k: round(v, 3) for k, v in stage_ms.items()},
+                'conv_tflops': round(FLOP_PER_IMG * args.batch / ((stage_ms['backbone'] + stage_ms['sr']) * 1e-3) / 1e12, 2) if stage_ms['backbone'] + stage_ms['sr'] > 0 else None,
+                'roofline': roofline(main_m, bool(rmod.mlp_bf16x3)),
+                'mfma_conv': main_m['mfma_conv'],
+                'mfma_real_data_ceiling': ceiling,
+                'exact_fp32': exact,
+                'configs': other,
+                'cpu_baseline': cpu,
+                'train_step': train,
+                'rccl': rccl,
+            })
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -7,6 +7,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 from conftest import ROOT
 
 
@@ -80,7 +83,7 @@ def test_committed_counter_passes_belong_to_this_trees_kernel():
 def test_bench_argument_surface():
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0
-    for flag in ('--gpus', '--steps', '--warmup', '--train-step', '--no-exact-fp32', '--no-cpu-baseline', '--cpu-reps', '--no-configs'):
+    for flag in ('--gpus', '--steps', '--warmup', '--train-step', '--no-exact-fp32', '--no-cpu-baseline', '--cpu-reps', '--no-configs', '--full', '--dump-outputs'):
         assert flag in r.stdout, flag
 
 
@@ -93,3 +96,53 @@ def test_multi_gpu_line_refuses_the_reference_scripts_p2p_switch(monkeypatch):
     monkeypatch.setenv('NCCL_P2P_DISABLE', '1')
     with pytest.raises(AssertionError, match='NCCL_P2P_DISABLE'):
         bench.collective_info(None, 2, 0, None)
+
+
+def _plain_run(out_dir, steps):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '1', '--batch', '1', '--dump-outputs', str(out_dir)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run (no --full) prints the headline keys and none of the --full objects, times exactly --steps steps, and --dump-outputs writes
+    G.synthesis's outputs of the last timed step as float32 .npy files (< 64 MB in all), the same on a second run with the same arguments."""
+    lines = [_plain_run(tmp_path / 'a', 3), _plain_run(tmp_path / 'b', 3)]
+    d = lines[0]
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'steps', 'warmup', 'config'):
+        assert k in d, k
+    for k in ('roofline', 'stage_ms', 'mfma_conv', 'exact_fp32', 'configs', 'cpu_baseline', 'train_step'):
+        assert k not in d, k
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['unit'] == 'img/s' and d['higher_is_better'] is True
+    assert abs(d['value'] - 1 / (d['ms_per_step'] * 1e-3)) < 0.01 * d['value']                      # batch 1, one GPU: img/s = 1 / time per step
+    names = sorted(p.name for p in (tmp_path / 'a').iterdir())
+    assert {'image.npy', 'image_raw.npy', 'image_depth.npy', 'semantic.npy', 'semantic_raw.npy'} <= set(names), names
+    assert sum((tmp_path / 'a' / n).stat().st_size for n in names) < 64e6
+    assert np.load(tmp_path / 'a' / 'image.npy').shape == (1, 3, 512, 512)
+    for n in names:
+        a, b = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all() and a.std() > 0, n
+        np.testing.assert_array_equal(a, b, err_msg=n)
+
+
+def test_dump_outputs_samples_large_outputs_the_same_way_every_time(tmp_path):
+    """Outputs above the dump budget are written as the same seeded share of each array on every call: float32, < 64 MB in all."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    outs = {'image': torch.randn(8, 3, 512, 512, generator=g).half(), 'semantic': torch.randn(8, 6, 512, 512, generator=g), 'weight': None}
+    bench.dump_outputs(outs, str(tmp_path / 'a'))
+    bench.dump_outputs(outs, str(tmp_path / 'b'))
+    names = sorted(p.name for p in (tmp_path / 'a').iterdir())
+    assert names == ['image.npy', 'semantic.npy']
+    assert sum((tmp_path / 'a' / n).stat().st_size for n in names) < 64e6
+    for n in names:
+        a, b = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert a.dtype == np.float32 and a.ndim == 1 and a.size > 1000, n
+        np.testing.assert_array_equal(a, b)
+    small = {'image': torch.randn(1, 3, 8, 8, generator=g)}
+    bench.dump_outputs(small, str(tmp_path / 'c'))
+    np.testing.assert_array_equal(np.load(tmp_path / 'c' / 'image.npy'), small['image'].numpy())      # under the budget: the whole array
