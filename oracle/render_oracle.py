@@ -305,3 +305,85 @@ def render_semantic(planes_t, planes_s, dec_t, dec_s, ray_o, ray_d, opts, u_coar
         rgb, sig, sem = run_model_semantic(planes_t, planes_s, dec_t, dec_s, pts, opts['box_warp'])
         return np.concatenate([rgb, sem], -1).astype(F32), sig
     return render(None, None, ray_o, ray_d, opts, u_coarse, u_fine, point_fn=point_fn)
+
+
+# ---- fp64 differentiable restatement of "render given depths" (torch; for the fused backward's tests) ----------------------------------
+# The backward of the fused renderer (csrc/render_bwd.hip) treats the sample depths as constants (renderer.py:198, 211: the importance
+# depths come out of no_grad + detach), so what it differentiates is the map (planes, decoder parameters) -> (feat, wsum) at FIXED sorted
+# depths.  The functions below restate that map in float64 torch ops, independently of this package's renderer and of the kernels, so
+# that autograd gives the reference gradients: the same steps as ``decode`` / ``ray_march`` above, the same reference lines.
+
+def decode_t(x, dec):
+    """``decode`` in float64 torch ops on the plane-mean features x [..., 32] -> colours [..., C], sigma [...].  dec: dict of tensors 'w1',
+    'b1','w2','b2' (+ 'w1s','b1s','w2s','b2s' for the two-net decoder), 'lr_mul', 'semantic_sigmoid'.  One net: OSGDecoder
+    (training/triplane.py:112-135); two nets: OSGDecoder_semantic_lateSeparate (training/triplane_cond.py:926-970), density from the label net."""
+    import torch
+    lr = float(dec.get('lr_mul', 1.0))
+
+    def fc(v, w, b):                                                    # FullyConnectedLayer, linear (networks_stylegan2.py:114-127)
+        return v @ (w * (lr / np.sqrt(w.shape[1]))).t() + b * lr
+
+    def squash(v):                                                      # MipNeRF sigmoid clamping (triplane.py:133)
+        return torch.sigmoid(v) * (1 + 2 * 0.001) - 0.001
+
+    def mlp(sfx):                                                       # FC - Softplus(beta 1, threshold 20) - FC
+        return fc(torch.nn.functional.softplus(fc(x, dec['w1' + sfx], dec['b1' + sfx])), dec['w2' + sfx], dec['b2' + sfx])
+    y = mlp('')
+    if 'w1s' not in dec:
+        return squash(y[..., 1:]), y[..., 0]
+    ys = mlp('s')
+    sem = squash(ys[..., 1:]) if dec.get('semantic_sigmoid', False) else ys[..., 1:]
+    return torch.cat([squash(y[..., 1:]), sem], -1), ys[..., 0]
+
+
+def plane_coords_t(coords, box_warp):
+    """renderer.py:39-65 up to the grid: world points [N,P,3] -> grid coordinates [N,3,P,2] of the three planes (inv(plane_axes))."""
+    import torch
+    inv = torch.tensor(np.linalg.inv(_PLANE_AXES), dtype=coords.dtype, device=coords.device)
+    return torch.einsum('npc,kcd->nkpd', (2.0 / box_warp) * coords, inv)[..., :2]
+
+
+def sample_points_t(planes, dec, coords, box_warp):
+    """run_model (renderer.py:142-148) in float64: planes [N,3,32,H,W], coords [N,P,3] -> colours [N,P,C], sigma [N,P].  The taps are
+    F.grid_sample(bilinear, zeros, align_corners=False) as in the reference (renderer.py:62), the features the mean over the 3 planes."""
+    import torch
+    n, k, c, h, w = planes.shape
+    uv = plane_coords_t(coords.to(planes.dtype), box_warp)
+    f = torch.nn.functional.grid_sample(planes.reshape(n * k, c, h, w), uv.reshape(n * k, 1, -1, 2), mode='bilinear', padding_mode='zeros',
+                                        align_corners=False)                          # [N*3, C, 1, P]
+    x = f.reshape(n, k, c, -1).permute(0, 3, 1, 2).mean(2)                             # [N, P, C]
+    return decode_t(x, dec)
+
+
+def ray_march_t(colors, sigmas, depths, white_back=False):
+    """ray_marcher.py:25-57 in torch ops (its own cumprod formulation): colors [R,S,C], sigmas [R,S], depths [R,S] -> rgb [R,C] (= raw * 2 - 1),
+    wsum [R], weights [R,S-1].  The depth output is left out: nothing differentiates it."""
+    import torch
+    deltas = depths[:, 1:] - depths[:, :-1]
+    c_mid = (colors[:, :-1] + colors[:, 1:]) / 2
+    dens = torch.nn.functional.softplus((sigmas[:, :-1] + sigmas[:, 1:]) / 2 - 1)
+    alpha = 1 - torch.exp(-dens * deltas)
+    shifted = torch.cat([torch.ones_like(alpha[:, :1]), 1 - alpha + 1e-10], 1)
+    weights = alpha * torch.cumprod(shifted, 1)[:, :-1]
+    rgb = (weights[..., None] * c_mid).sum(1)
+    wsum = weights.sum(1)
+    if white_back:
+        rgb = rgb + 1 - wsum[:, None]
+    return rgb * 2 - 1, wsum, weights
+
+
+def render_given_depths(planes, dec, ray_o, ray_d, z_all, box_warp, white_back=False):
+    """ImportanceRenderer.forward (renderer.py:88-140) from the sorted sample depths on: planes [N,3,32,H,W], ray_o / ray_d [N,M,3],
+    z_all [N*M,S] -> dict(feat [N,M,C], wsum [N,M], weights [R,S-1], colors [R,S,C], sigmas [R,S], uv [N,3,M*S,2]), all in float64.
+    Points o + z d, plane taps, OSG decoders, midpoint compositing.  Differentiable in planes and the tensors of ``dec``."""
+    import torch
+    f64 = torch.float64
+    n, m, _ = ray_o.shape
+    z = z_all.to(f64).reshape(n, m, -1)
+    s = z.shape[-1]
+    pts = (ray_o.to(f64)[:, :, None, :] + z[..., None] * ray_d.to(f64)[:, :, None, :]).reshape(n, m * s, 3)
+    colors, sigmas = sample_points_t(planes, dec, pts, box_warp)
+    colors, sigmas = colors.reshape(n * m, s, -1), sigmas.reshape(n * m, s)
+    rgb, wsum, weights = ray_march_t(colors, sigmas, z.reshape(n * m, s), white_back)
+    return dict(feat=rgb.reshape(n, m, -1), wsum=wsum.reshape(n, m), weights=weights, colors=colors, sigmas=sigmas,
+                uv=plane_coords_t(pts, box_warp))

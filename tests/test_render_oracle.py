@@ -118,3 +118,59 @@ def test_semantic_renderer_oracle_matches_reference_records(name):
     assert rel_err(rgb, g['pts_rgb']) < 2e-5 and rel_err(sig, g['pts_sigma'][..., 0]) < 2e-5 and rel_err(sem, g['pts_semantic']) < 2e-5
     feat, depth, wsum = R.render_semantic(g['planes_t'], g['planes_s'], dec_t, dec_s, g['ray_o'], g['ray_d'], opts, g['u_coarse'][..., 0], g['u_fine'])
     assert rel_err(feat, g['feat']) < 1e-4 and rel_err(depth, g['depth'][..., 0]) < 1e-4 and rel_err(wsum, g['wsum'][..., 0]) < 1e-4
+
+
+def _dec64(dec):
+    import torch
+    return {k: torch.tensor(v, dtype=torch.float64) if isinstance(v, np.ndarray) else v for k, v in dec.items()}
+
+
+def _oracle_depths(name):
+    """The numpy oracle's render of a recorded case with details, and the per-ray limits it used ('auto')."""
+    g, opts, dec = load_case(name)
+    kw = {}
+    if opts['ray_start'] == 'auto':
+        import torch
+        from pix2pix3d_amd.training.volumetric_rendering.renderer import ImportanceRenderer
+        t0, t1 = ImportanceRenderer()._ray_limits(torch.tensor(g['ray_o']), torch.tensor(g['ray_d']), opts)
+        kw = dict(t_start=t0.numpy(), t_end=t1.numpy())
+    return g, opts, dec, R.render(g['planes'], dec, g['ray_o'], g['ray_d'], opts, g['u_coarse'], g['u_fine'], details=True, **kw)
+
+
+@pytest.mark.parametrize('name', CASES)
+def test_fp64_render_given_depths_is_the_render_oracle(name):
+    """oracle.render_oracle.render_given_depths (float64 torch ops, what the GPU tests differentiate) at the depths the numpy oracle sampled:
+    per-sample colours and densities, feat and wsum agree to fp32 rounding (the numpy oracle evaluates in fp32; measured <= 2.4e-6)."""
+    import torch
+    g, opts, dec, (feat, _, wsum, det) = _oracle_depths(name)
+    out = R.render_given_depths(torch.tensor(g['planes'], dtype=torch.float64), _dec64(dec), torch.tensor(g['ray_o']), torch.tensor(g['ray_d']),
+                                torch.tensor(det['z_all']), opts['box_warp'], bool(opts.get('white_back', False)))
+    assert all(v.dtype == torch.float64 for v in out.values())
+    assert rel_err(out['colors'].numpy(), det['colors']) < 1e-5
+    assert rel_err(out['sigmas'].numpy(), det['sigmas']) < 1e-5
+    assert rel_err(out['feat'].numpy(), feat) < 1e-5
+    assert rel_err(out['wsum'].numpy(), wsum) < 1e-5
+    _, _, w = R.ray_march(det['colors'], det['sigmas'], det['z_all'], bool(opts.get('white_back', False)))
+    assert rel_err(out['weights'].numpy(), w) < 1e-5
+
+
+@pytest.mark.parametrize('name', CASES)
+def test_fp64_ray_march_autograd_is_the_compositing_backward_oracle(name):
+    """Autograd through oracle.render_oracle.ray_march_t (the march inside render_given_depths) w.r.t. the per-sample colours and densities equals
+    ray_march_backward — the two sweeps the fused backward runs — with and without a wsum gradient, on the recorded cases' own samples."""
+    import torch
+    _, opts, _, (_, _, _, det) = _oracle_depths(name)
+    rng = np.random.RandomState(7)
+    colors = torch.tensor(det['colors'], dtype=torch.float64, requires_grad=True)
+    sigmas = torch.tensor(det['sigmas'], dtype=torch.float64, requires_grad=True)
+    r, _, c = colors.shape
+    wb = bool(opts.get('white_back', False))
+    g_rgb = rng.randn(r, c)
+    for g_w in (None, rng.randn(r)):
+        rgb, wsum, _ = R.ray_march_t(colors, sigmas, torch.tensor(det['z_all'], dtype=torch.float64), wb)
+        loss = (rgb * torch.tensor(g_rgb)).sum() + (0.0 if g_w is None else (wsum * torch.tensor(g_w)).sum())
+        gc, gs = torch.autograd.grad(loss, [colors, sigmas])
+        dcol, dsig, _ = R.ray_march_backward(det['colors'], det['sigmas'], det['z_all'], g_rgb, g_w, white_back=wb)
+        assert float(np.abs(dsig).max()) > 0
+        assert rel_err(gc.numpy(), dcol) < 1e-12
+        assert rel_err(gs.numpy(), dsig) < 1e-10
