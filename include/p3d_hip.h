@@ -246,6 +246,36 @@ int p3d_sample_points_backward(const float* planes_cl, const float* decoder, con
                                const p3d_render_desc* desc, int32_t pts_per_img, const float* g_rgb, const float* g_sigma,
                                float* d_planes_cl, float* d_decoder, p3d_stream_t stream);
 
+/* ---- shape extraction (applications/extract_mesh.py:60-99, csrc/shape.hip) ---------------------------
+ * p3d_sample_lattice: get_sigma_field_np (extract_mesh.py:60-81) in one launch.  sigma [N][nx][ny][nz] <- the density at the point
+ * (xs[i], ys[j], zs[k]) of image n, for N = desc->n_img <= 65535 and nx*ny*nz <= 2^32 - 32; xs / ys / zs are device tables of nx / ny / nz
+ * floats.  Planes, decoder (p3d_pack_decoder, exact fp32) and desc as for p3d_sample_points; only the density net runs (net 0 of
+ * OSGDecoder, net 1 of OSGDecoder_semantic_lateSeparate), and the values equal p3d_sample_points' sigma at the same points.
+ * P3D_ERR_UNSUPPORTED when the planes exceed the 32-bit byte offsets of the kernel's buffer descriptor.                        */
+int p3d_sample_lattice(const float* planes_cl, const float* decoder, const p3d_render_desc* desc, const float* xs, const float* ys,
+                       const float* zs, int32_t nx, int32_t ny, int32_t nz, float* sigma, p3d_stream_t stream);
+
+/* Marching cubes (the role of mcubes.marching_cubes in extract_mesh.py:89) on a float32 field u [X][Y][Z] (contiguous, every
+ * dimension >= 2).  A corner is inside when u > threshold.  Output contract:
+ *   vertices float32 [V][3], in index space: one per lattice edge whose ends straddle the threshold, at the lower end (i, j, k) plus t
+ *     along the edge's axis a, t = (threshold - u_lower) / (u_upper - u_lower); numbered by lower corner in row-major order, then by a;
+ *   faces int64 [F][3]: by cube in row-major order, then in the order of the case table (csrc/mc_tables.h, generated by
+ *     pix2pix3d_amd/mc_table.py; ambiguous faces separate their two inside corners, so this is not the original Lorensen table);
+ *     (b - a) x (c - a) points from inside to outside.  No atomics: the output is a pure function of (u, threshold).
+ * Three steps, on one stream:
+ *   1. p3d_marching_cubes_classify: mask [X*Y*Z] uint8 (bit a: the edge along axis a is crossed), cases [X*Y*Z] uint8 (the case of
+ *      the cube whose lower corner this is, 0 when there is none), block_counts int32 [2][B] (vertices, then triangles, of every
+ *      block of 256 corners; B = p3d_marching_cubes_blocks(X, Y, Z));
+ *   2. the caller's exclusive scans of the two rows -> block_voff, block_foff int64 [B], and the totals V and F ON THE HOST (a
+ *      device-to-host copy: this sequence cannot be captured into a graph);
+ *   3. p3d_marching_cubes_emit: vbase int32 [X*Y*Z] scratch, vertices, faces.  P3D_ERR_UNSUPPORTED when V > INT32_MAX (32-bit vertex ids). */
+int64_t p3d_marching_cubes_blocks(int32_t X, int32_t Y, int32_t Z);
+int p3d_marching_cubes_classify(const float* u, int32_t X, int32_t Y, int32_t Z, float threshold, uint8_t* mask, uint8_t* cases,
+                                int32_t* block_counts, p3d_stream_t stream);
+int p3d_marching_cubes_emit(const float* u, int32_t X, int32_t Y, int32_t Z, float threshold, const uint8_t* mask, const uint8_t* cases,
+                            const int64_t* block_voff, const int64_t* block_foff, int64_t n_vertices, int64_t n_faces,
+                            int32_t* vbase, float* vertices, int64_t* faces, p3d_stream_t stream);
+
 /* z_coarse [R][S_c], w_coarse [R][S_c-1], u_fine [R][S_f] -> z_fine [R][S_f] (sorted ascending
  * when `sorted`, else in draw order as sample_pdf returns them).                               */
 int p3d_importance_sample(const float* z_coarse, const float* w_coarse, const float* u_fine, float* z_fine,

@@ -67,6 +67,11 @@ _lib.register('p3d_render_decoder_floats_dual', ctypes.c_int, [])
 _lib.register('p3d_pack_decoder_dual', ctypes.c_int, [_vp] * 8 + [_f32, _vp, _vp])
 _lib.register('p3d_render_forward_dual', ctypes.c_int, [_vp] * 9 + [ctypes.POINTER(_RenderDesc)] + [_vp] * 4 + [_vp])
 _lib.register('p3d_sample_points_dual', ctypes.c_int, [_vp] * 4 + [ctypes.POINTER(_RenderDesc), _i32, _vp, _vp, _vp])
+_lib.register('p3d_sample_lattice', ctypes.c_int, [_vp, _vp, ctypes.POINTER(_RenderDesc), _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp])
+_lib.register('p3d_marching_cubes_blocks', ctypes.c_int64, [_i32, _i32, _i32])
+_lib.register('p3d_marching_cubes_classify', ctypes.c_int, [_vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp])
+_lib.register('p3d_marching_cubes_emit', ctypes.c_int, [_vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64,
+                                                        _vp, _vp, _vp, _vp])
 
 
 def generate_planes():
@@ -634,6 +639,19 @@ def fused_sample_points(planes, decoder, coordinates, opt):
                                         _lib.ptr(rgb), _lib.ptr(sigma), _lib.stream_of(rgb))
     _lib.check(code, 'sample_points')
     return rgb, sigma
+
+
+def fused_sample_lattice(planes, decoder, xs, ys, zs, opt):
+    """One launch of p3d_sample_lattice: sigma [N, len(xs), len(ys), len(zs)], the density at every lattice point (xs[i], ys[j], zs[k])
+    — what ``fused_sample_points(...)[1]`` gives at those points, without the colour outputs (csrc/shape.hip)."""
+    ctx = _FusedContext(planes, _decoder_nets(decoder))
+    axes = [_f32c(t).to(planes.device) for t in (xs, ys, zs)]
+    sigma = torch.empty([ctx.n] + [len(t) for t in axes], device=planes.device, dtype=torch.float32)
+    d = ctx.desc(opt)
+    code = _lib.lib().p3d_sample_lattice(_lib.ptr(ctx.planes_cl), _lib.ptr(ctx.packed), ctypes.byref(d), *[_lib.ptr(t) for t in axes],
+                                         *[len(t) for t in axes], _lib.ptr(sigma), _lib.stream_of(sigma))
+    _lib.check(code, 'sample_lattice')
+    return sigma
 
 
 def _decoder_param_grads(decoder, nets, d_dec):
