@@ -276,6 +276,67 @@ int p3d_marching_cubes_emit(const float* u, int32_t X, int32_t Y, int32_t Z, flo
                             const int64_t* block_voff, const int64_t* block_foff, int64_t n_vertices, int64_t n_faces,
                             int32_t* vbase, float* vertices, int64_t* faces, p3d_stream_t stream);
 
+/* ---- mesh rendering (applications/extract_mesh.py:226-262, the role of pyrender; csrc/mesh_raster.hip) ----------------------------
+ * Cameras: cameras float [F][P3D_MESH_CAMERA_FLOATS], one row per frame: [0:16] cam2world row-major 4x4 in the OpenCV convention
+ *   (x right, y down, z forward: columns 0..2 are the camera axes in world space, column 3 its position), [16:21] the model's
+ *   parameters, [21] znear, [22] zfar with 0 < znear < zfar (so every depth is positive, as the z-test key needs), [23] unused.
+ *   `orthographic` selects the model for every frame of the call:
+ *     orthographic (1): xmag, ymag (pyrender's OrthographicCamera: half-extents in world units), then 3 unused floats;
+ *                       u = (x_c / xmag + 1) / 2, v = (y_c / ymag + 1) / 2;
+ *     pinhole      (0): fx, fy, cx, cy, skew, the normalised intrinsics of the 25-float camera label;
+ *                       u = (fx x_c + skew y_c) / z_c + cx, v = fy y_c / z_c + cy  (the inverse of ray_sampler.py:43-59's lift).
+ *   (x_c, y_c, z_c) = R^T (p - t) with R, t from cam2world.  Pixel (row r, col c) has its centre at u = (c + 0.5) / W,
+ *   v = (r + 0.5) / H, as p3d_ray_sample's rays: a pinhole render lines up pixel for pixel with G.synthesis at the same label.
+ * Projection: fp64, products summed left to right with no contraction.  Screen position in fixed point with 8 sub-pixel bits,
+ *   sx = rint(u * W * 256), sy = rint(v * H * 256) (round half to even); pixel centres sit at ((c << 8) + 128, (r << 8) + 128).
+ *   A vertex is DROPPED when z_c lies outside [znear, zfar] or sx / sy outside the guard band [-4096 * 256, (W or H + 4096) * 256]
+ *   (or is not finite).  A triangle with a dropped vertex, or with a vertex index outside [0, V), is not drawn.  There is no
+ *   clipping: a triangle that crosses znear or leaves the guard band disappears whole.
+ * Coverage: edge functions E_ab(p) = (b.x - a.x)(p.y - a.y) - (b.y - a.y)(p.x - a.x) in int64 on the fixed-point coordinates.
+ *   Triangles are two-sided: when E_01(v2) < 0, vertices 1 and 2 are swapped first (every later step uses that order); a triangle
+ *   with E_01(v2) == 0 covers nothing.  Weights w0 = E_12(p), w1 = E_20(p), w2 = E_01(p).  A pixel centre p is covered when every
+ *   w_i > 0, or w_i == 0 and the opposite edge a -> b is top-left: dy < 0, or dy == 0 and dx > 0 (y points down).  Two triangles
+ *   that share an edge therefore never both cover a pixel centre on it and never both miss it.
+ * Depth at a covered pixel: fp64 from the exact integer weights, in this order and with no contraction, then rounded to fp32:
+ *     s = w0 + w1;  s = s + w2;
+ *     orthographic: n = w0 z0;  n = n + w1 z1;  n = n + w2 z2;  depth = n / s;
+ *     pinhole:      q = w0 / z0;  q = q + w1 / z1;  q = q + w2 / z2;  depth = s / q   (perspective-correct view depth).
+ * Z test: key = (fp32 depth bits << 32) | face id as uint64; the smallest key wins.  A minimum does not depend on arrival order,
+ *   so face id and depth are a pure function of the inputs; on equal depth the lower face id wins.  Background: face -1, depth +inf.
+ * Steps of one render (all frames of the call together; F <= 65535, 1 <= W, H <= 2048, V and T <= INT32_MAX - 1):
+ *   1. p3d_mesh_project: vertices float32 [V][3] -> proj int32 [F][V][4] = (sx, sy, fp32 bits of z_c, dropped 0 / 1); a dropped
+ *      vertex has sx = sy = 0.
+ *   2. p3d_mesh_raster_count: faces int32 [T][3] -> tile_counts int32 [F][n_tiles], n_tiles = p3d_mesh_raster_tiles(W, H) screen tiles
+ *      of P3D_MESH_TILE x P3D_MESH_TILE pixels in row-major order (zeroed here): the triangles whose pixel-centre bounding box meets
+ *      each tile.  The caller scans it (exclusive) into tile_offsets int64 [F][n_tiles] and copies the total to THE HOST to size the
+ *      list: this sequence cannot be captured into a graph.
+ *   3. p3d_mesh_raster_bin: tile_list int32 [total] <- the triangle ids of each tile, in any order inside a tile (tile_cursor int64
+ *      [F][n_tiles] scratch).
+ *   4. p3d_mesh_raster: one work-group per tile and frame takes the z-test minimum in an LDS buffer (64-bit LDS atomicMin) and stores
+ *      face_id int32 [F][H][W] and depth float32 [F][H][W] once.
+ *   5. p3d_mesh_shade: face_id, proj -> rgb uint8 [F][H][W][3].  Barycentrics from the same integer weights: orthographic w_i / s,
+ *      pinhole (w_i / z_i) / q.  albedo = sum b_i colors[i] (colors uint8 [V][3], or NULL: uniform grey P3D_MESH_GREY), shaded by a
+ *      headlight Lambert term albedo * (ambient + (1 - ambient) |n . f|), n the face's world normal, f the camera's forward axis
+ *      (cam2world column 2); each channel rounded to nearest and clamped to 255.  Background pixels (and face ids outside [0, T))
+ *      get (bg_r, bg_g, bg_b).  This is not pyrender's physically based shading.                                                    */
+#define P3D_MESH_CAMERA_FLOATS 24
+#define P3D_MESH_TILE 32
+#define P3D_MESH_GREY 200
+int p3d_mesh_project(const float* vertices, int32_t n_vertices, const float* cameras, int32_t n_frames, int32_t orthographic,
+                     int32_t width, int32_t height, int32_t* proj, p3d_stream_t stream);
+int32_t p3d_mesh_raster_tiles(int32_t width, int32_t height);
+int p3d_mesh_raster_count(const int32_t* proj, int32_t n_vertices, const int32_t* faces, int32_t n_faces, int32_t n_frames,
+                          int32_t width, int32_t height, int32_t* tile_counts, p3d_stream_t stream);
+int p3d_mesh_raster_bin(const int32_t* proj, int32_t n_vertices, const int32_t* faces, int32_t n_faces, int32_t n_frames,
+                        int32_t width, int32_t height, const int64_t* tile_offsets, int64_t* tile_cursor, int32_t* tile_list,
+                        p3d_stream_t stream);
+int p3d_mesh_raster(const int32_t* proj, int32_t n_vertices, const int32_t* faces, int32_t n_frames, int32_t width, int32_t height,
+                    int32_t orthographic, const int32_t* tile_counts, const int64_t* tile_offsets, const int32_t* tile_list,
+                    int32_t* face_id, float* depth, p3d_stream_t stream);
+int p3d_mesh_shade(const int32_t* face_id, const int32_t* proj, const float* vertices, int32_t n_vertices, const int32_t* faces,
+                   int32_t n_faces, const uint8_t* colors, const float* cameras, int32_t n_frames, int32_t orthographic, int32_t width, int32_t height,
+                   float ambient, int32_t bg_r, int32_t bg_g, int32_t bg_b, uint8_t* rgb, p3d_stream_t stream);
+
 /* z_coarse [R][S_c], w_coarse [R][S_c-1], u_fine [R][S_f] -> z_fine [R][S_f] (sorted ascending
  * when `sorted`, else in draw order as sample_pdf returns them).                               */
 int p3d_importance_sample(const float* z_coarse, const float* w_coarse, const float* u_fine, float* z_fine,

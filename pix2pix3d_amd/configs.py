@@ -54,6 +54,21 @@ def oracle_cfg(name, depth=None, sr_num_fp16_res=4):
                 sr_clamp=256 if sr_num_fp16_res > 0 else None, lr_mul=kw['rendering_kwargs']['decoder_lr_mul'])
 
 
+def look_at(pos, target):
+    """OpenCV-convention cam2world float64 [4, 4] of a camera at ``pos`` looking at ``target`` with world +y up and no roll
+    (camera_utils.py:19-38, create_cam2world_matrix).  numpy only."""
+    import numpy as np
+    pos = np.asarray(pos, np.float64)
+    fwd = np.asarray(target, np.float64) - pos
+    fwd /= np.linalg.norm(fwd)
+    up = np.array([0.0, 1.0, 0.0])
+    right = -np.cross(up, fwd); right /= np.linalg.norm(right)
+    up2 = np.cross(fwd, right); up2 /= np.linalg.norm(up2)
+    c2w = np.eye(4)
+    c2w[:3, 0], c2w[:3, 1], c2w[:3, 2], c2w[:3, 3] = right, up2, fwd, pos
+    return c2w
+
+
 def orbit_camera(k, radius=2.7, focal=4.2647, n_frames=120, pivot=(0.0, 0.0, 0.0)):
     """25-float camera label of frame k of the orbit applications/generate_video.py:58-61, 127-137 renders:
     look-at pose (camera_utils.py:68-86, 118-137) + normalised intrinsics.  numpy only."""
@@ -65,13 +80,7 @@ def orbit_camera(k, radius=2.7, focal=4.2647, n_frames=120, pivot=(0.0, 0.0, 0.0
     theta, ph = h, math.acos(1 - 2 * (v / math.pi))
     pivot = np.asarray(pivot, np.float64)
     pos = pivot + radius * np.array([math.sin(ph) * math.cos(math.pi - theta), math.cos(ph), math.sin(ph) * math.sin(math.pi - theta)])
-    fwd = pivot - pos
-    fwd /= np.linalg.norm(fwd)
-    up = np.array([0.0, 1.0, 0.0])
-    right = -np.cross(up, fwd); right /= np.linalg.norm(right)                       # camera_utils.create_cam2world_matrix
-    up2 = np.cross(fwd, right); up2 /= np.linalg.norm(up2)
-    c2w = np.eye(4)
-    c2w[:3, 0], c2w[:3, 1], c2w[:3, 2], c2w[:3, 3] = right, up2, fwd, pos
+    c2w = look_at(pos, pivot)
     K = np.array([[focal, 0, 0.5], [0, focal, 0.5], [0, 0, 1]], np.float64)
     return np.concatenate([c2w.reshape(-1), K.reshape(-1)]).astype(np.float32)
 

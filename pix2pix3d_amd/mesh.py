@@ -1,0 +1,502 @@
+"""Render and export extracted meshes (applications/extract_mesh.py:196-262): what the script does with trimesh, pyrender and imageio.
+
+* ``project`` / ``rasterize`` / ``shade``: the three stages of a render.  Device tensors run csrc/mesh_raster.hip (p3d_mesh_project, a
+  screen-tiled rasterizer with an LDS z-buffer, p3d_mesh_shade); CPU tensors run the vectorised restatement below, which the kernels
+  are tested against.  Every convention (cameras, fixed point, top-left fill rule, fp64 depth, the z-test key) is include/p3d_hip.h's.
+* ``render``: the three stages over a batch of frames, the role of pyrender.OffscreenRenderer.render.  The shading is a headlight
+  Lambert term on interpolated vertex colours, not pyrender's physically based shading with a spot light.
+* ``turntable_poses``: the script's 120-frame orbit (:240-256), in the OpenCV convention (before its OpenGL column flip).
+* ``write_ply`` (trimesh's export), ``save_gif`` (imageio.mimsave, through PIL), ``vertex_labels`` (:196-218).
+* ``extract_mesh``: shape.extract_geometry, the labels and the turntable in one call.
+"""
+import math
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import _lib, configs, shape
+
+CAMERA_FLOATS = 24             # P3D_MESH_CAMERA_FLOATS
+GREY = 200                     # P3D_MESH_GREY: the albedo of a mesh without colours
+MAX_SIZE = 2048                # largest image edge the kernels take
+_GUARD = 4096 * 256            # guard band, sub-pixel units
+_KEY_BG = torch.iinfo(torch.int64).max
+_SCRIPT_PI = 3.14              # the script's turntable writes pi as 3.14 (extract_mesh.py:245-251)
+
+
+class Orthographic(NamedTuple):
+    """pyrender.OrthographicCamera: xmag, ymag are half-extents in world units.  znear / zfar as pyrender's defaults."""
+    xmag: float
+    ymag: float
+    znear: float = 0.05
+    zfar: float = 100.0
+
+
+class Pinhole(NamedTuple):
+    """The normalised intrinsics of the 25-float camera label: [3, 3], [F, 3, 3] or [F, 9] (fx, fy, cx, cy, skew are read from it)."""
+    intrinsics: object
+    znear: float = 0.05
+    zfar: float = 100.0
+
+
+class Projection(NamedTuple):
+    """p3d_mesh_project's output: packed int32 [F, V, 4] = (sx, sy, fp32 bits of z, dropped) on the vertices' device."""
+    packed: torch.Tensor
+    orthographic: bool
+
+    @property
+    def xy(self):
+        return self.packed[..., :2]
+
+    @property
+    def z(self):
+        return self.packed[..., 2].contiguous().view(torch.float32)
+
+    @property
+    def dropped(self):
+        return self.packed[..., 3] != 0
+
+    def to(self, device):
+        return Projection(self.packed.to(device), self.orthographic)
+
+
+def _size(resolution):
+    h, w = (resolution, resolution) if isinstance(resolution, int) else (int(resolution[0]), int(resolution[1]))
+    if not (1 <= h <= MAX_SIZE and 1 <= w <= MAX_SIZE):
+        raise ValueError(f'mesh: image size {h} x {w} outside [1, {MAX_SIZE}]^2')
+    return h, w
+
+
+def _cameras(cam2world, camera):
+    """cam2world [F, 4, 4] (or [4, 4]) and a camera model -> the float32 [F, 24] rows of include/p3d_hip.h, on the CPU."""
+    c2w = torch.as_tensor(cam2world, dtype=torch.float32).detach().cpu().reshape(-1, 16)
+    n = c2w.shape[0]
+    cams = torch.zeros([n, CAMERA_FLOATS], dtype=torch.float32)
+    cams[:, :16] = c2w
+    if isinstance(camera, Orthographic):
+        if not (float(camera.xmag) > 0 and float(camera.ymag) > 0):
+            raise ValueError(f'mesh: xmag and ymag must be positive, got {camera.xmag}, {camera.ymag}')
+        cams[:, 16], cams[:, 17] = float(camera.xmag), float(camera.ymag)
+    elif isinstance(camera, Pinhole):
+        k = torch.as_tensor(camera.intrinsics, dtype=torch.float32).detach().cpu().reshape(-1, 9).expand(n, 9)
+        cams[:, 16], cams[:, 17], cams[:, 18], cams[:, 19], cams[:, 20] = k[:, 0], k[:, 4], k[:, 2], k[:, 5], k[:, 1]
+    else:
+        raise TypeError(f'mesh: camera must be Orthographic or Pinhole, got {type(camera).__name__}')
+    znear, zfar = float(camera.znear), float(camera.zfar)
+    if not 0.0 < znear < zfar < math.inf:                                 # depths stay positive: the z-test key orders them as integers
+        raise ValueError(f'mesh: need 0 < znear < zfar < inf, got znear={znear}, zfar={zfar}')
+    cams[:, 21], cams[:, 22] = znear, zfar
+    return cams
+
+
+# ---- projection -------------------------------------------------------------------------------------------------------------
+def _project_cpu(vertices, cams, ortho, h, w):
+    c = cams.double()
+    p = vertices.double()
+    col = lambda j: c[:, j:j + 1]                                          # noqa: E731  [F, 1]
+    px, py, pz = p[:, 0] - col(3), p[:, 1] - col(7), p[:, 2] - col(11)    # [F, V]
+    xc = col(0) * px; xc = xc + col(4) * py; xc = xc + col(8) * pz
+    yc = col(1) * px; yc = yc + col(5) * py; yc = yc + col(9) * pz
+    zc = col(2) * px; zc = zc + col(6) * py; zc = zc + col(10) * pz
+    if ortho:
+        u = (xc / col(16) + 1.0) * 0.5
+        v = (yc / col(17) + 1.0) * 0.5
+    else:
+        a = col(16) * xc
+        a = a + col(20) * yc
+        u = a / zc + col(18)
+        v = (col(17) * yc) / zc + col(19)
+    sx, sy = u * float(w * 256), v * float(h * 256)
+    keep = (zc >= col(21)) & (zc <= col(22)) & (sx >= -_GUARD) & (sx <= w * 256 + _GUARD) & (sy >= -_GUARD) & (sy <= h * 256 + _GUARD)
+    zero = torch.zeros_like(sx)
+    packed = torch.stack([torch.where(keep, sx, zero).round().to(torch.int32), torch.where(keep, sy, zero).round().to(torch.int32),
+                          zc.float().view(torch.int32), (~keep).to(torch.int32)], dim=-1)
+    return packed
+
+
+def project(vertices, cam2world, camera, resolution):
+    """Project vertices float32 [V, 3] into F frames (cam2world [F, 4, 4], OpenCV convention): a ``Projection`` with fixed-point screen
+    positions (8 sub-pixel bits, round half to even), view depth and drop flags (include/p3d_hip.h)."""
+    h, w = _size(resolution)
+    vertices = vertices.detach().to(torch.float32).contiguous()
+    if vertices.ndim != 2 or vertices.shape[1] != 3 or vertices.shape[0] >= 2 ** 31 - 1:
+        raise ValueError(f'project: vertices must be [V, 3] with V < 2^31 - 1, got {tuple(vertices.shape)}')
+    cams = _cameras(cam2world, camera)
+    ortho = isinstance(camera, Orthographic)
+    if not vertices.is_cuda:
+        return Projection(_project_cpu(vertices, cams, ortho, h, w), ortho)
+    n, v = cams.shape[0], vertices.shape[0]
+    cams = cams.to(vertices.device)
+    packed = torch.empty([n, v, 4], dtype=torch.int32, device=vertices.device)
+    _lib.check(_lib.lib().p3d_mesh_project(_lib.ptr(vertices), v, _lib.ptr(cams), n, int(ortho), w, h, _lib.ptr(packed),
+                                           _lib.stream_of(vertices)), 'mesh_project')
+    return Projection(packed, ortho)
+
+
+# ---- rasterization ----------------------------------------------------------------------------------------------------------
+def _faces32(faces, n_vertices):
+    if faces.ndim != 2 or faces.shape[1] != 3 or faces.shape[0] >= 2 ** 31 - 1:
+        raise ValueError(f'mesh: faces must be [T, 3] with T < 2^31 - 1, got {tuple(faces.shape)}')
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f'mesh: faces must be int32 or int64, got {faces.dtype}')
+    return faces.detach().to(torch.int32).contiguous()
+
+
+def _setup_cpu(packed, faces):
+    """The triangle setup of csrc/mesh_raster.hip (tri_setup) for one frame: packed [V, 4], faces int64 [T, 3] ->
+    (drawn bool [T], vertex ids [T, 3] in weight order, x, y int64 [T, 3], z float32 [T, 3], c0, c1, r0, r1 before the box test)."""
+    nv = packed.shape[0]
+    idx = faces.long()
+    ok = ((idx >= 0) & (idx < nv)).all(1)
+    idx = idx.clamp(0, max(nv - 1, 0))
+    rec = packed[idx]                                                     # [T, 3, 4]
+    x, y = rec[..., 0].long(), rec[..., 1].long()
+    z = rec[..., 2].contiguous().view(torch.float32)
+    ok &= (rec[..., 3] == 0).all(1)
+    area = (x[:, 1] - x[:, 0]) * (y[:, 2] - y[:, 0]) - (y[:, 1] - y[:, 0]) * (x[:, 2] - x[:, 0])
+    ok &= area != 0
+    perm = torch.where((area < 0)[:, None], torch.tensor([0, 2, 1]), torch.tensor([0, 1, 2]))
+    idx, x, y, z = (t.gather(1, perm) for t in (idx, x, y, z))
+    return ok, idx, x, y, z
+
+
+def _bbox(x, y, h, w):
+    c0 = ((x.min(1).values - 128 + 255) >> 8).clamp(min=0)
+    c1 = ((x.max(1).values - 128) >> 8).clamp(max=w - 1)
+    r0 = ((y.min(1).values - 128 + 255) >> 8).clamp(min=0)
+    r1 = ((y.max(1).values - 128) >> 8).clamp(max=h - 1)
+    return c0, c1, r0, r1
+
+
+def _owns(dx, dy):
+    return (dy < 0) | ((dy == 0) & (dx > 0))
+
+
+def _weights(x, y, r, c):
+    """Edge weights and coverage at pixel centres (r, c); x, y [N, 3] int64 in weight order."""
+    px, py = (c << 8) + 128, (r << 8) + 128
+    dx0, dy0 = x[:, 2] - x[:, 1], y[:, 2] - y[:, 1]
+    dx1, dy1 = x[:, 0] - x[:, 2], y[:, 0] - y[:, 2]
+    dx2, dy2 = x[:, 1] - x[:, 0], y[:, 1] - y[:, 0]
+    w0 = dx0 * (py - y[:, 1]) - dy0 * (px - x[:, 1])
+    w1 = dx1 * (py - y[:, 2]) - dy1 * (px - x[:, 2])
+    w2 = dx2 * (py - y[:, 0]) - dy2 * (px - x[:, 0])
+    inside = ((w0 > 0) | ((w0 == 0) & _owns(dx0, dy0))) & ((w1 > 0) | ((w1 == 0) & _owns(dx1, dy1))) & \
+             ((w2 > 0) | ((w2 == 0) & _owns(dx2, dy2)))
+    return w0, w1, w2, inside
+
+
+def _depth(w0, w1, w2, z, ortho):
+    """include/p3d_hip.h's depth, in its operation order (separate torch ops: no contraction)."""
+    a, b, c = w0.double(), w1.double(), w2.double()
+    z0, z1, z2 = (z[:, k].double() for k in range(3))
+    s = a + b
+    s = s + c
+    if ortho:
+        n = a * z0
+        n = n + b * z1
+        n = n + c * z2
+        return (n / s).float()
+    q = a / z0
+    q = q + b / z1
+    q = q + c / z2
+    return (s / q).float()
+
+
+def _raster_cpu_frame(packed, faces, ortho, h, w, chunk_pairs=1 << 23):
+    ok, _, x, y, z = _setup_cpu(packed, faces)
+    c0, c1, r0, r1 = _bbox(x, y, h, w)
+    ok &= (c0 <= c1) & (r0 <= r1)
+    tid = ok.nonzero()[:, 0]
+    nc, nr = (c1 - c0 + 1)[tid], (r1 - r0 + 1)[tid]
+    pairs = nc * nr
+    keys = torch.full([h * w], _KEY_BG, dtype=torch.int64)
+    ends = torch.cumsum(pairs, 0)
+    start = 0
+    while start < len(tid):                                                # chunks of at most ~chunk_pairs candidate pairs
+        base = int(ends[start - 1]) if start else 0
+        stop = max(int(torch.searchsorted(ends, base + chunk_pairs, right=True)), start + 1)
+        sel = torch.arange(start, stop)
+        cnt = pairs[sel]
+        rep = torch.repeat_interleave(sel, cnt)
+        local = torch.arange(int(cnt.sum())) - torch.repeat_interleave(torch.cumsum(cnt, 0) - cnt, cnt)
+        t = tid[rep]
+        r = r0[t] + local // nc[rep]
+        c = c0[t] + local % nc[rep]
+        w0, w1, w2, inside = _weights(x[t], y[t], r, c)
+        t, r, c = t[inside], r[inside], c[inside]
+        d = _depth(w0[inside], w1[inside], w2[inside], z[t], ortho)
+        key = (d.view(torch.int32).long() << 32) | t
+        keys.scatter_reduce_(0, r * w + c, key, 'amin')
+        start = stop
+    bg = keys == _KEY_BG
+    face_id = torch.where(bg, torch.tensor(-1, dtype=torch.int64), keys & 0xffffffff).to(torch.int32)
+    depth = torch.where(bg, torch.tensor(float('inf')), (keys >> 32).to(torch.int32).view(torch.float32))
+    return face_id.reshape(h, w), depth.reshape(h, w)
+
+
+def _raster_device(proj, faces, h, w):
+    lib = _lib.lib()
+    packed = proj.packed.contiguous()
+    n, nv = packed.shape[0], packed.shape[1]
+    dev = packed.device
+    nf = faces.shape[0]
+    tiles = int(lib.p3d_mesh_raster_tiles(w, h))
+    stream = _lib.stream_of(packed)
+    counts = torch.empty([n, tiles], dtype=torch.int32, device=dev)
+    _lib.check(lib.p3d_mesh_raster_count(_lib.ptr(packed), nv, _lib.ptr(faces), nf, n, w, h, _lib.ptr(counts), stream), 'mesh_raster_count')
+    inclusive = torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64)
+    offsets = (inclusive - counts.reshape(-1)).contiguous()
+    total = int(inclusive[-1]) if inclusive.numel() else 0                # the one device-to-host copy: sizes the tile lists
+    tile_list = torch.empty([max(total, 1)], dtype=torch.int32, device=dev)
+    cursor = torch.empty_like(offsets)
+    stream = _lib.stream_of(packed)
+    _lib.check(lib.p3d_mesh_raster_bin(_lib.ptr(packed), nv, _lib.ptr(faces), nf, n, w, h, _lib.ptr(offsets), _lib.ptr(cursor),
+                                       _lib.ptr(tile_list), stream), 'mesh_raster_bin')
+    face_id = torch.empty([n, h, w], dtype=torch.int32, device=dev)
+    depth = torch.empty([n, h, w], dtype=torch.float32, device=dev)
+    _lib.check(lib.p3d_mesh_raster(_lib.ptr(packed), nv, _lib.ptr(faces), n, w, h, int(proj.orthographic), _lib.ptr(counts), _lib.ptr(offsets),
+                                   _lib.ptr(tile_list), _lib.ptr(face_id), _lib.ptr(depth), stream), 'mesh_raster')
+    return face_id, depth
+
+
+def rasterize(proj, faces, resolution):
+    """The nearest triangle at every pixel centre of every frame: (face_id int32 [F, H, W], -1 for background; depth float32 [F, H, W],
+    +inf for background).  Top-left fill rule, fp64 depth from the exact integer edge weights, smallest (depth, face id) key wins
+    (include/p3d_hip.h): the result does not depend on the order of the faces beyond their ids.  Device tensors run the tiled kernels
+    and copy one total to the host (not graph-capturable); CPU tensors run the restatement."""
+    h, w = _size(resolution)
+    faces32 = _faces32(faces, proj.packed.shape[1])
+    if proj.packed.is_cuda:
+        return _raster_device(proj, faces32.to(proj.packed.device), h, w)
+    out = [_raster_cpu_frame(p, faces32.long(), proj.orthographic, h, w) for p in proj.packed]
+    if not out:
+        return torch.empty([0, h, w], dtype=torch.int32), torch.empty([0, h, w])
+    return torch.stack([o[0] for o in out]), torch.stack([o[1] for o in out])
+
+
+# ---- shading ----------------------------------------------------------------------------------------------------------------
+def _shade_cpu(face_id, proj, vertices, faces, colors, cams, ambient, background):
+    n, h, w = face_id.shape
+    out = torch.empty([n, h, w, 3], dtype=torch.uint8)
+    out[:] = torch.tensor(background, dtype=torch.uint8)
+    nf = faces.shape[0]
+    verts = vertices.double()
+    for f in range(n):
+        fid = face_id[f].reshape(-1).long()
+        pix = ((fid >= 0) & (fid < nf)).nonzero()[:, 0]
+        t = fid[pix]
+        ok, idx, x, y, z = _setup_cpu(proj.packed[f], faces[t].long())
+        c0, c1, r0, r1 = _bbox(x, y, h, w)
+        ok &= (c0 <= c1) & (r0 <= r1)
+        pix, idx, x, y, z = pix[ok], idx[ok], x[ok], y[ok], z[ok]
+        r, c = pix // w, pix % w
+        w0, w1, w2, _ = _weights(x, y, r, c)
+        a0, a1, a2 = w0.double(), w1.double(), w2.double()
+        if proj.orthographic:
+            s = a0 + a1
+            s = s + a2
+            b = (a0 / s, a1 / s, a2 / s)
+        else:
+            q0, q1, q2 = a0 / z[:, 0].double(), a1 / z[:, 1].double(), a2 / z[:, 2].double()
+            q = q0 + q1
+            q = q + q2
+            b = (q0 / q, q1 / q, q2 / q)
+        e1 = verts[idx[:, 1]] - verts[idx[:, 0]]
+        e2 = verts[idx[:, 2]] - verts[idx[:, 0]]
+        nx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+        ny = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+        nz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+        f0, f1, f2 = (float(cams[f, j].double()) for j in (2, 6, 10))
+        nn = nx * nx
+        nn = nn + ny * ny
+        nn = nn + nz * nz
+        ff = f0 * f0
+        ff = ff + f1 * f1
+        ff = ff + f2 * f2
+        dot = nx * f0
+        dot = dot + ny * f1
+        dot = dot + nz * f2
+        den = nn.sqrt() * math.sqrt(ff)
+        cosv = torch.where(den > 0, dot.abs() / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(den))
+        amb = float(torch.tensor(ambient, dtype=torch.float32))
+        shade_ = amb + (1.0 - amb) * cosv
+        rgb = torch.empty([len(pix), 3], dtype=torch.uint8)
+        for ch in range(3):
+            if colors is None:
+                alb = torch.full_like(shade_, float(GREY))
+            else:
+                col = colors[:, ch].double()
+                alb = b[0] * col[idx[:, 0]]
+                alb = alb + b[1] * col[idx[:, 1]]
+                alb = alb + b[2] * col[idx[:, 2]]
+            rgb[:, ch] = torch.floor(alb * shade_ + 0.5).clamp(0, 255).to(torch.uint8)
+        out[f].reshape(-1, 3)[pix] = rgb
+    return out
+
+
+def shade(face_id, proj, vertices, faces, cam2world, colors=None, background=(255, 255, 255), ambient=0.3):
+    """uint8 [F, H, W, 3] frames from the raster buffers: barycentric vertex colours (perspective-correct under a pinhole camera) times
+    ambient + (1 - ambient) |n . f| (face normal, camera forward axis); colors uint8 [V, 3] or None for uniform grey; background where
+    face_id is -1.  cam2world as given to ``project``.  Every input is moved to face_id's device, which picks the path."""
+    if face_id.ndim != 3:
+        raise ValueError(f'shade: face_id must be [F, H, W], got {tuple(face_id.shape)}')
+    n, h, w = face_id.shape
+    dev = face_id.device                                                  # every input goes where face_id is: the kernel gets no host pointer
+    face_id = face_id.detach().to(torch.int32).contiguous()
+    vertices = vertices.detach().to(device=dev, dtype=torch.float32).contiguous()
+    faces32 = _faces32(faces, vertices.shape[0]).to(dev)
+    packed = proj.packed.detach().to(device=dev, dtype=torch.int32).contiguous()
+    if tuple(packed.shape) != (n, vertices.shape[0], 4):
+        raise ValueError(f'shade: the projection is {tuple(packed.shape)}, the buffers and vertices need ({n}, {vertices.shape[0]}, 4)')
+    if colors is not None:
+        colors = torch.as_tensor(colors).detach().to(device=dev, dtype=torch.uint8).contiguous()
+        if tuple(colors.shape) != (vertices.shape[0], 3):
+            raise ValueError(f'shade: colors must be uint8 [V, 3], got {tuple(colors.shape)}')
+    bg = tuple(int(v) & 255 for v in background)
+    # the camera rows only feed the forward axis here: the model's parameters do not matter
+    cams = _cameras(cam2world, Orthographic(1.0, 1.0))
+    if cams.shape[0] != n:
+        raise ValueError(f'shade: {cams.shape[0]} cameras for {n} frames')
+    if not face_id.is_cuda:
+        return _shade_cpu(face_id, Projection(packed, proj.orthographic), vertices, faces32, colors, cams, ambient, bg)
+    rgb = torch.empty([n, h, w, 3], dtype=torch.uint8, device=dev)
+    cams = cams.to(dev)
+    _lib.check(_lib.lib().p3d_mesh_shade(_lib.ptr(face_id), _lib.ptr(packed), _lib.ptr(vertices), vertices.shape[0],
+                                         _lib.ptr(faces32), faces32.shape[0], _lib.ptr(colors), _lib.ptr(cams), n, int(proj.orthographic),
+                                         w, h, float(ambient), *bg, _lib.ptr(rgb), _lib.stream_of(rgb)), 'mesh_shade')
+    return rgb
+
+
+@torch.no_grad()
+def render(vertices, faces, cam2world, camera, resolution=512, colors=None, background=(255, 255, 255), ambient=0.3, return_buffers=False,
+           max_bytes=1 << 30):
+    """The role of pyrender.OffscreenRenderer.render for every pose of cam2world [F, 4, 4] (OpenCV convention): uint8 frames
+    [F, H, W, 3] on the vertices' device.  ``camera`` is Orthographic(xmag, ymag) or Pinhole(intrinsics); faces int32 or int64 [T, 3];
+    colors uint8 [V, 3] or None (uniform grey).  With return_buffers=True also (face_id int32 [F, H, W], depth float32 [F, H, W]).
+    Frames go through project / rasterize / shade in groups whose projections take at most ``max_bytes``."""
+    h, w = _size(resolution)
+    vertices = vertices.detach().to(torch.float32).contiguous()
+    c2w = torch.as_tensor(cam2world, dtype=torch.float32).reshape(-1, 4, 4)
+    dev = vertices.device
+    faces32 = _faces32(faces, vertices.shape[0]).to(dev)
+    if colors is not None:
+        colors = torch.as_tensor(colors).to(device=dev, dtype=torch.uint8).contiguous()
+    if isinstance(camera, Pinhole):
+        k = torch.as_tensor(camera.intrinsics, dtype=torch.float32).reshape(-1, 9).expand(c2w.shape[0], 9)
+    group = max(1, min(c2w.shape[0], max_bytes // max(1, 16 * vertices.shape[0])))
+    frames, ids, depths = [], [], []
+    for s in range(0, c2w.shape[0], group):
+        cam = camera if not isinstance(camera, Pinhole) else camera._replace(intrinsics=k[s:s + group])
+        proj = project(vertices, c2w[s:s + group], cam, (h, w))
+        face_id, depth = rasterize(proj, faces32, (h, w))
+        frames.append(shade(face_id, proj, vertices, faces32, c2w[s:s + group], colors, background, ambient))
+        if return_buffers:
+            ids.append(face_id)
+            depths.append(depth)
+        del proj
+    out = torch.cat(frames) if frames else torch.empty([0, h, w, 3], dtype=torch.uint8, device=dev)
+    if return_buffers:
+        return out, torch.cat(ids), torch.cat(depths)
+    return out
+
+
+# ---- cameras ----------------------------------------------------------------------------------------------------------------
+def turntable_poses(pivot, radius, n_frames=120, yaw0=_SCRIPT_PI / 2, yaw_range=0.35, pitch_range=0.25, pitch0=_SCRIPT_PI / 2 - 0.05):
+    """float32 [n_frames, 4, 4] cam2world, OpenCV convention: frame k is LookAtPoseSampler.sample(yaw0 + yaw_range sin(2 3.14 k / n),
+    pitch0 + pitch_range cos(2 3.14 k / n), pivot, radius) as extract_mesh.py:240-256 draws it (before its OpenGL column flip).  As
+    in LookAtPoseSampler, the camera lies on the sphere of that radius about the world origin and looks at the pivot.  Defaults: the
+    seg2cat / seg2face turntable; edge2car is yaw0=-3.14/2, yaw_range=pi, pitch_range=pi/2 (and radius 1.2)."""
+    out = np.empty([n_frames, 4, 4], np.float64)
+    for k in range(n_frames):
+        h = yaw0 + yaw_range * math.sin(2 * _SCRIPT_PI * k / n_frames)
+        v = pitch0 + pitch_range * math.cos(2 * _SCRIPT_PI * k / n_frames)
+        v = min(max(v, 1e-5), math.pi - 1e-5)
+        phi = math.acos(1 - 2 * (v / math.pi))
+        pos = radius * np.array([math.sin(phi) * math.cos(math.pi - h), math.cos(phi), math.sin(phi) * math.sin(math.pi - h)])
+        out[k] = configs.look_at(pos, np.asarray(pivot, np.float64))
+    return torch.from_numpy(out).to(torch.float32)
+
+
+# ---- files ------------------------------------------------------------------------------------------------------------------
+def write_ply(path, vertices, faces, colors=None):
+    """Binary little-endian PLY (what trimesh's export writes for the script): vertex float x y z [+ uchar red green blue],
+    face list uchar int vertex_indices."""
+    v = vertices.detach().cpu().to(torch.float32).numpy()
+    f = faces.detach().cpu().numpy()
+    if f.size and (f.min() < 0 or f.max() >= len(v) or f.max() > np.iinfo(np.int32).max):
+        raise ValueError('write_ply: face index outside [0, V)')
+    vfields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
+    props = 'property float x\nproperty float y\nproperty float z\n'
+    if colors is not None:
+        vfields += [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
+        props += 'property uchar red\nproperty uchar green\nproperty uchar blue\n'
+    header = (f'ply\nformat binary_little_endian 1.0\nelement vertex {len(v)}\n{props}'
+              f'element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n')
+    vrec = np.empty(len(v), dtype=vfields)
+    vrec['x'], vrec['y'], vrec['z'] = v[:, 0], v[:, 1], v[:, 2]
+    if colors is not None:
+        c = torch.as_tensor(colors).detach().cpu().to(torch.uint8).numpy()
+        vrec['red'], vrec['green'], vrec['blue'] = c[:, 0], c[:, 1], c[:, 2]
+    frec = np.empty(len(f), dtype=[('n', 'u1'), ('i', '<i4', (3,))])
+    frec['n'] = 3
+    frec['i'] = f
+    with open(path, 'wb') as fh:
+        fh.write(header.encode('ascii'))
+        fh.write(vrec.tobytes())
+        fh.write(frec.tobytes())
+
+
+def save_gif(path, frames, fps=60):
+    """imageio.mimsave(path, frames, fps=fps) through PIL: frames uint8 [F, H, W, 3], looping forever."""
+    from PIL import Image
+    arr = torch.as_tensor(frames).detach().cpu().to(torch.uint8).numpy()
+    images = [Image.fromarray(a) for a in arr]
+    images[0].save(path, save_all=True, append_images=images[1:], duration=max(1, round(1000 / fps)), loop=0)
+
+
+# ---- labels and the whole script ---------------------------------------------------------------------------------------------
+def default_palette(n):
+    """uint8 [n, 3]: class 0 grey, the others spread round the hue circle by the golden angle (this package's own colours)."""
+    import colorsys
+    out = [(128, 128, 128)]
+    for k in range(1, n):
+        r, g, b = colorsys.hsv_to_rgb((k * 0.618033988749895) % 1.0, 0.65, 0.95)
+        out.append((round(r * 255), round(g * 255), round(b * 255)))
+    return torch.tensor(out[:n], dtype=torch.uint8)
+
+
+@torch.no_grad()
+def vertex_labels(G, ws, vertices, palette=None, max_batch=10_000_000):
+    """extract_mesh.py:196-218: the argmax over G's semantic channels of G.sample_mixed at the vertices (in chunks of max_batch
+    points), and its colour in ``palette`` uint8 [C, 3] (default: default_palette(C)).  Returns (labels int64 [V], colors uint8 [V, 3])
+    on the vertices' device."""
+    n_sem = int(G.semantic_channels)
+    pts = vertices.detach().to(device=ws.device, dtype=torch.float32)[None]
+    labels = torch.empty([pts.shape[1]], dtype=torch.int64, device=ws.device)
+    for head in range(0, pts.shape[1], max_batch):
+        out = G.sample_mixed(pts[:, head:head + max_batch], None, ws, truncation_psi=1, noise_mode='const')
+        labels[head:head + max_batch] = out['rgb'][0, :, 32:32 + n_sem].argmax(dim=-1)
+    pal = default_palette(n_sem) if palette is None else torch.as_tensor(palette, dtype=torch.uint8)
+    return labels.to(vertices.device), pal.to(vertices.device)[labels.to(vertices.device)]
+
+
+@torch.no_grad()
+def extract_mesh(G, ws, resolution=512, threshold=50., n_frames=120, image_size=512, palette=None, **synthesis_kwargs):
+    """applications/extract_mesh.py after its inputs: shape.extract_geometry, per-vertex label colours unless G is an edge-map
+    generator (data_type 'edge') or has no label channels, and the script's turntable — orthographic xmag = ymag = 0.3 at radius 1 (edge2car: 0.6 at 1.2) about
+    G.rendering_kwargs['avg_camera_pivot'], image_size^2 pixels.  Returns (vertices, faces, vertex_colors or None, frames uint8
+    [n_frames, image_size, image_size, 3])."""
+    vertices, faces = shape.extract_geometry(G, ws, resolution, threshold, **synthesis_kwargs)
+    edge = getattr(G, 'data_type', None) == 'edge'                      # the script's edge2car branch; every other generator is seg-like
+    labelled = not edge and int(getattr(G, 'semantic_channels', 0) or 0) > 1
+    colors = vertex_labels(G, ws, vertices, palette)[1] if labelled and len(vertices) else None
+    pivot = G.rendering_kwargs['avg_camera_pivot']
+    if not edge:
+        poses, camera = turntable_poses(pivot, 1.0, n_frames), Orthographic(0.3, 0.3)
+    else:
+        poses = turntable_poses(pivot, 1.2, n_frames, yaw0=-_SCRIPT_PI / 2, yaw_range=np.pi, pitch_range=np.pi / 2)
+        camera = Orthographic(0.6, 0.6)
+    frames = render(vertices, faces, poses, camera, image_size, colors=colors)
+    return vertices, faces, colors, frames

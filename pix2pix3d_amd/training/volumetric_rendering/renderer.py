@@ -72,6 +72,14 @@ _lib.register('p3d_marching_cubes_blocks', ctypes.c_int64, [_i32, _i32, _i32])
 _lib.register('p3d_marching_cubes_classify', ctypes.c_int, [_vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp])
 _lib.register('p3d_marching_cubes_emit', ctypes.c_int, [_vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64,
                                                         _vp, _vp, _vp, _vp])
+# mesh rendering (pix2pix3d_amd/mesh.py, csrc/mesh_raster.hip)
+_lib.register('p3d_mesh_project', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp])
+_lib.register('p3d_mesh_raster_tiles', ctypes.c_int32, [_i32, _i32])
+_lib.register('p3d_mesh_raster_count', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp])
+_lib.register('p3d_mesh_raster_bin', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp])
+_lib.register('p3d_mesh_raster', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp])
+_lib.register('p3d_mesh_shade', ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _i32,
+                                           _vp, _vp])
 
 
 def generate_planes():
