@@ -168,6 +168,34 @@ def upfirdn2d(x, f, up=1, down=1, padding=0, flip_filter=False, gain=1):
     return y.astype(x.dtype)
 
 
+def upfirdn2d_grad(gy, x_shape, f, up=1, down=1, padding=0, flip_filter=False, gain=1):
+    """Gradient of ``upfirdn2d`` w.r.t. x (its adjoint), float64: the forward above read backwards.  Each tap adds g * gy onto the
+    padded zero-stuffed grid at the positions it read; the input samples then take what landed on their grid positions.  Written
+    from the forward's own indexing, not from the up/down-swapped formulation the device backward uses (upfirdn2d.py:252-271)."""
+    gy = np.asarray(gy, np.float64)
+    n, c, h, w = x_shape
+    upx, upy = _two(up)
+    dnx, dny = _two(down)
+    px0, px1, py0, py1 = _pad4(padding)
+    f = np.ones([1, 1], np.float32) if f is None else np.asarray(f, np.float32)
+    f2 = np.outer(f, f) if f.ndim == 1 else f
+    fh, fw = f2.shape
+    g = (f2 if flip_filter else f2[::-1, ::-1]).astype(np.float64) * gain
+
+    uw, uh = w * upx + px0 + px1, h * upy + py0 + py1
+    oh, ow = (uh - fh + dny) // dny, (uw - fw + dnx) // dnx
+    assert gy.shape == (n, c, oh, ow), (gy.shape, (n, c, oh, ow))
+    gu = np.zeros([n, c, max(uh, 0), max(uw, 0)], np.float64)
+    for ky in range(fh):
+        for kx in range(fw):
+            gu[:, :, ky: ky + (oh - 1) * dny + 1: dny, kx: kx + (ow - 1) * dnx + 1: dnx] += g[ky, kx] * gy
+    ys, xs = np.arange(h) * upy + py0, np.arange(w) * upx + px0
+    my, mx = (ys >= 0) & (ys < uh), (xs >= 0) & (xs < uw)
+    gx = np.zeros([n, c, h, w], np.float64)
+    gx[:, :, np.flatnonzero(my)[:, None], np.flatnonzero(mx)[None, :]] = gu[:, :, ys[my][:, None], xs[mx][None, :]]
+    return gx
+
+
 def conv2d(x, w, stride=1, padding=0, groups=1):
     """Plain correlation (what torch.nn.functional.conv2d computes), NCHW, float64 accumulation."""
     x, w = np.asarray(x, np.float64), np.asarray(w, np.float64)
