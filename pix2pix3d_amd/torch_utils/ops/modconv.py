@@ -7,6 +7,7 @@ training/networks_stylegan2.py:34-69, 81-91), ``conv2d_resample`` (:114-136), th
 ``SynthesisLayer`` / ``ToRGBLayer`` use it when ``layer_supported`` says so (device tensor, channels_last, inference,
 per-sample "fused" modulation, enough pixels to fill 128-row MFMA tiles); every other case keeps the generic route.
 """
+import collections
 import ctypes
 import os
 
@@ -14,63 +15,36 @@ import torch
 
 from ... import _lib
 from . import upfirdn2d, bias_act
+from .prefetch_plan import PrefetchPlan
 
 enabled = True
 prefetch_styles = True       # run every layer's style affine + weight modulation ahead of the convolutions on a second stream
-_plan = {}                   # id(layer) -> (styles, (wmod, route tag) or None, event), filled by SynthesisNetwork.forward
-_side = {}
-
-
-def side_stream(device):
-    st = _side.get(device)
-    if st is None:
-        st = _side[device] = torch.cuda.Stream(device=device)
-    return st
-
-
-_plan_seq = [0]              # position of the newest event on the prefetch stream (monotonic for the life of the process)
-after_prefetch = []          # callables a network's prefetch_styles runs once its own plan is issued (the plans of networks LATER in the step: triplane._render)
-_ahead = {}                  # id(network) -> (the ws it was planned for, the plan's keys): plans issued ahead, picked up by that network's forward
-_plan_own_until = [0]        # waits for positions up to this one are for the entry's OWN event (the current network's first layer, then its ToRGB group); later ones for everything issued
-_plan_latest = [None, -1]    # (event, position): the newest event on the prefetch stream
-_plan_waited = {}            # consuming stream (its handle) -> position on the prefetch stream (the sequence number of an event) it already waits behind
-
-
-def take_plan(layer):
-    """Pop this layer's prefetched (styles, premodulated weights) and make the current stream wait for them.
-    Entries carry the POSITION of their event on the prefetch stream (prefetch_styles numbers them; layers that launched nothing new share the event of the
-    last one that did): a layer whose position the stream already waits behind adds no second wait.  In the captured step every such wait is an edge
-    between two branches of the graph — idle device in front of the layer's first kernel whether or not the event fired long ago (27 of them per step,
-    5.8 us each under the profiler: profiles/round5_u_step_trace.txt; same-box A/B of the elision: +0.4 ... +1.1 %, profiles/round6_a_*).
-    The waits for a network's first layer and for its ToRGB group (issued right behind it: prefetch_styles) are for those events themselves — the first layers
-    must not stand behind every modulation of the step; any LATER one is for everything issued so far (``_plan_latest``: by then — the first per-image-weight
-    layer, hundreds of microseconds into the network — the prefetch stream has long run dry), so a network costs three edges, and the heads whose plans were
-    issued ahead none."""
-    hit = _plan.pop(id(layer), None)
-    if hit is None:
-        return None
-    seq = hit[3] if len(hit) > 3 else None
-    cur = torch.cuda.current_stream()
-    waited = _plan_waited.get(cur.cuda_stream, -1)
-    if seq is None or not plan_wait_elision or seq > waited:
-        ev = hit[2]
-        if seq is not None and plan_wait_elision and plan_wait_latest and seq > _plan_own_until[0] and _plan_latest[0] is not None:
-            ev, seq = _plan_latest
-        cur.wait_event(ev)
-        if seq is not None:
-            _plan_waited[cur.cuda_stream] = seq
-    return hit[0], hit[1]
-
-
-def plan_joined(stream):
-    """True when ``stream`` already waits behind everything on the prefetch stream (finish_prefetch then adds no further edge)."""
-    return plan_wait_elision and _plan_latest[0] is not None and _plan_waited.get(stream.cuda_stream, -1) >= _plan_latest[1]
-
-
 plan_wait_elision = os.environ.get('P3D_PLAN_WAIT_ELISION', '1') != '0'      # take_plan skips waits its stream already stands behind; 0 = one wait per layer (A/B)
 plan_wait_latest = os.environ.get('P3D_PLAN_WAIT_LATEST', '1') != '0'        # ... and a stream's SECOND wait on a plan is for everything issued so far (0 = the layer's own event)
 premodulate_rgb = os.environ.get('P3D_PREMODULATE_RGB', '1') != '0'          # ToRGB layers' weight modulation on the prefetch stream too (premodulate_torgb)
 sr_prefetch_ahead = os.environ.get('P3D_SR_PREFETCH_AHEAD', '1') != '0'      # the super-resolution heads' plans issued from inside the backbone's forward (superresolution.prefetch_ahead)
+_plan = PrefetchPlan.entries # id(layer) -> Entry of whichever device's plan; the layers test its truth before they ask take_plan
+_plans = {}                  # device -> its PrefetchPlan
+
+
+def plan_for(device):
+    if device not in _plans:
+        _plans[device] = PrefetchPlan(torch.cuda.Stream(device=device), torch.cuda.current_stream, torch.cuda.Event)
+    return _plans[device]
+
+
+def side_stream(device):
+    return plan_for(device).side
+
+
+def take_plan(layer):
+    """Pop this layer's prefetched Entry (styles, pre-modulated weights) and make the current stream wait for it (PrefetchPlan.take); the switches are read per call."""
+    return PrefetchPlan.take(layer, plan_wait_elision, plan_wait_latest)
+
+
+def plan_joined(stream):
+    """True when ``stream`` already waits behind everything on its device's prefetch stream (finish_prefetch then adds no further edge)."""
+    return plan_wait_elision and plan_for(stream.device).joined(stream)
 
 
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
@@ -78,7 +52,6 @@ _lib.register('p3d_modulate_weights', ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int
 _lib.register('p3d_conv2d_nhwc', ctypes.c_int, [_vp] * 3 + [ctypes.c_int] + [_vp] * 4 + [_i32] * 5 + [_i64, _i32, _i32, _i32, _f32, _f32, _vp])
 _lib.register('p3d_conv2d_nhwc_ws', ctypes.c_int, [_vp] * 3 + [ctypes.c_int] + [_vp] * 4 + [_i32] * 5 + [_i64, _i32, _i32, _i32, _f32, _f32, _vp, _i64, _vp])
 _lib.register('p3d_conv2d_nhwc_workspace', _i64, [ctypes.c_int] + [_i32] * 5 + [_i64, _i32, _i32])
-
 _lib.register('p3d_conv3x3_torgb_f16', ctypes.c_int, [_vp] * 8 + [_i32, _f32] + [_i32] * 5 + [ctypes.c_int64, _i32, _f32, _f32, _vp])
 _lib.register('p3d_conv3x3_torgb_split', ctypes.c_int, [_vp] * 11 + [_i32, _f32] + [_i32] * 5 + [ctypes.c_int64, _i32, _f32, _f32, _vp])
 _lib.register('p3d_conv2d_nhwc_scaled', ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp] + [_i32] * 5 + [ctypes.c_int64] + [_i32] * 3 + [_f32, _f32, _vp, ctypes.c_int64, _vp])
@@ -90,6 +63,13 @@ _lib.register('p3d_fir4_bias_act_nhwc', ctypes.c_int, [_vp, _vp, _vp, ctypes.c_i
 _lib.register('p3d_fc_forward', ctypes.c_int, [_vp] * 4 + [_i32] * 3 + [_i64, _f32, _f32, _i32, _f32, _f32, _f32, _vp])
 _lib.register('p3d_im2col3x3', ctypes.c_int, [_vp, _vp] + [_i32] * 6 + [_i64] * 4 + [_vp])
 _lib.register('p3d_noise_bias_act', ctypes.c_int, [_vp] * 5 + [_i32] * 4 + [_f32, _f32, _f32, _vp])
+_lib.register('p3d_torgb_nhwc_f16', ctypes.c_int, [_vp] * 5 + [_i32] * 4 + [_f32, _i32, _vp])
+_lib.register('p3d_conv2d_nhwc_bf16x3_io_plan', ctypes.c_int, [_i32] * 5 + [ctypes.c_int64, _i32, _i32, _i32, _i32, ctypes.POINTER(ctypes.c_int64)])
+_lib.register('p3d_conv2d_nhwc_bf16x3_io', ctypes.c_int, [_vp] * 7 + [_i32] * 5 + [ctypes.c_int64, _i32, _i32, _i32, _f32, _f32, _i32, _i32, _vp, ctypes.c_int64, _vp])
+_lib.register('p3d_torgb_wide_split', ctypes.c_int, [_vp] * 6 + [_i32] * 5 + [_f32, _vp])
+_lib.register('p3d_fir4_bias_act_nhwc_split', ctypes.c_int, [_vp] * 3 + [_i32] * 9 + [_f32, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _vp])
+_lib.register('p3d_demod_coefs_multi', ctypes.c_int, [ctypes.c_void_p, _i32, _i32, _vp])
+_lib.register('p3d_fc_multi', ctypes.c_int, [ctypes.c_void_p, _i32, _i32, _vp])
 
 min_pixels = 1               # every layer takes this module (the vendor conv library is never entered: its choices for the small
                              # layers — naive kernels on a fresh box — cost milliseconds)
@@ -107,11 +87,6 @@ def _zeros_page(device):
     if z is None:
         z = _zero_pages[device] = torch.zeros(256, dtype=torch.float32, device=device)
     return z
-_lib.register('p3d_torgb_nhwc_f16', ctypes.c_int, [_vp] * 5 + [_i32] * 4 + [_f32, _i32, _vp])
-_lib.register('p3d_conv2d_nhwc_bf16x3_io_plan', ctypes.c_int, [_i32] * 5 + [ctypes.c_int64, _i32, _i32, _i32, _i32, ctypes.POINTER(ctypes.c_int64)])
-_lib.register('p3d_conv2d_nhwc_bf16x3_io', ctypes.c_int, [_vp] * 7 + [_i32] * 5 + [ctypes.c_int64, _i32, _i32, _i32, _f32, _f32, _i32, _i32, _vp, ctypes.c_int64, _vp])
-_lib.register('p3d_torgb_wide_split', ctypes.c_int, [_vp] * 6 + [_i32] * 5 + [_f32, _vp])
-_lib.register('p3d_fir4_bias_act_nhwc_split', ctypes.c_int, [_vp] * 3 + [_i32] * 9 + [_f32, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _vp])
 
 
 def _is_nhwc(x, dtypes=(torch.float16, torch.float32)):
@@ -152,11 +127,7 @@ def layer_supported(x, weight, styles, noise_mode, fused_modconv, up):
 def torgb_supported(x, weight, styles, fused_modconv):
     if not enabled or not fused_modconv or tuple(weight.shape[2:]) != (1, 1) or not _dense_dev(x) or not _no_grad_needed(x, weight, styles):
         return False
-    if _is_nhwc_f16(x) and x.shape[1] in (64, 128, 256) and weight.shape[0] <= 32 and (x.shape[2] * x.shape[3]) % 4 == 0:
-        return True                                   # skinny streaming kernel
-    if is_small(x):
-        return True                                   # batched GEMM
-    return _is_nhwc(x) and x.shape[1] % (64 if x.dtype == torch.float16 else 32) == 0      # 1x1 through the MFMA kernel
+    return torgb_route(x.shape[1], weight.shape[0], x.shape[2] * x.shape[3], x.dtype, _is_nhwc(x)).kind is not None
 
 
 BF16X3 = 'bf16x3'            # dtype tag: fp32 tensors whose products run as three bf16 MFMAs of (hi, lo) splits (csrc/conv2d.hip)
@@ -208,20 +179,61 @@ def _raw(x):
     return x.t if isinstance(x, SplitActs) else x
 
 
+LayerRoute = collections.namedtuple('LayerRoute', 'kind split tag reads_split hands_split')
+RgbRoute = collections.namedtuple('RgbRoute', 'kind split tag pre_tag')
+
+
+def layer_route(n, ci, in_pixels, up, dtype, small=None):
+    """THE route decision of a modulated 3x3 layer with ``in_pixels`` input pixels per image, from sizes and switches alone; everything else asks here.
+    kind: 'gemm' (im2col + one batched library GEMM) / 'shared' (unmodulated weights shared by the batch, styles and demodulation as scales) / 'mfma' (per-image
+    weights); split: the products run as bf16x3; tag: what premodulate labels this route's product with and synthesis_layer accepts, (kind, up, dtype or BF16X3);
+    reads_split: its kernel reads SplitActs (the per-image bf16x3 routes do; the GEMM route, the shared-weight form — it scales x first — and the one-kernel fp32
+    x2 layer do not); hands_split: ... and can hand its result back as one (where the kernel that ends up producing it grants that).
+    ``small``: overrides the GEMM-size test (use_shared_weights: that question is asked of layers already known not to be GEMM-sized)."""
+    if (in_pixels <= (gemm_max_pixels if up == 1 else gemm_max_pixels_up)) if small is None else small:
+        return LayerRoute('gemm', False, ('gemm', up, dtype), False, False)
+    split = _bf16x3(dtype, in_pixels, ci)
+    # the low-resolution fp32 layers of a batch are bound by their weights: N modulated copies of a 9.4 MB tensor written and read back for a few KB of activations
+    kind = 'shared' if split and shared_weight_max_pixels > 0 and 1 < n <= 16 and in_pixels <= shared_weight_max_pixels else 'mfma'
+    one_kernel_x2 = up == 2 and fuse_up2 and fuse_up2_f32_min_res <= 1 << 20
+    return LayerRoute(kind, split, (kind, up, BF16X3 if split else dtype), bool(enabled and split and split_activations and kind == 'mfma' and not one_kernel_x2),
+                      bool(split and split_activations))
+
+
+def _rgb_tag(wtag):
+    return ('rgb', wtag)
+
+
+def torgb_route(ci, co, pixels, dtype, nhwc=True, fused=False):
+    """The route of a ToRGB layer (1x1, no demodulation), from sizes and switches alone.  ``fused``: the caller knows the block's conv1 takes it along (torgb_fuses).
+    kind: 'streaming' (skinny fp16 kernel, modulates in-kernel) / 'fused' (conv3x3_torgb) / 'gemm' / 'mfma' (1x1 through the MFMA kernel) / None: unsupported;
+    split: bf16x3 ('mfma' only); tag: ('rgb', dtype or BF16X3) of the modulated weights the route's consumer accepts from the plan, None: it takes none;
+    pre_tag: ... of what premodulate_torgb makes ahead for it, None: nothing."""
+    if fused:
+        return RgbRoute('fused', False, _rgb_tag(torch.float32), _rgb_tag(torch.float32))
+    if dtype == torch.float16 and nhwc and ci in (64, 128, 256) and co <= 32 and pixels % 4 == 0:
+        return RgbRoute('streaming', False, None, None)
+    split = _bf16x3(dtype, pixels, ci)
+    # (made ahead: bf16x3 K rows for the wide fp32 image, else plain fp32 — the form of the fused kernel, the one other reader of a plan's ToRGB weights; an fp16
+    # layer on the MFMA route and the GEMM route modulate in line, as they always have)
+    pre_tag = _rgb_tag(BF16X3 if split else torch.float32)
+    if pixels <= gemm_max_pixels:
+        return RgbRoute('gemm', False, None, pre_tag)
+    ok = nhwc and ci % (64 if dtype == torch.float16 else 32) == 0
+    return RgbRoute('mfma' if ok else None, split, _rgb_tag(BF16X3 if split else dtype), pre_tag)
+
+
 def accepts_split_input(n, ci, in_pixels, up):
-    """Will synthesis_layer / torgb run a layer with this input (per-image pixels, batch) on a kernel that reads SplitActs?  (The per-image bf16x3
-    routes do; the GEMM route of tiny images, the shared-weight form — it scales x first — and the one-kernel fp32 x2 layer do not.)"""
-    if not (enabled and split_bf16 and split_activations) or ci % 32 != 0 or in_pixels < split_bf16_min_pixels:
-        return False
-    if in_pixels <= (gemm_max_pixels if up == 1 else gemm_max_pixels_up):
-        return False
-    if shared_weight_max_pixels > 0 and 1 < n <= 16 and in_pixels <= shared_weight_max_pixels:
-        return False
-    return not (up == 2 and fuse_up2 and fuse_up2_f32_min_res <= 1 << 20)
+    """Will synthesis_layer run a (fp32) layer with this input (per-image pixels, batch) on a kernel that reads SplitActs?"""
+    return layer_route(n, ci, in_pixels, up, torch.float32).reads_split
+
+
+def _bf16x3(dtype, pixels, ci):
+    return split_bf16 and dtype == torch.float32 and pixels >= split_bf16_min_pixels and ci % 32 == 0
 
 
 def use_split_bf16(x, ci):
-    return split_bf16 and x.dtype == torch.float32 and x.shape[2] * x.shape[3] >= split_bf16_min_pixels and ci % 32 == 0
+    return _bf16x3(x.dtype, x.shape[2] * x.shape[3], ci)
 
 
 shared_weight_max_pixels = int(os.environ.get('P3D_SHARED_W_MAX_PIXELS', 1024))    # fp32 layers whose input has at most this many pixels per image (<= 32^2)
@@ -229,12 +241,9 @@ shared_weight_max_pixels = int(os.environ.get('P3D_SHARED_W_MAX_PIXELS', 1024)) 
 
 
 def use_shared_weights(x, weight, styles):
-    """The low-resolution fp32 layers of a batch are bound by their weights: N modulated copies of a 9.4 MB tensor are written and read back
-    for a few KB of activations.  The unfused form of the same function (networks_stylegan2.py:70-79: x * styles -> convolution with the
-    UNMODULATED weights -> * demodulation coefficients) reads one weight tensor for the whole batch, with the batch folded into the GEMM
-    rows; the scaling passes over the (tiny) activations instead."""
-    return (shared_weight_max_pixels > 0 and x.shape[0] > 1 and x.shape[0] <= 16 and x.dtype == torch.float32 and x.shape[2] * x.shape[3] <= shared_weight_max_pixels
-            and use_split_bf16(x, weight.shape[1]) and weight.shape[1] % 4 == 0 and tuple(weight.shape[2:]) == (3, 3))
+    """Does this (not GEMM-sized) layer take the shared-weight form?  The unfused form of the same function (networks_stylegan2.py:70-79: x * styles -> convolution with the
+    UNMODULATED weights -> * demodulation coefficients) reads one weight tensor for the whole batch, with the batch folded into the GEMM rows; the scaling passes over x instead."""
+    return tuple(weight.shape[2:]) == (3, 3) and layer_route(x.shape[0], weight.shape[1], x.shape[2] * x.shape[3], 1, x.dtype, small=False).kind == 'shared'
 
 
 def shared_split_weights(weight):
@@ -261,7 +270,6 @@ class _DemodJob(ctypes.Structure):
 
 
 DEMOD_MAX_JOBS = 24
-_lib.register('p3d_demod_coefs_multi', ctypes.c_int, [ctypes.c_void_p, _i32, _i32, _vp])
 
 
 def demod_coefs_many(pairs):
@@ -326,6 +334,32 @@ def _pad_channels(x, wmod, transposed=False):
 fuse_input_scale = os.environ.get('P3D_FUSE_INPUT_SCALE', '1') != '0'      # shared-weight layers: x * styles inside the convolution kernel (p3d_conv2d_nhwc_scaled_in); 0 = a pass of its own
 
 
+def _f32c(t):
+    return None if t is None else t.detach().float().contiguous()
+
+
+def _epilogue(bias, noise, noise_strength):
+    """(bias, noise image, noise strength [1]) as the contiguous fp32 tensors — or None — the kernels' epilogues read."""
+    return _f32c(bias), _f32c(noise), None if noise is None else noise_strength.detach().float().reshape(1).contiguous()
+
+
+def _conv_geometry(x, wmod, transposed, down):
+    """conv2d's sizes: (n, ci, h, w, co, k, oh, ow, per-image weight stride — 0: one set for the batch —, the kernels' mode code)."""
+    assert wmod.shape[2] in (1, 9) and down in (1, 2) and not (transposed and down == 2)
+    n, ci, h, w = x.shape
+    co, k = wmod.shape[1], (3 if wmod.shape[2] == 9 else 1)
+    oh, ow = (2 * h + 1, 2 * w + 1) if transposed else (((h - k) // 2 + 1, (w - k) // 2 + 1) if down == 2 else (h, w))
+    assert wmod.shape[0] in (1, n)
+    stride = 0 if wmod.shape[0] == 1 else wmod.shape[1] * wmod.shape[2] * wmod.shape[3]
+    return n, ci, h, w, co, k, oh, ow, stride, 1 if transposed else (2 if down == 2 else 0)
+
+
+def _log_flops(kind, flops):
+    log = _lib.kernel_events.get('conv_flops')
+    if log is not None:                                  # bench.py: FLOPs of the launches it is timing (2*Ci*Co*k*k per output / input pixel)
+        log.append((kind, flops))
+
+
 def conv2d(x, wmod, transposed=False, bias=None, noise=None, noise_strength=None, act=0, gain=1.0, clamp=-1.0, down=1, split=False, out_scale=None, out_split=False,
            in_scale=None):
     """x NHWC [N,Ci,H,W] (channels_last strides), wmod [N or 1][Co][k*k][Ci] of the same dtype -> NHWC, same dtype.
@@ -336,19 +370,11 @@ def conv2d(x, wmod, transposed=False, bias=None, noise=None, noise_strength=None
     if x_split or out_split:
         assert split and out_scale is None
         return _conv2d_split_io(x, wmod, transposed, bias, noise, noise_strength, act, gain, clamp, down, out_split)
-    assert _is_nhwc(x) and wmod.dtype == x.dtype and wmod.is_contiguous() and wmod.shape[2] in (1, 9)
-    assert down in (1, 2) and not (transposed and down == 2)
+    assert _is_nhwc(x) and wmod.dtype == x.dtype and wmod.is_contiguous()
     x, wmod = _pad_channels(x, wmod, transposed)
-    n, ci, h, w = x.shape
-    co, k = wmod.shape[1], (3 if wmod.shape[2] == 9 else 1)
-    oh, ow = (2 * h + 1, 2 * w + 1) if transposed else (((h - k) // 2 + 1, (w - k) // 2 + 1) if down == 2 else (h, w))
+    n, ci, h, w, co, k, oh, ow, stride, mode = _conv_geometry(x, wmod, transposed, down)
     y = torch.empty([n, co, oh, ow], dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    assert wmod.shape[0] in (1, n)
-    stride = 0 if wmod.shape[0] == 1 else wmod.shape[1] * wmod.shape[2] * wmod.shape[3]
-    b32 = None if bias is None else bias.detach().float().contiguous()
-    nz = None if noise is None else noise.detach().float().contiguous()
-    ns = None if noise is None else noise_strength.detach().float().reshape(1).contiguous()
-    mode = 1 if transposed else (2 if down == 2 else 0)
+    b32, nz, ns = _epilogue(bias, noise, noise_strength)
     code_dtype = DTYPE_F32_BF16X3 if split else _lib.DTYPE_CODE[x.dtype]          # split: wmod came from modulate_weights(dtype=BF16X3)
     x6 = f32_x6 and not split and x.dtype == torch.float32 and ci % 32 == 0
     if x6:
@@ -357,29 +383,21 @@ def conv2d(x, wmod, transposed=False, bias=None, noise=None, noise_strength=None
     nbytes = int(_lib.lib().p3d_conv2d_nhwc_workspace(code_dtype, n, h, w, ci, co, stride, k, mode))
     work = torch.empty([nbytes // 4], dtype=torch.float32, device=x.device) if nbytes > 0 else None          # split-K partial tiles (low-resolution layers)
     with _lib.kernel_timer('conv_bf16x3' if split else ('conv_f16' if x.dtype == torch.float16 else ('conv_bf16x6' if x6 else 'conv_f32')), x):
-        code = None
+        code, lib = None, _lib.lib()
+        args = (_lib.ptr(b32), _lib.ptr(nz), _lib.ptr(ns), _lib.ptr(_zeros_page(x.device)), n, h, w, ci, co, stride, k, mode, int(act), float(gain), float(clamp),
+                _lib.ptr(work), nbytes, _lib.stream_of(x))
         if in_scale is not None:                           # [N, Ci] fp32 on the activations as they enter the matrix cores (shared-weight form: the styles)
             assert out_scale is not None and split and tuple(in_scale.shape) == (n, ci) and in_scale.dtype == torch.float32 and in_scale.is_contiguous()
-            code = _lib.lib().p3d_conv2d_nhwc_scaled_in(_lib.ptr(x), _lib.ptr(wmod), _lib.ptr(y), code_dtype, _lib.ptr(in_scale), _lib.ptr(out_scale), _lib.ptr(b32), _lib.ptr(nz),
-                                                        _lib.ptr(ns), _lib.ptr(_zeros_page(x.device)), n, h, w, ci, co, stride, k, mode, int(act), float(gain), float(clamp),
-                                                        _lib.ptr(work), nbytes, _lib.stream_of(x))
+            code = lib.p3d_conv2d_nhwc_scaled_in(_lib.ptr(x), _lib.ptr(wmod), _lib.ptr(y), code_dtype, _lib.ptr(in_scale), _lib.ptr(out_scale), *args)
             if code == _lib.P3D_ERR_UNSUPPORTED:           # more scale rows per tile than the kernel's table holds: scale x in a pass of its own
                 x, code = scale_input(x, in_scale), None
-        if code is not None:
-            pass
-        elif out_scale is not None:                        # [N, Co] fp32 on the accumulator (shared-weight form: the demodulation coefficients)
+        if code is None and out_scale is not None:                        # [N, Co] fp32 on the accumulator (shared-weight form: the demodulation coefficients)
             assert out_scale.dtype == torch.float32 and out_scale.is_contiguous() and tuple(out_scale.shape) == (n, co) and x.dtype == torch.float32
-            code = _lib.lib().p3d_conv2d_nhwc_scaled(_lib.ptr(x), _lib.ptr(wmod), _lib.ptr(y), code_dtype, _lib.ptr(out_scale), _lib.ptr(b32), _lib.ptr(nz), _lib.ptr(ns),
-                                                     _lib.ptr(_zeros_page(x.device)), n, h, w, ci, co, stride, k, mode, int(act), float(gain), float(clamp),
-                                                     _lib.ptr(work), nbytes, _lib.stream_of(x))
-        else:
-            code = _lib.lib().p3d_conv2d_nhwc_ws(_lib.ptr(x), _lib.ptr(wmod), _lib.ptr(y), code_dtype, _lib.ptr(b32), _lib.ptr(nz), _lib.ptr(ns),
-                                                 _lib.ptr(_zeros_page(x.device)), n, h, w, ci, co, stride, k, mode, int(act), float(gain), float(clamp),
-                                                 _lib.ptr(work), nbytes, _lib.stream_of(x))
+            code = lib.p3d_conv2d_nhwc_scaled(_lib.ptr(x), _lib.ptr(wmod), _lib.ptr(y), code_dtype, _lib.ptr(out_scale), *args)
+        elif code is None:
+            code = lib.p3d_conv2d_nhwc_ws(_lib.ptr(x), _lib.ptr(wmod), _lib.ptr(y), code_dtype, *args)
     _lib.check(code, 'conv2d_nhwc')
-    log = _lib.kernel_events.get('conv_flops')
-    if log is not None:                                  # bench.py: FLOPs of the launches it is timing (2*Ci*Co*k*k per output / input pixel)
-        log.append(('bf16x3' if split else ('bf16x6' if x6 else str(x.dtype)), 2.0 * n * ci * co * k * k * (oh * ow if down == 2 else h * w)))
+    _log_flops('bf16x3' if split else ('bf16x6' if x6 else str(x.dtype)), 2.0 * n * ci * co * k * k * (oh * ow if down == 2 else h * w))
     return y
 
 
@@ -402,18 +420,10 @@ def _conv2d_split_io(x, wmod, transposed, bias, noise, noise_strength, act, gain
     """conv2d's bf16x3 form with the activations split on one or both sides (p3d_conv2d_nhwc_bf16x3_io)."""
     x_split = isinstance(x, SplitActs)
     xt = _raw(x)
-    assert _is_nhwc(xt, (torch.float32,)) and wmod.dtype == torch.float32 and wmod.is_contiguous() and wmod.shape[2] in (1, 9) and xt.shape[1] % 32 == 0
-    assert down in (1, 2) and not (transposed and down == 2)
-    n, ci, h, w = xt.shape
-    co, k = wmod.shape[1], (3 if wmod.shape[2] == 9 else 1)
-    oh, ow = (2 * h + 1, 2 * w + 1) if transposed else (((h - k) // 2 + 1, (w - k) // 2 + 1) if down == 2 else (h, w))
+    assert _is_nhwc(xt, (torch.float32,)) and wmod.dtype == torch.float32 and wmod.is_contiguous() and xt.shape[1] % 32 == 0 and wmod.shape[3] == xt.shape[1]
+    n, ci, h, w, co, k, oh, ow, stride, mode = _conv_geometry(xt, wmod, transposed, down)
     y = torch.empty([n, co, oh, ow], dtype=torch.float32, device=xt.device, memory_format=torch.channels_last)
-    assert wmod.shape[0] in (1, n) and wmod.shape[3] == ci
-    stride = 0 if wmod.shape[0] == 1 else wmod.shape[1] * wmod.shape[2] * wmod.shape[3]
-    b32 = None if bias is None else bias.detach().float().contiguous()
-    nz = None if noise is None else noise.detach().float().contiguous()
-    ns = None if noise is None else noise_strength.detach().float().reshape(1).contiguous()
-    mode = 1 if transposed else (2 if down == 2 else 0)
+    b32, nz, ns = _epilogue(bias, noise, noise_strength)
     y_split, nbytes = _split_io_plan(n, h, w, ci, co, stride, k, mode, int(x_split), int(bool(out_split) and co % 32 == 0 and k == 3 and mode == 0))
     work = torch.empty([nbytes // 4], dtype=torch.float32, device=xt.device) if nbytes > 0 else None          # scratch of the route that will run, if it has any
     with _lib.kernel_timer('conv_bf16x3', xt):
@@ -421,9 +431,7 @@ def _conv2d_split_io(x, wmod, transposed, bias, noise, noise_strength, act, gain
                                                     n, h, w, ci, co, stride, k, mode, int(act), float(gain), float(clamp), int(x_split), y_split,
                                                     _lib.ptr(work), nbytes, _lib.stream_of(xt))
     _lib.check(code, 'conv2d_nhwc_bf16x3_io')
-    log = _lib.kernel_events.get('conv_flops')
-    if log is not None:
-        log.append(('bf16x3', 2.0 * n * ci * co * k * k * (oh * ow if down == 2 else h * w)))
+    _log_flops('bf16x3', 2.0 * n * ci * co * k * k * (oh * ow if down == 2 else h * w))
     return SplitActs(y) if y_split else y
 
 
@@ -521,16 +529,12 @@ def plain_layer(x, weight, bias, weight_gain, resample_filter, down, padding, ac
     x = x.contiguous(memory_format=torch.channels_last)
     act_idx = {'linear': 0, 'lrelu': 1}[act]
     clampv = -1.0 if clamp is None else float(clamp)
-    if down == 1:
-        assert padding == k // 2
-        return conv2d(x, wmod, bias=bias, act=act_idx, gain=act_gain, clamp=clampv, split=split)
-    fw = resample_filter.shape[-1]
-    p0, p1 = padding + (fw - down + 1) // 2, padding + (fw - down) // 2
-    if k == 1:
-        x = upfirdn2d.upfirdn2d(x, resample_filter, down=down, padding=[p0, p1, p0, p1])
-        return conv2d(x, wmod, bias=bias, act=act_idx, gain=act_gain, clamp=clampv, split=split)
-    x = upfirdn2d.upfirdn2d(x, resample_filter, padding=[p0, p1, p0, p1])
-    return conv2d(x, wmod, bias=bias, act=act_idx, gain=act_gain, clamp=clampv, down=2, split=split)
+    assert down != 1 or padding == k // 2
+    if down != 1:
+        fw = resample_filter.shape[-1]
+        p0, p1 = padding + (fw - down + 1) // 2, padding + (fw - down) // 2
+        x = upfirdn2d.upfirdn2d(x, resample_filter, down=down if k == 1 else 1, padding=[p0, p1, p0, p1])
+    return conv2d(x, wmod, bias=bias, act=act_idx, gain=act_gain, clamp=clampv, down=1 if k == 1 else down, split=split)
 
 
 def fc_supported(x, weight, bias, activation):
@@ -554,7 +558,7 @@ def fc(x, weight, bias, weight_gain, bias_gain, activation='linear', out_scale=1
         w32 = weight.detach().contiguous()
     if x32.stride(1) != 1 or x32.stride(0) % 4 != 0 or x32.data_ptr() % 16 != 0:
         x32 = x32.contiguous()
-    b32 = None if bias is None else bias.detach().float().contiguous()
+    b32 = _f32c(bias)
     y = torch.empty([n, out_f], dtype=torch.float32, device=x.device)
     act_gain = bias_act.activation_funcs[activation].def_gain
     code = _lib.lib().p3d_fc_forward(_lib.ptr(x32), _lib.ptr(w32), _lib.ptr(b32), _lib.ptr(y), n, in_f, out_f, x32.stride(0) if n > 1 else in_f, float(weight_gain), float(bias_gain),
@@ -570,7 +574,6 @@ class _FcJob(ctypes.Structure):
 
 
 FC_MAX_JOBS = 40
-_lib.register('p3d_fc_multi', ctypes.c_int, [ctypes.c_void_p, _i32, _i32, _vp])
 
 
 def fc_multi(jobs):
@@ -610,9 +613,7 @@ def im2col3x3(x, pad=1, stride=1):
 def noise_bias_act(y, bias, noise, noise_strength, act, act_gain, clamp):
     """In place on a contiguous fp32 [N, C, H, W]: + noise * strength, + bias, activation, gain, clamp (networks_stylegan2.py:326-332)."""
     n, c, h, w = y.shape
-    b32 = None if bias is None else bias.detach().float().contiguous()
-    nz = None if noise is None else noise.detach().float().contiguous()
-    ns = None if noise is None else noise_strength.detach().float().reshape(1).contiguous()
+    b32, nz, ns = _epilogue(bias, noise, noise_strength)
     code = _lib.lib().p3d_noise_bias_act(_lib.ptr(y), _lib.ptr(y), _lib.ptr(nz), _lib.ptr(ns), _lib.ptr(b32), n, c, h * w, {'linear': 1, 'lrelu': 3}[act], 0.2,
                                          float(act_gain), -1.0 if clamp is None else float(clamp), _lib.stream_of(y))
     _lib.check(code, 'noise_bias_act')
@@ -639,72 +640,45 @@ def _small_layer(x, weight, styles, up, wm=None):
 
 def premodulate_many(items):
     """premodulate for a list of (weight, styles, up, in_pixels, dtype) — ``in_pixels`` None (a ToRGB layer) gives None — with the demodulation coefficients of
-    all the shared-weight layers among them computed by ONE launch.
+    all the shared-weight layers among them computed by ONE launch.  Yields (product, did asking for it launch anything?): a ToRGB layer launches nothing, the
+    shared-weight layers everything of all of them at the FIRST one (prefetch_styles gives the layers that launch nothing the event of the last one that did).
     A GENERATOR: each layer's product is launched when it is asked for, so that the caller can record the event a layer waits on right behind that layer's own
     work (the shared-weight coefficients — the low-resolution layers, which run first — are all issued at the first request)."""
-    shared = [k for k, (w, st, up, px, dt) in enumerate(items) if px is not None and _premod_route(w, st, up, px, dt) == 'shared']
+    routes = [None if px is None else layer_route(st.shape[0], w.shape[1], px, up, dt) for w, st, up, px, dt in items]
+    shared = [k for k, r in enumerate(routes) if r is not None and r.kind == 'shared']
     ds = dict(zip(shared, demod_coefs_many([(items[k][0], items[k][1]) for k in shared]))) if shared else {}
     for k in shared:
         shared_split_weights(items[k][0])                  # (warm the per-weight cache off the critical path; all of them HERE, so that a later shared layer launches nothing)
     for k, (w, st, up, px, dt) in enumerate(items):
-        if px is None:
-            yield None
+        if routes[k] is None:
+            yield None, False
         elif k in ds:
-            yield (ds[k], ('shared', up, BF16X3))
+            yield (ds[k], routes[k].tag), k == shared[0]
         else:
-            yield premodulate(w, st, up, px, dt)
+            yield premodulate(w, st, up, px, dt, routes[k]), True
 
 
-def premodulate_launches(items):
-    """For the list premodulate_many takes: does asking for item k launch anything?  (A ToRGB layer: nothing.  A shared-weight layer: everything of all of them
-    at the FIRST one.  Anything else: its own modulation.)  prefetch_styles gives the layers that launch nothing the event of the last one that did."""
-    out, first_shared = [], True
-    for w, st, up, px, dt in items:
-        if px is None:
-            out.append(False)
-        elif _premod_route(w, st, up, px, dt) == 'shared':
-            out.append(first_shared)
-            first_shared = False
-        else:
-            out.append(True)
-    return out
+def premodulate_torgb(weight, styles, pixels, dtype, fused=False):
+    """A ToRGB layer's modulated weights (no demodulation: networks_stylegan2.py:355-359) in the form and with the tag its route's consumer compares (torgb_route),
+    or None — nothing launched — where that route takes none (the streaming kernel modulates in-kernel): a 3-6 us launch per ToRGB layer that otherwise sits in
+    line in front of the layer (eleven per step)."""
+    tag = torgb_route(weight.shape[1], weight.shape[0], pixels, dtype, fused=fused).pre_tag
+    return None if tag is None else (modulate_weights(weight, styles, demodulate=False, dtype=tag[1]), tag)
 
 
-def _premod_route(weight, styles, up, in_pixels, dtype):
-    """'gemm' / 'shared' / 'mfma': which of premodulate's three products a layer gets."""
-    if in_pixels <= (gemm_max_pixels if up == 1 else gemm_max_pixels_up):
-        return 'gemm'
-    if split_bf16 and dtype == torch.float32 and in_pixels >= split_bf16_min_pixels and weight.shape[1] % 32 == 0:
-        if (shared_weight_max_pixels > 0 and 1 < styles.shape[0] <= 16 and in_pixels <= shared_weight_max_pixels and weight.shape[1] % 4 == 0
-                and tuple(weight.shape[2:]) == (3, 3)):
-            return 'shared'
-    return 'mfma'
-
-
-def premodulate_torgb(weight, styles, pixels, dtype):
-    """A ToRGB layer's modulated weights (no demodulation: networks_stylegan2.py:355-359) in the form the layer's route will ask for — bf16x3 K rows for the wide
-    fp32 image of a block with ``pixels`` pixels (torgb(), torgb_wide_skip), plain fp32 otherwise (the fused ToRGB of the fp16 heads) — with the tag the consumers
-    compare: a 3-6 us launch per ToRGB layer that otherwise sits in line in front of the layer (eleven per step)."""
-    ci = weight.shape[1]
-    split = split_bf16 and dtype == torch.float32 and pixels >= split_bf16_min_pixels and ci % 32 == 0
-    wtag = BF16X3 if split else torch.float32
-    return modulate_weights(weight, styles, demodulate=False, dtype=wtag), ('rgb', wtag)
-
-
-def premodulate(weight, styles, up, in_pixels, dtype):
+def premodulate(weight, styles, up, in_pixels, dtype, route=None):
     """The modulated weights synthesis_layer will want for a layer whose input has ``in_pixels`` pixels per image, in the layout of
     the route it will take; returns (tensor, route tag).  Used to run every layer's modulation ahead of the convolutions on a
     second stream (SynthesisNetwork.forward)."""
-    small = in_pixels <= (gemm_max_pixels if up == 1 else gemm_max_pixels_up)
-    if small:
-        return modulate_weights(weight, styles, demodulate=True, dtype=dtype, oihw=(up == 1)), ('gemm', up, dtype)
-    if split_bf16 and dtype == torch.float32 and in_pixels >= split_bf16_min_pixels and weight.shape[1] % 32 == 0:
-        if (shared_weight_max_pixels > 0 and 1 < styles.shape[0] <= 16 and in_pixels <= shared_weight_max_pixels and weight.shape[1] % 4 == 0
-                and tuple(weight.shape[2:]) == (3, 3)):
-            shared_split_weights(weight)                   # (warm the per-weight cache off the critical path)
-            return demod_coefs(weight, styles), ('shared', up, BF16X3)
-        return modulate_weights(weight, styles, demodulate=True, dtype=BF16X3), ('mfma', up, BF16X3)
-    return modulate_weights(weight, styles, demodulate=True, dtype=dtype), ('mfma', up, dtype)
+    route = route or layer_route(styles.shape[0], weight.shape[1], in_pixels, up, dtype)
+    if route.kind == 'shared':
+        shared_split_weights(weight)                       # (warm the per-weight cache off the critical path)
+        return demod_coefs(weight, styles), route.tag
+    return modulate_weights(weight, styles, demodulate=True, dtype=route.tag[2], oihw=(route.kind == 'gemm' and up == 1)), route.tag
+
+
+# The block's ToRGB for its last 3x3 layer, whose kernel adds clamp(ToRGB(y) + bias) into ``img``.  x_dead: the layer's activations have no other reader, not stored; pre: from the plan
+FusedRgb = collections.namedtuple('FusedRgb', 'weight styles bias clamp img x_dead pre', defaults=(False, None))
 
 
 def synthesis_layer(x, weight, styles, bias, up, resample_filter, noise_const=None, noise_strength=None, act='lrelu', act_gain=1.0, clamp=None, pre=None, rgb=None,
@@ -712,67 +686,54 @@ def synthesis_layer(x, weight, styles, bias, up, resample_filter, noise_const=No
     """Whole SynthesisLayer body after the style affine: modulated 3x3 conv (x2 up when ``up == 2``) + noise + bias + act.
     ``pre`` = (modulated weights, route tag) from ``premodulate`` — used when the tag matches the route taken here.
     x may be a SplitActs (bf16x3 inference); ``out_split`` asks for the result as one (granted where the producing kernel can)."""
-    small = is_small(x, up)
-    split = (not small) and use_split_bf16(x, weight.shape[1])
-    if isinstance(x, SplitActs) and not (split and accepts_split_input(x.shape[0], x.shape[1], x.shape[2] * x.shape[3], up)):
+    route = layer_route(x.shape[0], weight.shape[1], x.shape[2] * x.shape[3], up, x.dtype)
+    split, wtag = route.split, route.tag[2]
+    if isinstance(x, SplitActs) and not route.reads_split:
         x = x.dense()
-    out_split = bool(out_split) and split and split_activations and act in ('linear', 'lrelu')
-    wtag = BF16X3 if split else x.dtype
-    wpre = pre[0] if pre is not None and pre[1] == ('gemm' if small else 'mfma', up, wtag) else None
-    if small:
+    out_split = bool(out_split) and route.hands_split and act in ('linear', 'lrelu')
+    wpre = pre[0] if pre is not None and pre[1] == route.tag else None
+    def tensor_ops(y, fir, noise=True):                    # what no kernel's epilogue took: (4x4 low-pass with gain 4,) noise, bias + activation as passes of their own
+        if fir:
+            y = upfirdn2d.upfirdn2d(y, resample_filter, padding=[1, 1, 1, 1], gain=4)
+        if noise and noise_const is not None:
+            y = y.add_((noise_const * noise_strength).to(y.dtype))
+        return bias_act.bias_act(y, (None if bias is None else bias.to(y.dtype)), act=act, gain=act_gain, clamp=clamp)
+    if route.kind == 'gemm':
         y = _small_layer(x, weight, styles, up, wpre)
         if up == 2:
             y = upfirdn2d.upfirdn2d(y, resample_filter, padding=[1, 1, 1, 1], gain=4)
         if y.dtype == torch.float32 and act in ('linear', 'lrelu') and (y.shape[2] * y.shape[3]) % 4 == 0 and y.is_contiguous():
             return noise_bias_act(y, bias, noise_const, noise_strength, act, act_gain, clamp)
-        if noise_const is not None:
-            y = y.add_((noise_const * noise_strength).to(y.dtype))
-        return bias_act.bias_act(y, (None if bias is None else bias.to(y.dtype)), act=act, gain=act_gain, clamp=clamp)
+        return tensor_ops(y, False)
     act_idx = {'linear': 0, 'lrelu': 1}.get(act)
     clampv = -1.0 if clamp is None else float(clamp)
-    if split and use_shared_weights(x, weight, styles):
-        d = pre[0] if pre is not None and pre[1] == ('shared', up, BF16X3) else demod_coefs(weight, styles)
-        wsh = shared_split_weights(weight)
+    if route.kind == 'shared':                             # x * styles -> convolution with the unmodulated weights -> * demodulation coefficients
+        kw = dict(split=True, out_scale=wpre if wpre is not None else demod_coefs(weight, styles))
+        wmod = shared_split_weights(weight)
         if fuse_input_scale and x.shape[1] % 32 == 0:      # x * styles happens inside the convolution (bit-identical to the separate pass)
-            xs, isc = x, styles.detach().float().contiguous()
+            kw['in_scale'] = _f32c(styles)
         else:
-            xs, isc = scale_input(x, styles), None
-        if up == 1 and act_idx is not None:
-            return conv2d(xs, wsh, bias=bias, noise=noise_const, noise_strength=noise_strength, act=act_idx, gain=act_gain, clamp=clampv, split=True, out_scale=d, in_scale=isc)
-        if up == 1:
-            y = conv2d(xs, wsh, noise=noise_const, noise_strength=noise_strength, split=True, out_scale=d, in_scale=isc)
-            return bias_act.bias_act(y, (None if bias is None else bias.to(y.dtype)), act=act, gain=act_gain, clamp=clamp)
-        y = conv2d(xs, wsh, transposed=True, split=True, out_scale=d, in_scale=isc)
-        if act_idx is not None and tuple(resample_filter.shape) == (4, 4) and y.shape[1] % 32 == 0:
-            return fir4_bias_act(y, resample_filter, bias, noise_const, noise_strength, act, act_gain, clampv, out_split=out_split)
-        y = upfirdn2d.upfirdn2d(y, resample_filter, padding=[1, 1, 1, 1], gain=4)
-        if noise_const is not None:
-            y = y.add_((noise_const * noise_strength).to(y.dtype))
-        return bias_act.bias_act(y, (None if bias is None else bias.to(y.dtype)), act=act, gain=act_gain, clamp=clamp)
-    wmod = wpre if wpre is not None else modulate_weights(weight, styles, demodulate=True, dtype=wtag)
-    if rgb is not None:                                    # (rgb_weight, rgb_styles, rgb_bias, rgb_clamp, img[, x_dead]): checked by torgb_fusable
-        rgb_w, rgb_s, rgb_b, rgb_c, img = rgb[:5]
-        rgb_pre = rgb[6] if len(rgb) > 6 else None
-        rgb_wmod = rgb_pre[0] if rgb_pre is not None and rgb_pre[1] == ('rgb', torch.float32) else modulate_weights(rgb_w, rgb_s, demodulate=False, dtype=torch.float32)
-        return conv3x3_torgb(x, wmod, bias, act_idx, act_gain, clampv, rgb_wmod, rgb_b, rgb_c, img, store_y=not (len(rgb) > 5 and rgb[5]))
+            x = scale_input(x, styles)
+    else:
+        kw = dict(split=split)
+        wmod = wpre if wpre is not None else modulate_weights(weight, styles, demodulate=True, dtype=wtag)
+        if rgb is not None:                                # a FusedRgb: checked by torgb_fusable
+            rgb_wmod = rgb.pre[0] if rgb.pre is not None and rgb.pre[1] == _rgb_tag(torch.float32) else modulate_weights(rgb.weight, rgb.styles, demodulate=False, dtype=torch.float32)
+            return conv3x3_torgb(x, wmod, bias, act_idx, act_gain, clampv, rgb_wmod, rgb.bias, rgb.clamp, rgb.img, store_y=not rgb.x_dead)
     if up == 1 and act_idx is not None:
-        return conv2d(x, wmod, bias=bias, noise=noise_const, noise_strength=noise_strength, act=act_idx, gain=act_gain, clamp=clampv, split=split, out_split=out_split)
+        return conv2d(x, wmod, bias=bias, noise=noise_const, noise_strength=noise_strength, act=act_idx, gain=act_gain, clamp=clampv, out_split=out_split and route.kind == 'mfma', **kw)
     if up == 1:
-        y = conv2d(x, wmod, noise=noise_const, noise_strength=noise_strength, split=split)
-        return bias_act.bias_act(y, (None if bias is None else bias.to(y.dtype)), act=act, gain=act_gain, clamp=clamp)
-    if fuse_up2 and act_idx is not None and x.shape[1] % 32 == 0 and wmod.shape[1] % 32 == 0 and (
+        return tensor_ops(conv2d(x, wmod, noise=noise_const, noise_strength=noise_strength, **kw), False, noise=False)
+    if route.kind == 'mfma' and fuse_up2 and act_idx is not None and x.shape[1] % 32 == 0 and wmod.shape[1] % 32 == 0 and (
             x.dtype == torch.float16 or (split and min(x.shape[2], x.shape[3]) >= fuse_up2_f32_min_res)):
         taps = _separable_fir(resample_filter)
         if taps is not None:
             return up2_fir(x, wmod, taps, bias, noise_const, noise_strength, act_idx, act_gain, clampv)
     # x2: stride-2 transposed conv as four polyphase GEMMs, then the 4x4 low-pass with gain 4 (conv2d_resample.py:114-131)
-    y = conv2d(x, wmod, transposed=True, split=split)
+    y = conv2d(x, wmod, transposed=True, **kw)
     if act_idx is not None and tuple(resample_filter.shape) == (4, 4) and y.shape[1] % (64 if y.dtype == torch.float16 else 32) == 0:
         return fir4_bias_act(y, resample_filter, bias, noise_const, noise_strength, act, act_gain, clampv, out_split=out_split)     # FIR + noise + bias + act in one pass
-    y = upfirdn2d.upfirdn2d(y, resample_filter, padding=[1, 1, 1, 1], gain=4)
-    if noise_const is not None:
-        y = y.add_((noise_const * noise_strength).to(y.dtype))
-    return bias_act.bias_act(y, (None if bias is None else bias.to(y.dtype)), act=act, gain=act_gain, clamp=clamp)
+    return tensor_ops(y, True)
 
 
 def _separable_fir(f):
@@ -803,17 +764,13 @@ def up2_fir(x, wmod, taps, bias, noise, noise_strength, act, act_gain, clamp):
     assert wmod.shape[0] in (1, n) and wmod.shape[3] == ci
     y = torch.empty([n, co, 2 * h, 2 * w], dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     stride = 0 if wmod.shape[0] == 1 else co * 9 * ci
-    b32 = None if bias is None else bias.detach().float().contiguous()
-    nz = None if noise is None else noise.detach().float().contiguous()
-    ns = None if noise is None else noise_strength.detach().float().reshape(1).contiguous()
+    b32, nz, ns = _epilogue(bias, noise, noise_strength)
     with _lib.kernel_timer('conv_bf16x3' if split else 'conv_f16', x):
         fn = _lib.lib().p3d_up2_fir_bf16x3 if split else _lib.lib().p3d_up2_fir_f16
         code = fn(_lib.ptr(x), _lib.ptr(wmod), _lib.ptr(y), _lib.ptr(_zeros_page(x.device)), _lib.ptr(b32), _lib.ptr(nz), _lib.ptr(ns),
                   ctypes.cast(taps, ctypes.c_void_p), n, h, w, ci, co, stride, 1.0, int(act), float(act_gain), float(clamp), _lib.stream_of(x))
     _lib.check(code, 'up2_fir')
-    log = _lib.kernel_events.get('conv_flops')
-    if log is not None:
-        log.append(('bf16x3' if split else str(x.dtype), 2.0 * n * ci * co * 9 * h * w))
+    _log_flops('bf16x3' if split else str(x.dtype), 2.0 * n * ci * co * 9 * h * w)
     return y
 
 
@@ -821,20 +778,13 @@ def fir4_bias_act(y, f, bias, noise, noise_strength, act, act_gain, clamp, out_s
     """4x4 FIR (pad 1, gain 4) + noise + bias + activation on an NHWC tensor [N,C,2H+1,2W+1] -> [N,C,2H,2W] (``out_split``, fp32: a SplitActs)."""
     n, c, ih, iw = y.shape
     out = torch.empty([n, c, ih - 1, iw - 1], dtype=y.dtype, device=y.device, memory_format=torch.channels_last)
-    f32 = f.detach().float().contiguous()
-    b32 = None if bias is None else bias.detach().float().contiguous()
-    nz = None if noise is None else noise.detach().float().contiguous()
-    ns = None if noise is None else noise_strength.detach().float().reshape(1).contiguous()
+    f32 = _f32c(f)
+    b32, nz, ns = _epilogue(bias, noise, noise_strength)
+    args = (n, c, ih, iw, 1, 1, ih - 1, iw - 1, 0, 4.0, _lib.ptr(b32), _lib.ptr(nz), _lib.ptr(ns), {'linear': 1, 'lrelu': 3}[act], 0.2, float(act_gain), float(clamp), _lib.stream_of(y))
     if out_split and y.dtype == torch.float32 and c % 32 == 0:
-        code = _lib.lib().p3d_fir4_bias_act_nhwc_split(_lib.ptr(y), _lib.ptr(f32), _lib.ptr(out), n, c, ih, iw, 1, 1, ih - 1, iw - 1, 0, 4.0,
-                                                       _lib.ptr(b32), _lib.ptr(nz), _lib.ptr(ns), {'linear': 1, 'lrelu': 3}[act], 0.2, float(act_gain), float(clamp),
-                                                       _lib.stream_of(y))
-        _lib.check(code, 'fir4_bias_act_nhwc_split')
+        _lib.check(_lib.lib().p3d_fir4_bias_act_nhwc_split(_lib.ptr(y), _lib.ptr(f32), _lib.ptr(out), *args), 'fir4_bias_act_nhwc_split')
         return SplitActs(out)
-    code = _lib.lib().p3d_fir4_bias_act_nhwc(_lib.ptr(y), _lib.ptr(f32), _lib.ptr(out), _lib.DTYPE_CODE[y.dtype], n, c, ih, iw, 1, 1, ih - 1, iw - 1, 0, 4.0,
-                                             _lib.ptr(b32), _lib.ptr(nz), _lib.ptr(ns), {'linear': 1, 'lrelu': 3}[act], 0.2, float(act_gain), float(clamp),
-                                             _lib.stream_of(y))
-    _lib.check(code, 'fir4_bias_act_nhwc')
+    _lib.check(_lib.lib().p3d_fir4_bias_act_nhwc(_lib.ptr(y), _lib.ptr(f32), _lib.ptr(out), _lib.DTYPE_CODE[y.dtype], *args), 'fir4_bias_act_nhwc')
     return out
 
 
@@ -843,15 +793,21 @@ fuse_torgb_256 = os.environ.get('P3D_FUSE_TORGB_256', '1') != '0'      # ... and
 fuse_torgb = os.environ.get('P3D_FUSE_TORGB', '1') != '0'      # SynthesisBlock.conv1 + ToRGB + skip-image sum in one launch where the kernel allows (Co = 128, fp16)
 
 
+def torgb_fuses(n, ci, co, rgb_co, h, w, dtype, up, noise, act):
+    """The sizes-and-switches part of torgb_fusable (prefetch_styles asks it ahead of the layer: torgb_route's ``fused``).  co = 128: one channel block per
+    work-group; 256 (fuse_torgb_256): each work-group walks both blocks of its patch."""
+    return bool(fuse_torgb and enabled and up == 1 and not noise and act in ('linear', 'lrelu') and dtype == torch.float16
+                and n * ((h + 15) // 16) * ((w + 15) // 16) >= 192          # (fewer 16 x 16 patches do not fill the chip: the dispatcher would take the split-K kernel)
+                and co in ((128, 256) if fuse_torgb_256 else (128,)) and ci % 64 == 0 and h >= 32 and w >= 32 and rgb_co <= 8)
+
+
 def torgb_fusable(x, conv_weight, rgb_weight, img, up, noise_const, act):
     """Can the block's last 3x3 layer also produce its ToRGB contribution (csrc/conv2d.hip: p3d_conv3x3_torgb_f16)?  x is that layer's INPUT."""
-    if not (fuse_torgb and enabled and up == 1 and noise_const is None and act in ('linear', 'lrelu') and img is not None and _is_nhwc_f16(x)):
+    if img is None or not _is_nhwc_f16(x):
         return False
     n, ci, h, w = x.shape
-    if n * ((h + 15) // 16) * ((w + 15) // 16) < 192:         # too few 16 x 16 patches to fill the chip: the dispatcher would take the split-K kernel
-        return False
-    co = conv_weight.shape[0]                                  # 128: one channel block per work-group; 256 (fuse_torgb_256): each work-group walks both blocks of its patch
-    return (co in ((128, 256) if fuse_torgb_256 else (128,)) and tuple(conv_weight.shape[2:]) == (3, 3) and ci % 64 == 0 and h >= 32 and w >= 32 and rgb_weight.shape[0] <= 8
+    co = conv_weight.shape[0]
+    return (torgb_fuses(n, ci, co, rgb_weight.shape[0], h, w, x.dtype, up, noise_const is not None, act) and tuple(conv_weight.shape[2:]) == (3, 3)
             and tuple(rgb_weight.shape[1:]) == (co, 1, 1) and img.dtype == torch.float32 and img.is_contiguous() and tuple(img.shape) == (n, rgb_weight.shape[0], h, w)
             and not img.requires_grad and _no_grad_needed(x, conv_weight, rgb_weight))
 
@@ -864,8 +820,7 @@ def conv3x3_torgb(x, wmod, bias, act, gain, clamp, rgb_wmod, rgb_bias, rgb_clamp
     co = wmod.shape[1]
     y = torch.empty([n, co, h, w], dtype=x.dtype, device=x.device, memory_format=torch.channels_last) if store_y else None
     stride = 0 if wmod.shape[0] == 1 else co * 9 * ci
-    b32 = None if bias is None else bias.detach().float().contiguous()
-    rb32 = None if rgb_bias is None else rgb_bias.detach().float().contiguous()
+    b32, rb32 = _f32c(bias), _f32c(rgb_bias)
     rw = rgb_wmod.reshape(n, -1, co)
     assert rw.dtype == torch.float32 and rw.is_contiguous() and wmod.dtype == torch.float16 and wmod.is_contiguous()
     with _lib.kernel_timer('conv_f16', x):
@@ -875,9 +830,7 @@ def conv3x3_torgb(x, wmod, bias, act, gain, clamp, rgb_wmod, rgb_bias, rgb_clamp
     _lib.check(code, 'conv3x3_torgb_f16')
     global fused_torgb_calls
     fused_torgb_calls += 1
-    log = _lib.kernel_events.get('conv_flops')
-    if log is not None:
-        log.append((str(x.dtype), 2.0 * n * ci * co * 9 * h * w))
+    _log_flops(str(x.dtype), 2.0 * n * ci * co * 9 * h * w)
     return y
 
 
@@ -900,9 +853,7 @@ def torgb_wide_skip_supported(x, weight, prev, f):
     co = weight.shape[0]
     if ci not in (128, 256) or co not in (32, 64, 96) or w % 32 != 0:
         return False
-    if prev is None:
-        return True
-    return (f is not None and tuple(f.shape) == (4, 4) and prev.dtype == torch.float32 and tuple(prev.shape) == (n, co, h // 2, w // 2) and h % 2 == 0
+    return prev is None or (f is not None and tuple(f.shape) == (4, 4) and prev.dtype == torch.float32 and tuple(prev.shape) == (n, co, h // 2, w // 2) and h % 2 == 0
             and prev.is_cuda and prev.is_contiguous(memory_format=torch.channels_last) and not prev.requires_grad)
 
 
@@ -910,17 +861,15 @@ def torgb_wide_skip(x, weight, styles, bias, clamp, prev, f, pre=None):
     """ToRGB of a SplitActs (wide image: the backbone's tri-planes) + the block's skip-image sum ``upsample2d(prev, f) + y`` in one launch -> fp32 NHWC."""
     n, ci, h, w = x.shape
     co = weight.shape[0]
-    wmod = pre[0] if pre is not None and pre[1] == ('rgb', BF16X3) else modulate_weights(weight, styles, demodulate=False, dtype=BF16X3)
+    wmod = pre[0] if pre is not None and pre[1] == _rgb_tag(BF16X3) else modulate_weights(weight, styles, demodulate=False, dtype=BF16X3)
     y = torch.empty([n, co, h, w], dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    b32 = None if bias is None else bias.detach().float().contiguous()
+    b32 = _f32c(bias)
     fh = None if prev is None else _filter_host(f)
     with _lib.kernel_timer('conv_bf16x3', x.t):
         code = _lib.lib().p3d_torgb_wide_split(_lib.ptr(x.t), _lib.ptr(wmod), _lib.ptr(b32), _lib.ptr(y), _lib.ptr(prev), None if fh is None else ctypes.cast(fh, ctypes.c_void_p),
                                                n, h, w, ci, co, -1.0 if clamp is None else float(clamp), _lib.stream_of(x.t))
     _lib.check(code, 'torgb_wide_split')
-    log = _lib.kernel_events.get('conv_flops')
-    if log is not None:
-        log.append(('bf16x3', 2.0 * n * ci * co * h * w))
+    _log_flops('bf16x3', 2.0 * n * ci * co * h * w)
     return y
 
 
@@ -938,11 +887,9 @@ def conv3x3_torgb_wide_supported(x, conv_weight, rgb_weight, prev, f, up, act):
     n, ci, h, w = x.shape
     co, rco = conv_weight.shape[0], rgb_weight.shape[0]
     if (co != 128 or tuple(conv_weight.shape[1:]) != (ci, 3, 3) or tuple(rgb_weight.shape[1:]) != (co, 1, 1) or rco not in (32, 64, 96) or ci % 32 != 0 or h < 32 or w < 32
-            or (h | w) & 1 or n * ((h + 15) // 16) * ((w + 15) // 16) < 192 or use_shared_weights(x.t, conv_weight, None) or not use_split_bf16(x.t, ci)):
+            or (h | w) & 1 or n * ((h + 15) // 16) * ((w + 15) // 16) < 192 or not layer_route(n, ci, h * w, 1, torch.float32).reads_split):
         return False
-    if prev is None:
-        return True
-    return (f is not None and tuple(f.shape) == (4, 4) and prev.dtype == torch.float32 and tuple(prev.shape) == (n, rco, h // 2, w // 2)
+    return prev is None or (f is not None and tuple(f.shape) == (4, 4) and prev.dtype == torch.float32 and tuple(prev.shape) == (n, rco, h // 2, w // 2)
             and prev.is_cuda and prev.is_contiguous(memory_format=torch.channels_last) and not prev.requires_grad)
 
 
@@ -955,10 +902,7 @@ def conv3x3_torgb_wide(x, wmod, bias, noise, noise_strength, act, gain, clamp, r
     assert rgb_wmod.dtype == torch.float32 and rgb_wmod.is_contiguous() and tuple(rgb_wmod.shape) == (n, rco, 1, co)
     img = torch.empty([n, rco, h, w], dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     stride = 0 if wmod.shape[0] == 1 else co * 9 * ci
-    b32 = None if bias is None else bias.detach().float().contiguous()
-    rb32 = None if rgb_bias is None else rgb_bias.detach().float().contiguous()
-    nz = None if noise is None else noise.detach().float().contiguous()
-    ns = None if noise is None else noise_strength.detach().float().reshape(1).contiguous()
+    (b32, nz, ns), rb32 = _epilogue(bias, noise, noise_strength), _f32c(rgb_bias)
     fh = None if prev is None else _filter_host(f)
     with _lib.kernel_timer('conv_bf16x3', x.t):
         code = _lib.lib().p3d_conv3x3_torgb_split(_lib.ptr(x.t), _lib.ptr(wmod), _lib.ptr(b32), _lib.ptr(nz), _lib.ptr(ns), _lib.ptr(_zeros_page(x.device)), _lib.ptr(rgb_wmod),
@@ -967,16 +911,14 @@ def conv3x3_torgb_wide(x, wmod, bias, noise, noise_strength, act, gain, clamp, r
     _lib.check(code, 'conv3x3_torgb_split')
     global conv_wide_torgb_calls
     conv_wide_torgb_calls += 1
-    log = _lib.kernel_events.get('conv_flops')
-    if log is not None:
-        log.append(('bf16x3', 2.0 * n * ci * co * 9 * h * w + 2.0 * n * co * rco * h * w))
+    _log_flops('bf16x3', 2.0 * n * ci * co * 9 * h * w + 2.0 * n * co * rco * h * w)
     return img
 
 
 def torgb_accumulates(x, weight, out):
     """True when torgb(..., out=out) adds into ``out`` inside its own kernel (the fp16 streaming route) rather than with a separate add."""
     n, ci, h, w = x.shape
-    return (_is_nhwc_f16(x) and ci in (64, 128, 256) and weight.shape[0] <= 32 and (h * w) % 4 == 0 and out.dtype == torch.float32 and out.is_contiguous()
+    return (torgb_route(ci, weight.shape[0], h * w, x.dtype, _is_nhwc(x)).kind == 'streaming' and out.dtype == torch.float32 and out.is_contiguous()
             and tuple(out.shape) == (n, weight.shape[0], h, w) and not out.requires_grad)
 
 
@@ -986,22 +928,19 @@ def torgb(x, weight, styles, bias, clamp=None, out=None, pre=None):
     tri-plane image of the backbone) go through the MFMA kernel as a 1x1 conv and stay channels-last."""
     n, ci, h, w = x.shape
     co = weight.shape[0]
-    if isinstance(x, SplitActs) and not (not is_small(x) and use_split_bf16(x, ci)):
+    route = torgb_route(ci, co, h * w, x.dtype, _is_nhwc(x))
+    if isinstance(x, SplitActs) and not route.split:
         x = x.dense()
-    if is_small(x) and not (_is_nhwc_f16(x) and ci in (64, 128, 256) and co <= 32 and (h * w) % 4 == 0):
+    if route.kind == 'gemm':
         wm = modulate_weights(weight, styles, demodulate=False, dtype=x.dtype).reshape(n, co, ci)
         y = torch.bmm(wm, x.contiguous().reshape(n, ci, h * w)).reshape(n, co, h, w)
         y = bias_act.bias_act(y, None if bias is None else bias.to(y.dtype), clamp=clamp)
         return y if out is None else out.add_(y)
-    if not (x.dtype == torch.float16 and ci in (64, 128, 256) and co <= 32 and (h * w) % 4 == 0):
-        split = use_split_bf16(x, ci)                      # the wide fp32 ToRGB (96 tri-plane channels) as bf16x3 too: as exact-fp32 MFMA it ran at a
-        wtag = BF16X3 if split else x.dtype                # third of that pipe's peak, 0.29 ms per step
-        wmod = pre[0] if pre is not None and pre[1] == ('rgb', wtag) else modulate_weights(weight, styles, demodulate=False, dtype=wtag)
-        y = conv2d(x, wmod, bias=bias, clamp=-1.0 if clamp is None else float(clamp), split=split)
+    if route.kind != 'streaming':                          # the wide fp32 ToRGB (96 tri-plane channels) as bf16x3 too: as exact-fp32 MFMA it ran at a third of that pipe's peak, 0.29 ms per step
+        wmod = pre[0] if pre is not None and pre[1] == route.tag else modulate_weights(weight, styles, demodulate=False, dtype=route.tag[1])
+        y = conv2d(x, wmod, bias=bias, clamp=-1.0 if clamp is None else float(clamp), split=route.split)
         return y if out is None else out.add_(y)
-    w32 = weight.detach().float().reshape(co, ci).contiguous()
-    s32 = styles.detach().float().contiguous()
-    b32 = None if bias is None else bias.detach().float().contiguous()
+    w32, s32, b32 = weight.detach().float().reshape(co, ci).contiguous(), _f32c(styles), _f32c(bias)
     acc = out is not None
     y = out if acc else torch.empty([n, co, h, w], dtype=torch.float32, device=x.device)
     assert y.is_contiguous() and y.dtype == torch.float32

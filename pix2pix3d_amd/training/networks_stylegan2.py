@@ -280,11 +280,11 @@ class SynthesisLayer(torch.nn.Module):
             if fused_modconv is True and noise_mode != 'random' and x.is_cuda and \
                     modconv.conv3x3_torgb_wide_supported(x, self.weight, torgb.weight, prev, f, self.up, self.activation):
                 planned = modconv.take_plan(self) if modconv._plan else None
-                styles, pre = planned if planned is not None else (self.affine(w), None)
-                wmod = pre[0] if pre is not None and pre[1] == ('mfma', 1, modconv.BF16X3) else modconv.modulate_weights(self.weight, styles, demodulate=True, dtype=modconv.BF16X3)
+                styles, pre = (planned.styles, planned.pre) if planned is not None else (self.affine(w), None)
+                wmod = pre[0] if pre is not None and pre[1] == modconv.layer_route(x.shape[0], self.in_channels, in_res * in_res, 1, torch.float32).tag else modconv.modulate_weights(self.weight, styles, demodulate=True, dtype=modconv.BF16X3)
                 planned_rgb = modconv.take_plan(torgb) if modconv._plan else None
-                s_rgb, pre_rgb = planned_rgb if planned_rgb is not None else (torgb.affine(w_rgb, out_scale=torgb.weight_gain), None)
-                rgb_wmod = pre_rgb[0] if pre_rgb is not None and pre_rgb[1] == ('rgb', modconv.BF16X3) else \
+                s_rgb, pre_rgb = (planned_rgb.styles, planned_rgb.pre) if planned_rgb is not None else (torgb.affine(w_rgb, out_scale=torgb.weight_gain), None)
+                rgb_wmod = pre_rgb[0] if pre_rgb is not None and pre_rgb[1] == modconv.torgb_route(torgb.in_channels, torgb.out_channels, in_res * in_res, torch.float32).tag else \
                     modconv.modulate_weights(torgb.weight, s_rgb, demodulate=False, dtype=modconv.BF16X3)
                 const_noise = self.use_noise and noise_mode == 'const'
                 img = modconv.conv3x3_torgb_wide(x, wmod, self.bias, self.noise_const if const_noise else None, self.noise_strength if const_noise else None,
@@ -295,7 +295,7 @@ class SynthesisLayer(torch.nn.Module):
         if isinstance(x, modconv.SplitActs) and (rgb is not None or not modconv.layer_supported(x, self.weight, None, noise_mode, fused_modconv, self.up)):
             x = x.dense()
         planned = modconv.take_plan(self) if modconv._plan else None
-        styles, pre = planned if planned is not None else (self.affine(w), None)
+        styles, pre = (planned.styles, planned.pre) if planned is not None else (self.affine(w), None)
         noise = None
         if self.use_noise and noise_mode == 'random':
             noise = torch.randn([x.shape[0], 1, self.resolution, self.resolution], device=x.device) * self.noise_strength
@@ -319,9 +319,9 @@ class SynthesisLayer(torch.nn.Module):
                 torgb, w_rgb, img = rgb[:3]
                 if modconv.torgb_fusable(x, self.weight, torgb.weight, img, self.up, self.noise_const if const_noise else None, self.activation):
                     planned_rgb = modconv.take_plan(torgb) if modconv._plan else None
-                    s_rgb = planned_rgb[0] if planned_rgb is not None else torgb.affine(w_rgb, out_scale=torgb.weight_gain)
-                    fused_rgb = (torgb.weight, s_rgb, torgb.bias, torgb.conv_clamp, img, len(rgb) > 3 and bool(rgb[3]),      # [5]: x has no other reader
-                                 planned_rgb[1] if planned_rgb is not None else None)                                        # [6]: its weights, modulated ahead
+                    s_rgb = planned_rgb.styles if planned_rgb is not None else torgb.affine(w_rgb, out_scale=torgb.weight_gain)
+                    fused_rgb = modconv.FusedRgb(torgb.weight, s_rgb, torgb.bias, torgb.conv_clamp, img, x_dead=len(rgb) > 3 and bool(rgb[3]),
+                                                 pre=planned_rgb.pre if planned_rgb is not None else None)
             y = modconv.synthesis_layer(x, self.weight, styles, self.bias, self.up, self.resample_filter,
                                         noise_const=self.noise_const if const_noise else None,
                                         noise_strength=self.noise_strength if const_noise else None,
@@ -356,10 +356,10 @@ class ToRGBLayer(torch.nn.Module):
         """``accumulate_into`` (device inference): an fp32 image the native kernel may add its result to in place — the skip-image sum of
         SynthesisBlock without a separate launch.  The return value is then that image; callers check identity."""
         planned = modconv.take_plan(self) if modconv._plan else None
-        styles = planned[0] if planned is not None else self.affine(w, out_scale=self.weight_gain)
+        styles = planned.styles if planned is not None else self.affine(w, out_scale=self.weight_gain)
         if modconv.torgb_supported(x, self.weight, styles, fused_modconv):
             out = accumulate_into if accumulate_into is not None and modconv.torgb_accumulates(x, self.weight, accumulate_into) else None
-            return modconv.torgb(x, self.weight, styles, self.bias, clamp=self.conv_clamp, out=out, pre=planned[1] if planned is not None else None)      # fp32 NCHW, bias + clamp fused
+            return modconv.torgb(x, self.weight, styles, self.bias, clamp=self.conv_clamp, out=out, pre=planned.pre if planned is not None else None)      # fp32 NCHW, bias + clamp fused
         if isinstance(x, modconv.SplitActs):
             x = x.dense()
         x = modulated_conv2d(x=x, weight=self.weight, styles=styles, demodulate=False, fused_modconv=fused_modconv)
@@ -500,9 +500,9 @@ class SynthesisBlock(torch.nn.Module):
             if fused_modconv is True and modconv.torgb_wide_skip_supported(x, self.torgb.weight, img, self.resample_filter):
                 # split activations in: ToRGB and the skip-image sum in ONE pass over the image (csrc/torgb_split.hip)
                 planned = modconv.take_plan(self.torgb) if modconv._plan else None
-                s_rgb = planned[0] if planned is not None else self.torgb.affine(per_layer[self.num_conv], out_scale=self.torgb.weight_gain)
+                s_rgb = planned.styles if planned is not None else self.torgb.affine(per_layer[self.num_conv], out_scale=self.torgb.weight_gain)
                 img = modconv.torgb_wide_skip(x, self.torgb.weight, s_rgb, self.torgb.bias, self.torgb.conv_clamp, img, self.resample_filter,
-                                              pre=planned[1] if planned is not None else None)
+                                              pre=planned.pre if planned is not None else None)
                 return x, img
             y = self.torgb(x, per_layer[self.num_conv], fused_modconv=fused_modconv)
             if y.dtype == torch.float32 and y.is_contiguous(memory_format=torch.channels_last):
@@ -586,18 +586,19 @@ def prefetch_styles(blocks, block_ws, block_kwargs, ahead=False):
     a layer waits for its entry's event (modconv.take_plan).  Anything the plan gets wrong (a layer that ends up on another route) is
     simply recomputed.  Returns the plan's keys when a plan was made — the caller joins the side stream and drops them afterwards (finish_prefetch) — else None.
     ``ahead``: issued for a network that runs LATER in the step (the super-resolution heads, from inside the backbone's forward right after its own plan,
-    ``modconv.after_prefetch``): the side stream is already ordered behind whatever made ``ws`` and nothing of the earlier plan has been released yet, so
+    ``PrefetchPlan.defer``): the side stream is already ordered behind whatever made ``ws`` and nothing of the earlier plan has been released yet, so
     it neither waits for the calling stream again nor touches other networks' entries."""
     ws0 = block_ws[0]
     fused = block_kwargs.get('fused_modconv')
     own = [id(l) for b in blocks for l in (getattr(b, 'conv0', None), b.conv1, getattr(b, 'torgb', None)) if l is not None]
-    for k in own:
-        modconv._plan.pop(k, None)    # entries an interrupted forward left behind must never reach a layer of this one
+    if modconv._plan:
+        modconv.PrefetchPlan.drop(own)    # entries an interrupted forward left behind must never reach a layer of this one
     if not (modconv.prefetch_styles and modconv.enabled and native_channels_last and ws0.is_cuda and not torch.is_grad_enabled()
             and (fused is None or fused is True)):
         return None
     force_fp32 = bool(block_kwargs.get('force_fp32', False))
-    main, side = torch.cuda.current_stream(), modconv.side_stream(ws0.device)
+    plan = modconv.plan_for(ws0.device)
+    main, side = torch.cuda.current_stream(), plan.side
     if not ahead:
         side.wait_stream(main)
     keys = []
@@ -613,8 +614,11 @@ def prefetch_styles(blocks, block_ws, block_kwargs, ahead=False):
             for layer, in_res in layers:
                 todo.append((layer, next(ws_iter), 1, in_res * in_res, dtype))
             if block.is_last or block.architecture == 'skip':
-                # (its modulated weights too — ('rgb', pixels) — where the layer would otherwise launch that modulation in line; premodulate_torgb)
-                todo.append((block.torgb, next(ws_iter), block.torgb.weight_gain, ('rgb', res * res) if modconv.premodulate_rgb else None, dtype))
+                # (its modulated weights too — ('rgb', pixels, fused into conv1?) — where something would otherwise launch that modulation in line; premodulate_torgb)
+                rgb_fused = (block.in_channels != 0 and block.architecture == 'skip' and block.img_channels <= 8 and block_kwargs.get('noise_mode', 'random') != 'random'
+                         and modconv.torgb_fuses(ws0.shape[0], block.conv1.in_channels, block.conv1.out_channels, block.img_channels, res, res, dtype, block.conv1.up,
+                                                 block.conv1.use_noise and block_kwargs.get('noise_mode') == 'const', block.conv1.activation))
+                todo.append((block.torgb, next(ws_iter), block.torgb.weight_gain, ('rgb', res * res, rgb_fused) if modconv.premodulate_rgb else None, dtype))
         # every style affine of the network in one launch (they are ~6 us of launch latency each on their own)
         batched = (0 < len(todo) <= modconv.FC_MAX_JOBS and len({t[1].shape[0] for t in todo}) == 1 and all(t[1].shape[1] % 4 == 0 for t in todo)   # (fc_multi takes whole float4 rows; fc() pads)
                    and all(modconv.fc_supported(w, l.affine.weight, l.affine.bias, l.affine.activation) for l, w, *_ in todo))
@@ -623,56 +627,26 @@ def prefetch_styles(blocks, block_ws, block_kwargs, ahead=False):
         # (ToRGB entries carry ('rgb', pixels): premodulate_many itself launches nothing for them — their modulations are issued together, below)
         items = [(layer.weight, styles, getattr(layer, 'up', 1), None if isinstance(in_pixels, tuple) else in_pixels, dtype) for (layer, _, _, in_pixels, dtype), styles in zip(todo, all_styles)]
         pres = modconv.premodulate_many(items)
-        # one event per layer that LAUNCHED something; a layer that did not (a shared-weight layer after the first) shares the event of the last one that did, and
-        # take_plan skips a position its stream already waits behind — every wait is an edge between two branches of the captured graph.  Positions number the side
-        # stream's events for the life of the process (one side stream per device: a later position implies every earlier one).
-        # Right behind the FIRST layer's event: every ToRGB layer's weight modulation (3-6 us each, eleven per step, otherwise in line in front of their layers) and
-        # one event for all of them — the network's first layer does not stand behind them, its first ToRGB (tens of microseconds later) waits for that one event,
-        # and from there on a wait is for everything issued (modconv.take_plan).
-        ev, ev_seq = None, -1
-        rgb_entry = {}
-        for k, ((layer, _, _, in_pixels, dtype), styles, pre, fresh) in enumerate(zip(todo, all_styles, pres, modconv.premodulate_launches(items))):
-            if fresh or ev is None:
-                first = ev is None
-                ev = torch.cuda.Event()
-                ev.record(side)
-                modconv._plan_seq[0] += 1
-                ev_seq = modconv._plan_seq[0]
-                modconv._plan_latest[:] = [ev, ev_seq]
-                if first and not ahead:
-                    modconv._plan_own_until[0] = modconv._plan_seq[0]
+        # one event per layer that LAUNCHED something; a layer that did not (a shared-weight layer after the first) shares the event of the last one that did
+        # (PrefetchPlan.take skips a position its stream already waits behind).  Right behind the FIRST layer's event: every ToRGB layer's weight modulation (3-6 us
+        # each, eleven per step, otherwise in line in front of their layers) and one event for all that launched one — the network's first layer does not stand
+        # behind them, its first ToRGB (tens of microseconds later) waits for that one event, and from there on a wait is for everything issued.
+        mark, rgb_pre = None, {}
+        for k, ((layer, _, _, in_pixels, dtype), styles, (pre, fresh)) in enumerate(zip(todo, all_styles, pres)):
+            if fresh or mark is None:
+                first = mark is None
+                mark = plan.issue(own=first and not ahead)
                 if first:
-                    rgb = [j for j, t in enumerate(todo) if isinstance(t[3], tuple)]
-                    if rgb:
-                        rgb_pre = [modconv.premodulate_torgb(todo[j][0].weight, all_styles[j], todo[j][3][1], todo[j][4]) for j in rgb]
-                        ev_rgb = torch.cuda.Event()
-                        ev_rgb.record(side)
-                        modconv._plan_seq[0] += 1
-                        modconv._plan_latest[:] = [ev_rgb, modconv._plan_seq[0]]
-                        if not ahead:
-                            modconv._plan_own_until[0] = modconv._plan_seq[0]
-                        rgb_entry = {j: (p, ev_rgb, modconv._plan_seq[0]) for j, p in zip(rgb, rgb_pre)}
-            if k in rgb_entry:
-                modconv._plan[id(layer)] = (styles,) + rgb_entry[k]
-            else:
-                modconv._plan[id(layer)] = (styles, pre, ev, ev_seq)
-            keys.append(id(layer))
+                    rgb_pre = {j: modconv.premodulate_torgb(t[0].weight, all_styles[j], t[3][1], t[4], fused=t[3][2]) for j, t in enumerate(todo) if isinstance(t[3], tuple)}
+                    rgb_mark = plan.issue(own=not ahead) if any(p is not None for p in rgb_pre.values()) else mark
+            keys.append(plan.add(layer, styles, rgb_pre[k], rgb_mark) if k in rgb_pre else plan.add(layer, styles, pre, mark))
     if not ahead:
-        hooks, modconv.after_prefetch[:] = list(modconv.after_prefetch), []
-        for hook in hooks:             # (networks later in the step: their plans follow this one on the side stream, before any of its tensors is released)
-            hook()
+        plan.run_deferred()            # (networks later in the step: their plans follow this one on the side stream, before any of its tensors is released)
     return keys
 
 
-def finish_prefetch(device, keys=None):
-    main = torch.cuda.current_stream()
-    if not modconv.plan_joined(main):                      # (a stream that already waits behind the prefetch stream's newest event IS joined: no further edge)
-        main.wait_stream(modconv.side_stream(device))
-    if keys is None:
-        modconv._plan.clear()
-    else:
-        for k in keys:
-            modconv._plan.pop(k, None)
+def finish_prefetch(device, keys):
+    modconv.plan_for(device).finish(keys, modconv.plan_wait_elision)
 
 
 @persistence.persistent_class

@@ -45,21 +45,18 @@ class _SuperresolutionBase(torch.nn.Module):
         row = ws[:, -1:, :].expand(-1, 3, -1)
         keys = prefetch_styles([self.block0, self.block1], [row, row], block_kwargs, ahead=True)
         if keys is not None:
-            modconv._ahead[id(self)] = (ws, keys)
+            modconv.plan_for(ws.device).hand_over(self, ws, keys)
 
     def forward(self, rgb, x, ws, **block_kwargs):
         from ..torch_utils.ops import modconv
-        ahead = modconv._ahead.pop(id(self), None)
-        if ahead is not None and ahead[0] is not ws:             # planned for another latent tensor: not ours
-            for k in ahead[1]:
-                modconv._plan.pop(k, None)
-            ahead = None
+        plan = modconv._plans.get(ws.device) if modconv._plans else None
+        ahead = plan.claim(self, ws) if plan is not None else None      # (a plan for another latent tensor is not ours: dropped)
         if ws.is_cuda and not torch.is_grad_enabled():
             ws = ws[:, -1:, :].expand(-1, 3, -1)                  # device inference: the three layers read the SAME row in place (a stride-0 view; repeat() is three launches per head)
         else:
             ws = ws[:, -1:, :].repeat(1, 3, 1)
         rgb, x = self._prep(rgb, x)
-        planned = ahead[1] if ahead is not None else prefetch_styles([self.block0, self.block1], [ws, ws], block_kwargs)
+        planned = ahead if ahead is not None else prefetch_styles([self.block0, self.block1], [ws, ws], block_kwargs)
         try:
             x, rgb = self.block0(x, rgb, ws, **block_kwargs)
             # block1's x is returned to nobody (:297-354 of the reference return rgb only): unless somebody hooked the block to look at it, its last

@@ -125,13 +125,15 @@ class _TriPlaneCore(torch.nn.Module):
             self.neural_rendering_resolution = neural_rendering_resolution
         ray_o, ray_d = self.ray_sampler(cam2world, intrinsics, neural_rendering_resolution)
         n = ray_o.shape[0]
-        if heads and modconv.sr_prefetch_ahead and ws.is_cuda and not torch.is_grad_enabled():
+        plan = modconv.plan_for(ws.device) if heads and modconv.sr_prefetch_ahead and ws.is_cuda and not torch.is_grad_enabled() else None
+        if plan is not None:
             sr_kw = self._sr_kwargs(synthesis_kwargs)
-            modconv.after_prefetch.append(lambda: [h.prefetch_ahead(ws, **sr_kw) for h in heads if hasattr(h, 'prefetch_ahead')])
+            plan.defer(lambda: [h.prefetch_ahead(ws, **sr_kw) for h in heads if hasattr(h, 'prefetch_ahead')])
         try:
             planes = self._planes(ws, update_emas, synthesis_kwargs, cache_backbone, use_cached_backbone)
         finally:
-            modconv.after_prefetch.clear()                         # (a backbone that made no plan never ran it)
+            if plan is not None:
+                plan.run_deferred(run=False)                       # (a backbone that made no plan never ran it)
         feat, depth, _ = self.renderer(planes, self.decoder, ray_o, ray_d, self.rendering_kwargs)
         r = self.neural_rendering_resolution
         if feat.is_cuda and not torch.is_grad_enabled():
