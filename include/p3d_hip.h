@@ -125,6 +125,7 @@ int p3d_filtered_lrelu_act(void* x, uint8_t* s, int dtype, const int32_t x_size[
  * with the OSG decoders (training/triplane.py:112-135 one net; training/triplane_cond.py:926-970
  * two nets, density from the second) evaluated on the f32 MFMA path.  Random numbers are inputs
  * (the host draws them exactly where the reference would: renderer.py:190, :237).            */
+#define P3D_RENDER_SHARED_PLANES 2
 typedef struct p3d_render_desc {
     int32_t n_img;                        /* N                                                  */
     int32_t rays_per_img;                 /* M (ignored by p3d_sample_points)                   */
@@ -142,7 +143,9 @@ typedef struct p3d_render_desc {
      * channels-last backbone output [N][H][W][96] is (image H*W*96, plane 32, pixel 96).                 */
     int64_t image_stride, plane_stride, pixel_stride;
     int32_t raster_order;                 /* != 0: ray m of an image is pixel (m / R, m % R) of an R x R raster (R*R = rays_per_img):
-                                             lets the kernel assign 16 x 16 pixel blocks to workgroups for L2 locality  */
+                                             lets the kernel assign 16 x 16 pixel blocks to workgroups for L2 locality.
+                                             Bit 1 (P3D_RENDER_SHARED_PLANES; p3d_render_forward / _dual / _debug only): the plane tensor holds ONE
+                                             image that all n_img ray sets read (many cameras of one latent) — the strides describe that one image  */
     int32_t mlp_bf16x3;                   /* p3d_render_forward only, != 0: the decoder stream comes from p3d_pack_decoder_bf16x3 and the MLPs run
                                              as three bf16 MFMAs per fp32 product (hi/lo splits, fp32 accumulation: ~5e-6 of the hidden range per
                                              layer) instead of f32-input MFMAs at 1/16 of that rate.  0 = exact fp32 (p3d_pack_decoder).
@@ -607,6 +610,34 @@ int p3d_ray_sample(const float* cam2world, const float* intrinsics, float* origi
 /* The same straight from the 25-float camera labels the generators take (training/triplane.py:57-60: c[:, :16] is cam2world, c[:, 16:25] the
  * intrinsics): labels [n_cam][label_stride] fp32, label_stride >= 25 floats between rows — no contiguous copies of the two slices.       */
 int p3d_ray_sample_labels(const float* labels, int64_t label_stride, float* origins, float* dirs, int32_t n_cam, int32_t resolution, p3d_stream_t stream);
+
+/* Displayable uint8 frames from the float outputs of a chunk of views, in ONE launch (csrc/frame_ops.hip) — the host-side finishing of the reference's
+ * scripts: (clip(x, -1, 1) + 1) * 127.5 -> uint8 (applications/generate_video.py:65, 81-82; generate_samples.py:116-120) and
+ * color_mask(argmax(semantic)) (generate_video.py:67; training/utils.py:5-15).  jobs_host is a HOST array of at most P3D_FRAME_MAX_JOBS jobs whose
+ * contents travel in the kernel arguments (no device allocation; graph-capturable), so image + label map (+ depth) of a chunk are one launch.
+ *
+ * Per job: src is fp32 [n][c][h][w] addressed by the four ELEMENT strides src_stride = (n, c, y, x) — planar, channels-last or any view of either.
+ * dst is uint8 with dst_bpp (1 or 3) bytes per pixel: pixel (i, y, x) of the job lands at dst + i * dst_frame_pitch + (y0 + y) * dst_row_pitch
+ * + (x0 + x) * dst_bpp (pitches in BYTES), so a chunk can be written into a slice of [F][H][W][3], one half of a side-by-side video or a tile of a
+ * canvas; bytes outside the rectangle are not touched.  The rectangle must lie inside its pitches.
+ *   mode P3D_FRAME_SCALE (c = 1 or 3, dst_bpp = c): u8 = (uint8)clamp((x - lo) * scale, 0, 255), fp32, difference and product rounded separately,
+ *     truncation toward zero, NaN -> 0; the caller passes scale = 255 / (hi - lo) rounded once (lo = -1, scale = 127.5 for images).
+ *   mode P3D_FRAME_LABEL (2 <= c <= 64, dst_bpp = 3): k = argmax over the channels by torch.argmax's CPU rules (the first maximal channel wins a
+ *     tie; a NaN counts as the maximum, the first NaN wins); dst gets palette[k] (uint8 [c][3]: `palette` by value, or palette_dev on the device
+ *     when non-null) and, when dst_index is non-null, k itself goes as one byte per pixel to dst_index (same origin, its own pitches).            */
+#define P3D_FRAME_MAX_JOBS 4
+#define P3D_FRAME_SCALE 0
+#define P3D_FRAME_LABEL 1
+typedef struct p3d_frame_job {
+    const float* src; int64_t src_stride[4];
+    uint8_t* dst; int64_t dst_row_pitch, dst_frame_pitch;
+    uint8_t* dst_index; int64_t index_row_pitch, index_frame_pitch;
+    const uint8_t* palette_dev;
+    int32_t mode, n, c, h, w, x0, y0, dst_bpp;
+    float lo, scale;
+    uint8_t palette[192];
+} p3d_frame_job;
+int p3d_frame_finish(const p3d_frame_job* jobs_host, int32_t n_jobs, p3d_stream_t stream);
 
 #ifdef __cplusplus
 }

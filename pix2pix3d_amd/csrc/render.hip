@@ -327,6 +327,9 @@ static int render_forward_impl(const float* planes_cl, const float* planes_sem_c
     a.t_start = t_start; a.t_end = t_end; a.feat = feat; a.depth = depth; a.wsum = wsum;
     a.dbg_fine = dbg_fine; a.dbg_wcoarse = dbg_wcoarse; a.dbg_bins = dbg_bins; a.minmax = minmax_ws;
     a.total_rays = (int)total; a.rays_per_img = d->rays_per_img;
+    if (d->raster_order & P3D_RENDER_SHARED_PLANES) {      // one plane set for all n_img ray sets: a zero image stride, and the buffer bound is that one set's
+        a.planes_total_bytes = a.img_bytes; a.img_bytes = 0; a.img_stride = 0;
+    }
     { int r = 1; while (r * r < d->rays_per_img) ++r; a.res = (r * r == d->rays_per_img && d->raster_order) ? r : 0; }
     hipStream_t s = (hipStream_t)stream;
     // a block is one-per-CU (LDS): small launches take fewer waves per block so that every CU still gets one

@@ -114,6 +114,17 @@ class _TriPlaneCore(torch.nn.Module):
             self._last_planes = planes
         return planes.view(len(planes), 3, 32, planes.shape[-2], planes.shape[-1])
 
+    @frozen_pass
+    def backbone_planes(self, ws, update_emas=False, **synthesis_kwargs):
+        """The backbone's output for ``ws`` — what ``cache_backbone`` keeps in ``_last_planes`` — as a value (``views.render_views`` renders many cameras from it)."""
+        return self.backbone.synthesis(ws, update_emas=update_emas, **synthesis_kwargs)
+
+    def _shared_ws(self, ws, c, use_cached_backbone):
+        """Cached planes of batch 1 with B cameras (one latent, B views): the super-resolution heads take the one latent B times."""
+        if use_cached_backbone and self._last_planes is not None and len(self._last_planes) == 1 and len(ws) == 1 and len(c) > 1:
+            return ws.expand(len(c), -1, -1).contiguous()
+        return ws
+
     def _render(self, ws, c, neural_rendering_resolution, update_emas, cache_backbone, use_cached_backbone, synthesis_kwargs, heads=()):
         """Planes -> fused ray-marcher.  ``heads``: the super-resolution modules the caller runs on the result with THIS ``ws`` — on the device their style affines
         and weight modulations are issued by the backbone's forward right behind its own (``prefetch_ahead``), under the backbone's launch-bound first layers."""
@@ -180,6 +191,7 @@ class TriPlaneGenerator(_TriPlaneCore):
 
     @frozen_pass
     def synthesis(self, ws, c, neural_rendering_resolution=None, update_emas=False, cache_backbone=False, use_cached_backbone=False, **synthesis_kwargs):
+        ws = self._shared_ws(ws, c, use_cached_backbone)
         feature_image, depth_image = self._render(ws, c, neural_rendering_resolution, update_emas, cache_backbone, use_cached_backbone, synthesis_kwargs)
         rgb_image = feature_image[:, :3]
         sr_image = self.superresolution(rgb_image, feature_image, ws, **self._sr_kwargs(synthesis_kwargs))

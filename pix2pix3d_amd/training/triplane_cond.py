@@ -436,6 +436,7 @@ class TriPlaneGenerator(_TriPlaneBase):
 
     @frozen_pass
     def synthesis(self, ws, c, neural_rendering_resolution=None, update_emas=False, cache_backbone=False, use_cached_backbone=False, **synthesis_kwargs):
+        ws = self._shared_ws(ws, c, use_cached_backbone)
         feature_image, depth_image = self._render(ws, c, neural_rendering_resolution, update_emas, cache_backbone, use_cached_backbone, synthesis_kwargs, heads=(self.superresolution,))
         rgb_image = feature_image[:, :3]
         sr_image = self.superresolution(rgb_image, feature_image, ws, **self._sr_kwargs(synthesis_kwargs))
@@ -461,6 +462,7 @@ class TriPlaneSemanticEntangleGenerator(_TriPlaneBase):
 
     @frozen_pass
     def synthesis(self, ws, c, neural_rendering_resolution=None, update_emas=False, cache_backbone=False, use_cached_backbone=False, **synthesis_kwargs):
+        ws = self._shared_ws(ws, c, use_cached_backbone)
         feature_image, depth_image = self._render(ws, c, neural_rendering_resolution, update_emas, cache_backbone, use_cached_backbone, synthesis_kwargs,
                                                   heads=(self.superresolution, self.superresolution_semantic))
         half = feature_image.shape[1] // 2
@@ -563,6 +565,7 @@ class TriPlaneSemanticEntangleGenerator_withBG(TriPlaneSemanticEntangleGenerator
 
     @frozen_pass
     def synthesis(self, ws, c, neural_rendering_resolution=None, update_emas=False, cache_backbone=False, use_cached_backbone=False, **synthesis_kwargs):
+        ws = self._shared_ws(ws, c, use_cached_backbone)
         cam2world, intrinsics = c[:, :16].view(-1, 4, 4), c[:, 16:25].view(-1, 3, 3)
         if neural_rendering_resolution is None:
             neural_rendering_resolution = self.neural_rendering_resolution

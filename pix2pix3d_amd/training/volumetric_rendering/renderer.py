@@ -167,6 +167,16 @@ def pack_decoder(decoder_info, device, bf16x3):
     return packed, ws
 
 
+def shared_planes(n_planes, n_rays, who):
+    """One plane set for every camera?  Planes of batch 1 serve ray batches of any size (a video: one latent, B views per launch); equal batches are the
+    ordinary case; anything else is an error on every route, before any launch."""
+    if n_planes == n_rays:
+        return False
+    if n_planes != 1:
+        raise ValueError(f'{who}: planes of batch {n_planes} cannot serve rays of batch {n_rays} (the batches must be equal, or the planes of batch 1)')
+    return True
+
+
 class _FusedContext:
     """Device-side operands shared by the fused entry points: channels-last planes + packed decoder."""
 
@@ -194,8 +204,8 @@ class _FusedContext:
             self.packed, self._keep = pack_decoder(decoder_info, planes.device, self.bf16x3)
         self.n_nets, self.sem_sigmoid, self.n, self.h, self.w = len(nets), sem_sigmoid, n, h, w
 
-    def desc(self, options, rays_per_img=1, start=0.0, end=0.0, raster=False):
-        return _RenderDesc(self.n, rays_per_img, self.h, self.w, self.n_nets, int(self.sem_sigmoid),
+    def desc(self, options, rays_per_img=1, start=0.0, end=0.0, raster=False, n_img=None):
+        return _RenderDesc(self.n if n_img is None else n_img, rays_per_img, self.h, self.w, self.n_nets, int(self.sem_sigmoid),
                            int(options.get('depth_resolution', 0)), int(options.get('depth_resolution_importance', 0)),
                            int(bool(options.get('disparity_space_sampling', False))), int(bool(options.get('white_back', False))),
                            float(start), float(end), float(options['box_warp']), *self.strides, int(raster), int(self.bf16x3))
@@ -238,11 +248,16 @@ class ImportanceRenderer(torch.nn.Module):
         needs_grad = torch.is_grad_enabled() and (planes.requires_grad or ray_origins.requires_grad or ray_directions.requires_grad
                                                   or any(p.requires_grad for p in decoder.parameters()))
         reason = self._fused_reason(planes, decoder, rendering_options, needs_grad)
+        if planes.ndim == 5 and shared_planes(planes.shape[0], ray_origins.shape[0], type(self).__name__) and (reason is not None or needs_grad):
+            # shared planes outside the graph-less fused launch (which reads the one set in place): broadcast, as if they had been repeated
+            planes = planes.expand(ray_origins.shape[0], -1, -1, -1, -1)
         if reason is None:
             out = self._forward_fused(planes, decoder, ray_origins, ray_directions, rendering_options, needs_grad)
             if out is not None:
                 return out
             reason = 'sample counts outside the fused kernel envelope (<= 64 coarse, 1..64 fine)'
+            if planes.shape[0] != ray_origins.shape[0]:
+                planes = planes.expand(ray_origins.shape[0], -1, -1, -1, -1)
         self._tensor_op_guard(planes, reason)
         return self._forward_tensor_ops(planes, decoder, ray_origins, ray_directions, rendering_options)
 
@@ -478,6 +493,9 @@ class ImportanceSemanticRenderer(ImportanceRenderer):
         opt = rendering_options
         needs_grad = torch.is_grad_enabled() and (planes_texture.requires_grad or planes_semantic.requires_grad or ray_origins.requires_grad
                                                   or any(p.requires_grad for d in (decoder_texture, decoder_semantic) for p in d.parameters()))
+        for pl in (planes_texture, planes_semantic):
+            if pl.shape[0] != ray_origins.shape[0]:                  # (no shared-plane form of the two-plane-set kernel)
+                raise ValueError(f'{type(self).__name__}: planes of batch {pl.shape[0]} cannot serve rays of batch {ray_origins.shape[0]}')
         ops = self._dual_operands(planes_texture, planes_semantic, decoder_texture, decoder_semantic, opt, needs_grad)
         sc, sf = int(opt['depth_resolution']), int(opt['depth_resolution_importance'])
         if not isinstance(ops, str) and not (4 <= sc <= 64 and 1 <= sf <= 64):
@@ -777,12 +795,15 @@ def fused_render_backward(planes, decoder, ray_origins, ray_directions, opt, u_c
 
 def fused_render(planes, decoder, ray_origins, ray_directions, opt, u_coarse, u_fine, t_start=None, t_end=None, debug=False, exact_fp32=False, packed=None):
     """One launch of the fused ray-marcher with explicit uniforms (u_coarse [N,M,Sc(,1)], u_fine [N*M,Sf]).
+    ``planes`` of batch 1 with N > 1 ray sets is the SHARED-PLANE launch (P3D_RENDER_SHARED_PLANES): all N ray sets read the one plane set — a zero image
+    stride — with the schedule and the launch-wide depth clamp of a batch of N, exactly as if the planes had been repeated N times, without the copies.
     Returns (feat [N,M,C], depth [N,M,1], wsum [N,M,1]) and, with debug, the sorted fine depths [N*M,Sf] and the
     coarse weights [N*M,Sc-1] the kernel used; with debug='bins' also the searchsorted index of every draw [N*M,Sf] (int32, draw order)."""
     info = _decoder_nets(decoder)
     if info is None:
         raise RuntimeError(f'fused_render: unsupported decoder {type(decoder).__name__}')
     n, m, _ = ray_origins.shape
+    shared = shared_planes(planes.shape[0], n, 'fused_render')
     sc, sf = int(opt['depth_resolution']), int(opt['depth_resolution_importance'])
     dev = planes.device
     from pix2pix3d_amd.torch_utils.ops import modconv
@@ -800,8 +821,8 @@ def fused_render(planes, decoder, ray_origins, ray_directions, opt, u_coarse, u_
     dbg_f = torch.empty([n * m, sf], device=dev, dtype=torch.float32) if debug else None
     dbg_w = torch.empty([n * m, sc - 1], device=dev, dtype=torch.float32) if debug else None
     dbg_b = torch.empty([n * m, sf], device=dev, dtype=torch.int32) if debug == 'bins' else None
-    # raster=True is a pure scheduling hint (which wave takes which ray); results never depend on it
-    d = ctx.desc(opt, rays_per_img=m, start=0.0 if auto else opt['ray_start'], end=0.0 if auto else opt['ray_end'], raster=True)
+    # raster=True is a pure scheduling hint; P3D_RENDER_SHARED_PLANES (2): the N ray sets all read the one plane set, each keeping its own R x R raster
+    d = ctx.desc(opt, rays_per_img=m, start=0.0 if auto else opt['ray_start'], end=0.0 if auto else opt['ray_end'], raster=3 if shared else True, n_img=n)
     with _lib.kernel_timer('render_forward', feat):
         if dbg_b is not None:
             code = _lib.lib().p3d_render_forward_debug(_lib.ptr(ctx.planes_cl), _lib.ptr(ctx.packed), _lib.ptr(ro), _lib.ptr(rd), _lib.ptr(uc), _lib.ptr(uf),
