@@ -9,6 +9,7 @@
 * ``write_ply`` (trimesh's export), ``save_gif`` (imageio.mimsave, through PIL), ``vertex_labels`` (:196-218).
 * ``extract_mesh``: shape.extract_geometry, the labels and the turntable in one call.
 """
+import ctypes
 import math
 from typing import NamedTuple
 
@@ -23,6 +24,15 @@ MAX_SIZE = 2048                # largest image edge the kernels take
 _GUARD = 4096 * 256            # guard band, sub-pixel units
 _KEY_BG = torch.iinfo(torch.int64).max
 _SCRIPT_PI = 3.14              # the script's turntable writes pi as 3.14 (extract_mesh.py:245-251)
+
+_vp, _i32, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float              # csrc/mesh_raster.hip
+_lib.register('p3d_mesh_project', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp])
+_lib.register('p3d_mesh_raster_tiles', ctypes.c_int32, [_i32, _i32])
+_lib.register('p3d_mesh_raster_count', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp])
+_lib.register('p3d_mesh_raster_bin', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp])
+_lib.register('p3d_mesh_raster', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp])
+_lib.register('p3d_mesh_shade', ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _i32,
+                                           _vp, _vp])
 
 
 class Orthographic(NamedTuple):

@@ -14,7 +14,7 @@ The script's three steps and what stands in for each here:
 The per-vertex colour step (:198-215) needs nothing new: ``G.sample_mixed(vertices[None], None, ws, noise_mode='const')['rgb']``
 already runs on the point kernel.
 """
-import warnings
+import ctypes
 
 import torch
 
@@ -23,7 +23,6 @@ from .training.triplane import _TriPlaneCore, frozen_pass
 from .training.volumetric_rendering import renderer as _rmod
 
 BLOCK_RESOLUTION = 64          # the script's block edge (extract_mesh.py:60)
-_warned = set()
 
 
 def _axis(resolution, bound):
@@ -32,30 +31,16 @@ def _axis(resolution, bound):
 
 
 def _lattice_reason(G, ws):
-    """None when sigma_grid can take the lattice kernel, else why not."""
-    if _rmod.fused_policy == 'never':
-        return 'fused_policy == never'
-    if not ws.is_cuda:
-        return 'CPU tensors'
-    if not isinstance(G, _TriPlaneCore) or type(G).sample_mixed is not _TriPlaneCore.sample_mixed:
-        return f'{type(G).__name__} samples through a sample_mixed of its own'
-    if type(G.renderer) is not _rmod.ImportanceRenderer:
-        return f'renderer {type(G.renderer).__name__} is not an ImportanceRenderer'
-    if G.rendering_kwargs.get('density_noise', 0) > 0:
-        return 'density_noise > 0'
-    if _rmod._decoder_nets(G.decoder) is None:
-        return f'decoder {type(G.decoder).__name__} is not an OSG 32-64-33 decoder'
-    return None
+    """None when sigma_grid can take the lattice kernel, else why not: the renderer's own conditions (``renderer.fallback_reason``) and, between them, the
+    two that make ``G.sample_mixed`` something other than ``ImportanceRenderer.run_model`` on G's planes."""
+    own = [(not isinstance(G, _TriPlaneCore) or type(G).sample_mixed is not _TriPlaneCore.sample_mixed, f'{type(G).__name__} samples through a sample_mixed of its own'),
+           (type(G.renderer) is not _rmod.ImportanceRenderer, f'renderer {type(G.renderer).__name__} is not an ImportanceRenderer')]
+    return _rmod.fallback_reason(_rmod.fused_policy, ws.is_cuda, G.rendering_kwargs, (G.decoder,), clamp_mode=False, own=own)
 
 
 def _fallback_guard(ws, reason):
-    if not ws.is_cuda or _rmod.fused_policy == 'never':
-        return
-    if _rmod.fused_policy == 'require':
-        raise RuntimeError(f'sigma_grid: density lattice kernel required but unavailable: {reason}')
-    if reason not in _warned:
-        _warned.add(reason)
-        warnings.warn(f'sigma_grid: device tensors on the block loop of G.sample_mixed, not the lattice kernel: {reason}', RuntimeWarning, stacklevel=3)
+    _rmod._tensor_op_guard('sigma_grid', ws.is_cuda, reason, required='density lattice kernel required but unavailable',
+                           instead='the block loop of G.sample_mixed, not the lattice kernel')
 
 
 def _sigma_blocks(G, ws, axis, synthesis_kwargs):
@@ -102,6 +87,11 @@ def sigma_grid(G, ws, resolution=512, bound=None, **synthesis_kwargs):
 
 
 # ---- marching cubes -----------------------------------------------------------------------------------------
+_vp, _i32, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
+_lib.register('p3d_marching_cubes_blocks', ctypes.c_int64, [_i32, _i32, _i32])
+_lib.register('p3d_marching_cubes_classify', ctypes.c_int, [_vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp])
+_lib.register('p3d_marching_cubes_emit', ctypes.c_int, [_vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64,
+                                                        _vp, _vp, _vp, _vp])
 _cpu_tables = None
 
 

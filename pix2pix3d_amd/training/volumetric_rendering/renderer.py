@@ -13,6 +13,7 @@ into an error.
 """
 import ctypes
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -24,14 +25,21 @@ fused_policy = 'auto'          # 'auto' | 'require' | 'never'
 _warned_routes = set()
 
 
-def _warn_tensor_op_route(who, reason):
-    """A device tensor is about to take the tensor-op formulation instead of the fused kernel: say so, once per reason — a silent
-    fallback would look like the native path in every output but the profile.  (Expected cases: a gradient w.r.t. rays, depth or point coordinates, density_noise > 0, more than 64 coarse / fine samples per ray, a decoder that is not the OSG 32-64-33 MLP.)"""
-    key = (who, reason)
-    if key not in _warned_routes:
-        _warned_routes.add(key)
+def _tensor_op_guard(who, on_device, reason, required='fused HIP path required but unavailable', instead='the tensor-op renderer, not the fused HIP kernel'):
+    """Device tensors are about to leave the native route for ``reason``: nothing under ``fused_policy = 'never'`` (and for CPU tensors), an error under
+    'require', else one warning per (who, reason) — a silent fallback would look like the native path in every output but the profile.  (Expected cases: a
+    gradient w.r.t. rays, depth or point coordinates, density_noise > 0, sample counts outside 4..64 coarse / 1..64 fine, a decoder that is not the OSG
+    32-64-33 MLP.)  ``shape.sigma_grid`` passes its own two texts."""
+    if not on_device or fused_policy == 'never':
+        return
+    if fused_policy == 'require':
+        raise RuntimeError(f'{who}: {required}: {reason}')
+    if (who, reason) not in _warned_routes:
+        _warned_routes.add((who, reason))
         import warnings
-        warnings.warn(f'{who}: device tensors on the tensor-op renderer, not the fused HIP kernel: {reason}', RuntimeWarning, stacklevel=3)
+        warnings.warn(f'{who}: device tensors on {instead}: {reason}', RuntimeWarning, stacklevel=3)
+
+
 fused_training = True          # graphs that need gradients: fused forward + recompute-in-backward (see _FusedRenderFn)
 fused_backward = True          # ... with the backward on the device kernels of csrc/render_bwd.hip (False: replay the tensor-op renderer)
 mlp_bf16x3 = os.environ.get('P3D_MLP_BF16X3', '1') != '0'      # inference: the decoder MLPs as three bf16 MFMAs per fp32 product (csrc/render_device.h)
@@ -68,18 +76,6 @@ _lib.register('p3d_pack_decoder_dual', ctypes.c_int, [_vp] * 8 + [_f32, _vp, _vp
 _lib.register('p3d_render_forward_dual', ctypes.c_int, [_vp] * 9 + [ctypes.POINTER(_RenderDesc)] + [_vp] * 4 + [_vp])
 _lib.register('p3d_sample_points_dual', ctypes.c_int, [_vp] * 4 + [ctypes.POINTER(_RenderDesc), _i32, _vp, _vp, _vp])
 _lib.register('p3d_sample_lattice', ctypes.c_int, [_vp, _vp, ctypes.POINTER(_RenderDesc), _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp])
-_lib.register('p3d_marching_cubes_blocks', ctypes.c_int64, [_i32, _i32, _i32])
-_lib.register('p3d_marching_cubes_classify', ctypes.c_int, [_vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp])
-_lib.register('p3d_marching_cubes_emit', ctypes.c_int, [_vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64,
-                                                        _vp, _vp, _vp, _vp])
-# mesh rendering (pix2pix3d_amd/mesh.py, csrc/mesh_raster.hip)
-_lib.register('p3d_mesh_project', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp])
-_lib.register('p3d_mesh_raster_tiles', ctypes.c_int32, [_i32, _i32])
-_lib.register('p3d_mesh_raster_count', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp])
-_lib.register('p3d_mesh_raster_bin', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp])
-_lib.register('p3d_mesh_raster', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp])
-_lib.register('p3d_mesh_shade', ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _i32,
-                                           _vp, _vp])
 
 
 def generate_planes():
@@ -119,96 +115,202 @@ def sample_from_3dgrid(grid, coordinates):
     return out.permute(0, 4, 3, 2, 1).reshape(n, h * w * d, c)
 
 
+def _osg_mlp_layers(seq, n_in):
+    """(fc1, fc2, lr_mul) of the MLP the kernels implement — FC(n_in, 64) - Softplus(1, 20) - FC(64, 33), linear, biased, gains consistent with one
+    lr_mul — else None."""
+    if not (isinstance(seq, torch.nn.Sequential) and len(seq) == 3 and isinstance(seq[1], torch.nn.Softplus)):
+        return None
+    fc1, fc2 = seq[0], seq[2]
+    if not all(hasattr(fc, 'weight_gain') and hasattr(fc, 'bias_gain') and getattr(fc, 'activation', None) == 'linear' and fc.bias is not None for fc in (fc1, fc2)):
+        return None
+    if tuple(fc1.weight.shape) != (64, n_in) or tuple(fc2.weight.shape) != (33, 64) or seq[1].beta != 1 or seq[1].threshold != 20:
+        return None
+    lr = float(fc1.bias_gain)
+    if abs(fc1.weight_gain - lr / n_in ** 0.5) > 1e-12 or abs(fc2.weight_gain - lr / 64 ** 0.5) > 1e-12 or fc2.bias_gain != lr:
+        return None
+    return fc1, fc2, lr
+
+
 def _decoder_nets(decoder):
     """Recognise the OSG decoders the fused kernel implements; returns (nets, lr_mul-free raw params, sigmoid flag) or None.
 
     OSGDecoder (training/triplane.py:112-135): one 32->64->33 MLP.  OSGDecoder_semantic_lateSeparate
     (training/triplane_cond.py:926-970): colour net + label net, density from the label net."""
-    nets = []
-    for name in ('net', 'net_semantic'):
-        seq = getattr(decoder, name, None)
-        if seq is None:
-            continue
-        if not (isinstance(seq, torch.nn.Sequential) and len(seq) == 3 and isinstance(seq[1], torch.nn.Softplus)):
-            return None
-        fc1, fc2 = seq[0], seq[2]
-        ok = all(hasattr(fc, 'weight_gain') and hasattr(fc, 'bias_gain') and getattr(fc, 'activation', None) == 'linear' and fc.bias is not None for fc in (fc1, fc2))
-        if not ok or tuple(fc1.weight.shape) != (64, 32) or tuple(fc2.weight.shape) != (33, 64):
-            return None
-        if seq[1].beta != 1 or seq[1].threshold != 20:
-            return None
-        nets.append((fc1, fc2))
-    if len(nets) not in (1, 2) or (len(nets) == 2 and not hasattr(decoder, 'semantic_sigmoid')):
+    found = [_osg_mlp_layers(getattr(decoder, name), 32) for name in ('net', 'net_semantic') if getattr(decoder, name, None) is not None]
+    if len(found) not in (1, 2) or None in found or any(lr != found[0][2] for _, _, lr in found):
         return None
-    if len(nets) == 1 and type(decoder).__name__ != 'OSGDecoder':
+    if len(found) == 2 and not hasattr(decoder, 'semantic_sigmoid'):
+        return None
+    if len(found) == 1 and type(decoder).__name__ != 'OSGDecoder':
         return None                                  # e.g. OSGDecoder_semantic slices its outputs differently
-    lr = float(nets[0][0].bias_gain)
-    for fc1, fc2 in nets:
-        if abs(fc1.weight_gain - lr / 32 ** 0.5) > 1e-12 or abs(fc2.weight_gain - lr / 64 ** 0.5) > 1e-12 or fc1.bias_gain != lr or fc2.bias_gain != lr:
-            return None
-    return nets, lr, bool(getattr(decoder, 'semantic_sigmoid', False))
+    return [net[:2] for net in found], found[0][2], bool(getattr(decoder, 'semantic_sigmoid', False))
+
+
+def _dual_decoder_nets(decoder_texture, decoder_semantic):
+    """``_decoder_nets`` for the two-plane-set kernels: OSGDecoder(64) on cat(texture, semantic) + OSGDecoder_semantic(32), one lr_mul."""
+    if type(decoder_texture).__name__ != 'OSGDecoder' or not hasattr(decoder_semantic, 'final_sigmoid') or hasattr(decoder_texture, 'net_semantic') \
+            or hasattr(decoder_semantic, 'net_semantic'):
+        return None
+    tex, sem = _osg_mlp_layers(getattr(decoder_texture, 'net', None), 64), _osg_mlp_layers(getattr(decoder_semantic, 'net', None), 32)
+    if tex is None or sem is None or tex[2] != sem[2]:
+        return None
+    return [tex[:2], sem[:2]], tex[2], bool(decoder_semantic.final_sigmoid)
 
 
 def _f32c(t):
     return t.detach().to(torch.float32).contiguous()
 
 
-def pack_decoder(decoder_info, device, bf16x3):
-    """The decoder's FullyConnectedLayer parameters in the kernels' LDS image (p3d_pack_decoder / _bf16x3 / _l1x6 for ``bf16x3`` = 0 / 1 / 2), on the current stream."""
-    nets, lr_mul, _ = decoder_info
-    lib = _lib.lib()
-    packed = torch.empty([lib.p3d_render_decoder_floats()], dtype=torch.float32, device=device)
-    ws = []
-    for fc1, fc2 in nets:
-        ws += [_f32c(fc1.weight), _f32c(fc1.bias), _f32c(fc2.weight), _f32c(fc2.bias)]
-    ptrs = [_lib.ptr(t) for t in ws] + [None] * (8 - len(ws))
-    pack = (lib.p3d_pack_decoder, lib.p3d_pack_decoder_bf16x3, lib.p3d_pack_decoder_l1x6)[int(bf16x3)]
-    _lib.check(pack(*ptrs, len(nets), lr_mul, _lib.ptr(packed), _lib.stream_of(packed)), 'pack_decoder')
-    return packed, ws
-
-
-def shared_planes(n_planes, n_rays, who):
+def shared_planes(n_planes, n_rays, who, allowed=True):
     """One plane set for every camera?  Planes of batch 1 serve ray batches of any size (a video: one latent, B views per launch); equal batches are the
-    ordinary case; anything else is an error on every route, before any launch."""
+    ordinary case; anything else is an error on every route, before any launch.  (``allowed=False``: the two-plane-set kernel has no shared-plane form.)"""
     if n_planes == n_rays:
         return False
-    if n_planes != 1:
-        raise ValueError(f'{who}: planes of batch {n_planes} cannot serve rays of batch {n_rays} (the batches must be equal, or the planes of batch 1)')
+    if n_planes != 1 or not allowed:
+        raise ValueError(f'{who}: planes of batch {n_planes} cannot serve rays of batch {n_rays} (the batches must be equal' + (', or the planes of batch 1)' if allowed else ')'))
     return True
 
 
+# ---- the route decision ---------------------------------------------------------------------------------------------------------
+def fallback_reason(policy, on_device, options, decoders, graph=False, plane_shapes=None, clamp_mode=True, own=()):
+    """Why a call cannot take its device kernel — the first failing condition, in the one order every entry point reports them — or None.  ``decoders``: the
+    one decoder, or the (texture, semantic) pair of the two-plane-set renderer; ``graph``: an autograd graph is needed that the entry point cannot give;
+    ``own``: (failed, text) conditions of the caller's, after the plane shapes (``shape.sigma_grid``)."""
+    dual = len(decoders) == 2
+    if policy == 'never':
+        return 'fused_policy == never'
+    if not on_device:
+        return 'CPU tensors'
+    if graph:
+        return 'autograd graph requested (no fused backward for this entry point, or fused_training is off)'
+    if plane_shapes is not None and (len(set(map(tuple, plane_shapes))) != 1 or len(plane_shapes[0]) != 5 or tuple(plane_shapes[0][1:3]) != (3, 32)):
+        return f"planes of shape {' / '.join(str(tuple(s)) for s in plane_shapes)} are not [N,3,32,H,W]" + (' sets of one shape' if dual else '')
+    for failed, text in own:
+        if failed:
+            return text
+    if options.get('density_noise', 0) > 0:
+        return 'density_noise > 0'
+    if clamp_mode and options.get('clamp_mode', 'softplus') != 'softplus':
+        return "clamp_mode != 'softplus' (the tensor-op route raises the reference's assertion, ray_marcher.py:35)"
+    if (_dual_decoder_nets(*decoders) if dual else _decoder_nets(*decoders)) is None:
+        return f"decoder {' + '.join(type(d).__name__ for d in decoders)} is not " + ('OSGDecoder(64) + OSGDecoder_semantic(32)' if dual else 'an OSG 32-64-33 decoder')
+    return None
+
+
+class Route(NamedTuple):
+    kind: str                      # 'fused': one launch | 'fused_autograd': the same forward inside _FusedRenderFn / _FusedPointsFn | 'tensor_ops'
+    reason: Optional[str]          # why not fused; None when fused
+    expand: bool                   # planes of batch 1 serve B ray sets: True = broadcast them first (only the graph-less fused launch reads the one set in place)
+
+
+def render_route(entry, policy, on_device, needs_grad, has_backward, plane_shapes, n_rays, options, decoders, who='ImportanceRenderer'):
+    """What one call of ``entry`` ('forward' | 'run_model' | 'dual_forward' | 'dual_run_model') runs on, from facts only.  ``needs_grad``: the call is part of
+    an autograd graph; ``has_backward``: this entry point can give that graph a fused backward (``fused_training``; never for a gradient w.r.t. point
+    coordinates, never for two plane sets).  Raises the batch-mismatch ``ValueError`` of ``shared_planes`` for the ray entry points (point queries take the
+    planes' batch as it comes)."""
+    dual, rays = entry.startswith('dual'), entry.endswith('forward')
+    shared = False
+    if rays and (dual or len(plane_shapes[0]) == 5):
+        shared = any([shared_planes(s[0], n_rays, who, allowed=not dual) for s in plane_shapes])
+    reason = fallback_reason(policy, on_device, options, decoders, graph=needs_grad and not has_backward, plane_shapes=plane_shapes)
+    if reason is None and rays:
+        sc, sf = int(options['depth_resolution']), int(options['depth_resolution_importance'])
+        if not (4 <= sc <= 64 and 1 <= sf <= 64):
+            reason = 'sample counts outside the fused kernel envelope (4..64 coarse, 1..64 fine)'
+    kind = 'tensor_ops' if reason is not None else ('fused_autograd' if needs_grad else 'fused')
+    return Route(kind, reason, shared and kind != 'fused')
+
+
+def _needs_grad(tensors, decoders):
+    return torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or any(p.requires_grad for d in decoders for p in d.parameters()))
+
+
+# ---- the operands of every launch -------------------------------------------------------------------------------------------------
+def render_desc(n_img, rays_per_img, plane_h, plane_w, strides, n_nets, semantic_sigmoid, mode, options, numeric_limits=False, raster=0):
+    """p3d_render_desc from shapes, plane strides, decoder form, MLP mode and options.  ``numeric_limits``: the rays run from options['ray_start'] to
+    ['ray_end'] (else per-ray limits travel as tensors, or — point queries — there are no rays); ``raster`` is a pure scheduling hint, plus
+    P3D_RENDER_SHARED_PLANES (2)."""
+    start, end = (options['ray_start'], options['ray_end']) if numeric_limits else (0.0, 0.0)
+    return _RenderDesc(n_img, rays_per_img, plane_h, plane_w, n_nets, int(semantic_sigmoid), int(options.get('depth_resolution', 0)),
+                       int(options.get('depth_resolution_importance', 0)), int(bool(options.get('disparity_space_sampling', False))),
+                       int(bool(options.get('white_back', False))), float(start), float(end), float(options['box_warp']), *strides, int(raster), int(mode))
+
+
+def _plane_set_cl(planes):
+    """[N,3,32,H,W] planes as the kernels read them: (tensor, (image, plane, pixel) strides in floats).  A channels-last [N,96,H,W]
+    backbone output viewed as [N,3,32,H,W] is read in place; anything else goes through one re-layout pass to [N][3][H][W][32]."""
+    n, k, c, h, w = planes.shape
+    assert k == 3 and c == 32
+    st = planes.stride()
+    if planes.dtype == torch.float32 and st[2] == 1 and st[1] == 32 and st[4] >= 96 and st[3] == w * st[4] and st[0] == h * st[3] and st[4] % 4 == 0 \
+            and planes.data_ptr() % 16 == 0:
+        return planes.detach(), (st[0], st[1], st[4])
+    src = _f32c(planes)
+    out = torch.empty([n, 3, h, w, 32], dtype=torch.float32, device=planes.device)
+    _lib.check(_lib.lib().p3d_planes_to_channels_last(_lib.ptr(src), _lib.ptr(out), n, h, w, _lib.stream_of(src)), 'planes_to_channels_last')
+    return out, (0, 0, 0)
+
+
 class _FusedContext:
-    """Device-side operands shared by the fused entry points: channels-last planes + packed decoder."""
+    """Device-side operands shared by the fused entry points: texel-major planes + packed decoder + descriptor.  ``decoder_info``: ``_decoder_nets``'
+    result, or — with ``planes_semantic`` — ``_dual_decoder_nets``' for the two-plane-set kernels."""
 
-    def __init__(self, planes, decoder_info, bf16x3=False, packed=None):
-        nets, lr_mul, sem_sigmoid = decoder_info
-        self.bf16x3 = int(bf16x3)                               # p3d_render_desc.mlp_bf16x3: 0 exact, 1 bf16x3, 2 layer 1 as bf16x6
+    def __init__(self, planes, decoder_info, bf16x3=0, planes_semantic=None):
+        nets, lr_mul, self.sem_sigmoid = decoder_info
+        dual = planes_semantic is not None
+        self.bf16x3 = 0 if dual else int(bf16x3)                # p3d_render_desc.mlp_bf16x3: 0 exact, 1 bf16x3, 2 layer 1 as bf16x6
+        self.n, _, _, self.h, self.w = planes.shape
+        self.n_nets = len(nets)
+        self.planes_cl, self.strides = _plane_set_cl(planes)
+        if dual:
+            self.planes_semantic_cl, st = _plane_set_cl(planes_semantic)
+            if st != self.strides:                               # one descriptor describes both sets: bring the odd one to the default layout
+                if self.strides != (0, 0, 0):
+                    self.planes_cl, self.strides = _plane_set_cl(planes.contiguous())
+                if st != (0, 0, 0):
+                    self.planes_semantic_cl, _ = _plane_set_cl(planes_semantic.contiguous())
+        # the FullyConnectedLayer parameters in the kernels' LDS image, on the current stream
         lib = _lib.lib()
-        n, k, c, h, w = planes.shape
-        assert k == 3 and c == 32
-        self.strides = (0, 0, 0)
-        st = planes.stride()
-        if planes.dtype == torch.float32 and st[2] == 1 and st[1] == 32 and st[4] >= 96 and st[3] == w * st[4] and st[0] == h * st[3] and st[4] % 4 == 0 \
-                and planes.data_ptr() % 16 == 0:
-            # already texel-major (a channels-last [N,96,H,W] backbone output viewed as [N,3,32,H,W]): read it in place
-            self.planes_cl = planes.detach()
-            self.strides = (st[0], st[1], st[4])
-            src = self.planes_cl
+        self._keep = [_f32c(t) for fc1, fc2 in nets for t in (fc1.weight, fc1.bias, fc2.weight, fc2.bias)]
+        ptrs = [_lib.ptr(t) for t in self._keep] + [None] * (8 - len(self._keep))
+        self.packed = torch.empty([lib.p3d_render_decoder_floats_dual() if dual else lib.p3d_render_decoder_floats()], dtype=torch.float32, device=planes.device)
+        if dual:
+            code = lib.p3d_pack_decoder_dual(*ptrs, lr_mul, _lib.ptr(self.packed), _lib.stream_of(self.packed))
         else:
-            src = _f32c(planes)
-            self.planes_cl = torch.empty([n, 3, h, w, 32], dtype=torch.float32, device=planes.device)
-            _lib.check(lib.p3d_planes_to_channels_last(_lib.ptr(src), _lib.ptr(self.planes_cl), n, h, w, _lib.stream_of(src)), 'planes_to_channels_last')
-        if packed is not None:                                 # (packed by pack_decoder() ahead of time, same arithmetic)
-            self.packed, self._keep = packed
-        else:
-            self.packed, self._keep = pack_decoder(decoder_info, planes.device, self.bf16x3)
-        self.n_nets, self.sem_sigmoid, self.n, self.h, self.w = len(nets), sem_sigmoid, n, h, w
+            pack = (lib.p3d_pack_decoder, lib.p3d_pack_decoder_bf16x3, lib.p3d_pack_decoder_l1x6)[self.bf16x3]
+            code = pack(*ptrs, len(nets), lr_mul, _lib.ptr(self.packed), _lib.stream_of(self.packed))
+        _lib.check(code, 'pack_decoder_dual' if dual else 'pack_decoder')
 
-    def desc(self, options, rays_per_img=1, start=0.0, end=0.0, raster=False, n_img=None):
-        return _RenderDesc(self.n if n_img is None else n_img, rays_per_img, self.h, self.w, self.n_nets, int(self.sem_sigmoid),
-                           int(options.get('depth_resolution', 0)), int(options.get('depth_resolution_importance', 0)),
-                           int(bool(options.get('disparity_space_sampling', False))), int(bool(options.get('white_back', False))),
-                           float(start), float(end), float(options['box_warp']), *self.strides, int(raster), int(self.bf16x3))
+    def desc(self, options, rays_per_img=1, numeric_limits=False, raster=0, n_img=None):
+        return render_desc(self.n if n_img is None else n_img, rays_per_img, self.h, self.w, self.strides, self.n_nets, self.sem_sigmoid, self.bf16x3, options,
+                           numeric_limits, raster)
+
+
+def _flat_limits(t):
+    """Per-ray near / far limits as the kernels read them: flat fp32, or None for numeric limits."""
+    return None if t is None else _f32c(t).reshape(-1)
+
+
+def _ray_outputs(n, m, channels, device):
+    """(feat [N,M,C], depth [N,M,1], wsum [N,M,1], the launch-wide depth min / max the kernel clamps with)."""
+    return (torch.empty([n, m, channels], device=device, dtype=torch.float32), torch.empty([n, m, 1], device=device, dtype=torch.float32),
+            torch.empty([n, m, 1], device=device, dtype=torch.float32), torch.empty([2], device=device, dtype=torch.int32))
+
+
+def _plane_grad(d_planes, planes):
+    """The channels-last gradient as a gradient of ``planes``: a [N,3,32,H,W] view, contiguous if the planes were."""
+    g_planes = d_planes.permute(0, 1, 4, 2, 3)
+    return g_planes.contiguous() if planes.dim() == 5 and planes.is_contiguous() else g_planes
+
+
+def _draw_uniforms(n, m, sc, sf, device, tensor_limits):
+    """The reference's two draws, in its order: rand_like(depths_coarse) [N,M,Sc,1] (renderer.py:190) then sample_pdf's rand(N*M, Sf) (:237).  With tensor
+    limits the reference's rand_like fills a permuted [S,N,M,1] linspace in ITS memory order (:184-186)."""
+    if tensor_limits:
+        u_c = torch.rand([sc, n, m, 1], device=device, dtype=torch.float32).permute(1, 2, 0, 3)
+    else:
+        u_c = torch.rand([n, m, sc, 1], device=device, dtype=torch.float32)
+    return u_c, torch.rand([n * m, sf], device=device, dtype=torch.float32)
 
 
 class ImportanceRenderer(torch.nn.Module):
@@ -218,48 +320,26 @@ class ImportanceRenderer(torch.nn.Module):
         self.plane_axes = generate_planes()
 
     # ------------------------------------------------------------------------------------------------
-    def _fused_reason(self, planes, decoder, options, needs_grad, trainable=True):
-        """None when the fused kernel applies, else why not."""
-        if fused_policy == 'never':
-            return 'fused_policy == never'
-        if planes.device.type != 'cuda':
-            return 'CPU tensors'
-        if needs_grad and not (fused_training and trainable):
-            return 'autograd graph requested (no fused backward for this entry point / fused_training is off)'
-        if planes.ndim != 5 or planes.shape[1] != 3 or planes.shape[2] != 32:
-            return f'planes shape {tuple(planes.shape)} is not [N,3,32,H,W]'
-        if options.get('density_noise', 0) > 0:
-            return 'density_noise > 0'
-        if options.get('clamp_mode', 'softplus') != 'softplus':
-            return "clamp_mode != 'softplus' (the tensor-op route raises the reference's assertion, ray_marcher.py:35)"
-        if _decoder_nets(decoder) is None:
-            return f'decoder {type(decoder).__name__} is not an OSG 32-64-33 decoder'
-        return None
-
-    def _tensor_op_guard(self, planes, reason):
-        if planes.device.type != 'cuda' or fused_policy == 'never':
-            return
-        if fused_policy == 'require':
-            raise RuntimeError(f'ImportanceRenderer: fused HIP path required but unavailable: {reason}')
-        _warn_tensor_op_route(type(self).__name__, reason)
+    def _route(self, entry, plane_sets, decoders, tensors, n_rays, options, has_backward):
+        """``render_route`` for this call's tensors, and the plane sets as its route reads them (shared planes outside the graph-less fused launch:
+        broadcast, as if they had been repeated)."""
+        route = render_route(entry, fused_policy, plane_sets[0].device.type == 'cuda', _needs_grad(plane_sets + tensors, decoders), has_backward,
+                             [p.shape for p in plane_sets], n_rays, options, decoders, who=type(self).__name__)
+        if route.expand:
+            plane_sets = [p.expand(n_rays, -1, -1, -1, -1) for p in plane_sets]
+        if route.reason is not None:
+            _tensor_op_guard(type(self).__name__, plane_sets[0].device.type == 'cuda', route.reason)
+        return route, plane_sets
 
     def forward(self, planes, decoder, ray_origins, ray_directions, rendering_options):
         self.plane_axes = self.plane_axes.to(ray_origins.device)
-        needs_grad = torch.is_grad_enabled() and (planes.requires_grad or ray_origins.requires_grad or ray_directions.requires_grad
-                                                  or any(p.requires_grad for p in decoder.parameters()))
-        reason = self._fused_reason(planes, decoder, rendering_options, needs_grad)
-        if planes.ndim == 5 and shared_planes(planes.shape[0], ray_origins.shape[0], type(self).__name__) and (reason is not None or needs_grad):
-            # shared planes outside the graph-less fused launch (which reads the one set in place): broadcast, as if they had been repeated
-            planes = planes.expand(ray_origins.shape[0], -1, -1, -1, -1)
-        if reason is None:
-            out = self._forward_fused(planes, decoder, ray_origins, ray_directions, rendering_options, needs_grad)
-            if out is not None:
-                return out
-            reason = 'sample counts outside the fused kernel envelope (<= 64 coarse, 1..64 fine)'
-            if planes.shape[0] != ray_origins.shape[0]:
-                planes = planes.expand(ray_origins.shape[0], -1, -1, -1, -1)
-        self._tensor_op_guard(planes, reason)
-        return self._forward_tensor_ops(planes, decoder, ray_origins, ray_directions, rendering_options)
+        route, (planes,) = self._route('forward', [planes], (decoder,), [ray_origins, ray_directions], ray_origins.shape[0], rendering_options, fused_training)
+        if route.kind == 'tensor_ops':
+            return self._forward_tensor_ops(planes, decoder, ray_origins, ray_directions, rendering_options)
+        u_c, u_f, t0, t1 = self._fused_draws(ray_origins, ray_directions, rendering_options)
+        if route.kind == 'fused_autograd':
+            return _FusedRenderFn.apply(self, decoder, rendering_options, u_c, u_f, t0, t1, planes, ray_origins, ray_directions, *decoder.parameters())
+        return fused_render(planes, decoder, ray_origins, ray_directions, rendering_options, u_c, u_f, t0, t1)
 
     # ------------------------------------------------------------------------------------------------
     def _ray_limits(self, ray_origins, ray_directions, opt):
@@ -271,25 +351,15 @@ class ImportanceRenderer(torch.nn.Module):
             t1[~ok] = t0[ok].max()
         return t0, t1
 
-    def _forward_fused(self, planes, decoder, ray_origins, ray_directions, opt, needs_grad=False):
+    def _fused_draws(self, ray_origins, ray_directions, opt):
+        """What a fused ray launch takes besides planes, decoder and rays: (u_coarse, u_fine, t_start, t_end).  The limits come first, as in the reference:
+        ``_ray_limits`` synchronises, and the draws keep their place after it."""
         n, m, _ = ray_origins.shape
-        sc, sf = int(opt['depth_resolution']), int(opt['depth_resolution_importance'])
-        if not (4 <= sc <= 64 and 1 <= sf <= 64):
-            return None
-        dev = planes.device
         t0 = t1 = None
         if opt['ray_start'] == opt['ray_end'] == 'auto':
             t0, t1 = self._ray_limits(ray_origins, ray_directions, opt)
-        # the reference's draws, in its order: rand_like(depths_coarse) [N,M,Sc,1] (renderer.py:190) then rand(N*M, Sf) (:237)
-        if t0 is None:
-            u_c = torch.rand([n, m, sc, 1], device=dev, dtype=torch.float32)
-        else:   # tensor-limits branch: rand_like of the permuted [S,N,M,1] linspace fills in ITS memory order (:184-186)
-            u_c = torch.rand([sc, n, m, 1], device=dev, dtype=torch.float32).permute(1, 2, 0, 3)
-        u_f = torch.rand([n * m, sf], device=dev, dtype=torch.float32)
-        if needs_grad:
-            params = [p for p in decoder.parameters()]
-            return _FusedRenderFn.apply(self, decoder, opt, u_c, u_f, t0, t1, planes, ray_origins, ray_directions, *params)
-        return fused_render(planes, decoder, ray_origins, ray_directions, opt, u_c, u_f, t0, t1)
+        u_c, u_f = _draw_uniforms(n, m, int(opt['depth_resolution']), int(opt['depth_resolution_importance']), ray_origins.device, t0 is not None)
+        return u_c, u_f, t0, t1
 
     # ------------------------------------------------------------------------------------------------
     def _forward_tensor_ops(self, planes, decoder, ray_origins, ray_directions, opt, point_fn=None):
@@ -329,19 +399,17 @@ class ImportanceRenderer(torch.nn.Module):
     def run_model(self, planes, decoder, sample_coordinates, sample_directions, options):
         """Sample the planes at 3-D points and decode: {'rgb': [N,P,C], 'sigma': [N,P,1]} (renderer.py:142-148)."""
         self.plane_axes = self.plane_axes.to(sample_coordinates.device)
-        needs_grad = torch.is_grad_enabled() and (planes.requires_grad or sample_coordinates.requires_grad
-                                                  or any(p.requires_grad for p in decoder.parameters()))
         # a graph that needs gradients (the density regularisation, loss.py:681-706) takes the fused forward + p3d_sample_points_backward;
         # only a gradient w.r.t. the coordinates themselves has no fused form
-        reason = self._fused_reason(planes, decoder, options, needs_grad, trainable=not (torch.is_grad_enabled() and sample_coordinates.requires_grad))
-        if reason is None:
-            if needs_grad:
-                rgb, sigma = _FusedPointsFn.apply(decoder, options, sample_coordinates, planes, *decoder.parameters())
-            else:
-                rgb, sigma = fused_sample_points(planes, decoder, sample_coordinates, options)
-            return {'rgb': rgb, 'sigma': sigma}
-        self._tensor_op_guard(planes, reason)
-        return self._points_tensor_ops(planes, decoder, sample_coordinates, sample_directions, options)
+        route, (planes,) = self._route('run_model', [planes], (decoder,), [sample_coordinates], sample_coordinates.shape[0], options,
+                                       fused_training and not sample_coordinates.requires_grad)
+        if route.kind == 'tensor_ops':
+            return self._points_tensor_ops(planes, decoder, sample_coordinates, sample_directions, options)
+        if route.kind == 'fused_autograd':
+            rgb, sigma = _FusedPointsFn.apply(decoder, options, sample_coordinates, planes, *decoder.parameters())
+        else:
+            rgb, sigma = fused_sample_points(planes, decoder, sample_coordinates, options)
+        return {'rgb': rgb, 'sigma': sigma}
 
     def _points_tensor_ops(self, planes, decoder, sample_coordinates, sample_directions, options):
         """run_model as the reference writes it (renderer.py:142-148): grid_sample + decoder, differentiable in everything."""
@@ -414,36 +482,6 @@ class ImportanceRenderer(torch.nn.Module):
         return b0 + (u - c0) / span * (b1 - b0)
 
 
-def _osg_pair(decoder, n_in, squash_required=None):
-    """(fc1, fc2, lr_mul) of a single-MLP OSG decoder FC(n_in, 64) - Softplus - FC(64, 33), else None."""
-    seq = getattr(decoder, 'net', None)
-    if not (isinstance(seq, torch.nn.Sequential) and len(seq) == 3 and isinstance(seq[1], torch.nn.Softplus)) or hasattr(decoder, 'net_semantic'):
-        return None
-    fc1, fc2 = seq[0], seq[2]
-    if not all(hasattr(fc, 'weight_gain') and getattr(fc, 'activation', None) == 'linear' and fc.bias is not None for fc in (fc1, fc2)):
-        return None
-    if tuple(fc1.weight.shape) != (64, n_in) or tuple(fc2.weight.shape) != (33, 64) or seq[1].beta != 1 or seq[1].threshold != 20:
-        return None
-    lr = float(fc1.bias_gain)
-    if abs(fc1.weight_gain - lr / n_in ** 0.5) > 1e-12 or abs(fc2.weight_gain - lr / 8.0) > 1e-12 or fc2.bias_gain != lr:
-        return None
-    return fc1, fc2, lr
-
-
-def _plane_set_cl(planes):
-    """[N,3,32,H,W] planes as the kernels read them: (tensor, (image, plane, pixel) strides in floats).  A channels-last [N,96,H,W]
-    backbone output viewed as [N,3,32,H,W] is read in place; anything else goes through one re-layout pass to [N][3][H][W][32]."""
-    n, k, c, h, w = planes.shape
-    st = planes.stride()
-    if planes.dtype == torch.float32 and st[2] == 1 and st[1] == 32 and st[4] >= 96 and st[3] == w * st[4] and st[0] == h * st[3] and st[4] % 4 == 0 \
-            and planes.data_ptr() % 16 == 0:
-        return planes.detach(), (st[0], st[1], st[4])
-    src = _f32c(planes)
-    out = torch.empty([n, 3, h, w, 32], dtype=torch.float32, device=planes.device)
-    _lib.check(_lib.lib().p3d_planes_to_channels_last(_lib.ptr(src), _lib.ptr(out), n, h, w, _lib.stream_of(src)), 'planes_to_channels_last')
-    return out, (0, 0, 0)
-
-
 class ImportanceSemanticRenderer(ImportanceRenderer):
     """Renderer of the two-backbone generator (reference: renderer.py:256-438): a texture plane set and a semantic plane set; the label
     decoder reads the semantic features and provides density + labels, the colour decoder reads cat(texture, semantic).  Sampling
@@ -454,76 +492,13 @@ class ImportanceSemanticRenderer(ImportanceRenderer):
     64 inputs as two 32-wide MFMA blocks.  Graphs that need gradients (train.py no longer selects this generator, :375) and CPU tensors
     take the tensor-op formulation."""
 
-    def _dual_operands(self, planes_texture, planes_semantic, decoder_texture, decoder_semantic, options, needs_grad):
-        """Packed operands of the DUAL kernels, or the reason they do not apply."""
-        if fused_policy == 'never':
-            return 'fused_policy == never'
-        if planes_texture.device.type != 'cuda':
-            return 'CPU tensors'
-        if needs_grad:
-            return 'autograd graph requested (the two-plane-set kernel is inference only)'
-        if planes_texture.shape != planes_semantic.shape or planes_texture.ndim != 5 or tuple(planes_texture.shape[1:3]) != (3, 32):
-            return f'plane sets {tuple(planes_texture.shape)} / {tuple(planes_semantic.shape)} are not two [N,3,32,H,W] sets'
-        if options.get('density_noise', 0) > 0 or options.get('clamp_mode', 'softplus') != 'softplus':
-            return 'density_noise / clamp_mode outside the kernel'
-        tex, sem = _osg_pair(decoder_texture, 64), _osg_pair(decoder_semantic, 32)
-        if tex is None or sem is None or tex[2] != sem[2] or type(decoder_texture).__name__ != 'OSGDecoder' or not hasattr(decoder_semantic, 'final_sigmoid'):
-            return 'decoders are not OSGDecoder(64) + OSGDecoder_semantic(32)'
-        pt, st_t = _plane_set_cl(planes_texture)
-        ps, st_s = _plane_set_cl(planes_semantic)
-        if st_t != st_s:                                     # one descriptor describes both sets: bring the odd one to the default layout
-            if st_t != (0, 0, 0):
-                pt, st_t = _plane_set_cl(planes_texture.contiguous())
-            if st_s != (0, 0, 0):
-                ps, st_s = _plane_set_cl(planes_semantic.contiguous())
-        lib = _lib.lib()
-        packed = torch.empty([lib.p3d_render_decoder_floats_dual()], dtype=torch.float32, device=pt.device)
-        ws = [_f32c(t) for t in (tex[0].weight, tex[0].bias, tex[1].weight, tex[1].bias, sem[0].weight, sem[0].bias, sem[1].weight, sem[1].bias)]
-        _lib.check(lib.p3d_pack_decoder_dual(*[_lib.ptr(t) for t in ws], tex[2], _lib.ptr(packed), _lib.stream_of(packed)), 'pack_decoder_dual')
-        n, _, _, h, w = planes_texture.shape
-
-        def desc(rays_per_img=1, start=0.0, end=0.0):
-            return _RenderDesc(n, rays_per_img, h, w, 2, int(bool(decoder_semantic.final_sigmoid)), int(options.get('depth_resolution', 0)),
-                               int(options.get('depth_resolution_importance', 0)), int(bool(options.get('disparity_space_sampling', False))),
-                               int(bool(options.get('white_back', False))), float(start), float(end), float(options['box_warp']), *st_t, 1, 0)
-        return pt, ps, packed, desc, ws
-
     def forward(self, planes_texture, planes_semantic, decoder_texture, decoder_semantic, ray_origins, ray_directions, rendering_options):
         self.plane_axes = self.plane_axes.to(ray_origins.device)
-        opt = rendering_options
-        needs_grad = torch.is_grad_enabled() and (planes_texture.requires_grad or planes_semantic.requires_grad or ray_origins.requires_grad
-                                                  or any(p.requires_grad for d in (decoder_texture, decoder_semantic) for p in d.parameters()))
-        for pl in (planes_texture, planes_semantic):
-            if pl.shape[0] != ray_origins.shape[0]:                  # (no shared-plane form of the two-plane-set kernel)
-                raise ValueError(f'{type(self).__name__}: planes of batch {pl.shape[0]} cannot serve rays of batch {ray_origins.shape[0]}')
-        ops = self._dual_operands(planes_texture, planes_semantic, decoder_texture, decoder_semantic, opt, needs_grad)
-        sc, sf = int(opt['depth_resolution']), int(opt['depth_resolution_importance'])
-        if not isinstance(ops, str) and not (4 <= sc <= 64 and 1 <= sf <= 64):
-            ops = 'sample counts outside the fused kernel envelope (4..64 coarse, 1..64 fine)'
-        if not isinstance(ops, str):
-            pt, ps, packed, desc, _keep = ops
-            n, m, _ = ray_origins.shape
-            dev = pt.device
-            auto = opt['ray_start'] == opt['ray_end'] == 'auto'
-            t0 = t1 = None
-            if auto:                                                        # tensor limits: the reference's rand_like fills a permuted [S,N,M,1] tensor
-                t0, t1 = self._ray_limits(ray_origins, ray_directions, opt)
-                u_c = torch.rand([sc, n, m, 1], device=dev, dtype=torch.float32).permute(1, 2, 0, 3)
-                t0, t1 = _f32c(t0).reshape(-1), _f32c(t1).reshape(-1)
-            else:
-                u_c = torch.rand([n, m, sc, 1], device=dev, dtype=torch.float32)    # rand_like(depths_coarse) (renderer.py:190)
-            u_f = torch.rand([n * m, sf], device=dev, dtype=torch.float32)           # sample_pdf's draw (:237)
-            feat = torch.empty([n, m, 64], device=dev, dtype=torch.float32)
-            depth = torch.empty([n, m, 1], device=dev, dtype=torch.float32)
-            wsum = torch.empty([n, m, 1], device=dev, dtype=torch.float32)
-            mm = torch.empty([2], device=dev, dtype=torch.int32)
-            d = desc(m, 0.0 if auto else opt['ray_start'], 0.0 if auto else opt['ray_end'])
-            code = _lib.lib().p3d_render_forward_dual(_lib.ptr(pt), _lib.ptr(ps), _lib.ptr(packed), _lib.ptr(_f32c(ray_origins)), _lib.ptr(_f32c(ray_directions)),
-                                                      _lib.ptr(_f32c(u_c)), _lib.ptr(u_f), _lib.ptr(t0), _lib.ptr(t1), ctypes.byref(d), _lib.ptr(feat), _lib.ptr(depth),
-                                                      _lib.ptr(wsum), _lib.ptr(mm), _lib.stream_of(feat))
-            _lib.check(code, 'render_forward_dual')
-            return feat, depth, wsum
-        self._tensor_op_guard(planes_texture, ops)
+        route, _ = self._route('dual_forward', [planes_texture, planes_semantic], (decoder_texture, decoder_semantic), [ray_origins, ray_directions],
+                               ray_origins.shape[0], rendering_options, False)
+        if route.kind == 'fused':
+            return fused_render_dual(planes_texture, planes_semantic, decoder_texture, decoder_semantic, ray_origins, ray_directions, rendering_options,
+                                     *self._fused_draws(ray_origins, ray_directions, rendering_options))
 
         def point_fn(pts, dirs):
             out = self._run_model_tensor_ops(planes_texture, planes_semantic, decoder_texture, decoder_semantic, pts, dirs, rendering_options)
@@ -533,20 +508,11 @@ class ImportanceSemanticRenderer(ImportanceRenderer):
     def run_model(self, planes_texture, planes_semantic, decoder_texture, decoder_semantic, sample_coordinates, sample_directions, options):
         """-> {'rgb': [N,P,32], 'sigma': [N,P,1], 'semantic': [N,P,32]}  (renderer.py:324-333)."""
         self.plane_axes = self.plane_axes.to(sample_coordinates.device)
-        needs_grad = torch.is_grad_enabled() and (planes_texture.requires_grad or planes_semantic.requires_grad or sample_coordinates.requires_grad
-                                                  or any(p.requires_grad for d in (decoder_texture, decoder_semantic) for p in d.parameters()))
-        ops = self._dual_operands(planes_texture, planes_semantic, decoder_texture, decoder_semantic, options, needs_grad)
-        if isinstance(ops, str):
-            self._tensor_op_guard(planes_texture, ops)
+        route, _ = self._route('dual_run_model', [planes_texture, planes_semantic], (decoder_texture, decoder_semantic), [sample_coordinates],
+                               sample_coordinates.shape[0], options, False)
+        if route.kind != 'fused':
             return self._run_model_tensor_ops(planes_texture, planes_semantic, decoder_texture, decoder_semantic, sample_coordinates, sample_directions, options)
-        pt, ps, packed, desc, _keep = ops
-        n, p, _ = sample_coordinates.shape
-        both = torch.empty([n, p, 64], device=pt.device, dtype=torch.float32)
-        sigma = torch.empty([n, p, 1], device=pt.device, dtype=torch.float32)
-        d = desc()
-        code = _lib.lib().p3d_sample_points_dual(_lib.ptr(pt), _lib.ptr(ps), _lib.ptr(packed), _lib.ptr(_f32c(sample_coordinates)), ctypes.byref(d), p,
-                                                 _lib.ptr(both), _lib.ptr(sigma), _lib.stream_of(both))
-        _lib.check(code, 'sample_points_dual')
+        both, sigma = fused_sample_points_dual(planes_texture, planes_semantic, decoder_texture, decoder_semantic, sample_coordinates, options)
         return {'sigma': sigma, 'rgb': both[..., :32], 'semantic': both[..., 32:]}
 
     def _run_model_tensor_ops(self, planes_texture, planes_semantic, decoder_texture, decoder_semantic, sample_coordinates, sample_directions, options):
@@ -585,7 +551,8 @@ def importance_sample_index_native(z_coarse, w_coarse, u_fine):
 
 
 class _replay_draws:
-    """Make torch.rand_like / torch.rand hand back given tensors, in order (the renderer's two uniform draws)."""
+    """Make torch.rand_like / torch.rand hand back given tensors, in order (the renderer's two uniform draws): logical [N,M,Sc,1] / [N*M,Sf] draws, whichever
+    way a route asks for them — the tensor-limits branch of the fused route draws [Sc,N,M,1] and permutes (``_draw_uniforms``) and gets the permuted view."""
 
     def __init__(self, *draws):
         self.draws = list(draws)
@@ -593,8 +560,15 @@ class _replay_draws:
     def __enter__(self):
         self._rl, self._r = torch.rand_like, torch.rand
         it = iter(self.draws)
+
+        def rand(*size, **kw):
+            size = tuple(size[0]) if len(size) == 1 and isinstance(size[0], (list, tuple, torch.Size)) else tuple(size)
+            u = next(it)
+            if u.ndim == 4 and size == (u.shape[2], u.shape[0], u.shape[1], 1) and size != tuple(u.shape):
+                return u.permute(2, 0, 1, 3)
+            return u.reshape(size)
         torch.rand_like = lambda t, *a, **k: next(it).to(t.device).reshape(t.shape)
-        torch.rand = lambda *a, **k: next(it)
+        torch.rand = rand
         return self
 
     def __exit__(self, *exc):
@@ -722,10 +696,7 @@ def fused_sample_points_backward(planes, decoder, coordinates, opt, g_rgb, g_sig
     code = lib.p3d_sample_points_backward(_lib.ptr(ctx.planes_cl), _lib.ptr(ctx.packed), _lib.ptr(packed_bwd), _lib.ptr(xyz), ctypes.byref(d), p,
                                           _lib.ptr(gr), _lib.ptr(gs), _lib.ptr(d_planes), _lib.ptr(d_dec), _lib.stream_of(d_planes))
     _lib.check(code, 'sample_points_backward')
-    g_planes = d_planes.permute(0, 1, 4, 2, 3)                    # [N, 3, 32, H, W] view of the channels-last gradient
-    if planes.dim() == 5 and planes.is_contiguous():
-        g_planes = g_planes.contiguous()
-    return g_planes, _decoder_param_grads(decoder, nets, d_dec)
+    return _plane_grad(d_planes, planes), _decoder_param_grads(decoder, nets, d_dec)
 
 
 class _FusedPointsFn(torch.autograd.Function):
@@ -769,9 +740,7 @@ def fused_render_backward(planes, decoder, ray_origins, ray_directions, opt, u_c
     dev = planes.device
     ctx = _FusedContext(planes, info)
     packed_bwd = _pack_decoder_bwd(nets, lr_mul, dev)
-    auto = t_start is not None
-    t0 = _f32c(t_start).reshape(-1) if auto else None
-    t1 = _f32c(t_end).reshape(-1) if auto else None
+    t0, t1 = _flat_limits(t_start), _flat_limits(t_end)
     ro, rd, uc, uf = _f32c(ray_origins), _f32c(ray_directions), _f32c(u_coarse), _f32c(u_fine)
     gf = _f32c(g_feat)
     gw = None if g_wsum is None else _f32c(g_wsum).reshape(-1)
@@ -779,26 +748,24 @@ def fused_render_backward(planes, decoder, ray_origins, ray_directions, opt, u_c
     tape_s = torch.empty([n * m, s_all, 4], dtype=torch.float32, device=dev)
     d_planes = torch.empty([n, 3, ctx.h, ctx.w, 32], dtype=torch.float32, device=dev)
     d_dec = torch.empty([lib.p3d_render_grad_decoder_floats()], dtype=torch.float32, device=dev)
-    d = ctx.desc(opt, rays_per_img=m, start=0.0 if auto else opt['ray_start'], end=0.0 if auto else opt['ray_end'], raster=True)
+    d = ctx.desc(opt, rays_per_img=m, numeric_limits=t0 is None, raster=1)
     code = lib.p3d_render_backward(_lib.ptr(ctx.planes_cl), _lib.ptr(ctx.packed), _lib.ptr(packed_bwd), _lib.ptr(ro), _lib.ptr(rd), _lib.ptr(uc), _lib.ptr(uf),
                                    _lib.ptr(t0), _lib.ptr(t1), ctypes.byref(d), _lib.ptr(gf), _lib.ptr(gw), _lib.ptr(tape_i), _lib.ptr(tape_s),
                                    _lib.ptr(d_planes), _lib.ptr(d_dec), _lib.stream_of(d_planes))
     _lib.check(code, 'render_backward')
-    g_planes = d_planes.permute(0, 1, 4, 2, 3)                    # [N, 3, 32, H, W] view of the channels-last gradient
-    if planes.dim() == 5 and planes.is_contiguous():
-        g_planes = g_planes.contiguous()
-    g_params = _decoder_param_grads(decoder, nets, d_dec)
+    g_planes, g_params = _plane_grad(d_planes, planes), _decoder_param_grads(decoder, nets, d_dec)
     if debug:                                                     # the per-sample tape: z, colour weight, dL/dsigma (tests)
         return g_planes, g_params, tape_s
     return g_planes, g_params
 
 
-def fused_render(planes, decoder, ray_origins, ray_directions, opt, u_coarse, u_fine, t_start=None, t_end=None, debug=False, exact_fp32=False, packed=None):
+def fused_render(planes, decoder, ray_origins, ray_directions, opt, u_coarse, u_fine, t_start=None, t_end=None, debug=False, exact_fp32=False):
     """One launch of the fused ray-marcher with explicit uniforms (u_coarse [N,M,Sc(,1)], u_fine [N*M,Sf]).
     ``planes`` of batch 1 with N > 1 ray sets is the SHARED-PLANE launch (P3D_RENDER_SHARED_PLANES): all N ray sets read the one plane set — a zero image
     stride — with the schedule and the launch-wide depth clamp of a batch of N, exactly as if the planes had been repeated N times, without the copies.
     Returns (feat [N,M,C], depth [N,M,1], wsum [N,M,1]) and, with debug, the sorted fine depths [N*M,Sf] and the
-    coarse weights [N*M,Sc-1] the kernel used; with debug='bins' also the searchsorted index of every draw [N*M,Sf] (int32, draw order)."""
+    coarse weights [N*M,Sc-1] the kernel used; with debug='bins' also the searchsorted index of every draw [N*M,Sf] (int32, draw order).
+    None when the library reports the sample counts unsupported."""
     info = _decoder_nets(decoder)
     if info is None:
         raise RuntimeError(f'fused_render: unsupported decoder {type(decoder).__name__}')
@@ -808,21 +775,16 @@ def fused_render(planes, decoder, ray_origins, ray_directions, opt, u_coarse, u_
     dev = planes.device
     from pix2pix3d_amd.torch_utils.ops import modconv
     mode = 1 if (mlp_bf16x3 and not exact_fp32) else (2 if (mlp_l1x6 and modconv.f32_x6) else 0)      # (the training forward stays fp32-accurate: its backward recomputes in fp32)
-    ctx = _FusedContext(planes, info, bf16x3=mode, packed=packed)
-    auto = t_start is not None
-    t0 = _f32c(t_start).reshape(-1) if auto else None
-    t1 = _f32c(t_end).reshape(-1) if auto else None
+    ctx = _FusedContext(planes, info, bf16x3=mode)
+    t0, t1 = _flat_limits(t_start), _flat_limits(t_end)
     ro, rd, uc, uf = _f32c(ray_origins), _f32c(ray_directions), _f32c(u_coarse), _f32c(u_fine)
     assert uc.numel() == n * m * sc and uf.numel() == n * m * sf
-    feat = torch.empty([n, m, 32 * ctx.n_nets], device=dev, dtype=torch.float32)
-    depth = torch.empty([n, m, 1], device=dev, dtype=torch.float32)
-    wsum = torch.empty([n, m, 1], device=dev, dtype=torch.float32)
-    mm = torch.empty([2], device=dev, dtype=torch.int32)
+    feat, depth, wsum, mm = _ray_outputs(n, m, 32 * ctx.n_nets, dev)
     dbg_f = torch.empty([n * m, sf], device=dev, dtype=torch.float32) if debug else None
     dbg_w = torch.empty([n * m, sc - 1], device=dev, dtype=torch.float32) if debug else None
     dbg_b = torch.empty([n * m, sf], device=dev, dtype=torch.int32) if debug == 'bins' else None
-    # raster=True is a pure scheduling hint; P3D_RENDER_SHARED_PLANES (2): the N ray sets all read the one plane set, each keeping its own R x R raster
-    d = ctx.desc(opt, rays_per_img=m, start=0.0 if auto else opt['ray_start'], end=0.0 if auto else opt['ray_end'], raster=3 if shared else True, n_img=n)
+    # raster 1 is a pure scheduling hint; + P3D_RENDER_SHARED_PLANES (2): the N ray sets all read the one plane set, each keeping its own R x R raster
+    d = ctx.desc(opt, rays_per_img=m, numeric_limits=t0 is None, raster=3 if shared else 1, n_img=n)
     with _lib.kernel_timer('render_forward', feat):
         if dbg_b is not None:
             code = _lib.lib().p3d_render_forward_debug(_lib.ptr(ctx.planes_cl), _lib.ptr(ctx.packed), _lib.ptr(ro), _lib.ptr(rd), _lib.ptr(uc), _lib.ptr(uf),
@@ -838,3 +800,32 @@ def fused_render(planes, decoder, ray_origins, ray_directions, opt, u_coarse, u_
     if dbg_b is not None:
         return feat, depth, wsum, dbg_f, dbg_w, dbg_b
     return (feat, depth, wsum, dbg_f, dbg_w) if debug else (feat, depth, wsum)
+
+
+def fused_render_dual(planes_texture, planes_semantic, decoder_texture, decoder_semantic, ray_origins, ray_directions, opt, u_coarse, u_fine, t_start=None, t_end=None):
+    """``fused_render`` over two plane sets (p3d_render_forward_dual, csrc/render_device.h): both sets are gathered per sample, the colour net's first
+    layer takes its 64 inputs as two 32-wide MFMA blocks.  feat [N,M,64] = cat(colour, label).  Inference only; no shared-plane form."""
+    n, m, _ = ray_origins.shape
+    ctx = _FusedContext(planes_texture, _dual_decoder_nets(decoder_texture, decoder_semantic), planes_semantic=planes_semantic)
+    t0, t1 = _flat_limits(t_start), _flat_limits(t_end)
+    ro, rd, uc, uf = _f32c(ray_origins), _f32c(ray_directions), _f32c(u_coarse), _f32c(u_fine)
+    feat, depth, wsum, mm = _ray_outputs(n, m, 64, ctx.packed.device)
+    d = ctx.desc(opt, rays_per_img=m, numeric_limits=t0 is None, raster=1)
+    code = _lib.lib().p3d_render_forward_dual(_lib.ptr(ctx.planes_cl), _lib.ptr(ctx.planes_semantic_cl), _lib.ptr(ctx.packed), _lib.ptr(ro), _lib.ptr(rd),
+                                              _lib.ptr(uc), _lib.ptr(uf), _lib.ptr(t0), _lib.ptr(t1), ctypes.byref(d), _lib.ptr(feat), _lib.ptr(depth),
+                                              _lib.ptr(wsum), _lib.ptr(mm), _lib.stream_of(feat))
+    _lib.check(code, 'render_forward_dual')
+    return feat, depth, wsum
+
+
+def fused_sample_points_dual(planes_texture, planes_semantic, decoder_texture, decoder_semantic, coordinates, opt):
+    """``fused_sample_points`` over two plane sets (p3d_sample_points_dual): (cat(colour, label) [N,P,64], sigma [N,P,1])."""
+    n, p, _ = coordinates.shape
+    ctx = _FusedContext(planes_texture, _dual_decoder_nets(decoder_texture, decoder_semantic), planes_semantic=planes_semantic)
+    both = torch.empty([n, p, 64], device=ctx.packed.device, dtype=torch.float32)
+    sigma = torch.empty([n, p, 1], device=ctx.packed.device, dtype=torch.float32)
+    d = ctx.desc(opt, raster=1)                              # (the two-plane-set launches have always set the hint, point queries included)
+    code = _lib.lib().p3d_sample_points_dual(_lib.ptr(ctx.planes_cl), _lib.ptr(ctx.planes_semantic_cl), _lib.ptr(ctx.packed), _lib.ptr(_f32c(coordinates)),
+                                             ctypes.byref(d), p, _lib.ptr(both), _lib.ptr(sigma), _lib.stream_of(both))
+    _lib.check(code, 'sample_points_dual')
+    return both, sigma

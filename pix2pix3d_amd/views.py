@@ -247,23 +247,7 @@ def video_cameras(G, cfg='seg2cat', n_frames=120):
 
 
 # ---- many views ---------------------------------------------------------------------------------------------------------------
-class _frozen_draws(rmod._replay_draws):
-    """``_replay_draws`` for one chunk: hands the renderer's two draws back as logical [n, M, Sc, 1] / [n * M, Sf] tensors whichever way a route asks for
-    them (the tensor-limits branch of the fused route draws [Sc, n, M, 1] and permutes, renderer.py:184-186)."""
-
-    def __enter__(self):
-        self._rl, self._r = torch.rand_like, torch.rand
-        it = iter(self.draws)
-
-        def rand(*size, **kw):
-            size = tuple(size[0]) if len(size) == 1 and isinstance(size[0], (list, tuple, torch.Size)) else tuple(size)
-            u = next(it)
-            if u.ndim == 4 and size == (u.shape[2], u.shape[0], u.shape[1], 1) and size != tuple(u.shape):
-                return u.permute(2, 0, 1, 3)
-            return u.reshape(size)
-        torch.rand_like = lambda t, *a, **k: next(it).to(t.device).reshape(t.shape)
-        torch.rand = rand
-        return self
+_frozen_draws = rmod._replay_draws      # (one chunk's draws: logical [n, M, Sc, 1] / [n * M, Sf], whichever way a route asks for them)
 
 
 @torch.no_grad()
