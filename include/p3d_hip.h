@@ -639,6 +639,34 @@ typedef struct p3d_frame_job {
 } p3d_frame_job;
 int p3d_frame_finish(const p3d_frame_job* jobs_host, int32_t n_jobs, p3d_stream_t stream);
 
+/* ---- edit sessions (csrc/edit_ops.hip; pix2pix3d_amd/edit.py) -----------------------------------
+ * p3d_paint_strokes: every brush stroke of a session into a uint8 label map in ONE launch — the demo's make_mask, a cv2.line per stroke over a
+ * numpy mask followed by a host-to-device copy (applications/demo/qt_demo_seg2cat.py:459-463, called for every label at :432-433).
+ *   base    uint8 [h][w], rows base_row_pitch bytes apart; dst the same with its own pitch, a different buffer: every pixel of dst is written
+ *           exactly once, with the base value or the label of the LAST stroke in table order that covers it (= painting the strokes in order).
+ *   strokes int32 [n_strokes][6] = (x0, y0, x1, y1, thickness, label) on the device, contiguous; n_strokes = 0 copies base.
+ * Coverage is defined in integers (cv2's polygon fill is not specified): with d = b - a, p = pixel - a, L = d.d, s = p.d and t the thickness,
+ *   s <= 0: 4 |p|^2 <= t^2;   s >= L: 4 |p - d|^2 <= t^2;   otherwise: 4 (p x d)^2 <= t^2 L
+ * — the capsule of radius t / 2 about the segment; a zero-length stroke is a disc.  The caller keeps 1 <= t <= 255, 0 <= label <= 255 and the
+ * endpoints in [P3D_PAINT_MIN_COORD, P3D_PAINT_MAX_COORD] (the table is device memory: pix2pix3d_amd/edit.py checks them on the host); with
+ * h, w <= P3D_PAINT_MAX_SIZE these keep 4 (p x d)^2 below 2^60.  Values outside them cannot make the kernel leave the mask.
+ *
+ * p3d_label_features: a uint8 label map straight to the activations of the Encoder's first layer.  For a one-hot image b{res}.fromrgb (1x1
+ * convolution, bias, lrelu; training/networks_stylegan2.py DiscriminatorBlock) is a lookup, out[i, :, y, x] = table[min(mask[i, y, x], n_labels)]:
+ *   mask  uint8 [n][h][w], frames / rows mask_frame_pitch / mask_row_pitch bytes apart;
+ *   table fp32 [n_labels + 1][c] contiguous on the device: row k the layer's output for label k, row n_labels its output for an all-zero pixel
+ *         (what every byte >= n_labels reads); c % 4 == 0, 1 <= n_labels <= 255, (n_labels + 1) * (c + 4) + 4 c floats within 64 KB;
+ *   out   [n][c][h][w] fp32 (P3D_F32) or fp16 (P3D_F16, round to nearest even) through the four ELEMENT strides out_stride = (n, c, y, x):
+ *         16-byte stores along c (channels-last) or x (planar) where pointer and strides allow, single elements otherwise.                      */
+#define P3D_PAINT_MAX_SIZE 4096
+#define P3D_PAINT_MAX_STROKES 65535
+#define P3D_PAINT_MIN_COORD (-4096)
+#define P3D_PAINT_MAX_COORD 8191
+int p3d_paint_strokes(const uint8_t* base, int64_t base_row_pitch, uint8_t* dst, int64_t dst_row_pitch, int32_t h, int32_t w,
+                      const int32_t* strokes, int32_t n_strokes, p3d_stream_t stream);
+int p3d_label_features(const uint8_t* mask, int64_t mask_frame_pitch, int64_t mask_row_pitch, const float* table, int32_t n_labels,
+                       void* out, int32_t dtype, const int64_t* out_stride, int32_t n, int32_t c, int32_t h, int32_t w, p3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,9 @@ _SIGNATURES = {
                                    ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64),
                                    _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_float, _c_void_p]),
     'p3d_frame_finish': (_c_int, [_c_void_p, _c_i32, _c_void_p]),      # (host array of p3d_frame_job: pix2pix3d_amd/views.py)
+    'p3d_paint_strokes': (_c_int, [_c_void_p, _c_i64, _c_void_p, _c_i64, _c_i32, _c_i32, _c_void_p, _c_i32, _c_void_p]),      # (pix2pix3d_amd/edit.py)
+    'p3d_label_features': (_c_int, [_c_void_p, _c_i64, _c_i64, _c_void_p, _c_i32, _c_void_p, _c_i32, ctypes.POINTER(_c_i64),
+                                    _c_i32, _c_i32, _c_i32, _c_i32, _c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,414 @@
+"""Interactive editing: the compute core of the reference's ``applications/demo/qt_demo_seg2cat.py`` — paint on a label map, see the 3-D result, turn the
+camera, take the rendered label map of the new view back as the canvas, paint again — as a library (no UI).
+
+Per event the demo repaints every stroke ever drawn with ``cv2.line`` on the host and copies the mask to the device, builds the int64 one-hot image, runs the
+whole ``G.mapping`` and then the whole ``G.synthesis`` — also when only a camera slider moved and the planes cannot have changed — and finishes the frame in numpy
+with a Python loop over 512^2 pixels (:343-399, 429-463).  ``EditSession`` keeps each stage's result until its input changes:
+
+    mask (base + stroke log, ONE ``p3d_paint_strokes`` launch)  ->  geometry ws (``p3d_label_features`` + Encoder)  ->  planes (backbone)  ->  frame
+
+    s = edit.EditSession(G, cfg='seg2cat', seed=0)
+    s.load(mask, pose)                                    # uint8 [512, 512] label map, [25] camera label of the dataset item
+    s.paint([(200, 260, 300, 250, 35, 2)])                # (x0, y0, x1, y1, thickness, label); one call = one undo step
+    frame = s.frame()                                     # {'image' [H,W,3], 'label' [H,W,3], 'label_index' [H,W]} uint8 numpy
+    s.set_camera(yaw=60, pitch=50)                        # slider units; only the ray-marcher, the heads and the finishing launch run
+    s.render()                                            # the same dict as device tensors
+    s.take_view_as_mask()                                 # cross-view edit: the rendered label map becomes the canvas
+    s.paint([(250, 300, 260, 340, 20, 4)]); s.undo(); s.save('out/')
+
+Stroke coverage (identical bytes on the device kernel and in the torch formulation CPU tensors take).  cv2's polygon fill is not specified, so the rule is
+integer: with d = b - a, p = pixel - a, L = d.d, s = p.d, thickness t, all int64, a pixel is covered iff
+    s <= 0: 4 |p|^2 <= t^2;    s >= L: 4 |p - d|^2 <= t^2;    otherwise: 4 (p x d)^2 <= t^2 L
+— the capsule of radius t / 2 about the segment; a zero-length stroke is a disc; t = 1 strokes are 8-connected and hold both endpoints.  The last stroke in
+table order that covers a pixel gives it its label.  Limits (ValueError before any launch): 1 <= t <= 255, 0 <= label <= 255, H, W <= 4096, endpoints in
+[-4096, 8191], at most 65 535 strokes; they keep 4 (p x d)^2 below 2^60.
+
+The fast label entry exists for ``MaskMappingNetwork_disentangle`` with ``one_hot=True`` and a 'resnet' Encoder.  ``one_hot=False`` masks, the edge networks
+and the entangled mapping networks have float conditioning images (no table): a session serves them through the ordinary ``G.mapping``, staleness tracking unchanged.
+"""
+import contextlib
+import copy
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import _lib, mesh, views
+
+MAX_SIZE, MAX_STROKES, MIN_COORD, MAX_COORD = 4096, 65535, -4096, 8191         # P3D_PAINT_* (include/p3d_hip.h)
+SLIDER_RANGE = dict(yaw=math.pi / 2, pitch=math.pi, roll=math.pi / 4)         # radians per 100 slider units (qt_demo_seg2cat.py:374-379)
+DEMO_RADIUS = 2.7                                                              # (:381)
+FORWARD_FOCAL = 4.2647                                                         # (:439)
+TEXTURE_FROM = 8                                                               # ws[:, 8:] is the demo's ws_texture (:446-449)
+
+
+# ---- strokes ------------------------------------------------------------------------------------------------------------------
+def stroke_table(strokes):
+    """``strokes`` (sequence / array / tensor of (x0, y0, x1, y1, thickness, label)) as a checked int32 [K, 6] CPU tensor."""
+    t = torch.as_tensor(np.asarray(strokes.cpu() if torch.is_tensor(strokes) else strokes))
+    if t.numel() == 0:
+        return torch.zeros([0, 6], dtype=torch.int32)
+    if t.is_floating_point() or t.dtype == torch.bool or t.ndim != 2 or t.shape[1] != 6:
+        raise ValueError(f'strokes must be integers [K, 6] = (x0, y0, x1, y1, thickness, label), got {t.dtype} {tuple(t.shape)}')
+    t = t.to(torch.int64)
+    if t.shape[0] > MAX_STROKES:
+        raise ValueError(f'at most {MAX_STROKES} strokes per mask, got {t.shape[0]}')
+    xy, th, lab = t[:, :4], t[:, 4], t[:, 5]
+    if int(xy.min()) < MIN_COORD or int(xy.max()) > MAX_COORD:
+        raise ValueError(f'stroke endpoints must lie in [{MIN_COORD}, {MAX_COORD}]')
+    if int(th.min()) < 1 or int(th.max()) > 255:
+        raise ValueError('stroke thickness must be 1 .. 255')
+    if int(lab.min()) < 0 or int(lab.max()) > 255:
+        raise ValueError('stroke labels must be 0 .. 255')
+    return t.to(torch.int32).contiguous()
+
+
+def _check_mask(mask, what):
+    if not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.ndim != 2 or mask.stride(1) != 1 or mask.stride(0) < mask.shape[1]:
+        raise ValueError(f'{what} must be a uint8 [H, W] tensor with contiguous rows')
+    h, w = mask.shape
+    if not (1 <= h <= MAX_SIZE and 1 <= w <= MAX_SIZE):
+        raise ValueError(f'{what}: 1 .. {MAX_SIZE} pixels a side, got {h} x {w}')
+    return h, w
+
+
+def _paint_cpu(out, table):
+    """The torch formulation of the coverage rule, stroke after stroke, each inside its bounding box (identical bytes)."""
+    h, w = out.shape
+    for x0, y0, x1, y1, t, label in table.tolist():
+        r = (t + 1) // 2
+        xa, xb, ya, yb = max(min(x0, x1) - r, 0), min(max(x0, x1) + r, w - 1), max(min(y0, y1) - r, 0), min(max(y0, y1) + r, h - 1)
+        if xa > xb or ya > yb:
+            continue
+        px = torch.arange(xa, xb + 1, dtype=torch.int64)[None, :] - x0
+        py = torch.arange(ya, yb + 1, dtype=torch.int64)[:, None] - y0
+        dx, dy = x1 - x0, y1 - y0
+        big_l, s, t2 = dx * dx + dy * dy, px * dx + py * dy, t * t
+        cross = px * dy - py * dx
+        cov = torch.where(s <= 0, 4 * (px * px + py * py) <= t2,
+                          torch.where(s >= big_l, 4 * ((px - dx) ** 2 + (py - dy) ** 2) <= t2, 4 * cross * cross <= t2 * big_l))
+        out[ya:yb + 1, xa:xb + 1][cov] = label
+
+
+def paint_strokes(base, strokes, out=None):
+    """``base`` uint8 [H, W] (rows may be a view of a larger canvas) with ``strokes`` painted in table order -> ``out`` (a new tensor, or the caller's uint8
+    [H, W] view, written out of place; bytes around it stay untouched).  Device tensors: ONE ``p3d_paint_strokes`` launch (the checked table is copied to the
+    device); CPU tensors: the torch formulation."""
+    h, w = _check_mask(base, 'base')
+    table = stroke_table(strokes)
+    if out is None:
+        out = torch.empty([h, w], dtype=torch.uint8, device=base.device)
+    elif _check_mask(out, 'out') != (h, w) or out.device != base.device:
+        raise ValueError(f'out must be uint8 {h} x {w} on {base.device}')
+    if out.data_ptr() == base.data_ptr():
+        raise ValueError('paint_strokes writes out of place: out must not be base')
+    if not base.is_cuda:
+        out.copy_(base)
+        _paint_cpu(out, table)
+        return out
+    dev_table = table.to(base.device) if len(table) else None
+    with _lib.kernel_timer('paint_strokes', out):
+        code = _lib.lib().p3d_paint_strokes(_lib.ptr(base), base.stride(0), _lib.ptr(out), out.stride(0), h, w, _lib.ptr(dev_table), len(table), _lib.stream_of(out))
+    _lib.check(code, 'paint_strokes')
+    return out
+
+
+def replay_order(table, replay):
+    """'time': as drawn.  'label': all strokes of label 0, then label 1, ... each in the order drawn — the demo's ``for i in range(6): make_mask`` (:432-433)."""
+    if replay not in ('time', 'label'):
+        raise ValueError(f"replay must be 'time' or 'label', got {replay!r}")
+    if replay == 'time' or len(table) == 0:
+        return table
+    return table[torch.sort(table[:, 5], stable=True).indices]
+
+
+# ---- label entry ----------------------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def label_table(fromrgb, n_labels):
+    """float32 [n_labels + 1, C] on the CPU: ``fromrgb`` (the Encoder's first 1x1 ``Conv2dLayer``) applied in fp32 to the n_labels one-hot pixels and, row
+    n_labels, to an all-zero pixel.  Made by the layer itself, so its gains, bias, activation and clamp are carried, not restated."""
+    if fromrgb.in_channels != n_labels or tuple(fromrgb.weight.shape[2:]) != (1, 1) or fromrgb.up != 1 or fromrgb.down != 1:
+        raise ValueError(f'label_table: needs the 1x1 layer over {n_labels} label channels, got {fromrgb}')
+    layer = copy.deepcopy(fromrgb).to('cpu', torch.float32)
+    pixels = torch.cat([torch.eye(n_labels), torch.zeros(n_labels, 1)], dim=1).reshape(1, n_labels, 1, n_labels + 1)
+    return layer(pixels)[0, :, 0, :].t().contiguous()
+
+
+def label_features(mask, table, dtype=torch.float32, memory_format=torch.contiguous_format):
+    """``fromrgb(one_hot(mask))`` without the one-hot image: mask uint8 [N, H, W] (any pitches, contiguous pixels), ``table`` = ``label_table`` on the mask's
+    device -> [N, C, H, W] ``dtype`` (fp32 / fp16) in ``memory_format``; out[n, :, y, x] = table[min(mask[n, y, x], L)].  Device tensors: one
+    ``p3d_label_features`` launch; CPU tensors: an index."""
+    if not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.ndim != 3 or mask.stride(2) != 1 or mask.numel() == 0:
+        raise ValueError('label_features: mask must be a non-empty uint8 [N, H, W] tensor with contiguous pixels')
+    if table.dtype != torch.float32 or table.ndim != 2 or table.shape[0] < 2 or table.shape[0] > 256 or table.shape[1] % 4 or table.device != mask.device:
+        raise ValueError(f'label_features: table must be float32 [L + 1, C] (1 <= L <= 255, C % 4 == 0) on {mask.device}, got {table.dtype} {tuple(table.shape)} on {table.device}')
+    if dtype not in (torch.float32, torch.float16):
+        raise ValueError(f'label_features: dtype must be float32 or float16, got {dtype}')
+    n, h, w = mask.shape
+    n_labels, c = table.shape[0] - 1, table.shape[1]
+    if mask.stride(1) < w or (n > 1 and mask.stride(0) < h * mask.stride(1)):
+        raise ValueError('label_features: overlapping mask rows / frames')
+    if not mask.is_cuda:
+        y = table[mask.long().clamp(max=n_labels)].permute(0, 3, 1, 2).to(dtype)
+        return y.contiguous(memory_format=memory_format)
+    out = torch.empty([n, c, h, w], dtype=dtype, device=mask.device, memory_format=memory_format)
+    table = table.contiguous()
+    with _lib.kernel_timer('label_features', out):
+        code = _lib.lib().p3d_label_features(_lib.ptr(mask), mask.stride(0), mask.stride(1), _lib.ptr(table), n_labels, _lib.ptr(out), _lib.DTYPE_CODE[dtype],
+                                             _lib.i64x4(*out.stride()), n, c, h, w, _lib.stream_of(out))
+    _lib.check(code, 'label_features')
+    return out
+
+
+# ---- cameras ------------------------------------------------------------------------------------------------------------------
+def camera_from_euler(roll, yaw, pitch, radius=DEMO_RADIUS):
+    """float32 [4, 4] cam2world of the demo's sliders in radians (:80-86, 381): the rotation ``Rotation.from_euler('zyx', [roll, yaw, pitch + pi])`` —
+    Rx(pitch + pi) Ry(yaw) Rz(roll) — with the camera ``radius`` behind the origin along its own viewing axis."""
+    a, b, c = float(roll), float(yaw), float(pitch) + math.pi
+    rz = np.array([[math.cos(a), -math.sin(a), 0], [math.sin(a), math.cos(a), 0], [0, 0, 1]])
+    ry = np.array([[math.cos(b), 0, math.sin(b)], [0, 1, 0], [-math.sin(b), 0, math.cos(b)]])
+    rx = np.array([[1, 0, 0], [0, math.cos(c), -math.sin(c)], [0, math.sin(c), math.cos(c)]])
+    m = np.eye(4)
+    m[:3, :3] = rx @ ry @ rz
+    m[:3, 3] = -m[:3, 2] * float(radius)
+    return torch.from_numpy(m).to(torch.float32)
+
+
+def slider_angles(yaw=0.0, pitch=0.0, roll=0.0):
+    """The demo's slider units (range per 100: yaw pi/2, pitch pi, roll pi/4; :374-379) -> (roll, yaw, pitch) in radians, ``camera_from_euler``'s order."""
+    return (roll / 100 * SLIDER_RANGE['roll'], yaw / 100 * SLIDER_RANGE['yaw'], pitch / 100 * SLIDER_RANGE['pitch'])
+
+
+def forward_label(G):
+    """float32 [1, 25]: the forward-facing conditioning pose the demo maps z with (:437-441)."""
+    rk = G.rendering_kwargs
+    pose = mesh.turntable_poses(rk['avg_camera_pivot'], rk['avg_camera_radius'], n_frames=1, yaw0=3.14 / 2, yaw_range=0.0, pitch_range=0.0, pitch0=3.14 / 2)
+    f = FORWARD_FOCAL
+    return views.camera_labels(pose, torch.tensor([[f, 0, 0.5], [0, f, 0.5], [0, 0, 1]], dtype=torch.float32))
+
+
+# ---- the session ----------------------------------------------------------------------------------------------------------------
+class EditSession:
+    """One editing session on the device ``G`` lives on; every method runs under ``torch.no_grad()``.
+
+    Four stages, each recomputed only when its input changed: mask -> geometry ws -> planes -> frame.  ``paint`` / ``undo`` / ``clear`` / ``load`` /
+    ``take_view_as_mask`` dirty the mask; ``set_seed`` / ``clear_texture`` the ws; a camera change only the frame: ``render()`` after it is
+    ``G.synthesis(ws, c, use_cached_backbone=True)`` on the kept planes and ``views.finish_frames`` — neither the Encoder nor the backbone runs.
+
+    cfg            a key of ``views.VIDEO_CFG``: the ray resolution (``neural_rendering_resolution`` overrides it).
+    truncation_psi as ``G.mapping``'s.
+    jitter         'frozen' (one set of stratified draws for the whole session: a frame changes only with its inputs), 'random', or a pair of draws, as
+                   ``views.render_views``.
+    hold_texture   keep ``ws[:, 8:]`` of the first ``encode()`` until ``clear_texture()`` — the demo's ``ws_texture`` (:446-449).
+    replay         'time': strokes in the order drawn; 'label': the demo's order, label by label (:432-433)."""
+
+    def __init__(self, G, cfg='seg2cat', seed=0, truncation_psi=1, jitter='frozen', hold_texture=True, replay='time', neural_rendering_resolution=None,
+                 palette=None):
+        if cfg not in views.VIDEO_CFG:
+            raise ValueError(f'EditSession: cfg must be one of {sorted(views.VIDEO_CFG)}, got {cfg!r}')
+        if not hasattr(G, 'backbone_planes') or not hasattr(G, 'mapping_label') or not hasattr(G, 'semantic_channels') or G.semantic_channels < 2:
+            raise TypeError(f'EditSession: {type(G).__name__} is not a label-map generator on the one-backbone tri-plane core')
+        replay_order(torch.zeros([0, 6], dtype=torch.int32), replay)
+        self.G, self.cfg, self.truncation_psi, self.hold_texture, self.replay = G, cfg, truncation_psi, hold_texture, replay
+        self.device = next(G.parameters()).device
+        self.nrr = int(views.VIDEO_CFG[cfg]['neural_rendering_resolution'] if neural_rendering_resolution is None else neural_rendering_resolution)
+        self.n_labels = int(G.semantic_channels)
+        self.palette = mesh.default_palette(self.n_labels) if palette is None else torch.as_tensor(palette)
+        if self.device.type == 'cuda':
+            self.palette = self.palette.to(self.device)                        # read in place by every finishing launch
+        mapping = G.backbone.mapping
+        self.fast_entry = hasattr(mapping, 'geometry_ws') and getattr(mapping, 'one_hot', False) and mapping.embed_mask.architecture == 'resnet' \
+            and not mapping.embed_mask.progressive
+        self._table = None
+        if self.fast_entry:
+            enc = mapping.embed_mask
+            self._table = label_table(getattr(enc, f'b{enc.block_resolutions[0]}').fromrgb, self.n_labels).to(self.device)
+        rk = G.rendering_kwargs
+        m, sc, sf = self.nrr * self.nrr, int(rk['depth_resolution']), int(rk['depth_resolution_importance'])
+        if isinstance(jitter, (tuple, list)):
+            self._draws = tuple(torch.as_tensor(u, dtype=torch.float32).to(self.device) for u in jitter)
+            if tuple(self._draws[0].shape) != (1, m, sc, 1) or tuple(self._draws[1].shape) != (m, sf):
+                raise ValueError(f'EditSession: frozen draws must be [1, {m}, {sc}, 1] and [{m}, {sf}]')
+        elif jitter == 'frozen':
+            self._draws = (torch.rand([1, m, sc, 1], device=self.device), torch.rand([m, sf], device=self.device))
+        elif jitter == 'random':
+            self._draws = None
+        else:
+            raise ValueError(f"EditSession: jitter must be 'frozen', 'random' or a pair of draws, got {jitter!r}")
+        self._forward_c = G.mapping_label(forward_label(G).to(self.device))
+        self._base = self._pose = self._intrinsics = self._cam2world = None
+        self._log = []                                                         # one checked int32 [k, 6] table per paint() call
+        self._mask = self._geometry = self._ws = self._held = self._planes = self._frame = self._floats = None
+        self._appearance = {}                                                  # seed -> [1, w_dim]
+        self.seed = int(seed)
+
+    # -- inputs ---------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def load(self, mask, pose):
+        """``mask`` uint8 [H, W] (numpy or tensor), H = W = the mapping network's ``in_resolution``, every label < ``semantic_channels`` (checked here, once, on
+        the host); ``pose`` [25]: the item's camera label — its intrinsics serve every later camera (:335) and it is the first camera."""
+        mask = torch.as_tensor(mask)
+        res = int(self.G.backbone.mapping.in_resolution)
+        if mask.dtype != torch.uint8 or tuple(mask.shape) != (res, res):
+            raise ValueError(f'load: mask must be uint8 [{res}, {res}], got {mask.dtype} {tuple(mask.shape)}')
+        if int(mask.max()) >= self.n_labels:
+            raise ValueError(f'load: label {int(mask.max())} in a mask of {self.n_labels} labels')
+        pose = torch.as_tensor(pose, dtype=torch.float32).reshape(-1)
+        if pose.numel() != 25:
+            raise ValueError(f'load: pose must hold 25 floats, got {pose.numel()}')
+        self._base = mask.to(self.device).contiguous()
+        self._pose = pose.to(self.device).reshape(1, 25)
+        self._intrinsics = self._pose[:, 16:25].reshape(3, 3)
+        self._cam2world = self._pose[:, :16].reshape(4, 4)
+        self._log = []
+        self._dirty_mask()
+        self._frame = None
+
+    def set_seed(self, seed):
+        if int(seed) != self.seed:
+            self.seed = int(seed)
+            self._dirty_ws()
+
+    def clear_texture(self):
+        """Release the held ``ws[:, 8:]``: the next ``encode()`` takes the appearance rows of the current seed and holds those."""
+        self._held = None
+        self._dirty_ws()
+
+    # -- painting ---------------------------------------------------------------------------------------------------------------
+    def paint(self, strokes):
+        """Append strokes (x0, y0, x1, y1, thickness, label) to the log; one call is one undo step."""
+        table = stroke_table(strokes)
+        if len(table) and int(table[:, 5].max()) >= self.n_labels:
+            raise ValueError(f'paint: label {int(table[:, 5].max())} in a mask of {self.n_labels} labels')
+        if sum(len(t) for t in self._log) + len(table) > MAX_STROKES:
+            raise ValueError(f'paint: more than {MAX_STROKES} strokes in the log; take_view_as_mask() or clear() starts a new one')
+        if len(table):
+            self._log.append(table)
+            self._dirty_mask()
+
+    def undo(self):
+        if self._log:
+            self._log.pop()
+            self._dirty_mask()
+
+    def clear(self):
+        if self._log:
+            self._log = []
+            self._dirty_mask()
+
+    @property
+    def strokes(self):
+        """The log as one int32 [K, 6] CPU table, in the order the mask is painted in."""
+        table = torch.cat(self._log) if self._log else torch.zeros([0, 6], dtype=torch.int32)
+        return replay_order(table, self.replay)
+
+    @property
+    @torch.no_grad()
+    def mask(self):
+        """uint8 [H, W] on the device: the base with the log painted into it (one launch when the log changed; the base itself while the log is empty)."""
+        self._need_load()
+        if self._mask is None:
+            self._mask = paint_strokes(self._base, self.strokes) if self._log else self._base
+        return self._mask
+
+    # -- cameras ----------------------------------------------------------------------------------------------------------------
+    def set_camera(self, yaw=0.0, pitch=0.0, roll=0.0, radius=DEMO_RADIUS):
+        """The demo's three sliders (units of 1/100 of pi/2, pi and pi/4)."""
+        self.set_pose(camera_from_euler(*slider_angles(yaw, pitch, roll), radius=radius))
+
+    def set_pose(self, cam2world):
+        cam2world = torch.as_tensor(cam2world, dtype=torch.float32).reshape(4, 4).to(self.device)
+        self._need_load()
+        if not torch.equal(cam2world, self._cam2world):
+            self._cam2world = cam2world
+            self._frame = None
+
+    @property
+    def camera(self):
+        """float32 [1, 25]: the current pose with the loaded item's intrinsics."""
+        self._need_load()
+        return views.camera_labels(self._cam2world, self._intrinsics)
+
+    # -- stages -----------------------------------------------------------------------------------------------------------------
+    def _need_load(self):
+        if self._base is None:
+            raise RuntimeError('EditSession: load(mask, pose) first')
+
+    def _dirty_mask(self):
+        self._mask = self._geometry = None
+        self._dirty_ws()
+
+    def _dirty_ws(self):
+        self._ws = self._planes = self._frame = None
+
+    def _z(self):
+        return torch.from_numpy(np.random.RandomState(self.seed).randn(1, self.G.z_dim).astype('float32')).to(self.device)      # (:430)
+
+    @torch.no_grad()
+    def encode(self):
+        """``ws`` [1, num_ws, w_dim]: geometry rows from the mask, appearance rows from z(seed) under the forward-facing conditioning pose (cached per seed),
+        truncated as ``G.mapping`` does; with ``hold_texture`` rows 8.. are those of the first encode."""
+        if self._ws is not None:
+            return self._ws
+        mask, mapping = self.mask, self.G.backbone.mapping
+        if self.fast_entry:
+            from .training.networks_stylegan2 import truncate_ws
+            if self._geometry is None:
+                self._geometry = mapping.geometry_ws(mask[None], self._table)
+            if self.seed not in self._appearance:
+                self._appearance[self.seed] = mapping.appearance_w(self._z(), self._forward_c)
+            w = self._appearance[self.seed]
+            ws = torch.cat([self._geometry, w.unsqueeze(1).repeat([1, mapping.num_ws - mapping.geometry_layer, 1])], dim=1)
+            ws = truncate_ws(mapping, ws, self.truncation_psi, None)
+        else:
+            ws = self.G.mapping(self._z(), forward_label(self.G).to(self.device), {'mask': mask[None, None], 'pose': self._pose}, truncation_psi=self.truncation_psi)
+        if self.hold_texture:
+            if self._held is None:
+                self._held = ws[:, TEXTURE_FROM:].clone()
+            else:
+                ws = torch.cat([ws[:, :TEXTURE_FROM], self._held], dim=1)
+        self._ws = ws
+        return ws
+
+    @torch.no_grad()
+    def render(self, return_float=False):
+        """{'image' [H,W,3], 'label' [H,W,3], 'label_index' [H,W]} uint8 on the device — the demo's output image, its coloured label map and its
+        ``buffer_mask``; with ``return_float`` also 'float', the ``G.synthesis`` dict the frame was finished from."""
+        ws, G = self.encode(), self.G
+        if self._planes is None:
+            self._planes = G.backbone_planes(ws, noise_mode='const')
+        if self._frame is None:
+            found, G._last_planes = G._last_planes, self._planes
+            try:
+                draws = views._frozen_draws(self._draws[0], self._draws[1]) if self._draws is not None else contextlib.nullcontext()
+                with draws:
+                    out = G.synthesis(ws, self.camera, neural_rendering_resolution=self.nrr, use_cached_backbone=True, noise_mode='const')
+            finally:
+                G._last_planes = found
+            self._frame = {k: v[0] for k, v in views.finish_frames(out, palette=self.palette, label_mode='palette').items()}
+            self._floats = out
+        return dict(self._frame, float=self._floats) if return_float else dict(self._frame)
+
+    def frame(self):
+        """``render()`` on the host, as numpy arrays."""
+        return {k: v.cpu().numpy() for k, v in self.render().items()}
+
+    @torch.no_grad()
+    def take_view_as_mask(self):
+        """The cross-view edit (``get_mask``, :343-349): the label map of the last rendered view becomes the base, the log empties; nothing leaves the device."""
+        base = self.render()['label_index']
+        res = int(self.G.backbone.mapping.in_resolution)
+        if tuple(base.shape) != (res, res):
+            raise ValueError(f'take_view_as_mask: the rendered label map is {tuple(base.shape)}, the mapping network takes {res} x {res}')
+        self._base, self._log = base.clone(), []
+        self._dirty_mask()
+
+    def save(self, directory):
+        """The demo's three PNGs (:465-472): mask.png (labels), mask_color.png (palette colours), output.png (the rendered image)."""
+        from PIL import Image
+        os.makedirs(directory, exist_ok=True)
+        mask = self.mask.cpu()
+        Image.fromarray(mask.numpy()).save(os.path.join(directory, 'mask.png'))
+        Image.fromarray(self.palette.cpu()[mask.long()].numpy()).save(os.path.join(directory, 'mask_color.png'))
+        Image.fromarray(self.render()['image'].cpu().numpy()).save(os.path.join(directory, 'output.png'))

@@ -756,13 +756,21 @@ class DiscriminatorBlock(torch.nn.Module):
             self.skip = Conv2dLayer(tmp_channels, out_channels, kernel_size=1, bias=False, down=2, trainable=next(trainable),
                                     resample_filter=resample_filter, channels_last=self.channels_last)
 
-    def forward(self, x, img, force_fp32=False):
-        probe = img if x is None else x
+    def forward(self, x, img, force_fp32=False, feats=None):
+        """``feats``: what ``self.fromrgb(img)`` would return, computed by the caller (the label entry of an edit session: a label map's
+        one-hot image never has to exist); ``img`` is then not read.  'resnet' blocks that read the image only."""
+        if feats is not None and not (self.in_channels == 0 and self.architecture == 'resnet'):
+            raise ValueError(f"DiscriminatorBlock: feats stands in for fromrgb(img) in a 'resnet' block that reads the image; this is a "
+                             f"'{self.architecture}' block with {self.in_channels} input channels (the 'skip' pyramid needs img itself)")
+        probe = (img if feats is None else feats) if x is None else x
         dtype, fmt = self._working_format(probe, force_fp32)
         if x is not None:
             misc.assert_shape(x, [None, self.in_channels, self.resolution, self.resolution])
             x = x.to(dtype=dtype, memory_format=fmt)
-        if self.in_channels == 0 or self.architecture == 'skip':            # this block reads the image
+        if feats is not None:
+            misc.assert_shape(feats, [None, self.fromrgb.out_channels, self.resolution, self.resolution])
+            x, img = feats.to(dtype=dtype, memory_format=fmt), None
+        elif self.in_channels == 0 or self.architecture == 'skip':          # this block reads the image
             misc.assert_shape(img, [None, self.img_channels, self.resolution, self.resolution])
             img = img.to(dtype=dtype, memory_format=fmt)
             feats = self.fromrgb(img)

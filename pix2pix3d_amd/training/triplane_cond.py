@@ -124,7 +124,16 @@ class Encoder(torch.nn.Module):
                 block_resolutions = [res for res in self.block_resolutions if res <= lowres_head]
         return block_resolutions, alpha, lowres_head
 
-    def forward(self, inputs, **block_kwargs):
+    def forward(self, inputs, entry_features=None, **block_kwargs):
+        """``entry_features``: the first block's ``fromrgb(img)``, computed by the caller (``MaskMappingNetwork_disentangle.geometry_ws``); ``inputs`` is
+        then not read and may be None.  Full pyramid only."""
+        if entry_features is not None:
+            if self.progressive or self.predict_camera:
+                raise ValueError('Encoder: entry_features enters the full, non-progressive pyramid only')
+            x, img = None, None
+            for k, res in enumerate(self.block_resolutions):
+                x, img = getattr(self, f'b{res}')(x, img, **block_kwargs, **({'feats': entry_features} if k == 0 else {}))
+            return self._project(x)
         img = inputs['img'] if isinstance(inputs, dict) else inputs
         block_resolutions, alpha, lowres_head = self.get_block_resolutions(img)
         blending = self.progressive and (self.lowres_head is not None) and (-1 < self.alpha < 1) and (alpha > 0)
@@ -138,6 +147,9 @@ class Encoder(torch.nn.Module):
         x = None if (not self.progressive) or (block_resolutions[0] == self.img_resolution) else getattr(self, f'b{block_resolutions[0]}').fromrgb(img)
         for res in block_resolutions:
             x, img = getattr(self, f'b{res}')(x, img, **block_kwargs)
+        return self._project(x)
+
+    def _project(self, x):
         out = self.projector(x)[:, :, 0, 0]
         if self.output_mode == 'W+':
             out = out.reshape(out.shape[0], self.num_ws, self.w_dim)
@@ -252,8 +264,8 @@ class _DisentangledMapping(torch.nn.Module):
     def _condition_image(self, batch, n):
         raise NotImplementedError
 
-    def forward(self, z=None, c=None, batch=None, truncation_psi=1, truncation_cutoff=None, update_emas=False, **unused_kwargs):
-        """ws = [geometry ws from the conditioning image (Encoder, W+ mode)] ++ [the z / camera MLP's w, repeated]."""
+    def appearance_w(self, z, c):
+        """The z / camera MLP alone: [N, w_dim], the w that ``forward`` repeats over the appearance layers (before truncation)."""
         feats = []
         if self.z_dim > 0:
             misc.assert_shape(z, [None, self.z_dim])
@@ -264,7 +276,11 @@ class _DisentangledMapping(torch.nn.Module):
         x = torch.cat(feats, dim=1) if len(feats) > 1 else feats[0]
         for idx in range(self.num_layers):
             x = getattr(self, f'fc{idx}')(x)
+        return x
 
+    def forward(self, z=None, c=None, batch=None, truncation_psi=1, truncation_cutoff=None, update_emas=False, **unused_kwargs):
+        """ws = [geometry ws from the conditioning image (Encoder, W+ mode)] ++ [the z / camera MLP's w, repeated]."""
+        x = self.appearance_w(z, c)
         batch_size = z.shape[0]
         cond = self._condition_image(batch, batch_size)
         misc.assert_shape(cond, [batch_size, self.in_channels, self.in_resolution, self.in_resolution])
@@ -293,6 +309,27 @@ class MaskMappingNetwork_disentangle(_DisentangledMapping):
         if self.one_hot:
             return torch.nn.functional.one_hot(batch['mask'].squeeze(1).long(), self.in_channels).permute(0, 3, 1, 2)
         return batch['mask']
+
+    def geometry_ws(self, mask_u8, table=None):
+        """The geometry rows [N, 7, w_dim] of ``forward`` (before truncation) from a uint8 label map [N, H, W] without its one-hot image: the first
+        block's ``fromrgb`` over one-hot pixels is a table lookup (``edit.label_features``: one launch on the device), the rest of the Encoder runs
+        as always.  ``table`` is ``edit.label_table`` of that layer on the mask's device (an edit session makes it once); bytes >= in_channels
+        read the layer's answer to an all-zero pixel, where the one-hot route raises.  ``forward`` keeps the one-hot route.  There is no such
+        entry for ``one_hot=False`` masks, the edge networks or the entangled mapping networks (their images are float: no table) — sessions
+        serve those through the ordinary ``G.mapping``."""
+        from .. import edit
+        if not self.one_hot:
+            raise ValueError('geometry_ws: one_hot=False masks are float images to the Encoder; use forward')
+        misc.assert_shape(mask_u8, [None, self.in_resolution, self.in_resolution])
+        enc = self.embed_mask
+        block = getattr(enc, f'b{enc.block_resolutions[0]}')
+        if table is None:
+            table = edit.label_table(block.fromrgb, self.in_channels).to(mask_u8.device)
+        dtype, fmt = block._working_format(mask_u8, False)
+        feats = edit.label_features(mask_u8, table, dtype=dtype, memory_format=fmt)
+        geometry = enc(None, entry_features=feats)['ws']
+        misc.assert_shape(geometry, [None, self.geometry_layer, self.w_dim])
+        return geometry
 
 
 @persistence.persistent_class
@@ -398,11 +435,15 @@ class _TriPlaneBase(_TriPlaneCore):
     """The conditional generators' entry points: ``mapping`` / ``sample`` / ``forward`` take the data batch (label map + pose)."""
     _backbone_class = None      # Generator_cond, set below the class
 
-    @frozen_pass
-    def mapping(self, z, c, batch, truncation_psi=1, truncation_cutoff=None, update_emas=False):
+    def mapping_label(self, c):
+        """The camera label as ``mapping`` hands it to the mapping network."""
         if self.rendering_kwargs['c_gen_conditioning_zero']:
             c = torch.zeros_like(c)
-        return self.backbone.mapping(z, c * self.rendering_kwargs.get('c_scale', 0), batch, truncation_psi=truncation_psi,
+        return c * self.rendering_kwargs.get('c_scale', 0)
+
+    @frozen_pass
+    def mapping(self, z, c, batch, truncation_psi=1, truncation_cutoff=None, update_emas=False):
+        return self.backbone.mapping(z, self.mapping_label(c), batch, truncation_psi=truncation_psi,
                                      truncation_cutoff=truncation_cutoff, update_emas=update_emas)
 
     def sample(self, coordinates, directions, z, c, batch, truncation_psi=1, truncation_cutoff=None, update_emas=False, **synthesis_kwargs):
