@@ -340,6 +340,39 @@ int p3d_mesh_shade(const int32_t* face_id, const int32_t* proj, const float* ver
                    int32_t n_faces, const uint8_t* colors, const float* cameras, int32_t n_frames, int32_t orthographic, int32_t width, int32_t height,
                    float ambient, int32_t bg_r, int32_t bg_g, int32_t bg_b, uint8_t* rgb, p3d_stream_t stream);
 
+/* ---- mesh clean-up: connected components and vertex clustering (csrc/mesh_ops.hip; pix2pix3d_amd/mesh.py) --------------------------
+ * Meshes are indexed: faces int32 [T][3] into V vertices, V and T <= INT32_MAX - 1 (P3D_ERR_UNSUPPORTED beyond).  Marching cubes
+ * output is welded (one vertex per crossed lattice edge), so connectivity is read off the index buffer; positions are not hashed.
+ * Components: two vertices are connected when a face uses both.
+ *   p3d_mesh_components: label int32 [V] <- the SMALLEST vertex id of v's connected component.  A vertex no face uses is its own
+ *     component; a face with an index outside [0, V) is ignored.  Union-find: label[] starts as the identity, one thread per face
+ *     hooks the larger of two roots under the smaller with a 32-bit compare-and-swap (path halving while finding), a last pass
+ *     flattens every vertex to its root: three launches for any mesh.  Only roots are hooked and only under smaller ids, so each
+ *     tree's root is its component's minimum whatever the order of arrival: the result is a pure function of (faces, V), the same
+ *     for every face order and from run to run.  A failed compare-and-swap means another thread's hook succeeded; no thread waits
+ *     for a value another thread has yet to write.
+ * Vertex clustering (decimation on a regular grid of cubic cells of edge `cell` whose origin is lo, the per-axis minimum of the
+ * vertices); the caller sorts and scans between the steps:
+ *   1. p3d_mesh_cluster_keys: key int64 [V], key[v] = (iz * ny + iy) * nx + ix with, per axis,
+ *        i = floor(((double)v - (double)lo) / (double)cell), clamped to [0, n - 1]
+ *      (one IEEE fp64 subtract and one divide: a host restatement gets the same integers).  cell > 0 and finite, lo finite,
+ *      nx, ny, nz >= 1 (P3D_ERR_ARGUMENT); nx * ny * nz < 2^62 (P3D_ERR_UNSUPPORTED).
+ *   2. the caller sorts the vertex ids STABLY by key -> order int32 [V] (ascending vertex id inside a cell) and takes the run
+ *      boundaries -> offsets int64 [C + 1] (offsets[0] = 0, offsets[C] = V); cluster c is the c-th occupied cell by ascending key.
+ *      p3d_mesh_cluster_means: means float32 [C][3] <- per cluster the sum of its members in fp64, in the order of `order`, divided
+ *      by their number in fp64 and rounded once to fp32.
+ *   3. p3d_mesh_cluster_faces, with cluster int32 [V] the cluster of every vertex: mapped int32 [T][3] <- the face's corners as
+ *      cluster ids, in the face's own order (its winding); sorted int32 [T][3] <- the same three ids ascending; degenerate uint8 [T]
+ *      <- 1 when two corners share a cluster (or an index lies outside [0, V)), else 0.  The caller drops degenerate faces and,
+ *      among faces with one `sorted` triple, keeps the first in input order.                                                       */
+int p3d_mesh_components(const int32_t* faces, int32_t n_faces, int32_t n_vertices, int32_t* label, p3d_stream_t stream);
+int p3d_mesh_cluster_keys(const float* vertices, int32_t n_vertices, float lo_x, float lo_y, float lo_z, double cell,
+                          int32_t nx, int32_t ny, int32_t nz, int64_t* key, p3d_stream_t stream);
+int p3d_mesh_cluster_means(const float* vertices, int32_t n_vertices, const int32_t* order, const int64_t* offsets,
+                           int32_t n_clusters, float* means, p3d_stream_t stream);
+int p3d_mesh_cluster_faces(const int32_t* faces, int32_t n_faces, int32_t n_vertices, const int32_t* cluster, int32_t* mapped,
+                           int32_t* sorted, uint8_t* degenerate, p3d_stream_t stream);
+
 /* z_coarse [R][S_c], w_coarse [R][S_c-1], u_fine [R][S_f] -> z_fine [R][S_f] (sorted ascending
  * when `sorted`, else in draw order as sample_pdf returns them).                               */
 int p3d_importance_sample(const float* z_coarse, const float* w_coarse, const float* u_fine, float* z_fine,

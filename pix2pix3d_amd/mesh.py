@@ -7,7 +7,10 @@
   Lambert term on interpolated vertex colours, not pyrender's physically based shading with a spot light.
 * ``turntable_poses``: the script's 120-frame orbit (:240-256), in the OpenCV convention (before its OpenGL column flip).
 * ``write_ply`` (trimesh's export), ``save_gif`` (imageio.mimsave, through PIL), ``vertex_labels`` (:196-218).
-* ``extract_mesh``: shape.extract_geometry, the labels and the turntable in one call.
+* ``components`` / ``clean`` / ``simplify``: what a trimesh user does between extraction and export (``mesh.split()``, keep the
+  largest part, decimate), on the bare geometry: connected components by union-find, a keep-the-largest filter, vertex-clustering
+  decimation (csrc/mesh_ops.hip on device tensors, a restatement on CPU tensors; the rules are include/p3d_hip.h's).
+* ``extract_mesh``: shape.extract_geometry, the optional clean-up, the labels and the turntable in one call.
 """
 import ctypes
 import math
@@ -33,6 +36,11 @@ _lib.register('p3d_mesh_raster_bin', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, 
 _lib.register('p3d_mesh_raster', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp])
 _lib.register('p3d_mesh_shade', ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _i32,
                                            _vp, _vp])
+_f64 = ctypes.c_double                                                          # csrc/mesh_ops.hip
+_lib.register('p3d_mesh_components', ctypes.c_int, [_vp, _i32, _i32, _vp, _vp])
+_lib.register('p3d_mesh_cluster_keys', ctypes.c_int, [_vp, _i32, _f32, _f32, _f32, _f64, _i32, _i32, _i32, _vp, _vp])
+_lib.register('p3d_mesh_cluster_means', ctypes.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp])
+_lib.register('p3d_mesh_cluster_faces', ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp])
 
 
 class Orthographic(NamedTuple):
@@ -466,6 +474,182 @@ def save_gif(path, frames, fps=60):
     images[0].save(path, save_all=True, append_images=images[1:], duration=max(1, round(1000 / fps)), loop=0)
 
 
+# ---- clean-up: connected components, keep the largest, vertex clustering -------------------------------------------------------
+def _mesh_vertices(what, vertices):
+    vertices = vertices.detach().to(torch.float32).contiguous()
+    if vertices.ndim != 2 or vertices.shape[1] != 3 or vertices.shape[0] >= 2 ** 31 - 1:
+        raise ValueError(f'{what}: vertices must be [V, 3] with V < 2^31 - 1, got {tuple(vertices.shape)}')
+    if not bool(torch.isfinite(vertices).all()):
+        raise ValueError(f'{what}: vertices must be finite')
+    return vertices
+
+
+def _mesh_faces(what, faces, n_vertices):
+    """faces [T, 3], int32 or int64, every index in [0, V) -> int64 (on a device the range check is one device-to-host copy)."""
+    n_vertices = int(n_vertices)
+    if not 0 <= n_vertices < 2 ** 31 - 1:
+        raise ValueError(f'{what}: n_vertices must be in [0, 2^31 - 1), got {n_vertices}')
+    _faces32(faces, n_vertices)
+    faces = faces.detach().long().contiguous()
+    if faces.numel():
+        lo, hi = torch.stack(torch.aminmax(faces)).tolist()
+        if lo < 0 or hi >= n_vertices:
+            raise ValueError(f'{what}: face index outside [0, {n_vertices}) (indices span [{lo}, {hi}])')
+    return faces
+
+
+def _components_cpu(faces, n_vertices):
+    """Union-find by rounds: every root an edge joins to a smaller root is hooked under the smallest such root (scatter amin), pointer
+    jumping flattens the forest, and the edges that still join two roots go round again.  O(log V) rounds on any mesh."""
+    parent = torch.arange(n_vertices, dtype=torch.int64, device=faces.device)
+    a = torch.cat([faces[:, 0], faces[:, 1]])                              # (corner 0, corner 2) follows from the other two edges
+    b = torch.cat([faces[:, 1], faces[:, 2]])
+    while True:
+        ra, rb = parent[a], parent[b]
+        live = ra != rb
+        if not bool(live.any()):
+            return parent
+        a, b, ra, rb = a[live], b[live], ra[live], rb[live]
+        parent.scatter_reduce_(0, torch.maximum(ra, rb), torch.minimum(ra, rb), 'amin')
+        while True:
+            up = parent[parent]
+            if torch.equal(up, parent):
+                break
+            parent = up
+
+
+def components(faces, n_vertices):
+    """int64 [V] labels: label[v] is the smallest vertex id of v's connected component, two vertices being connected when a face uses
+    both (a vertex no face uses is its own component).  A pure function of the inputs: the same for any order of the faces.  Device
+    faces run p3d_mesh_components (union-find, three launches); CPU faces run the same rule in vectorised rounds."""
+    faces = _mesh_faces('components', faces, n_vertices)
+    n_vertices = int(n_vertices)
+    if not faces.is_cuda:
+        return _components_cpu(faces, n_vertices)
+    faces32 = faces.to(torch.int32)
+    label = torch.empty([n_vertices], dtype=torch.int32, device=faces.device)
+    _lib.check(_lib.lib().p3d_mesh_components(_lib.ptr(faces32), faces32.shape[0], n_vertices, _lib.ptr(label), _lib.stream_of(faces32)),
+               'mesh_components')
+    return label.long()
+
+
+def clean(vertices, faces, keep=1, min_faces=1):
+    """Keep the largest connected components (the role of trimesh's ``mesh.split()`` and a pick): components are ranked by face
+    count, descending, ties to the smaller label; the first ``keep`` of those with at least ``min_faces`` faces survive (keep=None:
+    all of them).  Vertices no surviving face uses are dropped; vertex and face order are kept.  Returns (vertices', faces' int64,
+    kept int64 [V'] = the original id of every vertex that is left)."""
+    if keep is not None and int(keep) < 1:
+        raise ValueError(f'clean: keep must be >= 1 or None, got {keep}')
+    vertices = _mesh_vertices('clean', vertices)
+    nv, dev = vertices.shape[0], vertices.device
+    faces = _mesh_faces('clean', faces, nv).to(dev)
+    label = components(faces, nv)
+    face_label = label[faces[:, 0]]
+    # the components that have faces, ascending by label (so a stable sort leaves ties to the smaller label), and their face counts; by
+    # sorting, not a histogram: on a device that is atomics, and one large component puts nearly all of them on one word
+    roots, count = torch.unique(face_label, return_counts=True)
+    rank = torch.sort(count, descending=True, stable=True).indices
+    rank = rank[count[rank] >= int(min_faces)]
+    if keep is not None:
+        rank = rank[:int(keep)]
+    alive = torch.zeros([nv], dtype=torch.bool, device=dev)
+    alive[roots[rank]] = True
+    faces = faces[alive[face_label]]
+    used = torch.zeros([nv], dtype=torch.bool, device=dev)
+    used[faces.reshape(-1)] = True
+    kept = used.nonzero()[:, 0]
+    remap = torch.cumsum(used, 0) - 1
+    return vertices[kept], remap[faces], kept
+
+
+def _cluster_keys_cpu(vertices, lo, cell, n):
+    top = torch.tensor([k - 1 for k in n], dtype=torch.float64)
+    i = torch.floor(torch.div(vertices.double() - lo.double(), torch.tensor(cell, dtype=torch.float64)))      # a true fp64 divide
+    i = torch.minimum(i.clamp(min=0.0), top).long()
+    return (i[:, 2] * n[1] + i[:, 1]) * n[0] + i[:, 0]
+
+
+def _cluster_means_cpu(vertices, order, offsets):
+    """Per segment of ``order`` the fp64 sum in that order, one member of every segment per pass (as many passes as the fullest
+    cell has vertices), the fp64 quotient, one rounding to fp32: p3d_mesh_cluster_means' arithmetic exactly."""
+    counts = offsets[1:] - offsets[:-1]
+    acc = torch.zeros([len(counts), 3], dtype=torch.float64)
+    v64 = vertices.double()
+    live = torch.arange(len(counts))
+    for j in range(int(counts.max()) if len(counts) else 0):
+        live = live[counts[live] > j]
+        acc[live] += v64[order[offsets[live] + j]]
+    return (acc / counts.double()[:, None]).float()
+
+
+def simplify(vertices, faces, cell):
+    """Vertex-clustering decimation: a grid of cubic cells of edge ``cell`` (in the vertices' units) from the vertices' per-axis
+    minimum; every occupied cell becomes one vertex, the mean of its members (fp64 sum in ascending vertex id, rounded once), in
+    ascending cell order (z outermost).  Faces are remapped; a face with two corners in one cell is dropped, and of the faces with
+    the same three vertices the first in input order stays, with its winding (a thin sheet whose two sides collapse into the same
+    cells becomes one single-sided sheet).  Carries no vertex attributes: label the result.  Returns (vertices', faces' int64).
+    Device tensors run csrc/mesh_ops.hip's kernels, with the sorts and scans between them in torch and one device-to-host copy of
+    the bounding box; CPU tensors run the restatement."""
+    cell = float(cell)
+    if not (cell > 0.0 and math.isfinite(cell)):
+        raise ValueError(f'simplify: cell must be positive and finite, got {cell}')
+    vertices = _mesh_vertices('simplify', vertices)
+    nv, dev = vertices.shape[0], vertices.device
+    faces = _mesh_faces('simplify', faces, nv).to(dev)
+    nf = faces.shape[0]
+    if nv == 0:
+        return vertices, faces
+    box = torch.stack([vertices.min(0).values, vertices.max(0).values]).cpu()
+    lo = box[0]
+    n = (torch.floor(torch.div(box[1].double() - lo.double(), torch.tensor(cell, dtype=torch.float64))) + 1.0).tolist()
+    if max(n) > 2 ** 31 - 1 or n[0] * n[1] * n[2] >= 2.0 ** 62:
+        raise ValueError(f'simplify: cell {cell} gives {n[0]:.0f} x {n[1]:.0f} x {n[2]:.0f} cells, beyond the 2^62 a key holds')
+    n = [int(k) for k in n]
+    lib = _lib.lib() if vertices.is_cuda else None
+    if lib is None:
+        key = _cluster_keys_cpu(vertices, lo, cell, n)
+    else:
+        key = torch.empty([nv], dtype=torch.int64, device=dev)
+        _lib.check(lib.p3d_mesh_cluster_keys(_lib.ptr(vertices), nv, float(lo[0]), float(lo[1]), float(lo[2]), cell, n[0], n[1], n[2],
+                                             _lib.ptr(key), _lib.stream_of(vertices)), 'mesh_cluster_keys')
+    sorted_key, order = torch.sort(key, stable=True)                       # ascending vertex id inside a cell
+    counts = torch.unique_consecutive(sorted_key, return_counts=True)[1]
+    nc = counts.shape[0]
+    offsets = torch.zeros([nc + 1], dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(counts, 0)
+    cluster = torch.empty([nv], dtype=torch.int64, device=dev)
+    cluster[order] = torch.repeat_interleave(torch.arange(nc, device=dev), counts)
+    if lib is None:
+        means = _cluster_means_cpu(vertices, order, offsets)
+    else:
+        order32 = order.to(torch.int32)
+        means = torch.empty([nc, 3], dtype=torch.float32, device=dev)
+        _lib.check(lib.p3d_mesh_cluster_means(_lib.ptr(vertices), nv, _lib.ptr(order32), _lib.ptr(offsets), nc, _lib.ptr(means),
+                                              _lib.stream_of(vertices)), 'mesh_cluster_means')
+    if nf == 0:
+        return means, faces
+    if lib is None:
+        mapped = cluster[faces]
+        triple = mapped.sort(1).values
+        degenerate = (triple[:, 0] == triple[:, 1]) | (triple[:, 1] == triple[:, 2])
+    else:
+        faces32, cluster32 = faces.to(torch.int32), cluster.to(torch.int32)
+        mapped, triple = torch.empty_like(faces32), torch.empty_like(faces32)
+        flags = torch.empty([nf], dtype=torch.uint8, device=dev)
+        _lib.check(lib.p3d_mesh_cluster_faces(_lib.ptr(faces32), nf, nv, _lib.ptr(cluster32), _lib.ptr(mapped), _lib.ptr(triple),
+                                              _lib.ptr(flags), _lib.stream_of(faces32)), 'mesh_cluster_faces')
+        degenerate = flags != 0
+    idx = (~degenerate).nonzero()[:, 0]
+    triple = triple[idx].long()
+    # one int64 per vertex set: the rank of the first two ids (below T), then the third (below C)
+    pair = torch.unique(triple[:, 0] * nc + triple[:, 1], return_inverse=True)[1]
+    sorted_set, by_set = torch.sort(pair * nc + triple[:, 2], stable=True)  # input order inside a run of equal sets
+    first = torch.ones_like(sorted_set, dtype=torch.bool)
+    first[1:] = sorted_set[1:] != sorted_set[:-1]
+    keep = torch.sort(idx[by_set[first]]).values
+    return means, mapped[keep].long()
+
+
 # ---- labels and the whole script ---------------------------------------------------------------------------------------------
 def default_palette(n):
     """uint8 [n, 3]: class 0 grey, the others spread round the hue circle by the golden angle (this package's own colours)."""
@@ -493,12 +677,23 @@ def vertex_labels(G, ws, vertices, palette=None, max_batch=10_000_000):
 
 
 @torch.no_grad()
-def extract_mesh(G, ws, resolution=512, threshold=50., n_frames=120, image_size=512, palette=None, **synthesis_kwargs):
+def extract_mesh(G, ws, resolution=512, threshold=50., n_frames=120, image_size=512, palette=None, keep=None, min_faces=1, cell=None,
+                 **synthesis_kwargs):
     """applications/extract_mesh.py after its inputs: shape.extract_geometry, per-vertex label colours unless G is an edge-map
     generator (data_type 'edge') or has no label channels, and the script's turntable — orthographic xmag = ymag = 0.3 at radius 1 (edge2car: 0.6 at 1.2) about
     G.rendering_kwargs['avg_camera_pivot'], image_size^2 pixels.  Returns (vertices, faces, vertex_colors or None, frames uint8
-    [n_frames, image_size, image_size, 3])."""
+    [n_frames, image_size, image_size, 3]).  Clean-up, off by default, runs on the bare geometry before the labels and the
+    turntable: ``clean(keep, min_faces)`` when ``keep`` is given or ``min_faces`` exceeds 1, then ``simplify(cell)`` when ``cell``
+    (world units) is given.  Clustering can pinch a thin neck into an edge, which no face carries, and so detach a crumb (and leaves
+    the vertices of cells whose faces all collapsed): with both ``keep`` and ``cell`` the component count asked for is applied to the
+    simplified mesh once more, so that keep=1 hands over one component."""
     vertices, faces = shape.extract_geometry(G, ws, resolution, threshold, **synthesis_kwargs)
+    if keep is not None or min_faces > 1:
+        vertices, faces, _ = clean(vertices, faces, keep, min_faces)
+    if cell is not None:
+        vertices, faces = simplify(vertices, faces, cell)
+        if keep is not None:
+            vertices, faces, _ = clean(vertices, faces, keep)
     edge = getattr(G, 'data_type', None) == 'edge'                      # the script's edge2car branch; every other generator is seg-like
     labelled = not edge and int(getattr(G, 'semantic_channels', 0) or 0) > 1
     colors = vertex_labels(G, ws, vertices, palette)[1] if labelled and len(vertices) else None
