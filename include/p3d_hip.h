@@ -373,6 +373,48 @@ int p3d_mesh_cluster_means(const float* vertices, int32_t n_vertices, const int3
 int p3d_mesh_cluster_faces(const int32_t* faces, int32_t n_faces, int32_t n_vertices, const int32_t* cluster, int32_t* mapped,
                            int32_t* sorted, uint8_t* degenerate, p3d_stream_t stream);
 
+/* ---- mesh baking: vertex normals and per-vertex colours from rendered views (csrc/mesh_bake.hip; pix2pix3d_amd/texture.py) ---------
+ * One thread per vertex; every sum runs in fp64 in a fixed order and every product and sum below is rounded on its own (no
+ * contraction), so the outputs are pure functions of the inputs.  The CPU formulation of pix2pix3d_amd/texture.py, written operation
+ * by operation, is the definition; the kernels' bytes equal it.  sqrt below is the correctly rounded IEEE square root (the kernels
+ * check the target's fp64 sqrt against an exact fma residual; torch.sqrt on the CPU is NOT correctly rounded, numpy's is).  V and T <= INT32_MAX - 1 (P3D_ERR_UNSUPPORTED beyond).
+ * Vertex normals (p3d_mesh_vertex_normals):
+ *   The caller lists the corners of all faces per vertex in ascending (face id, corner) order — a STABLE sort of the 3 T entries of
+ *   faces by vertex id — as corner_face int32 [3 T], the face of every listed corner, and offsets int64 [V + 1] (offsets[0] = 0,
+ *   offsets[V] = 3 T).  normals float32 [V][3] <- the sum over v's list, in list order, starting from 0, of
+ *     cross(p1 - p0, p2 - p0), each component a * b - c * d with both products rounded,
+ *   p0, p1, p2 the face's corners in fp64 (area weighting; the sign follows the faces' winding, nothing below depends on it), divided
+ *   by len = sqrt(x * x + y * y + z * z) (summed left to right) and rounded to fp32.  A vertex with no faces, or with a zero or
+ *   non-finite len, gets (0, 0, 0).  A face that uses a vertex twice is listed twice by it (its cross product is 0); a list entry or a
+ *   face index out of range is skipped.
+ * Baking (p3d_mesh_bake_accumulate, then p3d_mesh_bake_finish).  Inputs per view f and vertex v: proj int32 [F][V][4] = (sx, sy, fp32
+ *   bits of z, dropped) from p3d_mesh_project; face_id int32 / depth float [F][H][W] from p3d_mesh_raster for the same mesh and
+ *   cameras; images uint8 [F][H][W][3]; vertices, normals float32 [V][3]; cameras float [F][P3D_MESH_CAMERA_FLOATS] (only the pose is
+ *   read).  F <= 65535, 1 <= W, H <= 2048, power in 1 .. 8, tolerance and min_cos finite and >= 0 (else P3D_ERR_ARGUMENT, before any
+ *   launch).
+ *   1. Texel position: tx = sx - 128, ty = sy - 128; c0 = tx >> 8, r0 = ty >> 8, fx = tx & 255, fy = ty & 255.  The footprint is
+ *      pixels (r0, c0), (r0, c0 + 1), (r0 + 1, c0), (r0 + 1, c0 + 1): the four pixel centres around the vertex.
+ *   2. The sample counts only if v is not dropped, the whole footprint lies inside the frame, all four face_id >= 0 (no image
+ *      background bleeds in at silhouettes) and (double)z <= (double)min(depth of the four) + tolerance.
+ *   3. View direction d = camera position - p (pinhole) or minus the camera's forward axis (orthographic);
+ *      cos = |n . d| / (sqrt(n . n) sqrt(d . d)) in fp64, dot products summed left to right, 0 when the denominator is not > 0.  The
+ *      sample counts only if cos >= min_cos.  Weight w = cos^power by repeated multiplication (w = cos; w = w * cos; ...).
+ *   4. Colour per channel: ((256 - fy)(256 - fx) I00 + (256 - fy) fx I01 + fy (256 - fx) I10 + fy fx I11) / 65536, the numerator an
+ *      exact integer converted to fp64.
+ *   5. In view order, for every sample that counts: acc[v] += (w r, w g, w b, w) (double [V][4]) and seen[v] += 1 (int32 [V]).  acc
+ *      and seen are IN/OUT: groups of views chain into exactly the sums of one call.  A frame less than 2 pixels wide or high holds
+ *      no footprint: nothing is launched.
+ *   6. p3d_mesh_bake_finish: colors uint8 [V][3] <- floor(acc.rgb / acc.w + 0.5) clamped to [0, 255] where acc.w > 0; elsewhere
+ *      fallback[v] (uint8 [V][3]) or, with fallback NULL, (fb_r, fb_g, fb_b).                                                       */
+int p3d_mesh_vertex_normals(const float* vertices, int32_t n_vertices, const int32_t* faces, int32_t n_faces,
+                            const int32_t* corner_face, const int64_t* offsets, float* normals, p3d_stream_t stream);
+int p3d_mesh_bake_accumulate(const int32_t* proj, const int32_t* face_id, const float* depth, const uint8_t* images,
+                             const float* vertices, const float* normals, const float* cameras, int32_t n_vertices, int32_t n_frames,
+                             int32_t orthographic, int32_t width, int32_t height, double tolerance, double min_cos, int32_t power,
+                             double* acc, int32_t* seen, p3d_stream_t stream);
+int p3d_mesh_bake_finish(const double* acc, int32_t n_vertices, const uint8_t* fallback, int32_t fb_r, int32_t fb_g, int32_t fb_b,
+                         uint8_t* colors, p3d_stream_t stream);
+
 /* z_coarse [R][S_c], w_coarse [R][S_c-1], u_fine [R][S_f] -> z_fine [R][S_f] (sorted ascending
  * when `sorted`, else in draw order as sample_pdf returns them).                               */
 int p3d_importance_sample(const float* z_coarse, const float* w_coarse, const float* u_fine, float* z_fine,

@@ -438,15 +438,18 @@ def turntable_poses(pivot, radius, n_frames=120, yaw0=_SCRIPT_PI / 2, yaw_range=
 
 
 # ---- files ------------------------------------------------------------------------------------------------------------------
-def write_ply(path, vertices, faces, colors=None):
-    """Binary little-endian PLY (what trimesh's export writes for the script): vertex float x y z [+ uchar red green blue],
-    face list uchar int vertex_indices."""
+def write_ply(path, vertices, faces, colors=None, normals=None):
+    """Binary little-endian PLY (what trimesh's export writes for the script): vertex float x y z [+ float nx ny nz]
+    [+ uchar red green blue], face list uchar int vertex_indices."""
     v = vertices.detach().cpu().to(torch.float32).numpy()
     f = faces.detach().cpu().numpy()
     if f.size and (f.min() < 0 or f.max() >= len(v) or f.max() > np.iinfo(np.int32).max):
         raise ValueError('write_ply: face index outside [0, V)')
     vfields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
     props = 'property float x\nproperty float y\nproperty float z\n'
+    if normals is not None:
+        vfields += [('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')]
+        props += 'property float nx\nproperty float ny\nproperty float nz\n'
     if colors is not None:
         vfields += [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
         props += 'property uchar red\nproperty uchar green\nproperty uchar blue\n'
@@ -454,6 +457,11 @@ def write_ply(path, vertices, faces, colors=None):
               f'element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n')
     vrec = np.empty(len(v), dtype=vfields)
     vrec['x'], vrec['y'], vrec['z'] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        n = torch.as_tensor(normals).detach().cpu().to(torch.float32).numpy()
+        if n.shape != v.shape:
+            raise ValueError(f'write_ply: normals must be [V, 3] like the vertices, got {n.shape}')
+        vrec['nx'], vrec['ny'], vrec['nz'] = n[:, 0], n[:, 1], n[:, 2]
     if colors is not None:
         c = torch.as_tensor(colors).detach().cpu().to(torch.uint8).numpy()
         vrec['red'], vrec['green'], vrec['blue'] = c[:, 0], c[:, 1], c[:, 2]
@@ -676,6 +684,28 @@ def vertex_labels(G, ws, vertices, palette=None, max_batch=10_000_000):
     return labels.to(vertices.device), pal.to(vertices.device)[labels.to(vertices.device)]
 
 
+def _clean_geometry(G, ws, resolution, threshold, keep, min_faces, cell, **synthesis_kwargs):
+    """extract_mesh's geometry: shape.extract_geometry and the optional clean-up (see ``extract_mesh``)."""
+    vertices, faces = shape.extract_geometry(G, ws, resolution, threshold, **synthesis_kwargs)
+    if keep is not None or min_faces > 1:
+        vertices, faces, _ = clean(vertices, faces, keep, min_faces)
+    if cell is not None:
+        vertices, faces = simplify(vertices, faces, cell)
+        if keep is not None:
+            vertices, faces, _ = clean(vertices, faces, keep)
+    return vertices, faces
+
+
+def script_turntable(G, n_frames=120):
+    """(poses [n_frames, 4, 4], camera): the script's turntable for G, orthographic xmag = ymag = 0.3 at radius 1 about
+    G.rendering_kwargs['avg_camera_pivot'] (an edge-map generator, the script's edge2car branch: 0.6 at 1.2, the full orbit)."""
+    pivot = G.rendering_kwargs['avg_camera_pivot']
+    if getattr(G, 'data_type', None) != 'edge':
+        return turntable_poses(pivot, 1.0, n_frames), Orthographic(0.3, 0.3)
+    poses = turntable_poses(pivot, 1.2, n_frames, yaw0=-_SCRIPT_PI / 2, yaw_range=np.pi, pitch_range=np.pi / 2)
+    return poses, Orthographic(0.6, 0.6)
+
+
 @torch.no_grad()
 def extract_mesh(G, ws, resolution=512, threshold=50., n_frames=120, image_size=512, palette=None, keep=None, min_faces=1, cell=None,
                  **synthesis_kwargs):
@@ -687,21 +717,10 @@ def extract_mesh(G, ws, resolution=512, threshold=50., n_frames=120, image_size=
     (world units) is given.  Clustering can pinch a thin neck into an edge, which no face carries, and so detach a crumb (and leaves
     the vertices of cells whose faces all collapsed): with both ``keep`` and ``cell`` the component count asked for is applied to the
     simplified mesh once more, so that keep=1 hands over one component."""
-    vertices, faces = shape.extract_geometry(G, ws, resolution, threshold, **synthesis_kwargs)
-    if keep is not None or min_faces > 1:
-        vertices, faces, _ = clean(vertices, faces, keep, min_faces)
-    if cell is not None:
-        vertices, faces = simplify(vertices, faces, cell)
-        if keep is not None:
-            vertices, faces, _ = clean(vertices, faces, keep)
+    vertices, faces = _clean_geometry(G, ws, resolution, threshold, keep, min_faces, cell, **synthesis_kwargs)
     edge = getattr(G, 'data_type', None) == 'edge'                      # the script's edge2car branch; every other generator is seg-like
     labelled = not edge and int(getattr(G, 'semantic_channels', 0) or 0) > 1
     colors = vertex_labels(G, ws, vertices, palette)[1] if labelled and len(vertices) else None
-    pivot = G.rendering_kwargs['avg_camera_pivot']
-    if not edge:
-        poses, camera = turntable_poses(pivot, 1.0, n_frames), Orthographic(0.3, 0.3)
-    else:
-        poses = turntable_poses(pivot, 1.2, n_frames, yaw0=-_SCRIPT_PI / 2, yaw_range=np.pi, pitch_range=np.pi / 2)
-        camera = Orthographic(0.6, 0.6)
+    poses, camera = script_turntable(G, n_frames)
     frames = render(vertices, faces, poses, camera, image_size, colors=colors)
     return vertices, faces, colors, frames
