@@ -415,6 +415,48 @@ int p3d_mesh_bake_accumulate(const int32_t* proj, const int32_t* face_id, const 
 int p3d_mesh_bake_finish(const double* acc, int32_t n_vertices, const uint8_t* fallback, int32_t fb_r, int32_t fb_g, int32_t fb_b,
                          uint8_t* colors, p3d_stream_t stream);
 
+/* ---- mesh atlas: a per-triangle texture atlas, its texels' geometry, its image and a shade that samples it (csrc/mesh_atlas.hip;
+ * pix2pix3d_amd/atlas.py) ----------------------------------------------------------------------------------------------------------
+ * As in "mesh baking": fp64, every product and sum rounded on its own in the stated order; the CPU formulation of atlas.py is the
+ * definition and the kernels' bytes equal it (a shaded frame: within the one level of p3d_mesh_shade's headlight term).
+ * Layout.  The texture is size x size texels, 16 <= size <= 8192, row 0 at the top.  Square cells of cell x cell texels, cell >= 4, lie
+ *   on a grid of per_row = size / cell (integer division) cells per row in row-major order; cell k holds face 2 k (its "lower" half)
+ *   and face 2 k + 1 (its "upper" half), so T faces take n_cells = (T + 1) / 2 cells, and n_cells <= per_row^2 is required
+ *   (P3D_ERR_ARGUMENT; atlas.layout picks the largest cell that fits).  Inside a cell, texel (column i, row j) belongs to the lower
+ *   face when i + j <= cell - 2, else to the upper face.  With m = cell - 3 the triangle's side in texels, the corners sit at the
+ *   texel CENTRES (0, 0), (m, 0), (0, m) (lower, corners 0, 1, 2) and (cell - 1, cell - 1), (cell - 1 - m, cell - 1),
+ *   (cell - 1, cell - 1 - m) (upper).  A texel's barycentric numerators over m are (n0, n1, n2) = (m - i' - j', i', j') with
+ *   (i', j') = (i, j) (lower) or (cell - 1 - i, cell - 1 - j) (upper); n0 < 0 (one diagonal of the lower half, two of the upper) is the
+ *   gutter, which takes the same formula: linear extrapolation in the triangle's plane, so that a bilinear lookup of a field that is
+ *   linear over the face is exact up to the hypotenuse.  A 2 x 2 bilinear footprint at any point of a face's triangle, placed by the
+ *   fixed-point rule below, puts non-zero weight only on texels that face owns: nothing bleeds between halves or cells.
+ * p3d_mesh_atlas_texels: one texel per thread in cell-major order, q = (k * cell + j) * cell + i, K = n_cells * cell^2 texels.
+ *   face int32 [K] <- 2 k + half, or -1 when that face does not exist (the upper half of the last cell for odd T) or one of its
+ *   vertex indices lies outside [0, V); points, texel_normals float32 [K][3] <- per component, with a_c the fp64 value of vertices
+ *   (or normals) float32 [V][3] at the face's corner c,
+ *     s = n0 a_0;  s = s + n1 a_1;  s = s + n2 a_2;  s / m, rounded to fp32
+ *   (0 where face is -1).  A texel at a corner reproduces that vertex bit for bit.  The normals are not normalised.
+ * p3d_mesh_atlas_assemble: colors uint8 [K][3], face int32 [K] -> texture uint8 [size][size][3]: texel (i, j) of cell k goes to row
+ *   (k / per_row) cell + j, column (k % per_row) cell + i; texels with face -1, unused cells and the right and bottom margins get
+ *   (bg_r, bg_g, bg_b).  Every byte of the texture is written.
+ * p3d_mesh_shade_textured: p3d_mesh_shade with the albedo taken from the texture; swap rule, barycentrics b_0..2, headlight term,
+ *   rounding and background are p3d_mesh_shade's, n_faces is both the mesh's and the atlas's face count, and a face id outside
+ *   [0, n_faces) is background.  The barycentrics are first put back into the face's STORED corner order (the swap rule may have
+ *   exchanged corners 1 and 2).  x = b_1 m, y = b_2 m; for the upper half x = (cell - 1) - b_1 m, y = (cell - 1) - b_2 m.
+ *   X = rint(x * 256), Y = rint(y * 256) (half to even), clamped to [0, (cell - 1) * 256] (a NaN to 0);
+ *   c0 = min(X >> 8, cell - 2), r0 = min(Y >> 8, cell - 2), fx = X - (c0 << 8), fy = Y - (r0 << 8), both in 0 .. 256.  The four taps
+ *   T00, T01, T10, T11 are the texture's texels at the cell's origin + (r0, c0), (r0, c0 + 1), (r0 + 1, c0), (r0 + 1, c0 + 1), and per
+ *   channel  albedo = ((256 - fy)(256 - fx) T00 + (256 - fy) fx T01 + fy (256 - fx) T10 + fy fx T11) / 65536, the numerator an exact
+ *   integer converted to fp64.  F <= 65535, 1 <= W, H <= 2048.                                                                      */
+int p3d_mesh_atlas_texels(const float* vertices, int32_t n_vertices, const int32_t* faces, int32_t n_faces, const float* normals,
+                          int32_t size, int32_t cell, float* points, float* texel_normals, int32_t* face, p3d_stream_t stream);
+int p3d_mesh_atlas_assemble(const uint8_t* colors, const int32_t* face, int32_t n_faces, int32_t size, int32_t cell,
+                            int32_t bg_r, int32_t bg_g, int32_t bg_b, uint8_t* texture, p3d_stream_t stream);
+int p3d_mesh_shade_textured(const int32_t* face_id, const int32_t* proj, const float* vertices, int32_t n_vertices,
+                            const int32_t* faces, int32_t n_faces, const uint8_t* texture, int32_t size, int32_t cell,
+                            const float* cameras, int32_t n_frames, int32_t orthographic, int32_t width, int32_t height,
+                            float ambient, int32_t bg_r, int32_t bg_g, int32_t bg_b, uint8_t* rgb, p3d_stream_t stream);
+
 /* z_coarse [R][S_c], w_coarse [R][S_c-1], u_fine [R][S_f] -> z_fine [R][S_f] (sorted ascending
  * when `sorted`, else in draw order as sample_pdf returns them).                               */
 int p3d_importance_sample(const float* z_coarse, const float* w_coarse, const float* u_fine, float* z_fine,

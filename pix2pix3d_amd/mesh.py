@@ -295,51 +295,62 @@ def rasterize(proj, faces, resolution):
 
 
 # ---- shading ----------------------------------------------------------------------------------------------------------------
+def _shade_terms_cpu(f, face_id, proj, vertices, faces, cams, ambient):
+    """What p3d_mesh_shade works out at every drawn pixel of frame f before the albedo: (pix, the flat pixel indices; t, their faces;
+    idx [N, 3], the vertex ids in weight order; b, the three barycentrics; the headlight factor)."""
+    _, h, w = face_id.shape
+    nf = faces.shape[0]
+    verts = vertices.double()
+    fid = face_id[f].reshape(-1).long()
+    pix = ((fid >= 0) & (fid < nf)).nonzero()[:, 0]
+    t = fid[pix]
+    ok, idx, x, y, z = _setup_cpu(proj.packed[f], faces[t].long())
+    c0, c1, r0, r1 = _bbox(x, y, h, w)
+    ok &= (c0 <= c1) & (r0 <= r1)
+    pix, t, idx, x, y, z = pix[ok], t[ok], idx[ok], x[ok], y[ok], z[ok]
+    r, c = pix // w, pix % w
+    w0, w1, w2, _ = _weights(x, y, r, c)
+    a0, a1, a2 = w0.double(), w1.double(), w2.double()
+    if proj.orthographic:
+        s = a0 + a1
+        s = s + a2
+        b = (a0 / s, a1 / s, a2 / s)
+    else:
+        q0, q1, q2 = a0 / z[:, 0].double(), a1 / z[:, 1].double(), a2 / z[:, 2].double()
+        q = q0 + q1
+        q = q + q2
+        b = (q0 / q, q1 / q, q2 / q)
+    e1 = verts[idx[:, 1]] - verts[idx[:, 0]]
+    e2 = verts[idx[:, 2]] - verts[idx[:, 0]]
+    nx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+    ny = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+    nz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+    f0, f1, f2 = (float(cams[f, j].double()) for j in (2, 6, 10))
+    nn = nx * nx
+    nn = nn + ny * ny
+    nn = nn + nz * nz
+    ff = f0 * f0
+    ff = ff + f1 * f1
+    ff = ff + f2 * f2
+    dot = nx * f0
+    dot = dot + ny * f1
+    dot = dot + nz * f2
+    den = nn.sqrt() * math.sqrt(ff)
+    cosv = torch.where(den > 0, dot.abs() / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(den))
+    amb = float(torch.tensor(ambient, dtype=torch.float32))
+    return pix, t, idx, b, amb + (1.0 - amb) * cosv
+
+
+def _shaded_bytes(albedo, shade_):
+    return torch.floor(albedo * shade_ + 0.5).clamp(0, 255).to(torch.uint8)
+
+
 def _shade_cpu(face_id, proj, vertices, faces, colors, cams, ambient, background):
     n, h, w = face_id.shape
     out = torch.empty([n, h, w, 3], dtype=torch.uint8)
     out[:] = torch.tensor(background, dtype=torch.uint8)
-    nf = faces.shape[0]
-    verts = vertices.double()
     for f in range(n):
-        fid = face_id[f].reshape(-1).long()
-        pix = ((fid >= 0) & (fid < nf)).nonzero()[:, 0]
-        t = fid[pix]
-        ok, idx, x, y, z = _setup_cpu(proj.packed[f], faces[t].long())
-        c0, c1, r0, r1 = _bbox(x, y, h, w)
-        ok &= (c0 <= c1) & (r0 <= r1)
-        pix, idx, x, y, z = pix[ok], idx[ok], x[ok], y[ok], z[ok]
-        r, c = pix // w, pix % w
-        w0, w1, w2, _ = _weights(x, y, r, c)
-        a0, a1, a2 = w0.double(), w1.double(), w2.double()
-        if proj.orthographic:
-            s = a0 + a1
-            s = s + a2
-            b = (a0 / s, a1 / s, a2 / s)
-        else:
-            q0, q1, q2 = a0 / z[:, 0].double(), a1 / z[:, 1].double(), a2 / z[:, 2].double()
-            q = q0 + q1
-            q = q + q2
-            b = (q0 / q, q1 / q, q2 / q)
-        e1 = verts[idx[:, 1]] - verts[idx[:, 0]]
-        e2 = verts[idx[:, 2]] - verts[idx[:, 0]]
-        nx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
-        ny = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
-        nz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
-        f0, f1, f2 = (float(cams[f, j].double()) for j in (2, 6, 10))
-        nn = nx * nx
-        nn = nn + ny * ny
-        nn = nn + nz * nz
-        ff = f0 * f0
-        ff = ff + f1 * f1
-        ff = ff + f2 * f2
-        dot = nx * f0
-        dot = dot + ny * f1
-        dot = dot + nz * f2
-        den = nn.sqrt() * math.sqrt(ff)
-        cosv = torch.where(den > 0, dot.abs() / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(den))
-        amb = float(torch.tensor(ambient, dtype=torch.float32))
-        shade_ = amb + (1.0 - amb) * cosv
+        pix, _, idx, b, shade_ = _shade_terms_cpu(f, face_id, proj, vertices, faces, cams, ambient)
         rgb = torch.empty([len(pix), 3], dtype=torch.uint8)
         for ch in range(3):
             if colors is None:
@@ -349,7 +360,7 @@ def _shade_cpu(face_id, proj, vertices, faces, colors, cams, ambient, background
                 alb = b[0] * col[idx[:, 0]]
                 alb = alb + b[1] * col[idx[:, 1]]
                 alb = alb + b[2] * col[idx[:, 2]]
-            rgb[:, ch] = torch.floor(alb * shade_ + 0.5).clamp(0, 255).to(torch.uint8)
+            rgb[:, ch] = _shaded_bytes(alb, shade_)
         out[f].reshape(-1, 3)[pix] = rgb
     return out
 

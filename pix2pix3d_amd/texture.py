@@ -15,7 +15,7 @@ every vertex takes the weighted mean of the frames it is visible in.
 * ``bake_cameras`` / ``bake_views`` / ``textured_mesh``: the generator's video cameras, their frames baked onto a mesh, and the whole
   of ``mesh.extract_mesh`` with baked colours.
 
-Per-vertex colours only: no UV atlas, no texture image.
+Per-vertex colours only; a UV atlas and a texture image baked by these same two steps are ``pix2pix3d_amd.atlas``.
 """
 import ctypes
 import math
