@@ -20,6 +20,7 @@ DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.float64: 2}
 FAMILY = {'bias_act': 0, 'upfirdn2d': 1, 'filtered_lrelu': 2, 'render': 3, 'conv': 4, 'aux': 5}
 
 _c_void_p, _c_int, _c_i32, _c_i64, _c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+_vp, _i32, _f32, _f64 = _c_void_p, _c_i32, _c_float, ctypes.c_double      # short names for the op modules' register() calls
 _i32x4, _i64x4 = ctypes.c_int32 * 4, ctypes.c_int64 * 4
 _i32x2, _i64x2 = ctypes.c_int32 * 2, ctypes.c_int64 * 2
 

@@ -17,7 +17,7 @@ cells of 4.  Chart-based unwrapping, mip maps and inpainting of unseen texels ar
 * ``bake_texture``: the texels are points with normals, so the bake is ``texture.bake_accumulate`` / ``bake_finish`` on them against the
   mesh's raster buffers; ``assemble`` puts the colours into the image (p3d_mesh_atlas_assemble).
 * ``shade_textured`` / ``render_textured``: ``mesh.shade`` / ``mesh.render`` with the albedo looked up in the texture
-  (p3d_mesh_shade_textured).
+  (p3d_mesh_shade_textured): the operands and the CPU frame loop of ``mesh.shade``, the loop over groups of views of ``mesh.render``.
 * ``write_obj``; ``atlas_views`` / ``atlas_mesh``: the generator's views baked into a texture, and the whole pipeline.
 
 Device tensors run csrc/mesh_atlas.hip, CPU tensors the formulation below, written operation by operation: it is the definition
@@ -30,13 +30,13 @@ from typing import NamedTuple
 
 import torch
 
-from . import _lib, mesh, texture, views
+from . import _lib, mesh, texture
+from ._lib import _f32, _i32, _vp
 
 GREY = mesh.GREY
 MIN_SIZE, MAX_SIZE, MIN_CELL = 16, 8192, 4
 
-_vp, _i32, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float              # csrc/mesh_atlas.hip
-_lib.register('p3d_mesh_atlas_texels', ctypes.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp])
+_lib.register('p3d_mesh_atlas_texels', ctypes.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp])             # csrc/mesh_atlas.hip
 _lib.register('p3d_mesh_atlas_assemble', ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp])
 _lib.register('p3d_mesh_shade_textured', ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _f32,
                                                         _i32, _i32, _i32, _vp, _vp])
@@ -177,11 +177,9 @@ def texel_points(vertices, faces, normals, lay):
     number of faces) or has a vertex index outside [0, V)."""
     vertices = mesh._mesh_vertices('texel_points', vertices)
     nv, dev = vertices.shape[0], vertices.device
-    faces32 = mesh._faces32(faces, nv).to(dev)
+    faces32 = mesh._faces32(faces).to(dev)
     lay = _layout('texel_points', lay, faces32.shape[0])
-    normals = torch.as_tensor(normals).detach().to(device=dev, dtype=torch.float32).contiguous()
-    if tuple(normals.shape) != (nv, 3):
-        raise ValueError(f'texel_points: normals must be [{nv}, 3], got {tuple(normals.shape)}')
+    normals = texture._normals('texel_points', normals, vertices)
     if not vertices.is_cuda:
         return _texels_cpu(vertices, faces32, normals, lay)
     k = lay.n_texels
@@ -230,40 +228,17 @@ def assemble(colors, face, lay, background=(GREY, GREY, GREY)):
 
 
 # ---- baking -----------------------------------------------------------------------------------------------------------------
-def _views(what, images, cam2world, camera):
-    """The checked views of a bake: (images uint8 [F, H, W, 3], cam2world [F, 4, 4] on the CPU, intrinsics [F, 9] or None)."""
-    images = torch.as_tensor(images)
-    if images.dtype != torch.uint8 or images.ndim != 4 or images.shape[3] != 3:
-        raise ValueError(f'{what}: images must be uint8 [F, H, W, 3], got {images.dtype} {tuple(images.shape)}')
-    n, h, w = images.shape[:3]
-    mesh._size((h, w))
-    c2w = torch.as_tensor(cam2world, dtype=torch.float32).detach().cpu().reshape(-1, 4, 4)
-    if c2w.shape[0] != n:
-        raise ValueError(f'{what}: {c2w.shape[0]} cameras for {n} frames')
-    k = None
-    if isinstance(camera, mesh.Pinhole):
-        k = torch.as_tensor(camera.intrinsics, dtype=torch.float32).detach().cpu().reshape(-1, 9)
-        if k.shape[0] not in (1, n):
-            raise ValueError(f'{what}: {k.shape[0]} intrinsics for {n} frames')
-        k = k.expand(n, 9)
-    return images, c2w, k
-
-
-def _bake(vertices, faces32, texels, lay, images, c2w, k, camera, tolerance, power, min_cos, fallback, background, max_bytes):
+def _bake(what, vertices, faces32, texels, lay, images, c2w, camera, tolerance, power, min_cos, fallback, background, max_bytes):
     points, tnormals, face = texels
-    dev, n, (h, w) = vertices.device, images.shape[0], images.shape[1:3]
+    dev, size = vertices.device, tuple(images.shape[1:3])
     nk = lay.n_texels
     images = images.detach().to(dev).contiguous()
     acc, seen = texture.bake_buffers(nk, dev)
-    group = max(1, min(n, max_bytes // max(1, 16 * nk)))
-    for s in range(0, n if nk else 0, group):
-        cam = camera if k is None else camera._replace(intrinsics=k[s:s + group])
-        proj = mesh.project(vertices, c2w[s:s + group], cam, (h, w))
-        face_id, depth = mesh.rasterize(proj, faces32, (h, w))
-        del proj
-        proj = mesh.project(points, c2w[s:s + group], cam, (h, w))
-        texture.bake_accumulate(acc, seen, proj, face_id, depth, images[s:s + group], points, tnormals, c2w[s:s + group], tolerance, power,
-                                min_cos)
+    for part, poses, cam in mesh._view_groups(what, c2w, camera, nk, max_bytes) if nk else ():
+        proj, face_id, depth = mesh._raster_group(vertices, faces32, poses, cam, size)
+        del proj                                                           # before the texels' is made: max_bytes bounds what is alive at once
+        proj = mesh.project(points, poses, cam, size)
+        texture.bake_accumulate(acc, seen, proj, face_id, depth, images[part], points, tnormals, poses, tolerance, power, min_cos)
         del proj, face_id, depth
     colors = texture.bake_finish(acc, fallback)
     seen = torch.where(face >= 0, seen, torch.zeros_like(seen))          # (at min_cos = 0 the zero normal of a texel without a face counts)
@@ -272,14 +247,9 @@ def _bake(vertices, faces32, texels, lay, images, c2w, k, camera, tolerance, pow
 
 def _bake_mesh(what, vertices, faces, normals, lay):
     vertices = mesh._mesh_vertices(what, vertices)
-    nv, dev = vertices.shape[0], vertices.device
-    faces32 = mesh._mesh_faces(what, faces, nv).to(device=dev, dtype=torch.int32)
+    faces32 = mesh._mesh_faces(what, faces, vertices.shape[0]).to(device=vertices.device, dtype=torch.int32)
     lay = _layout(what, lay, faces32.shape[0])
-    normals = texture.vertex_normals(vertices, faces32) if normals is None else \
-        torch.as_tensor(normals).detach().to(device=dev, dtype=torch.float32)
-    if tuple(normals.shape) != (nv, 3):
-        raise ValueError(f'{what}: normals must be [{nv}, 3], got {tuple(normals.shape)}')
-    return vertices, faces32, normals, lay
+    return vertices, faces32, texture._normals(what, normals, vertices, faces32), lay
 
 
 @torch.no_grad()
@@ -296,11 +266,12 @@ def bake_texture(vertices, faces, images, cam2world, camera, layout_or_size, nor
     grouping.  Everything runs on the vertices' device."""
     texture._bake_parameters(tolerance, power, min_cos)
     vertices, faces32, normals, lay = _bake_mesh('bake_texture', vertices, faces, normals, layout_or_size)
-    images, c2w, k = _views('bake_texture', images, cam2world, camera)
+    images, c2w, camera = texture._views('bake_texture', images, cam2world, camera)
     texture._fallback(fallback, lay.n_texels, vertices.device)             # checked here: before any launch
     _rgb('bake_texture: background', background)
     texels = texel_points(vertices, faces32, normals, lay)
-    return _bake(vertices, faces32, texels, lay, images, c2w, k, camera, tolerance, power, min_cos, fallback, background, max_bytes)
+    return _bake('bake_texture', vertices, faces32, texels, lay, images, c2w, camera, tolerance, power, min_cos, fallback, background,
+                 max_bytes)
 
 
 # ---- rendering with the texture ---------------------------------------------------------------------------------------------
@@ -323,19 +294,17 @@ def _lookup(b1, b2, t, lay):
     return row, col, xi - (c0 << 8), yi - (r0 << 8)
 
 
-def _shade_textured_cpu(face_id, proj, vertices, faces, cams, tex, lay, ambient, background):
-    n, h, w = face_id.shape
-    out = torch.empty([n, h, w, 3], dtype=torch.uint8)
-    out[:] = torch.tensor(background, dtype=torch.uint8)
+def _atlas_albedo(faces, tex, lay):
+    """The albedo of ``shade_textured`` for ``mesh._shade_cpu``: the lookup and the integer bilinear mix of the 2 x 2 texels."""
     tex = tex.long()
-    for f in range(n):
-        pix, t, idx, b, shade_ = mesh._shade_terms_cpu(f, face_id, proj, vertices, faces, cams, ambient)
+
+    def albedo(t, idx, b):
         swapped = idx[:, 1] != faces[t, 1].long()                          # back into the stored corner order
         row, col, fx, fy = _lookup(torch.where(swapped, b[2], b[1]), torch.where(swapped, b[1], b[2]), t, lay)
         num = (256 - fy)[:, None] * ((256 - fx)[:, None] * tex[row, col] + fx[:, None] * tex[row, col + 1]) + \
             fy[:, None] * ((256 - fx)[:, None] * tex[row + 1, col] + fx[:, None] * tex[row + 1, col + 1])      # exact integers
-        out[f].reshape(-1, 3)[pix] = mesh._shaded_bytes(num.double() / 65536.0, shade_[:, None])
-    return out
+        return num.double() / 65536.0
+    return albedo
 
 
 def shade_textured(face_id, proj, vertices, faces, cam2world, tex, lay, background=(255, 255, 255), ambient=0.3):
@@ -343,32 +312,20 @@ def shade_textured(face_id, proj, vertices, faces, cam2world, tex, lay, backgrou
     pixel's barycentrics, in the face's stored corner order, give a point of the face's UV triangle, and the albedo is the bilinear mix
     of the 2 x 2 texels around it with weights in 1 / 256 (include/p3d_hip.h).  Every input is moved to face_id's device, which picks
     the path."""
-    if face_id.ndim != 3:
-        raise ValueError(f'shade_textured: face_id must be [F, H, W], got {tuple(face_id.shape)}')
-    n, h, w = face_id.shape
-    dev = face_id.device
-    face_id = face_id.detach().to(torch.int32).contiguous()
-    vertices = vertices.detach().to(device=dev, dtype=torch.float32).contiguous()
-    faces32 = mesh._faces32(faces, vertices.shape[0]).to(dev)
+    face_id, proj, vertices, faces32, cams, bg = mesh._shade_operands('shade_textured', face_id, proj, vertices, faces, cam2world, background)
     lay = _layout('shade_textured', lay, faces32.shape[0])
-    packed = proj.packed.detach().to(device=dev, dtype=torch.int32).contiguous()
-    if tuple(packed.shape) != (n, vertices.shape[0], 4):
-        raise ValueError(f'shade_textured: the projection is {tuple(packed.shape)}, the buffers and vertices need ({n}, {vertices.shape[0]}, 4)')
     tex = torch.as_tensor(tex)
     if tex.dtype != torch.uint8 or tuple(tex.shape) != (lay.size, lay.size, 3):
         raise ValueError(f'shade_textured: the texture must be uint8 [{lay.size}, {lay.size}, 3], got {tex.dtype} {tuple(tex.shape)}')
-    tex = tex.detach().to(dev).contiguous()
-    bg = tuple(int(v) & 255 for v in background)
-    cams = mesh._cameras(cam2world, mesh.Orthographic(1.0, 1.0))          # only the forward axis is read
-    if cams.shape[0] != n:
-        raise ValueError(f'shade_textured: {cams.shape[0]} cameras for {n} frames')
+    tex = tex.detach().to(face_id.device).contiguous()
     if not face_id.is_cuda:
-        return _shade_textured_cpu(face_id, mesh.Projection(packed, proj.orthographic), vertices, faces32, cams, tex, lay, ambient, bg)
-    rgb = torch.empty([n, h, w, 3], dtype=torch.uint8, device=dev)
-    cams = cams.to(dev)
-    _lib.check(_lib.lib().p3d_mesh_shade_textured(_lib.ptr(face_id), _lib.ptr(packed), _lib.ptr(vertices), vertices.shape[0], _lib.ptr(faces32),
-                                                  lay.n_faces, _lib.ptr(tex), lay.size, lay.cell, _lib.ptr(cams), n, int(proj.orthographic),
-                                                  w, h, float(ambient), *bg, _lib.ptr(rgb), _lib.stream_of(rgb)), 'mesh_shade_textured')
+        return mesh._shade_cpu(face_id, proj, vertices, faces32, cams, ambient, bg, _atlas_albedo(faces32, tex, lay))
+    n, h, w = face_id.shape
+    rgb = torch.empty([n, h, w, 3], dtype=torch.uint8, device=face_id.device)
+    _lib.check(_lib.lib().p3d_mesh_shade_textured(_lib.ptr(face_id), _lib.ptr(proj.packed), _lib.ptr(vertices), vertices.shape[0],
+                                                  _lib.ptr(faces32), lay.n_faces, _lib.ptr(tex), lay.size, lay.cell, _lib.ptr(cams), n,
+                                                  int(proj.orthographic), w, h, float(ambient), *bg, _lib.ptr(rgb), _lib.stream_of(rgb)),
+               'mesh_shade_textured')
     return rgb
 
 
@@ -377,30 +334,14 @@ def render_textured(vertices, faces, cam2world, camera, resolution, tex, lay, ba
                     max_bytes=1 << 30):
     """``mesh.render`` with ``shade_textured`` as its last stage: uint8 frames [F, H, W, 3] of the mesh with the texture ``tex`` of the
     atlas ``lay``, on the vertices' device; with return_buffers=True also (face_id, depth)."""
-    h, w = mesh._size(resolution)
-    vertices = vertices.detach().to(torch.float32).contiguous()
-    c2w = torch.as_tensor(cam2world, dtype=torch.float32).reshape(-1, 4, 4)
-    dev = vertices.device
-    faces32 = mesh._faces32(faces, vertices.shape[0]).to(dev)
+    size = mesh._size(resolution)
+    faces32 = mesh._faces32(faces)                                         # checked before the layout; _render takes them as they are (no second copy)
     lay = _layout('render_textured', lay, faces32.shape[0])
-    tex = torch.as_tensor(tex).to(dev)
-    if isinstance(camera, mesh.Pinhole):
-        k = torch.as_tensor(camera.intrinsics, dtype=torch.float32).reshape(-1, 9).expand(c2w.shape[0], 9)
-    group = max(1, min(c2w.shape[0], max_bytes // max(1, 16 * vertices.shape[0])))
-    frames, ids, depths = [], [], []
-    for s in range(0, c2w.shape[0], group):
-        cam = camera if not isinstance(camera, mesh.Pinhole) else camera._replace(intrinsics=k[s:s + group])
-        proj = mesh.project(vertices, c2w[s:s + group], cam, (h, w))
-        face_id, depth = mesh.rasterize(proj, faces32, (h, w))
-        frames.append(shade_textured(face_id, proj, vertices, faces32, c2w[s:s + group], tex, lay, background, ambient))
-        if return_buffers:
-            ids.append(face_id)
-            depths.append(depth)
-        del proj
-    out = torch.cat(frames) if frames else torch.empty([0, h, w, 3], dtype=torch.uint8, device=dev)
-    if return_buffers:
-        return out, torch.cat(ids), torch.cat(depths)
-    return out
+    tex = torch.as_tensor(tex).to(vertices.device)
+
+    def stage(*buffers):
+        return shade_textured(*buffers, tex, lay, background, ambient)
+    return mesh._render('render_textured', vertices, faces32, cam2world, camera, size, stage, return_buffers, max_bytes)
 
 
 # ---- files ------------------------------------------------------------------------------------------------------------------
@@ -456,16 +397,11 @@ def atlas_views(G, ws, vertices, faces, cfg='seg2cat', size=2048, n_views=24, ji
     vertices, faces32, normals, lay = _bake_mesh('atlas_views', vertices, faces, normals, size)
     if 'fallback' in bake_kwargs:
         texture._fallback(bake_kwargs['fallback'], lay.n_texels, vertices.device)
-    cams = texture.bake_cameras(G, cfg, n_views).to(ws.device)
-    render_kwargs = dict(render_kwargs or {})
-    render_kwargs.setdefault('noise_mode', 'const')
-    render_kwargs.setdefault('neural_rendering_resolution', views.VIDEO_CFG[cfg]['neural_rendering_resolution'])
-    frames = views.render_views(G, ws, cams, jitter=jitter, **render_kwargs)
-    camera = mesh.Pinhole(cams[:, 16:25])
-    images, c2w, k = _views('atlas_views', frames['image'], cams[:, :16].reshape(-1, 4, 4), camera)
+    frames, c2w, camera = texture._generator_views(G, ws, cfg, n_views, jitter, render_kwargs)
+    images, c2w, camera = texture._views('atlas_views', frames['image'], c2w, camera)
     texels = texel_points(vertices, faces32, normals, lay)
     fallback = bake_kwargs['fallback'] if 'fallback' in bake_kwargs else texture.vertex_rgb(G, ws, texels[0])
-    tex, seen = _bake(vertices, faces32, texels, lay, images, c2w, k, camera, fallback=fallback, **params)
+    tex, seen = _bake('atlas_views', vertices, faces32, texels, lay, images, c2w, camera, fallback=fallback, **params)
     return (tex, seen, lay, frames) if return_frames else (tex, seen, lay)
 
 

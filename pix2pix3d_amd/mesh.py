@@ -5,6 +5,8 @@
   are tested against.  Every convention (cameras, fixed point, top-left fill rule, fp64 depth, the z-test key) is include/p3d_hip.h's.
 * ``render``: the three stages over a batch of frames, the role of pyrender.OffscreenRenderer.render.  The shading is a headlight
   Lambert term on interpolated vertex colours, not pyrender's physically based shading with a spot light.
+* ``_view_groups`` / ``_raster_group``: how every loop over views (``render``, ``atlas.render_textured``, ``texture.bake_colors``,
+  ``atlas.bake_texture``) is cut into groups whose projections fit ``max_bytes``, and the raster buffers of the mesh for one group.
 * ``turntable_poses``: the script's 120-frame orbit (:240-256), in the OpenCV convention (before its OpenGL column flip).
 * ``write_ply`` (trimesh's export), ``save_gif`` (imageio.mimsave, through PIL), ``vertex_labels`` (:196-218).
 * ``components`` / ``clean`` / ``simplify``: what a trimesh user does between extraction and export (``mesh.split()``, keep the
@@ -13,6 +15,7 @@
 * ``extract_mesh``: shape.extract_geometry, the optional clean-up, the labels and the turntable in one call.
 """
 import ctypes
+import functools
 import math
 from typing import NamedTuple
 
@@ -20,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib, configs, shape
+from ._lib import _f32, _f64, _i32, _vp
 
 CAMERA_FLOATS = 24             # P3D_MESH_CAMERA_FLOATS
 GREY = 200                     # P3D_MESH_GREY: the albedo of a mesh without colours
@@ -28,15 +32,13 @@ _GUARD = 4096 * 256            # guard band, sub-pixel units
 _KEY_BG = torch.iinfo(torch.int64).max
 _SCRIPT_PI = 3.14              # the script's turntable writes pi as 3.14 (extract_mesh.py:245-251)
 
-_vp, _i32, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float              # csrc/mesh_raster.hip
 _lib.register('p3d_mesh_project', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp])
 _lib.register('p3d_mesh_raster_tiles', ctypes.c_int32, [_i32, _i32])
 _lib.register('p3d_mesh_raster_count', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp])
 _lib.register('p3d_mesh_raster_bin', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp])
 _lib.register('p3d_mesh_raster', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp])
 _lib.register('p3d_mesh_shade', ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _i32,
-                                           _vp, _vp])
-_f64 = ctypes.c_double                                                          # csrc/mesh_ops.hip
+                                           _vp, _vp])                       # (the above: csrc/mesh_raster.hip; below: csrc/mesh_ops.hip)
 _lib.register('p3d_mesh_components', ctypes.c_int, [_vp, _i32, _i32, _vp, _vp])
 _lib.register('p3d_mesh_cluster_keys', ctypes.c_int, [_vp, _i32, _f32, _f32, _f32, _f64, _i32, _i32, _i32, _vp, _vp])
 _lib.register('p3d_mesh_cluster_means', ctypes.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp])
@@ -109,6 +111,14 @@ def _cameras(cam2world, camera):
 
 
 # ---- projection -------------------------------------------------------------------------------------------------------------
+def _vertices32(what, vertices):
+    """vertices as contiguous float32 [V, 3], V < 2^31 - 1: the shape alone (no device-to-host copy; ``_mesh_vertices`` adds finiteness)."""
+    vertices = vertices.detach().to(torch.float32).contiguous()
+    if vertices.ndim != 2 or vertices.shape[1] != 3 or vertices.shape[0] >= 2 ** 31 - 1:
+        raise ValueError(f'{what}: vertices must be [V, 3] with V < 2^31 - 1, got {tuple(vertices.shape)}')
+    return vertices
+
+
 def _project_cpu(vertices, cams, ortho, h, w):
     c = cams.double()
     p = vertices.double()
@@ -137,9 +147,7 @@ def project(vertices, cam2world, camera, resolution):
     """Project vertices float32 [V, 3] into F frames (cam2world [F, 4, 4], OpenCV convention): a ``Projection`` with fixed-point screen
     positions (8 sub-pixel bits, round half to even), view depth and drop flags (include/p3d_hip.h)."""
     h, w = _size(resolution)
-    vertices = vertices.detach().to(torch.float32).contiguous()
-    if vertices.ndim != 2 or vertices.shape[1] != 3 or vertices.shape[0] >= 2 ** 31 - 1:
-        raise ValueError(f'project: vertices must be [V, 3] with V < 2^31 - 1, got {tuple(vertices.shape)}')
+    vertices = _vertices32('project', vertices)
     cams = _cameras(cam2world, camera)
     ortho = isinstance(camera, Orthographic)
     if not vertices.is_cuda:
@@ -153,7 +161,7 @@ def project(vertices, cam2world, camera, resolution):
 
 
 # ---- rasterization ----------------------------------------------------------------------------------------------------------
-def _faces32(faces, n_vertices):
+def _faces32(faces):
     if faces.ndim != 2 or faces.shape[1] != 3 or faces.shape[0] >= 2 ** 31 - 1:
         raise ValueError(f'mesh: faces must be [T, 3] with T < 2^31 - 1, got {tuple(faces.shape)}')
     if faces.dtype not in (torch.int32, torch.int64):
@@ -261,21 +269,20 @@ def _raster_device(proj, faces, h, w):
     dev = packed.device
     nf = faces.shape[0]
     tiles = int(lib.p3d_mesh_raster_tiles(w, h))
-    stream = _lib.stream_of(packed)
     counts = torch.empty([n, tiles], dtype=torch.int32, device=dev)
-    _lib.check(lib.p3d_mesh_raster_count(_lib.ptr(packed), nv, _lib.ptr(faces), nf, n, w, h, _lib.ptr(counts), stream), 'mesh_raster_count')
+    _lib.check(lib.p3d_mesh_raster_count(_lib.ptr(packed), nv, _lib.ptr(faces), nf, n, w, h, _lib.ptr(counts), _lib.stream_of(packed)),
+               'mesh_raster_count')
     inclusive = torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64)
     offsets = (inclusive - counts.reshape(-1)).contiguous()
     total = int(inclusive[-1]) if inclusive.numel() else 0                # the one device-to-host copy: sizes the tile lists
     tile_list = torch.empty([max(total, 1)], dtype=torch.int32, device=dev)
     cursor = torch.empty_like(offsets)
-    stream = _lib.stream_of(packed)
     _lib.check(lib.p3d_mesh_raster_bin(_lib.ptr(packed), nv, _lib.ptr(faces), nf, n, w, h, _lib.ptr(offsets), _lib.ptr(cursor),
-                                       _lib.ptr(tile_list), stream), 'mesh_raster_bin')
+                                       _lib.ptr(tile_list), _lib.stream_of(packed)), 'mesh_raster_bin')
     face_id = torch.empty([n, h, w], dtype=torch.int32, device=dev)
     depth = torch.empty([n, h, w], dtype=torch.float32, device=dev)
     _lib.check(lib.p3d_mesh_raster(_lib.ptr(packed), nv, _lib.ptr(faces), n, w, h, int(proj.orthographic), _lib.ptr(counts), _lib.ptr(offsets),
-                                   _lib.ptr(tile_list), _lib.ptr(face_id), _lib.ptr(depth), stream), 'mesh_raster')
+                                   _lib.ptr(tile_list), _lib.ptr(face_id), _lib.ptr(depth), _lib.stream_of(packed)), 'mesh_raster')
     return face_id, depth
 
 
@@ -285,7 +292,7 @@ def rasterize(proj, faces, resolution):
     (include/p3d_hip.h): the result does not depend on the order of the faces beyond their ids.  Device tensors run the tiled kernels
     and copy one total to the host (not graph-capturable); CPU tensors run the restatement."""
     h, w = _size(resolution)
-    faces32 = _faces32(faces, proj.packed.shape[1])
+    faces32 = _faces32(faces)
     if proj.packed.is_cuda:
         return _raster_device(proj, faces32.to(proj.packed.device), h, w)
     out = [_raster_cpu_frame(p, faces32.long(), proj.orthographic, h, w) for p in proj.packed]
@@ -345,57 +352,120 @@ def _shaded_bytes(albedo, shade_):
     return torch.floor(albedo * shade_ + 0.5).clamp(0, 255).to(torch.uint8)
 
 
-def _shade_cpu(face_id, proj, vertices, faces, colors, cams, ambient, background):
+def _shade_cpu(face_id, proj, vertices, faces, cams, ambient, background, albedo):
+    """The CPU shade of every frame: ``albedo(t, idx, b)`` gives the float64 albedo [N, 3] (or [N, 1]) of the N drawn pixels from
+    ``_shade_terms_cpu``'s faces, vertex ids and barycentrics."""
     n, h, w = face_id.shape
     out = torch.empty([n, h, w, 3], dtype=torch.uint8)
     out[:] = torch.tensor(background, dtype=torch.uint8)
     for f in range(n):
-        pix, _, idx, b, shade_ = _shade_terms_cpu(f, face_id, proj, vertices, faces, cams, ambient)
-        rgb = torch.empty([len(pix), 3], dtype=torch.uint8)
-        for ch in range(3):
-            if colors is None:
-                alb = torch.full_like(shade_, float(GREY))
-            else:
-                col = colors[:, ch].double()
-                alb = b[0] * col[idx[:, 0]]
-                alb = alb + b[1] * col[idx[:, 1]]
-                alb = alb + b[2] * col[idx[:, 2]]
-            rgb[:, ch] = _shaded_bytes(alb, shade_)
-        out[f].reshape(-1, 3)[pix] = rgb
+        pix, t, idx, b, shade_ = _shade_terms_cpu(f, face_id, proj, vertices, faces, cams, ambient)
+        out[f].reshape(-1, 3)[pix] = _shaded_bytes(albedo(t, idx, b), shade_[:, None])
     return out
+
+
+def _vertex_albedo(colors):
+    """The albedo of ``shade``: the barycentric mix of the vertex colours (one torch operation per rounding), or uniform grey."""
+    if colors is None:
+        return lambda t, idx, b: torch.full([len(t), 1], float(GREY), dtype=torch.float64)
+    col = colors.double()
+
+    def albedo(t, idx, b):
+        alb = b[0][:, None] * col[idx[:, 0]]
+        alb = alb + b[1][:, None] * col[idx[:, 1]]
+        alb = alb + b[2][:, None] * col[idx[:, 2]]
+        return alb
+    return albedo
+
+
+def _shade_operands(what, face_id, proj, vertices, faces, cam2world, background):
+    """What ``shade`` and ``atlas.shade_textured`` (``what``: the one that was called) hand to either path, checked and on face_id's
+    device (the kernel gets no host pointer): (face_id int32 [F, H, W], Projection, vertices float32 [V, 3], faces int32 [T, 3], camera
+    rows float32 [F, 24], background bytes)."""
+    if face_id.ndim != 3:
+        raise ValueError(f'{what}: face_id must be [F, H, W], got {tuple(face_id.shape)}')
+    n, dev = face_id.shape[0], face_id.device
+    face_id = face_id.detach().to(torch.int32).contiguous()
+    vertices = vertices.detach().to(device=dev, dtype=torch.float32).contiguous()
+    faces32 = _faces32(faces).to(dev)
+    packed = proj.packed.detach().to(device=dev, dtype=torch.int32).contiguous()
+    if tuple(packed.shape) != (n, vertices.shape[0], 4):
+        raise ValueError(f'{what}: the projection is {tuple(packed.shape)}, the buffers and vertices need ({n}, {vertices.shape[0]}, 4)')
+    # the camera rows only feed the forward axis here: the model's parameters do not matter
+    cams = _cameras(cam2world, Orthographic(1.0, 1.0))
+    if cams.shape[0] != n:
+        raise ValueError(f'{what}: {cams.shape[0]} cameras for {n} frames')
+    return face_id, Projection(packed, proj.orthographic), vertices, faces32, cams.to(dev), tuple(int(v) & 255 for v in background)
 
 
 def shade(face_id, proj, vertices, faces, cam2world, colors=None, background=(255, 255, 255), ambient=0.3):
     """uint8 [F, H, W, 3] frames from the raster buffers: barycentric vertex colours (perspective-correct under a pinhole camera) times
     ambient + (1 - ambient) |n . f| (face normal, camera forward axis); colors uint8 [V, 3] or None for uniform grey; background where
     face_id is -1.  cam2world as given to ``project``.  Every input is moved to face_id's device, which picks the path."""
-    if face_id.ndim != 3:
-        raise ValueError(f'shade: face_id must be [F, H, W], got {tuple(face_id.shape)}')
-    n, h, w = face_id.shape
-    dev = face_id.device                                                  # every input goes where face_id is: the kernel gets no host pointer
-    face_id = face_id.detach().to(torch.int32).contiguous()
-    vertices = vertices.detach().to(device=dev, dtype=torch.float32).contiguous()
-    faces32 = _faces32(faces, vertices.shape[0]).to(dev)
-    packed = proj.packed.detach().to(device=dev, dtype=torch.int32).contiguous()
-    if tuple(packed.shape) != (n, vertices.shape[0], 4):
-        raise ValueError(f'shade: the projection is {tuple(packed.shape)}, the buffers and vertices need ({n}, {vertices.shape[0]}, 4)')
+    face_id, proj, vertices, faces32, cams, bg = _shade_operands('shade', face_id, proj, vertices, faces, cam2world, background)
     if colors is not None:
-        colors = torch.as_tensor(colors).detach().to(device=dev, dtype=torch.uint8).contiguous()
+        colors = torch.as_tensor(colors).detach().to(device=face_id.device, dtype=torch.uint8).contiguous()
         if tuple(colors.shape) != (vertices.shape[0], 3):
             raise ValueError(f'shade: colors must be uint8 [V, 3], got {tuple(colors.shape)}')
-    bg = tuple(int(v) & 255 for v in background)
-    # the camera rows only feed the forward axis here: the model's parameters do not matter
-    cams = _cameras(cam2world, Orthographic(1.0, 1.0))
-    if cams.shape[0] != n:
-        raise ValueError(f'shade: {cams.shape[0]} cameras for {n} frames')
     if not face_id.is_cuda:
-        return _shade_cpu(face_id, Projection(packed, proj.orthographic), vertices, faces32, colors, cams, ambient, bg)
-    rgb = torch.empty([n, h, w, 3], dtype=torch.uint8, device=dev)
-    cams = cams.to(dev)
-    _lib.check(_lib.lib().p3d_mesh_shade(_lib.ptr(face_id), _lib.ptr(packed), _lib.ptr(vertices), vertices.shape[0],
+        return _shade_cpu(face_id, proj, vertices, faces32, cams, ambient, bg, _vertex_albedo(colors))
+    n, h, w = face_id.shape
+    rgb = torch.empty([n, h, w, 3], dtype=torch.uint8, device=face_id.device)
+    _lib.check(_lib.lib().p3d_mesh_shade(_lib.ptr(face_id), _lib.ptr(proj.packed), _lib.ptr(vertices), vertices.shape[0],
                                          _lib.ptr(faces32), faces32.shape[0], _lib.ptr(colors), _lib.ptr(cams), n, int(proj.orthographic),
                                          w, h, float(ambient), *bg, _lib.ptr(rgb), _lib.stream_of(rgb)), 'mesh_shade')
     return rgb
+
+
+# ---- groups of views --------------------------------------------------------------------------------------------------------
+def _host_camera(what, camera, n_frames):
+    """``camera`` for ``n_frames`` frames: a Pinhole with its intrinsics as float32 [F, 9] on the CPU (one set serves every frame),
+    another camera as it is."""
+    if not isinstance(camera, Pinhole):
+        return camera
+    k = torch.as_tensor(camera.intrinsics, dtype=torch.float32).detach().cpu().reshape(-1, 9)
+    if k.shape[0] not in (1, n_frames):
+        raise ValueError(f'{what}: {k.shape[0]} intrinsics for {n_frames} frames')
+    return camera._replace(intrinsics=k.expand(n_frames, 9))
+
+
+def _view_groups(what, cam2world, camera, n_points, max_bytes):
+    """The F views cut into groups whose projections of ``n_points`` points (16 bytes per point and view) take at most ``max_bytes``,
+    one view at least: a list of (the slice of the frames, their cam2world [G, 4, 4], their camera), poses and intrinsics on the CPU
+    (brought there once).  THE place that sizes a group and slices per-frame intrinsics; idempotent on views ``texture._views`` checked."""
+    c2w = torch.as_tensor(cam2world, dtype=torch.float32).detach().cpu().reshape(-1, 4, 4)
+    n = c2w.shape[0]
+    camera = _host_camera(what, camera, n)
+    group = max(1, min(n, max_bytes // max(1, 16 * n_points)))
+    parts = [slice(s, s + group) for s in range(0, n, group)]
+    pinhole = isinstance(camera, Pinhole)
+    return [(part, c2w[part], camera._replace(intrinsics=camera.intrinsics[part]) if pinhole else camera) for part in parts]
+
+
+def _raster_group(vertices, faces32, cam2world, camera, size):
+    """(proj, face_id, depth) of the mesh for one group of views.  Not folded into ``_view_groups`` as a generator: its caller decides
+    when the projection dies (``atlas._bake`` drops it before it projects the texels), and a suspended generator would keep it."""
+    proj = project(vertices, cam2world, camera, size)
+    return (proj,) + rasterize(proj, faces32, size)
+
+
+def _render(what, vertices, faces, cam2world, camera, resolution, shade_stage, return_buffers, max_bytes):
+    """``render`` with ``shade_stage(face_id, proj, vertices, faces32, cam2world)`` as the last stage of every group."""
+    h, w = _size(resolution)
+    vertices = vertices.detach().to(torch.float32).contiguous()
+    faces32 = _faces32(faces).to(vertices.device)
+    frames, ids, depths = [], [], []
+    for _, c2w, cam in _view_groups(what, cam2world, camera, vertices.shape[0], max_bytes):
+        proj, face_id, depth = _raster_group(vertices, faces32, c2w, cam, (h, w))
+        frames.append(shade_stage(face_id, proj, vertices, faces32, c2w))
+        if return_buffers:
+            ids.append(face_id)
+            depths.append(depth)
+        del proj
+    out = torch.cat(frames) if frames else torch.empty([0, h, w, 3], dtype=torch.uint8, device=vertices.device)
+    if return_buffers:
+        return out, torch.cat(ids), torch.cat(depths)
+    return out
 
 
 @torch.no_grad()
@@ -405,30 +475,10 @@ def render(vertices, faces, cam2world, camera, resolution=512, colors=None, back
     [F, H, W, 3] on the vertices' device.  ``camera`` is Orthographic(xmag, ymag) or Pinhole(intrinsics); faces int32 or int64 [T, 3];
     colors uint8 [V, 3] or None (uniform grey).  With return_buffers=True also (face_id int32 [F, H, W], depth float32 [F, H, W]).
     Frames go through project / rasterize / shade in groups whose projections take at most ``max_bytes``."""
-    h, w = _size(resolution)
-    vertices = vertices.detach().to(torch.float32).contiguous()
-    c2w = torch.as_tensor(cam2world, dtype=torch.float32).reshape(-1, 4, 4)
-    dev = vertices.device
-    faces32 = _faces32(faces, vertices.shape[0]).to(dev)
     if colors is not None:
-        colors = torch.as_tensor(colors).to(device=dev, dtype=torch.uint8).contiguous()
-    if isinstance(camera, Pinhole):
-        k = torch.as_tensor(camera.intrinsics, dtype=torch.float32).reshape(-1, 9).expand(c2w.shape[0], 9)
-    group = max(1, min(c2w.shape[0], max_bytes // max(1, 16 * vertices.shape[0])))
-    frames, ids, depths = [], [], []
-    for s in range(0, c2w.shape[0], group):
-        cam = camera if not isinstance(camera, Pinhole) else camera._replace(intrinsics=k[s:s + group])
-        proj = project(vertices, c2w[s:s + group], cam, (h, w))
-        face_id, depth = rasterize(proj, faces32, (h, w))
-        frames.append(shade(face_id, proj, vertices, faces32, c2w[s:s + group], colors, background, ambient))
-        if return_buffers:
-            ids.append(face_id)
-            depths.append(depth)
-        del proj
-    out = torch.cat(frames) if frames else torch.empty([0, h, w, 3], dtype=torch.uint8, device=dev)
-    if return_buffers:
-        return out, torch.cat(ids), torch.cat(depths)
-    return out
+        colors = torch.as_tensor(colors).to(device=vertices.device, dtype=torch.uint8).contiguous()
+    stage = functools.partial(shade, colors=colors, background=background, ambient=ambient)
+    return _render('render', vertices, faces, cam2world, camera, resolution, stage, return_buffers, max_bytes)
 
 
 # ---- cameras ----------------------------------------------------------------------------------------------------------------
@@ -495,9 +545,7 @@ def save_gif(path, frames, fps=60):
 
 # ---- clean-up: connected components, keep the largest, vertex clustering -------------------------------------------------------
 def _mesh_vertices(what, vertices):
-    vertices = vertices.detach().to(torch.float32).contiguous()
-    if vertices.ndim != 2 or vertices.shape[1] != 3 or vertices.shape[0] >= 2 ** 31 - 1:
-        raise ValueError(f'{what}: vertices must be [V, 3] with V < 2^31 - 1, got {tuple(vertices.shape)}')
+    vertices = _vertices32(what, vertices)
     if not bool(torch.isfinite(vertices).all()):
         raise ValueError(f'{what}: vertices must be finite')
     return vertices
@@ -508,7 +556,7 @@ def _mesh_faces(what, faces, n_vertices):
     n_vertices = int(n_vertices)
     if not 0 <= n_vertices < 2 ** 31 - 1:
         raise ValueError(f'{what}: n_vertices must be in [0, 2^31 - 1), got {n_vertices}')
-    _faces32(faces, n_vertices)
+    _faces32(faces)
     faces = faces.detach().long().contiguous()
     if faces.numel():
         lo, hi = torch.stack(torch.aminmax(faces)).tolist()

@@ -9,8 +9,9 @@ every vertex takes the weighted mean of the frames it is visible in.
 
 * ``vertex_normals``: the normalised fp64 sum of a vertex's face cross products, in ascending (face id, corner) order.
 * ``bake_accumulate`` / ``bake_finish``: the two steps of a bake on given buffers; ``bake_colors``: project, rasterize and accumulate in
-  groups of views, then finish.  Device tensors run csrc/mesh_bake.hip, CPU tensors the formulation below, written operation by
-  operation: it is the definition (include/p3d_hip.h, "mesh baking"), and the kernels' bytes equal it.
+  groups of views (``mesh._view_groups`` / ``mesh._raster_group``, as every loop over views), then finish.  Device tensors run
+  csrc/mesh_bake.hip, CPU tensors the formulation below, written operation by operation: it is the definition (include/p3d_hip.h,
+  "mesh baking"), and the kernels' bytes equal it.
 * ``vertex_rgb``: the decoder's own colour at the vertices, the fallback for vertices no view sees.
 * ``bake_cameras`` / ``bake_views`` / ``textured_mesh``: the generator's video cameras, their frames baked onto a mesh, and the whole
   of ``mesh.extract_mesh`` with baked colours.
@@ -24,11 +25,11 @@ import numpy as np
 import torch
 
 from . import _lib, mesh, views
+from ._lib import _f64, _i32, _vp
 
 GREY = mesh.GREY
 
-_vp, _i32, _f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_double             # csrc/mesh_bake.hip
-_lib.register('p3d_mesh_vertex_normals', ctypes.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp])
+_lib.register('p3d_mesh_vertex_normals', ctypes.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp])                 # csrc/mesh_bake.hip
 _lib.register('p3d_mesh_bake_accumulate', ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _i32,
                                                          _vp, _vp, _vp])
 _lib.register('p3d_mesh_bake_finish', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp])
@@ -92,7 +93,37 @@ def vertex_normals(vertices, faces):
     return normals
 
 
+def _normals(what, normals, vertices, faces=None):
+    """``normals`` as float32 [V, 3] on the vertices' device; None stands for ``vertex_normals`` where the caller names the faces."""
+    if normals is None and faces is not None:
+        return vertex_normals(vertices, faces)
+    normals = torch.as_tensor(normals).detach().to(device=vertices.device, dtype=torch.float32).contiguous()
+    if tuple(normals.shape) != (vertices.shape[0], 3):
+        raise ValueError(f'{what}: normals must be [{vertices.shape[0]}, 3], got {tuple(normals.shape)}')
+    return normals
+
+
 # ---- baking -----------------------------------------------------------------------------------------------------------------
+def _frames(what, images):
+    """``images`` as a uint8 tensor [F, H, W, 3] of a size the kernels take."""
+    images = torch.as_tensor(images)
+    if images.dtype != torch.uint8 or images.ndim != 4 or images.shape[3] != 3:
+        raise ValueError(f'{what}: images must be uint8 [F, H, W, 3], got {images.dtype} {tuple(images.shape)}')
+    mesh._size(images.shape[1:3])
+    return images
+
+
+def _views(what, images, cam2world, camera):
+    """The checked views of a bake: (images uint8 [F, H, W, 3], cam2world [F, 4, 4] on the CPU, the camera with a ``mesh.Pinhole``'s
+    intrinsics as [F, 9] on the CPU)."""
+    images = _frames(what, images)
+    n = images.shape[0]
+    c2w = torch.as_tensor(cam2world, dtype=torch.float32).detach().cpu().reshape(-1, 4, 4)
+    if c2w.shape[0] != n:
+        raise ValueError(f'{what}: {c2w.shape[0]} cameras for {n} frames')
+    return images, c2w, mesh._host_camera(what, camera, n)
+
+
 def _accumulate_cpu(acc, seen, packed, face_id, depth, images, vertices, normals, cams, ortho, tolerance, min_cos, power):
     """include/p3d_hip.h's baking rules, one torch operation per rounding (no contraction), vectorised over the vertices."""
     n, h, w = face_id.shape
@@ -171,10 +202,8 @@ def bake_accumulate(acc, seen, proj, face_id, depth, images, vertices, normals, 
             seen.device != dev or not acc.is_contiguous() or not seen.is_contiguous():
         raise ValueError(f'bake_accumulate: acc must be contiguous float64 [V, 4] and seen int32 [V] on one device, got {acc.dtype} '
                          f'{tuple(acc.shape)} and {seen.dtype} {tuple(seen.shape)}')
-    if images.dtype != torch.uint8 or images.ndim != 4 or images.shape[3] != 3:
-        raise ValueError(f'bake_accumulate: images must be uint8 [F, H, W, 3], got {images.dtype} {tuple(images.shape)}')
+    images = _frames('bake_accumulate', images)
     n, h, w = images.shape[:3]
-    mesh._size((h, w))
     cams = mesh._cameras(cam2world, mesh.Orthographic(1.0, 1.0))           # position and forward axis only: the model does not matter
     if cams.shape[0] != n or tuple(face_id.shape) != (n, h, w) or tuple(depth.shape) != (n, h, w):
         raise ValueError(f'bake_accumulate: {n} frames of {h} x {w} with {cams.shape[0]} cameras, face_id {tuple(face_id.shape)}, '
@@ -251,30 +280,14 @@ def bake_colors(vertices, faces, images, cam2world, camera, normals=None, tolera
     vertices = mesh._mesh_vertices('bake_colors', vertices)
     nv, dev = vertices.shape[0], vertices.device
     faces32 = mesh._mesh_faces('bake_colors', faces, nv).to(device=dev, dtype=torch.int32)
-    images = torch.as_tensor(images)
-    if images.dtype != torch.uint8 or images.ndim != 4 or images.shape[3] != 3:
-        raise ValueError(f'bake_colors: images must be uint8 [F, H, W, 3], got {images.dtype} {tuple(images.shape)}')
-    n, h, w = images.shape[:3]
-    mesh._size((h, w))
-    c2w = torch.as_tensor(cam2world, dtype=torch.float32).detach().cpu().reshape(-1, 4, 4)
-    if c2w.shape[0] != n:
-        raise ValueError(f'bake_colors: {c2w.shape[0]} cameras for {n} frames')
-    if isinstance(camera, mesh.Pinhole):
-        k = torch.as_tensor(camera.intrinsics, dtype=torch.float32).detach().cpu().reshape(-1, 9)
-        if k.shape[0] not in (1, n):
-            raise ValueError(f'bake_colors: {k.shape[0]} intrinsics for {n} frames')
-        k = k.expand(n, 9)
+    images, c2w, camera = _views('bake_colors', images, cam2world, camera)
+    size = tuple(images.shape[1:3])
     images = images.detach().to(dev).contiguous()
-    normals = vertex_normals(vertices, faces32) if normals is None else torch.as_tensor(normals).detach().to(device=dev, dtype=torch.float32)
-    if tuple(normals.shape) != (nv, 3):
-        raise ValueError(f'bake_colors: normals must be [{nv}, 3], got {tuple(normals.shape)}')
+    normals = _normals('bake_colors', normals, vertices, faces32)
     acc, seen = bake_buffers(nv, dev)
-    group = max(1, min(n, max_bytes // max(1, 16 * nv)))
-    for s in range(0, n if nv else 0, group):
-        cam = camera if not isinstance(camera, mesh.Pinhole) else camera._replace(intrinsics=k[s:s + group])
-        proj = mesh.project(vertices, c2w[s:s + group], cam, (h, w))
-        face_id, depth = mesh.rasterize(proj, faces32, (h, w))
-        bake_accumulate(acc, seen, proj, face_id, depth, images[s:s + group], vertices, normals, c2w[s:s + group], tolerance, power, min_cos)
+    for part, poses, cam in mesh._view_groups('bake_colors', c2w, camera, nv, max_bytes) if nv else ():
+        proj, face_id, depth = mesh._raster_group(vertices, faces32, poses, cam, size)
+        bake_accumulate(acc, seen, proj, face_id, depth, images[part], vertices, normals, poses, tolerance, power, min_cos)
         del proj, face_id, depth
     colors = bake_finish(acc, fallback)
     return (colors, seen) if return_seen else colors
@@ -301,21 +314,29 @@ def bake_cameras(G, cfg='seg2cat', n_views=24):
     return views.video_cameras(G, cfg, n_views)
 
 
+def _generator_views(G, ws, cfg, n_views, jitter, render_kwargs):
+    """The views a bake of the generator's appearance takes: (the dict of ``views.render_views`` at ``bake_cameras(G, cfg, n_views)`` —
+    the script's ray resolution and noise_mode='const' unless ``render_kwargs`` says otherwise —, cam2world [F, 4, 4], the ``mesh.Pinhole``
+    of the labels' intrinsics)."""
+    cams = bake_cameras(G, cfg, n_views).to(ws.device)
+    render_kwargs = dict(render_kwargs or {})
+    render_kwargs.setdefault('noise_mode', 'const')
+    render_kwargs.setdefault('neural_rendering_resolution', views.VIDEO_CFG[cfg]['neural_rendering_resolution'])
+    frames = views.render_views(G, ws, cams, jitter=jitter, **render_kwargs)
+    return frames, cams[:, :16].reshape(-1, 4, 4), mesh.Pinhole(cams[:, 16:25])
+
+
 @torch.no_grad()
 def bake_views(G, ws, vertices, faces, cfg='seg2cat', n_views=24, jitter='frozen', return_frames=False, render_kwargs=None, **bake_kwargs):
     """Bake ``n_views`` views of the latent ``ws`` onto the mesh: ``views.render_views`` at ``bake_cameras(G, cfg, n_views)`` (the
     script's ray resolution and noise_mode='const' unless ``render_kwargs`` says otherwise), then ``bake_colors`` with
     ``mesh.Pinhole(cameras[:, 16:25])`` and ``return_seen=True``; the fallback, unless given, is ``vertex_rgb``.  Returns
     (colors uint8 [V, 3], seen int32 [V]) on the vertices' device, and with ``return_frames`` also the dict of ``render_views``."""
-    cams = bake_cameras(G, cfg, n_views).to(ws.device)
-    render_kwargs = dict(render_kwargs or {})
-    render_kwargs.setdefault('noise_mode', 'const')
-    render_kwargs.setdefault('neural_rendering_resolution', views.VIDEO_CFG[cfg]['neural_rendering_resolution'])
-    frames = views.render_views(G, ws, cams, jitter=jitter, **render_kwargs)
+    frames, c2w, camera = _generator_views(G, ws, cfg, n_views, jitter, render_kwargs)
     if 'fallback' not in bake_kwargs:
         bake_kwargs['fallback'] = vertex_rgb(G, ws, vertices)
     bake_kwargs['return_seen'] = True
-    colors, seen = bake_colors(vertices, faces, frames['image'], cams[:, :16].reshape(-1, 4, 4), mesh.Pinhole(cams[:, 16:25]), **bake_kwargs)
+    colors, seen = bake_colors(vertices, faces, frames['image'], c2w, camera, **bake_kwargs)
     return (colors, seen, frames) if return_frames else (colors, seen)
 
 

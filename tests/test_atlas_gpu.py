@@ -4,8 +4,9 @@ import numpy as np
 import pytest
 import torch
 
-from pix2pix3d_amd import _lib, atlas, mesh
+from pix2pix3d_amd import _lib, atlas, mesh, texture
 from test_atlas_host import baked, oriented, scene_views, shade_case
+from test_mesh_host import grouped_views
 from test_mesh_gpu import _gyroid_ball, _mc_mesh, _median_mesh
 from test_texture_host import camera_kinds, true_colors
 
@@ -100,7 +101,65 @@ def test_shade_textured_moves_inputs_to_the_face_id_device(hip_lib):
     assert not back.is_cuda and (back.int() - mixed.cpu().int()).abs().max() <= 1
 
 
-# ---- 5. a larger run ----------------------------------------------------------------------------------------------------------------
+# ---- 5. view groups: launches and slicing ---------------------------------------------------------------------------------------------
+_group_cases = {}
+
+
+def _group_case(call):
+    """(run(device, max_bytes) -> tensors, points per view, launches of g groups) of one whole-pipeline call on test_mesh_host.py's
+    three views with per-frame intrinsics; on the device the poses and the intrinsics are device tensors too."""
+    if not _group_cases:
+        v, f, colors, poses, cam = grouped_views()
+        f = atlas.orient_faces(v, f)
+        lay = atlas.layout(len(f), 256)
+        tex = torch.randint(0, 256, [256, 256, 3], generator=torch.Generator().manual_seed(8), dtype=torch.uint8)
+        frames = mesh.render(v, f, poses, cam, 96, colors=colors, ambient=1.0)
+        normals = texture.vertex_normals(v, f)
+
+        def on(device):
+            return [t.to(device) for t in (v, f, colors, poses, cam.intrinsics, tex, frames, normals)]
+
+        def render(device, max_bytes):
+            v, f, colors, poses, k, _, _, _ = on(device)
+            return (mesh.render(v, f, poses, mesh.Pinhole(k), 96, colors=colors, ambient=1.0, max_bytes=max_bytes),)
+
+        def render_textured(device, max_bytes):
+            v, f, _, poses, k, tex, _, _ = on(device)
+            return (atlas.render_textured(v, f, poses, mesh.Pinhole(k), 96, tex, lay, ambient=1.0, max_bytes=max_bytes),)
+
+        def bake_colors(device, max_bytes):
+            v, f, _, poses, k, _, frames, _ = on(device)
+            return texture.bake_colors(v, f, frames, poses, mesh.Pinhole(k), return_seen=True, max_bytes=max_bytes)
+
+        def bake_texture(device, max_bytes):
+            v, f, _, poses, k, _, frames, normals = on(device)
+            return atlas.bake_texture(v, f, frames, poses, mesh.Pinhole(k), lay, normals=normals, max_bytes=max_bytes)
+        # project, count, bin, raster + shade per group; the bakes: accumulate per group (bake_texture: and the texels' projection), the
+        # finish, and the normals (bake_colors) or the texels and the assembly (bake_texture)
+        _group_cases.update(render=(render, len(v), lambda g: 5 * g), render_textured=(render_textured, len(v), lambda g: 5 * g),
+                            bake_colors=(bake_colors, len(v), lambda g: 5 * g + 2),
+                            bake_texture=(bake_texture, lay.n_texels, lambda g: 6 * g + 3))
+    return _group_cases[call]
+
+
+@pytest.mark.parametrize('call', ['render', 'render_textured', 'bake_colors', 'bake_texture'])
+def test_view_groups_launch_counts_and_match_cpu(hip_lib, call):
+    """One group of three views and three groups of one: the aux launches of each, and the bytes of the CPU path from the three groups
+    (ambient = 1, so that the shade's factor is exactly 1 on both paths)."""
+    run, n_points, launches = _group_case(call)
+    for groups, max_bytes in ((1, 3 * 16 * n_points), (3, 1)):
+        n0 = _lib.launch_count('aux')
+        got = run('cuda', max_bytes)
+        torch.cuda.synchronize()
+        count = _lib.launch_count('aux') - n0
+        assert count == launches(groups), (groups, count)
+    want = run('cpu', 1 << 30)
+    for a, b in zip(got, want):
+        differ = int((a.cpu() != b).sum())
+        assert a.is_cuda and a.dtype == b.dtype and differ == 0, f'{differ} of {b.numel()} elements differ from the CPU path'
+
+
+# ---- 6. a larger run ----------------------------------------------------------------------------------------------------------------
 def test_large_mesh_bakes_renders_and_repeats(hip_lib):
     """A 112-lattice gyroid ball (some 250 000 faces: cells of 5 texels at 2048^2), 8 views of 512^2, 8 turntable frames."""
     v, f = _mc_mesh(_gyroid_ball(112, 44.0, 2.5))
@@ -135,7 +194,7 @@ def test_large_mesh_bakes_renders_and_repeats(hip_lib):
         assert torch.equal(a, b)
 
 
-# ---- 6. the whole pipeline ------------------------------------------------------------------------------------------------------------
+# ---- 7. the whole pipeline ------------------------------------------------------------------------------------------------------------
 def test_atlas_mesh_on_a_device_generator(hip_lib, tmp_path):
     from PIL import Image
     G, ws, thr = _median_mesh('seg2cat', 32)

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from pix2pix3d_amd import atlas, mesh, texture
+from test_mesh_host import check_view_groups, grouped_views
 from test_texture_host import camera_kinds, fib_cameras, flat_frames, small_generator, sphere_scene, two_sphere_scene
 
 _cache = {}
@@ -283,6 +284,23 @@ def test_one_view_per_group_gives_the_bytes_of_one_group():
         t2, s2 = atlas.bake_texture(v, f, frames, poses, cam, 256, normals=n, max_bytes=max_bytes)
         assert torch.equal(t2, tex) and torch.equal(s2, seen)
     assert int(seen.max()) > 1
+
+
+def test_render_textured_in_groups_of_views_gives_the_bytes_of_one_group():
+    v, f, _, poses, cam = grouped_views()
+    lay = atlas.layout(len(f), 256)
+    tex = torch.randint(0, 256, [256, 256, 3], generator=torch.Generator().manual_seed(8), dtype=torch.uint8)
+
+    def render(poses, camera, **kw):
+        return atlas.render_textured(v, f, poses, camera, 96, tex, lay, **kw)
+    check_view_groups(render, len(v), lambda k: render(poses[k:k + 1], mesh.Pinhole(cam.intrinsics[k])))
+
+
+def test_render_textured_names_an_intrinsics_count_that_fits_no_frame_count():
+    v, f, _, poses, cam = grouped_views()
+    tex = torch.zeros([256, 256, 3], dtype=torch.uint8)
+    with pytest.raises(ValueError, match='render_textured: 2 intrinsics for 3 frames'):
+        atlas.render_textured(v, f, poses, mesh.Pinhole(cam.intrinsics[:2]), 96, tex, 256)
 
 
 # ---- 9. the textured shade --------------------------------------------------------------------------------------------------------------

@@ -395,3 +395,47 @@ def test_extract_mesh_chooses_the_scripts_branch(monkeypatch, data_type, channel
         assert torch.equal(colors, mesh.default_palette(channels)[labels])
     else:
         assert colors is None
+
+
+# ---- view groups ------------------------------------------------------------------------------------------------------------------
+def grouped_views():
+    """(vertices, faces, colours, poses [3, 4, 4], camera) of test_texture_host.py's two spheres: three pinhole views, each with a focal
+    length of its own, so that a group of views that took another frame's intrinsics would show."""
+    from test_texture_host import camera_kinds, two_sphere_scene
+    v, f, colors = two_sphere_scene()
+    poses, cam = camera_kinds(2.2)['pinhole']
+    k = cam.intrinsics.repeat(3, 1, 1)
+    k[:, 0, 0] = k[:, 1, 1] = torch.tensor([2.0, 2.2, 2.5])
+    return v, f, colors, poses[:3], mesh.Pinhole(k)
+
+
+def check_view_groups(render, n_points, frame_of):
+    """``render(poses, camera, **kw)`` with one view per group and with groups of two gives the bytes of the single default group,
+    frames and buffers; ``frame_of(k)`` is frame k rendered alone with its own intrinsics."""
+    _, _, _, poses, cam = grouped_views()
+    whole = render(poses, cam, return_buffers=True)
+    assert len(whole) == 3 and all(len(t) == 3 for t in whole) and (whole[1] >= 0).sum() > 1000
+    for max_bytes in (1, 2 * 16 * n_points):
+        part = render(poses, cam, return_buffers=True, max_bytes=max_bytes)
+        for a, b, what in zip(part, whole, ('frames', 'face_id', 'depth')):
+            assert a.dtype == b.dtype and torch.equal(a, b), (max_bytes, what)
+        assert torch.equal(render(poses, cam, max_bytes=max_bytes), whole[0])
+    for k in range(3):
+        assert torch.equal(frame_of(k)[0], whole[0][k])
+    assert not torch.equal(render(poses[2:], mesh.Pinhole(cam.intrinsics[0]))[0], whole[0][2])       # the focal length shows
+    with pytest.raises((ValueError, RuntimeError)):                      # two sets of intrinsics for three frames
+        render(poses, mesh.Pinhole(cam.intrinsics[:2]))
+
+
+def test_render_in_groups_of_views_gives_the_bytes_of_one_group():
+    v, f, colors, poses, cam = grouped_views()
+
+    def render(poses, camera, **kw):
+        return mesh.render(v, f, poses, camera, 96, colors=colors, **kw)
+    check_view_groups(render, len(v), lambda k: render(poses[k:k + 1], mesh.Pinhole(cam.intrinsics[k])))
+
+
+def test_render_names_an_intrinsics_count_that_fits_no_frame_count():
+    v, f, _, poses, cam = grouped_views()
+    with pytest.raises(ValueError, match='render: 2 intrinsics for 3 frames'):
+        mesh.render(v, f, poses, mesh.Pinhole(cam.intrinsics[:2]), 96)
