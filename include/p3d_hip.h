@@ -279,7 +279,44 @@ int p3d_marching_cubes_emit(const float* u, int32_t X, int32_t Y, int32_t Z, flo
                             const int64_t* block_voff, const int64_t* block_foff, int64_t n_vertices, int64_t n_faces,
                             int32_t* vbase, float* vertices, int64_t* faces, p3d_stream_t stream);
 
-/* ---- mesh rendering (applications/extract_mesh.py:226-262, the role of pyrender; csrc/mesh_raster.hip) ----------------------------
+/* ---- surface casting (csrc/surface.hip) -------------------------------------------------------------------------------------
+ * A geometry view without a mesh.  Stands beside the pipeline of applications/extract_mesh.py:60-99 (density lattice, marching cubes,
+ * then a rasterizer: R^3 decoder evaluations before the first pixel): the level set {sigma > threshold} is found along the camera's
+ * rays only, up to its first crossing.
+ * p3d_surface_cast: N = desc->n_img ray sets of M = desc->rays_per_img rays, one launch; ray_o, ray_d [N*M][3] as for
+ *   p3d_render_forward; planes, decoder (p3d_pack_decoder, exact fp32) and desc as for p3d_sample_lattice, and bit 1 of
+ *   desc->raster_order (P3D_RENDER_SHARED_PLANES) is honoured: one plane set serves the N ray sets.  Only the density net runs (net
+ *   n_nets - 1: layer 1 and the sigma row); sigma(p) below is bit for bit what p3d_sample_points returns at p.
+ *   The contract is fp32, every operation individually rounded (no fused multiply-add):
+ *     samples   t_i = near + float(i) * dt, i = 0 .. steps - 1 (the caller computes dt = float32((far - near) / (steps - 1)) once);
+ *               p(t) = o + t * d per component;
+ *     box clip  half_box > 0: a point with any |component| > half_box is OUTSIDE — it is not above the threshold and no decoder
+ *               result is used for it (march and bisection alike); half_box <= 0: no clip;
+ *     hit       the first i with sigma(p(t_i)) > threshold.  i = 0: depth = t_0.  Else lo = t_{i-1}, hi = t_i and `refine` times
+ *               tm = 0.5 * (lo + hi); sigma(p(tm)) > threshold ? hi = tm : lo = tm; then depth = hi;
+ *     gradient  position = o + depth * d; grad[a] = sigma(position + eps e_a) - sigma(position - eps e_a): one subtraction per axis,
+ *               unnormalised, only component a of the point moves, no box clip.  grad is NOT finite at every hit: a decoder may
+ *               return non-finite densities, and a position can overflow fp32;
+ *     miss      hit = 0, depth = +inf, position = grad = 0.  A NaN density is never above the threshold.
+ *   Outputs: hit uint8 [N*M], depth float [N*M], position and grad float [N*M][3] (either may be null).
+ *   raster_width = R > 0 (R * R = M, R % 8 == 0): a wave takes an 8 x 4 pixel block instead of 32 consecutive rays — scheduling only,
+ *   the outputs are indexed by ray and have the same bytes.
+ *   Limits: 2 <= steps <= 4096, 0 <= refine <= 24 (else P3D_ERR_UNSUPPORTED), n_nets 1 or 2, N <= 65535, and p3d_sample_lattice's
+ *   32-bit plane addressing limits (P3D_ERR_UNSUPPORTED).  No GPU work on an error.
+ * p3d_surface_shade: rgb uint8 [F][H][W][3] from hit [F*H*W], grad [F*H*W][3], albedo uint8 [F*H*W][3] (null: P3D_MESH_GREY) and
+ *   cam2world float [F][16] (row-major 4x4; entries 2, 6, 10 are the camera's forward axis f).  fp64, products summed left to right,
+ *   no contraction — p3d_mesh_shade's headlight rule with the density gradient g for a normal:
+ *     mode 0 (lambert)  cos = |g.f| / (|g| |f|), 0 where the denominator is 0; shade = ambient + (1 - ambient) cos;
+ *                       byte = floor(albedo * shade + 0.5) clamped to [0, 255];
+ *     mode 1 (normal)   byte_k = floor((-g_k / |g| * 0.5 + 0.5) * 255 + 0.5); |g| = 0: 128 in every component.
+ *   A gradient with a non-finite component counts as the zero gradient in both modes.  hit == 0: the background colour.          */
+int p3d_surface_cast(const float* planes_cl, const float* decoder, const p3d_render_desc* desc, const float* ray_o, const float* ray_d,
+                     float near, float dt, int32_t steps, int32_t refine, float threshold, float eps, float half_box, int32_t raster_width,
+                     uint8_t* hit, float* depth, float* position, float* grad, p3d_stream_t stream);
+int p3d_surface_shade(const uint8_t* hit, const float* grad, const uint8_t* albedo, const float* cam2world, int32_t n_frames, int32_t height,
+                      int32_t width, float ambient, int32_t mode, int32_t bg_r, int32_t bg_g, int32_t bg_b, uint8_t* rgb, p3d_stream_t stream);
+
+/* ---- mesh rendering(applications/extract_mesh.py:226-262, the role of pyrender; csrc/mesh_raster.hip) ----------------------------
  * Cameras: cameras float [F][P3D_MESH_CAMERA_FLOATS], one row per frame: [0:16] cam2world row-major 4x4 in the OpenCV convention
  *   (x right, y down, z forward: columns 0..2 are the camera axes in world space, column 3 its position), [16:21] the model's
  *   parameters, [21] znear, [22] zfar with 0 < znear < zfar (so every depth is positive, as the z-test key needs), [23] unused.

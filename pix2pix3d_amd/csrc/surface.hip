@@ -1,0 +1,276 @@
+// Surface casting for gfx950: geometry frames straight from the density field, beside the lattice + marching cubes + rasterizer
+// pipeline (applications/extract_mesh.py:60-99; shape.hip, mesh_raster.hip) and without its R^3 evaluations.
+//
+// p3d_surface_cast: per ray the first sample t_i = near + i dt whose density exceeds the threshold, B bisection steps between it and
+// the sample before, and the central density differences at the point found (include/p3d_hip.h has the contract, operation by
+// operation).  The lattice kernel (shape.hip, lattice_sigma_kernel) with rays for a driver: the gather and the density net are
+// render_device.h's, fed `coord_scale * p` exactly as there, so every density equals p3d_sample_points' sigma at the same point bit
+// for bit and the whole cast equals the same procedure composed over the point kernel.
+//
+// Mapping: a wave owns 32 rays — lane (j, h) = (lane & 31, lane >> 5) holds ray j of the tile, the two halves gather channels
+// [16 h, 16 h + 16) and keep IDENTICAL ray state (mlp_sigma's cross-half sum is commutative, both halves see the same density).  The
+// march, the bisection and the six gradient evaluations are wave-uniform loops: mlp_layer1's MFMAs and mlp_sigma's cross-half
+// reduction need the full EXEC mask, so no lane branches round an evaluation — a ray that has finished, or a lane past the end of the
+// rays, evaluates the box centre (always a valid gather, and lines every such lane shares) and ignores the result.  The march ends
+// when a ballot shows no ray of the wave still searching, the later phases are skipped by a wave without a hit.  With raster_width a
+// tile is an 8 x 4 pixel block (8 rows, 4 columns), so the rays of a wave end together and their taps share lines; outputs are
+// indexed by ray either way.  Persistent grid: one grid row per ray set, about two blocks per CU over the launch, as the lattice.
+//
+// p3d_surface_shade: one thread per pixel, fp64, mesh_tri.h's headlight rule with the density gradient for a normal.
+#include "render_device.h"
+
+namespace p3d {
+
+struct CastArgs {
+    float near, dt, threshold, eps, half_box;
+    int steps, refine, raster;                       // raster: R when the M rays of a set are an R x R image (R % 8 == 0), else 0
+    unsigned rays_per_set;
+    uint8_t* hit; float* depth; float* position; float* grad;
+};
+
+// One individually rounded fp32 operation each.  Plain operators under contract(off), NOT __fmul_rn / __fadd_rn / __fsub_rn: in this
+// toolchain those are header functions whose bodies (x * y, x + y) are compiled contractable, and once inlined hipcc fuses them into
+// v_fma_f32 whatever the caller's pragma says (seen in this kernel's ISA); an operator written under the pragma carries no contract flag.
+__device__ __forceinline__ float mul_rn(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float sub_rn(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a - b;
+}
+// o + t d, per component: one rounded product, one rounded sum (never an fma)
+__device__ __forceinline__ float ray_at(float o, float t, float d) { return add_rn(o, mul_rn(t, d)); }
+__device__ __forceinline__ float sample_t(float near, int i, float dt) { return add_rn(near, mul_rn((float)i, dt)); }
+__device__ __forceinline__ float midpoint(float lo, float hi) { return mul_rn(0.5f, add_rn(lo, hi)); }
+// (a NaN component is not outside: the comparison is false)
+__device__ __forceinline__ bool outside_box(float half_box, float x, float y, float z)
+{
+    return half_box > 0.f && (fabsf(x) > half_box || fabsf(y) > half_box || fabsf(z) > half_box);
+}
+
+// The density at (x, y, z): the lattice kernel's three calls.  Every lane of the wave must get here.
+template <int SN>
+__device__ __forceinline__ float sigma_at(const RenderArgs& a, rsrc_t rsrc, unsigned img_off, const float* lds, int lane, int h, float x, float y, float z)
+{
+    const float cs = a.coord_scale;
+    float feat[16];
+    gather_features<true>(a, rsrc, img_off, h, cs * x, cs * y, cs * z, feat);
+    f32x16 h0, h1;
+    mlp_layer1(lds, SN, lane, h, feat, h0, h1);
+    return mlp_sigma(lds, h, h0, h1);
+}
+
+template <int NNETS>
+__global__ void __launch_bounds__(kWavesPerBlock * 64, 2)
+surface_cast_kernel(RenderArgs a, CastArgs c)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    for (int i = tid; i < kDecoderFloats / 4; i += blockDim.x) ((f32x4*)lds)[i] = ((const f32x4*)a.decoder)[i];
+    __syncthreads();
+    constexpr int SN = NNETS - 1;
+    const rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.planes, 0, a.planes_total_bytes, 0x00020000);
+    const unsigned set = blockIdx.y;                                 // one ray set per grid row
+    const unsigned img_off = set * a.img_bytes;                      // (0 for every set when the planes are shared)
+    const unsigned M = c.rays_per_set, tiles = (M + 31) / 32;
+    const size_t base = (size_t)set * M;
+    const unsigned tiles_x = c.raster > 0 ? (unsigned)c.raster / 4u : 1u;
+    for (unsigned t = blockIdx.x * kWavesPerBlock + wave; t < tiles; t += gridDim.x * kWavesPerBlock) {
+        unsigned q;
+        if (c.raster > 0) {                                          // 8 rows x 4 columns of the image
+            const unsigned ty = t / tiles_x, tx = t - ty * tiles_x;
+            q = (ty * 8u + (unsigned)(j & 7)) * (unsigned)c.raster + tx * 4u + (unsigned)(j >> 3);
+        } else
+            q = t * 32u + (unsigned)j;
+        const bool live = q < M;
+        const size_t g = base + (live ? q : M - 1);
+        const float ox = a.ray_o[g * 3], oy = a.ray_o[g * 3 + 1], oz = a.ray_o[g * 3 + 2];
+        const float dx = a.ray_d[g * 3], dy = a.ray_d[g * 3 + 1], dz = a.ray_d[g * 3 + 2];
+
+        // ---- march: the first sample above the threshold ----
+        bool searching = live, found = false, bisect = false;
+        float lo = c.near, hi = c.near;
+#pragma unroll 1
+        for (int i = 0; i < c.steps; ++i) {
+            if (__ballot(searching) == 0ull) break;
+            const float ti = sample_t(c.near, i, c.dt);
+            const float px = ray_at(ox, ti, dx), py = ray_at(oy, ti, dy), pz = ray_at(oz, ti, dz);
+            const bool use = searching && !outside_box(c.half_box, px, py, pz);
+            const float s = sigma_at<SN>(a, rsrc, img_off, lds, lane, h, use ? px : 0.f, use ? py : 0.f, use ? pz : 0.f);
+            if (use && s > c.threshold) { found = true; searching = false; bisect = i > 0; hi = ti; }
+            else if (searching) lo = ti;
+        }
+        // ---- bisection between the last sample below and the first above ----
+        if (__ballot(bisect) != 0ull) {
+#pragma unroll 1
+            for (int b = 0; b < c.refine; ++b) {
+                const float tm = midpoint(lo, hi);
+                const float px = ray_at(ox, tm, dx), py = ray_at(oy, tm, dy), pz = ray_at(oz, tm, dz);
+                const bool use = bisect && !outside_box(c.half_box, px, py, pz);
+                const float s = sigma_at<SN>(a, rsrc, img_off, lds, lane, h, use ? px : 0.f, use ? py : 0.f, use ? pz : 0.f);
+                if (bisect) { if (use && s > c.threshold) hi = tm; else lo = tm; }
+            }
+        }
+        const float depth = found ? hi : INFINITY;
+        const float wx = found ? ray_at(ox, hi, dx) : 0.f, wy = found ? ray_at(oy, hi, dy) : 0.f, wz = found ? ray_at(oz, hi, dz) : 0.f;
+        const bool store = live && h == 0;
+        if (store) {
+            c.hit[g] = found ? 1 : 0;
+            c.depth[g] = depth;
+            if (c.position) { c.position[g * 3] = wx; c.position[g * 3 + 1] = wy; c.position[g * 3 + 2] = wz; }
+        }
+        // ---- gradient: central differences of the density at the point found (no box clip) ----
+        if (c.grad) {
+            if (__ballot(found) != 0ull) {
+                float sp = 0.f;
+#pragma unroll 1
+                for (int k = 0; k < 6; ++k) {                        // (+x, -x, +y, -y, +z, -z): only component k >> 1 moves, x - eps as x + (-eps)
+                    const int ax = k >> 1;
+                    const float e = (k & 1) ? -c.eps : c.eps;
+                    const float s = sigma_at<SN>(a, rsrc, img_off, lds, lane, h, ax == 0 ? add_rn(wx, e) : wx, ax == 1 ? add_rn(wy, e) : wy,
+                                                 ax == 2 ? add_rn(wz, e) : wz);
+                    if (!(k & 1)) sp = s;
+                    else if (store) c.grad[g * 3 + ax] = found ? sub_rn(sp, s) : 0.f;
+                }
+            } else if (store) {
+                c.grad[g * 3] = 0.f; c.grad[g * 3 + 1] = 0.f; c.grad[g * 3 + 2] = 0.f;
+            }
+        }
+    }
+}
+
+// shape.hip's descriptor checks (file-local there), restated for the cast
+static int cast_check_desc(const p3d_render_desc* d)
+{
+    P3D_REQUIRE(d, "surface_cast: null descriptor");
+    P3D_REQUIRE(d->n_nets == 1 || d->n_nets == 2, "surface_cast: n_nets must be 1 or 2 (got %d)", d->n_nets);
+    P3D_REQUIRE(d->plane_h >= 1 && d->plane_w >= 1, "surface_cast: bad plane size");
+    P3D_REQUIRE(d->box_warp != 0.f, "surface_cast: box_warp must be non-zero");
+    P3D_REQUIRE(d->n_img >= 0 && d->n_img <= 65535, "surface_cast: n_img must be in [0, 65535] (got %d)", d->n_img);
+    P3D_REQUIRE(d->rays_per_img >= 1, "surface_cast: rays_per_img must be >= 1 (got %d)", d->rays_per_img);
+    {   // the planes are read through one buffer descriptor with 32-bit byte offsets (24-bit multiplies for texel indices and strides)
+        const int64_t istr = d->pixel_stride > 0 ? d->image_stride : (int64_t)3 * d->plane_h * d->plane_w * 32;
+        const int64_t sets = (d->raster_order & P3D_RENDER_SHARED_PLANES) ? 1 : d->n_img;
+        if (sets * istr * 4 >= ((int64_t)1 << 31) || (int64_t)d->plane_h * d->plane_w >= (1 << 24) || d->pixel_stride * 4 >= (1 << 16))
+            return fail(P3D_ERR_UNSUPPORTED, "surface_cast: plane tensor too large for 32-bit buffer addressing (%d images)", d->n_img);
+    }
+    P3D_REQUIRE(d->pixel_stride == 0 || (d->pixel_stride % 4 == 0 && d->plane_stride % 4 == 0 && d->image_stride % 4 == 0),
+                "surface_cast: plane strides must keep texels 16-byte aligned");
+    return P3D_OK;
+}
+
+// ---- shading ----------------------------------------------------------------------------------------------------------------
+constexpr double kSurfaceGrey = 200.0;               // P3D_MESH_GREY
+
+__device__ __forceinline__ uint8_t byte_of(double v)
+{
+    return (uint8_t)(v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v));
+}
+
+__global__ void __launch_bounds__(256) surface_shade_kernel(const uint8_t* __restrict__ hit, const float* __restrict__ grad, const uint8_t* __restrict__ albedo,
+                                                            const float* __restrict__ cam2world, int64_t total, int64_t per_frame, float ambient, int mode,
+                                                            int bg_r, int bg_g, int bg_b, uint8_t* __restrict__ rgb)
+{
+#pragma clang fp contract(off)
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= total) return;
+    uint8_t* dst = rgb + p * 3;
+    if (!hit[p]) { dst[0] = (uint8_t)bg_r; dst[1] = (uint8_t)bg_g; dst[2] = (uint8_t)bg_b; return; }
+    const float g32[3] = {grad[p * 3], grad[p * 3 + 1], grad[p * 3 + 2]};
+    const bool finite = isfinite(g32[0]) && isfinite(g32[1]) && isfinite(g32[2]);
+    const double g0 = finite ? (double)g32[0] : 0.0, g1 = finite ? (double)g32[1] : 0.0, g2 = finite ? (double)g32[2] : 0.0;
+    double nn = g0 * g0; nn = nn + g1 * g1; nn = nn + g2 * g2;
+    if (mode == 1) {                                                 // normal map: -g / |g| in [0, 255]; no direction -> 128
+        const double n = sqrt(nn);
+        const double gs[3] = {g0, g1, g2};
+        for (int k = 0; k < 3; ++k) {
+            const double u = n > 0.0 ? -gs[k] / n : 0.0;
+            dst[k] = byte_of(floor((u * 0.5 + 0.5) * 255.0 + 0.5));
+        }
+        return;
+    }
+    const float* cam = cam2world + (p / per_frame) * 16;
+    const double f0 = (double)cam[2], f1 = (double)cam[6], f2 = (double)cam[10];
+    double ff = f0 * f0; ff = ff + f1 * f1; ff = ff + f2 * f2;
+    double dot = g0 * f0; dot = dot + g1 * f1; dot = dot + g2 * f2;
+    const double den = sqrt(nn) * sqrt(ff);
+    const double cosv = den > 0.0 ? fabs(dot) / den : 0.0;
+    const double amb = (double)ambient;
+    const double shade = amb + (1.0 - amb) * cosv;
+    for (int k = 0; k < 3; ++k) {
+        const double alb = albedo ? (double)albedo[p * 3 + k] : kSurfaceGrey;
+        dst[k] = byte_of(floor(alb * shade + 0.5));
+    }
+}
+
+} // namespace p3d
+
+using namespace p3d;
+
+extern "C" int p3d_surface_cast(const float* planes_cl, const float* decoder, const p3d_render_desc* d, const float* ray_o, const float* ray_d,
+                                float near, float dt, int32_t steps, int32_t refine, float threshold, float eps, float half_box, int32_t raster_width,
+                                uint8_t* hit, float* depth, float* position, float* grad, p3d_stream_t stream)
+{
+    int rc = cast_check_desc(d);
+    if (rc != P3D_OK) return rc;
+    P3D_REQUIRE(planes_cl && decoder && ray_o && ray_d && hit && depth, "surface_cast: null pointer");
+    if (steps < 2 || steps > 4096 || refine < 0 || refine > 24)
+        return fail(P3D_ERR_UNSUPPORTED, "surface_cast: needs 2 <= steps <= 4096 and 0 <= refine <= 24 (got %d, %d)", steps, refine);
+    const int64_t M = d->rays_per_img;
+    P3D_REQUIRE(raster_width >= 0 && (raster_width == 0 || (raster_width % 8 == 0 && (int64_t)raster_width * raster_width == M)),
+                "surface_cast: raster_width %d must be 0, or a multiple of 8 whose square is rays_per_img (%d)", raster_width, d->rays_per_img);
+    if (M > (int64_t)INT32_MAX - 31)
+        return fail(P3D_ERR_UNSUPPORTED, "surface_cast: %lld rays per set do not fit the kernel's 32-bit in-set index", (long long)M);
+    if (d->n_img == 0) return P3D_OK;
+    RenderArgs a{};
+    a.H = d->plane_h; a.W = d->plane_w; a.coord_scale = 2.f / d->box_warp;
+    if (d->pixel_stride > 0) { a.plane_stride = d->plane_stride; a.pix_stride = d->pixel_stride; a.img_stride = d->image_stride; }
+    else { a.plane_stride = (int64_t)a.H * a.W * 32; a.pix_stride = 32; a.img_stride = 3 * a.plane_stride; }
+    a.plane_bytes = (unsigned)(a.plane_stride * 4); a.pix_bytes = (unsigned)(a.pix_stride * 4); a.img_bytes = (unsigned)(a.img_stride * 4);
+    a.planes_total_bytes = (unsigned)((int64_t)d->n_img * a.img_stride * 4);
+    if (d->raster_order & P3D_RENDER_SHARED_PLANES) {      // one plane set for all n_img ray sets: a zero image stride, and the buffer bound is that one set's
+        a.planes_total_bytes = a.img_bytes; a.img_bytes = 0; a.img_stride = 0;
+    }
+    a.planes = planes_cl; a.decoder = decoder; a.ray_o = ray_o; a.ray_d = ray_d;
+    CastArgs c{};
+    c.near = near; c.dt = dt; c.threshold = threshold; c.eps = eps; c.half_box = half_box;
+    c.steps = steps; c.refine = refine; c.raster = raster_width; c.rays_per_set = (unsigned)M;
+    c.hit = hit; c.depth = depth; c.position = position; c.grad = grad;
+    const int64_t tiles = (M + 31) / 32;
+    int64_t bx = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
+    const int64_t cap = (kNumCU * 2 + d->n_img - 1) / d->n_img;     // about two blocks per CU over the whole launch
+    if (bx > cap) bx = cap;
+    const size_t lds_bytes = (size_t)kDecoderFloats * sizeof(float);
+    const dim3 grid((unsigned)bx, (unsigned)d->n_img);
+    hipStream_t s = (hipStream_t)stream;
+    if (d->n_nets == 1) hipLaunchKernelGGL(surface_cast_kernel<1>, grid, dim3(kWavesPerBlock * 64), lds_bytes, s, a, c);
+    else                hipLaunchKernelGGL(surface_cast_kernel<2>, grid, dim3(kWavesPerBlock * 64), lds_bytes, s, a, c);
+    count_launch(FAM_RENDER);
+    return check_launch("surface_cast");
+}
+
+extern "C" int p3d_surface_shade(const uint8_t* hit, const float* grad, const uint8_t* albedo, const float* cam2world, int32_t n_frames, int32_t height,
+                                 int32_t width, float ambient, int32_t mode, int32_t bg_r, int32_t bg_g, int32_t bg_b, uint8_t* rgb, p3d_stream_t stream)
+{
+    P3D_REQUIRE(n_frames >= 0 && height >= 1 && width >= 1, "surface_shade: bad frame size %d x %d x %d", n_frames, height, width);
+    P3D_REQUIRE(mode == 0 || mode == 1, "surface_shade: mode must be 0 (lambert) or 1 (normal), got %d", mode);
+    if (n_frames == 0) return P3D_OK;
+    P3D_REQUIRE(hit && grad && cam2world && rgb, "surface_shade: null pointer");
+    const int64_t per_frame = (int64_t)height * width, total = per_frame * n_frames;
+    const int64_t blocks = (total + 255) / 256;
+    if (blocks > INT32_MAX)
+        return fail(P3D_ERR_UNSUPPORTED, "surface_shade: %lld pixels are more than one launch takes", (long long)total);
+    hipLaunchKernelGGL(surface_shade_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, hit, grad, albedo, cam2world, total, per_frame,
+                       ambient, mode, bg_r & 255, bg_g & 255, bg_b & 255, rgb);
+    count_launch(FAM_AUX);
+    return check_launch("surface_shade");
+}

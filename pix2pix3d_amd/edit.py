@@ -192,7 +192,7 @@ def forward_label(G):
 class EditSession:
     """One editing session on the device ``G`` lives on; every method runs under ``torch.no_grad()``.
 
-    Four stages, each recomputed only when its input changed: mask -> geometry ws -> planes -> frame.  ``paint`` / ``undo`` / ``clear`` / ``load`` /
+    Four stages, each recomputed only when its input changed: mask -> geometry ws -> planes -> frame (and, beside the frame, ``geometry()``'s surface frame).  ``paint`` / ``undo`` / ``clear`` / ``load`` /
     ``take_view_as_mask`` dirty the mask; ``set_seed`` / ``clear_texture`` the ws; a camera change only the frame: ``render()`` after it is
     ``G.synthesis(ws, c, use_cached_backbone=True)`` on the kept planes and ``views.finish_frames`` — neither the Encoder nor the backbone runs.
 
@@ -393,6 +393,26 @@ class EditSession:
     def frame(self):
         """``render()`` on the host, as numpy arrays."""
         return {k: v.cpu().numpy() for k, v in self.render().items()}
+
+    _surface = None                                                            # geometry()'s product: (planes, cam2world, arguments, frame)
+
+    @torch.no_grad()
+    def geometry(self, resolution=None, color='grey', **cast_kwargs):
+        """uint8 [R, R, 3] on the device: the SHAPE the current edit produced, seen from the current camera — ``surface.render`` on the kept planes
+        (R = ``resolution``, default ``G.img_resolution``; ``color`` and ``cast_kwargs`` as there).  A fifth kept product: it is recomputed when the planes
+        or the camera were replaced (whatever dirties them dirties it) or the arguments differ; a camera move runs one cast launch and the shade launch,
+        neither the Encoder nor the backbone ('rgb' / 'label' colours query ``G.sample_mixed``, which does run the backbone)."""
+        from . import surface
+        ws, G = self.encode(), self.G
+        if self._planes is None:
+            self._planes = G.backbone_planes(ws, noise_mode='const')
+        res = int(G.img_resolution if resolution is None else resolution)
+        key = (res, color, sorted(cast_kwargs.items()))
+        kept = self._surface
+        if kept is None or kept[0] is not self._planes or kept[1] is not self._cam2world or kept[2] != key:
+            frame = surface.render(G, ws, self.camera, res, color=color, palette=self.palette, planes=self._planes, **cast_kwargs)[0]
+            self._surface = kept = (self._planes, self._cam2world, key, frame)
+        return kept[3]
 
     @torch.no_grad()
     def take_view_as_mask(self):

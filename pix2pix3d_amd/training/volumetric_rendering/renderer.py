@@ -76,6 +76,7 @@ _lib.register('p3d_pack_decoder_dual', ctypes.c_int, [_vp] * 8 + [_f32, _vp, _vp
 _lib.register('p3d_render_forward_dual', ctypes.c_int, [_vp] * 9 + [ctypes.POINTER(_RenderDesc)] + [_vp] * 4 + [_vp])
 _lib.register('p3d_sample_points_dual', ctypes.c_int, [_vp] * 4 + [ctypes.POINTER(_RenderDesc), _i32, _vp, _vp, _vp])
 _lib.register('p3d_sample_lattice', ctypes.c_int, [_vp, _vp, ctypes.POINTER(_RenderDesc), _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp])
+_lib.register('p3d_surface_cast', ctypes.c_int, [_vp, _vp, ctypes.POINTER(_RenderDesc), _vp, _vp, _f32, _f32, _i32, _i32, _f32, _f32, _f32, _i32] + [_vp] * 5)
 
 
 def generate_planes():
@@ -652,6 +653,28 @@ def fused_sample_lattice(planes, decoder, xs, ys, zs, opt):
                                          *[len(t) for t in axes], _lib.ptr(sigma), _lib.stream_of(sigma))
     _lib.check(code, 'sample_lattice')
     return sigma
+
+
+def fused_surface_cast(planes, decoder, ray_o, ray_d, opt, near, far, steps, refine, threshold, eps, half_box=0.0, raster_width=0):
+    """One launch of p3d_surface_cast (csrc/surface.hip; the contract is include/p3d_hip.h's): rays [N, M, 3] against planes of batch N, or of batch 1
+    for every ray set (many cameras of one latent) -> (hit uint8 [N, M], depth float32 [N, M], position, grad float32 [N, M, 3]).  Every density the
+    cast compares or differences is ``fused_sample_points(...)[1]`` at the same point.  ``half_box <= 0``: no box clip; ``raster_width`` = R when
+    the M rays are an R x R image with R % 8 == 0 (scheduling only)."""
+    n, m, _ = ray_o.shape
+    shared = shared_planes(planes.shape[0], n, 'fused_surface_cast')
+    ctx = _FusedContext(planes, _decoder_nets(decoder))
+    o, d = _f32c(ray_o), _f32c(ray_d)
+    dev = planes.device
+    hit = torch.empty([n, m], dtype=torch.uint8, device=dev)
+    depth = torch.empty([n, m], dtype=torch.float32, device=dev)
+    position, grad = torch.empty([n, m, 3], dtype=torch.float32, device=dev), torch.empty([n, m, 3], dtype=torch.float32, device=dev)
+    desc = ctx.desc(opt, rays_per_img=m, raster=2 if shared else 0, n_img=n)             # P3D_RENDER_SHARED_PLANES (2): the N ray sets all read the one plane set
+    dt = (float(far) - float(near)) / (int(steps) - 1) if int(steps) > 1 else 0.0
+    code = _lib.lib().p3d_surface_cast(_lib.ptr(ctx.planes_cl), _lib.ptr(ctx.packed), ctypes.byref(desc), _lib.ptr(o), _lib.ptr(d), float(near), dt,
+                                       int(steps), int(refine), float(threshold), float(eps), float(half_box), int(raster_width),
+                                       _lib.ptr(hit), _lib.ptr(depth), _lib.ptr(position), _lib.ptr(grad), _lib.stream_of(hit))
+    _lib.check(code, 'surface_cast')
+    return hit, depth, position, grad
 
 
 def _decoder_param_grads(decoder, nets, d_dec):
