@@ -309,12 +309,46 @@ int p3d_marching_cubes_emit(const float* u, int32_t X, int32_t Y, int32_t Z, flo
  *     mode 0 (lambert)  cos = |g.f| / (|g| |f|), 0 where the denominator is 0; shade = ambient + (1 - ambient) cos;
  *                       byte = floor(albedo * shade + 0.5) clamped to [0, 255];
  *     mode 1 (normal)   byte_k = floor((-g_k / |g| * 0.5 + 0.5) * 255 + 0.5); |g| = 0: 128 in every component.
- *   A gradient with a non-finite component counts as the zero gradient in both modes.  hit == 0: the background colour.          */
+ *   A gradient with a non-finite component counts as the zero gradient in both modes.  hit == 0: the background colour.
+ * p3d_surface_occlusion: the second ray stage — what short rays from points ON the surface find.  N = desc->n_img point sets of
+ *   M = desc->rays_per_img points, one launch: origin, facing float [N*M][3], active uint8 [N*M], directions float [N][K][3] (per set:
+ *   a camera-attached light differs per view), K = n_directions.  planes, decoder, desc, P3D_RENDER_SHARED_PLANES, raster_width and
+ *   sigma(p) exactly as for p3d_surface_cast.  The contract is fp32, every operation individually rounded (no fused multiply-add):
+ *     samples   s_j = float(j + 1) * ds, j = 0 .. steps - 1 (the caller computes ds = float32(reach / steps) once);
+ *               p = o + s_j * d per component: one rounded product, one rounded sum;
+ *     used      direction k is USED by point p iff active[p] != 0 and ((f_x d_x) + (f_y d_y)) + (f_z d_z) > 0: three rounded products,
+ *               two rounded sums in that order (a NaN makes the comparison false);
+ *     blocked   a used direction is BLOCKED iff for some j the point is inside the box (p3d_surface_cast's clip: half_box > 0 and any
+ *               |component| > half_box is outside; half_box <= 0 clips nothing) and sigma(point) > threshold.  A NaN density never
+ *               blocks;
+ *     outputs   total[p] = the number of used directions, open[p] = the number of used directions that are not blocked; uint8 [N*M],
+ *               both 0 for an inactive point.
+ *   No value depends on which points share a launch or a wave.  (Every component of p is monotone in j, so a ray that has been inside
+ *   the box and has left it cannot be blocked any more; the kernel stops it there.)
+ *   Limits: 1 <= n_directions <= 255, 1 <= steps <= 4096 (else P3D_ERR_UNSUPPORTED), and p3d_surface_cast's descriptor checks and
+ *   raster_width rule.  No GPU work on an error.
+ * p3d_surface_shade_lit: p3d_surface_shade's mode 0 with a light, an ambient-occlusion pair and a shadow pair, each optional (null).
+ *   light float [F][3]: the world-space direction TOWARDS the light of every frame; ao_open / ao_total and sh_open / sh_total uint8
+ *   [F*H*W]: p3d_surface_occlusion's counts (a pair is given whole or not at all).  fp64, products summed left to right, no contraction:
+ *     v      = light of the frame, or without one the camera's forward axis f;
+ *     nn     = g.g, ll = v.v, dot = g.v, den = sqrt(nn) * sqrt(ll)   (a gradient with a non-finite component counts as zero);
+ *     cos    = 0 where den > 0 is false; with a light max(0, -dot / den) (the normal is n = -g / |g|: cos = n.l / |l|; NaN -> 0); without
+ *              one |dot| / den (p3d_surface_shade's headlight);
+ *     ao     = ao_total > 0 ? ao_open / ao_total : 1 (1 without the pair); sh likewise from the shadow pair;
+ *     shade  = (ambient * ao) + (((1 - ambient) * cos) * sh);  byte = floor(albedo * shade + 0.5) clamped to [0, 255].
+ *   hit == 0: the background colour.  With no light and no pair the bytes are p3d_surface_shade's (mode 0).                        */
 int p3d_surface_cast(const float* planes_cl, const float* decoder, const p3d_render_desc* desc, const float* ray_o, const float* ray_d,
                      float near, float dt, int32_t steps, int32_t refine, float threshold, float eps, float half_box, int32_t raster_width,
                      uint8_t* hit, float* depth, float* position, float* grad, p3d_stream_t stream);
 int p3d_surface_shade(const uint8_t* hit, const float* grad, const uint8_t* albedo, const float* cam2world, int32_t n_frames, int32_t height,
                       int32_t width, float ambient, int32_t mode, int32_t bg_r, int32_t bg_g, int32_t bg_b, uint8_t* rgb, p3d_stream_t stream);
+int p3d_surface_occlusion(const float* planes_cl, const float* decoder, const p3d_render_desc* desc, const float* origin, const float* facing,
+                          const uint8_t* active, const float* directions, int32_t n_directions, float ds, int32_t steps, float threshold,
+                          float half_box, int32_t raster_width, uint8_t* open, uint8_t* total, p3d_stream_t stream);
+int p3d_surface_shade_lit(const uint8_t* hit, const float* grad, const uint8_t* albedo, const float* cam2world, const float* light,
+                          const uint8_t* ao_open, const uint8_t* ao_total, const uint8_t* sh_open, const uint8_t* sh_total, int32_t n_frames,
+                          int32_t height, int32_t width, float ambient, int32_t bg_r, int32_t bg_g, int32_t bg_b, uint8_t* rgb,
+                          p3d_stream_t stream);
 
 /* ---- mesh rendering(applications/extract_mesh.py:226-262, the role of pyrender; csrc/mesh_raster.hip) ----------------------------
  * Cameras: cameras float [F][P3D_MESH_CAMERA_FLOATS], one row per frame: [0:16] cam2world row-major 4x4 in the OpenCV convention

@@ -17,6 +17,14 @@
 // indexed by ray either way.  Persistent grid: one grid row per ray set, about two blocks per CU over the launch, as the lattice.
 //
 // p3d_surface_shade: one thread per pixel, fp64, mesh_tri.h's headlight rule with the density gradient for a normal.
+//
+// p3d_surface_occlusion: the second ray stage — from every hit point short rays into the hemisphere the surface faces (ambient occlusion) or
+// towards a light (shadows); per point the number of directions it uses and the number of those that reach the end unblocked.  Same tile
+// mapping, same densities.  Each lane keeps a PRIVATE cursor (direction k, step j): every wave-uniform iteration evaluates each lane's own
+// current sample, and a lane whose ray is decided moves to its next used direction in a loop that holds no evaluation (so it may diverge).
+// No lane sits through a direction it does not use, neighbours whose hemispheres differ do not stall each other; the wave runs for as
+// long as its busiest lane.  The set's direction table sits in LDS behind the decoder copy.
+// p3d_surface_shade_lit: the shade with a directional light, an ambient-occlusion pair and a shadow pair, each optional.
 #include "render_device.h"
 
 namespace p3d {
@@ -148,6 +156,89 @@ surface_cast_kernel(RenderArgs a, CastArgs c)
     }
 }
 
+struct OcclusionArgs {
+    float ds, threshold, half_box;
+    int n_dirs, steps, raster;
+    unsigned points_per_set;
+    const uint8_t* active; const float* directions;  // [N*M], [N][K][3]; origins and facings travel as RenderArgs' ray_o, ray_d
+    uint8_t* open; uint8_t* total;
+};
+
+constexpr int kMaxDirections = 255;                  // the counts are bytes; 255 * 3 floats of LDS behind the decoder copy
+
+// facing . d > 0: three rounded products, two rounded sums, left to right (a NaN compares false)
+__device__ __forceinline__ bool faces(float fx, float fy, float fz, const float* d)
+{
+    return add_rn(add_rn(mul_rn(fx, d[0]), mul_rn(fy, d[1])), mul_rn(fz, d[2])) > 0.f;
+}
+
+template <int NNETS>
+__global__ void __launch_bounds__(kWavesPerBlock * 64, 2)
+surface_occlusion_kernel(RenderArgs a, OcclusionArgs c)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const unsigned set = blockIdx.y;                                 // one point set, and its direction table, per grid row
+    float* dirs = lds + kDecoderFloats;
+    for (int i = tid; i < kDecoderFloats / 4; i += blockDim.x) ((f32x4*)lds)[i] = ((const f32x4*)a.decoder)[i];
+    for (int i = tid; i < c.n_dirs * 3; i += blockDim.x) dirs[i] = c.directions[(size_t)set * c.n_dirs * 3 + i];
+    __syncthreads();
+    constexpr int SN = NNETS - 1;
+    const rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.planes, 0, a.planes_total_bytes, 0x00020000);
+    const unsigned img_off = set * a.img_bytes;                      // (0 for every set when the planes are shared)
+    const unsigned M = c.points_per_set, tiles = (M + 31) / 32;
+    const size_t base = (size_t)set * M;
+    const unsigned tiles_x = c.raster > 0 ? (unsigned)c.raster / 4u : 1u;
+    const int K = c.n_dirs, last = c.steps - 1;
+    for (unsigned t = blockIdx.x * kWavesPerBlock + wave; t < tiles; t += gridDim.x * kWavesPerBlock) {
+        unsigned q;
+        if (c.raster > 0) {                                          // 8 rows x 4 columns of the image
+            const unsigned ty = t / tiles_x, tx = t - ty * tiles_x;
+            q = (ty * 8u + (unsigned)(j & 7)) * (unsigned)c.raster + tx * 4u + (unsigned)(j >> 3);
+        } else
+            q = t * 32u + (unsigned)j;
+        const bool live = q < M;
+        const size_t g = base + (live ? q : M - 1);
+        const float ox = a.ray_o[g * 3], oy = a.ray_o[g * 3 + 1], oz = a.ray_o[g * 3 + 2];
+        const float fx = a.ray_d[g * 3], fy = a.ray_d[g * 3 + 1], fz = a.ray_d[g * 3 + 2];
+        const bool on = live && c.active[g] != 0;
+
+        // ---- the directions this point uses; the cursor starts at the first of them (K: none, or none left) ----
+        int total = 0, k = K;
+        if (on)
+            for (int i = K - 1; i >= 0; --i)
+                if (faces(fx, fy, fz, dirs + i * 3)) { ++total; k = i; }
+        int open = 0, step = 0;
+        bool entered = false;                                        // the current ray has had a sample inside the box
+        const int bound = K * c.steps;                               // (<= 255 * 4096) no lane has more samples than this
+#pragma unroll 1
+        for (int it = 0; it < bound; ++it) {
+            const bool work = k < K;
+            if (__ballot(work) == 0ull) break;
+            const float* d = dirs + (work ? k : 0) * 3;
+            const float s = mul_rn((float)(step + 1), c.ds);
+            const float px = ray_at(ox, s, d[0]), py = ray_at(oy, s, d[1]), pz = ray_at(oz, s, d[2]);
+            const bool out = outside_box(c.half_box, px, py, pz);
+            const bool use = work && !out;
+            const float sg = sigma_at<SN>(a, rsrc, img_off, lds, lane, h, use ? px : 0.f, use ? py : 0.f, use ? pz : 0.f);
+            if (work) {
+                const bool blocked = use && sg > c.threshold;        // (a NaN density never blocks)
+                // every component of the point is monotone in the step: a ray that was inside the box and has left it stays outside
+                const bool left = out && entered;
+                if (blocked || left || step == last) {
+                    if (!blocked) ++open;
+                    do ++k; while (k < K && !faces(fx, fy, fz, dirs + k * 3));      // no evaluation in here: free to diverge
+                    step = 0; entered = false;
+                } else {
+                    ++step; entered = entered || !out;
+                }
+            }
+        }
+        if (live && h == 0) { c.open[g] = (uint8_t)open; c.total[g] = (uint8_t)total; }
+    }
+}
+
 // shape.hip's descriptor checks (file-local there), restated for the cast
 static int cast_check_desc(const p3d_render_desc* d)
 {
@@ -166,6 +257,22 @@ static int cast_check_desc(const p3d_render_desc* d)
     P3D_REQUIRE(d->pixel_stride == 0 || (d->pixel_stride % 4 == 0 && d->plane_stride % 4 == 0 && d->image_stride % 4 == 0),
                 "surface_cast: plane strides must keep texels 16-byte aligned");
     return P3D_OK;
+}
+
+// What the kernels of this file read of a checked descriptor: the planes' sizes and strides, the decoder, one ray (or point) set per image.
+static RenderArgs cast_render_args(const p3d_render_desc* d, const float* planes_cl, const float* decoder, const float* ray_o, const float* ray_d)
+{
+    RenderArgs a{};
+    a.H = d->plane_h; a.W = d->plane_w; a.coord_scale = 2.f / d->box_warp;
+    if (d->pixel_stride > 0) { a.plane_stride = d->plane_stride; a.pix_stride = d->pixel_stride; a.img_stride = d->image_stride; }
+    else { a.plane_stride = (int64_t)a.H * a.W * 32; a.pix_stride = 32; a.img_stride = 3 * a.plane_stride; }
+    a.plane_bytes = (unsigned)(a.plane_stride * 4); a.pix_bytes = (unsigned)(a.pix_stride * 4); a.img_bytes = (unsigned)(a.img_stride * 4);
+    a.planes_total_bytes = (unsigned)((int64_t)d->n_img * a.img_stride * 4);
+    if (d->raster_order & P3D_RENDER_SHARED_PLANES) {      // one plane set for all n_img ray sets: a zero image stride, and the buffer bound is that one set's
+        a.planes_total_bytes = a.img_bytes; a.img_bytes = 0; a.img_stride = 0;
+    }
+    a.planes = planes_cl; a.decoder = decoder; a.ray_o = ray_o; a.ray_d = ray_d;
+    return a;
 }
 
 // ---- shading ----------------------------------------------------------------------------------------------------------------
@@ -212,6 +319,48 @@ __global__ void __launch_bounds__(256) surface_shade_kernel(const uint8_t* __res
     }
 }
 
+// The lit shade.  light [F][3] (null: the headlight), ao_* and sh_* [F*H*W] counts (null pairs: 1).  With all three null the operations
+// and their order are surface_shade_kernel's mode 0: amb * 1.0 and b * 1.0 are exact.
+__global__ void __launch_bounds__(256) surface_shade_lit_kernel(const uint8_t* __restrict__ hit, const float* __restrict__ grad, const uint8_t* __restrict__ albedo,
+                                                                const float* __restrict__ cam2world, const float* __restrict__ light,
+                                                                const uint8_t* __restrict__ ao_open, const uint8_t* __restrict__ ao_total,
+                                                                const uint8_t* __restrict__ sh_open, const uint8_t* __restrict__ sh_total, int64_t total,
+                                                                int64_t per_frame, float ambient, int bg_r, int bg_g, int bg_b, uint8_t* __restrict__ rgb)
+{
+#pragma clang fp contract(off)
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= total) return;
+    uint8_t* dst = rgb + p * 3;
+    if (!hit[p]) { dst[0] = (uint8_t)bg_r; dst[1] = (uint8_t)bg_g; dst[2] = (uint8_t)bg_b; return; }
+    const float g32[3] = {grad[p * 3], grad[p * 3 + 1], grad[p * 3 + 2]};
+    const bool finite = isfinite(g32[0]) && isfinite(g32[1]) && isfinite(g32[2]);
+    const double g0 = finite ? (double)g32[0] : 0.0, g1 = finite ? (double)g32[1] : 0.0, g2 = finite ? (double)g32[2] : 0.0;
+    double nn = g0 * g0; nn = nn + g1 * g1; nn = nn + g2 * g2;
+    const int64_t frame = p / per_frame;
+    const float* v = light ? light + frame * 3 : nullptr;            // the light, or the camera's forward axis
+    const float* cam = cam2world + frame * 16;
+    const double l0 = (double)(v ? v[0] : cam[2]), l1 = (double)(v ? v[1] : cam[6]), l2 = (double)(v ? v[2] : cam[10]);
+    double ll = l0 * l0; ll = ll + l1 * l1; ll = ll + l2 * l2;
+    double dot = g0 * l0; dot = dot + g1 * l1; dot = dot + g2 * l2;
+    const double den = sqrt(nn) * sqrt(ll);
+    double cosv = 0.0;
+    if (den > 0.0) {
+        if (light) { const double c = -dot / den; cosv = c > 0.0 ? c : 0.0; }       // n = -g / |g|: the side that faces the light (NaN: 0)
+        else cosv = fabs(dot) / den;
+    }
+    const double ao = ao_total && ao_total[p] > 0 ? (double)ao_open[p] / (double)ao_total[p] : 1.0;
+    const double sh = sh_total && sh_total[p] > 0 ? (double)sh_open[p] / (double)sh_total[p] : 1.0;
+    const double amb = (double)ambient;
+    const double lit_ambient = amb * ao;
+    double lit_direct = (1.0 - amb) * cosv;
+    lit_direct = lit_direct * sh;
+    const double shade = lit_ambient + lit_direct;
+    for (int k = 0; k < 3; ++k) {
+        const double alb = albedo ? (double)albedo[p * 3 + k] : kSurfaceGrey;
+        dst[k] = byte_of(floor(alb * shade + 0.5));
+    }
+}
+
 } // namespace p3d
 
 using namespace p3d;
@@ -231,16 +380,7 @@ extern "C" int p3d_surface_cast(const float* planes_cl, const float* decoder, co
     if (M > (int64_t)INT32_MAX - 31)
         return fail(P3D_ERR_UNSUPPORTED, "surface_cast: %lld rays per set do not fit the kernel's 32-bit in-set index", (long long)M);
     if (d->n_img == 0) return P3D_OK;
-    RenderArgs a{};
-    a.H = d->plane_h; a.W = d->plane_w; a.coord_scale = 2.f / d->box_warp;
-    if (d->pixel_stride > 0) { a.plane_stride = d->plane_stride; a.pix_stride = d->pixel_stride; a.img_stride = d->image_stride; }
-    else { a.plane_stride = (int64_t)a.H * a.W * 32; a.pix_stride = 32; a.img_stride = 3 * a.plane_stride; }
-    a.plane_bytes = (unsigned)(a.plane_stride * 4); a.pix_bytes = (unsigned)(a.pix_stride * 4); a.img_bytes = (unsigned)(a.img_stride * 4);
-    a.planes_total_bytes = (unsigned)((int64_t)d->n_img * a.img_stride * 4);
-    if (d->raster_order & P3D_RENDER_SHARED_PLANES) {      // one plane set for all n_img ray sets: a zero image stride, and the buffer bound is that one set's
-        a.planes_total_bytes = a.img_bytes; a.img_bytes = 0; a.img_stride = 0;
-    }
-    a.planes = planes_cl; a.decoder = decoder; a.ray_o = ray_o; a.ray_d = ray_d;
+    const RenderArgs a = cast_render_args(d, planes_cl, decoder, ray_o, ray_d);
     CastArgs c{};
     c.near = near; c.dt = dt; c.threshold = threshold; c.eps = eps; c.half_box = half_box;
     c.steps = steps; c.refine = refine; c.raster = raster_width; c.rays_per_set = (unsigned)M;
@@ -273,4 +413,57 @@ extern "C" int p3d_surface_shade(const uint8_t* hit, const float* grad, const ui
                        ambient, mode, bg_r & 255, bg_g & 255, bg_b & 255, rgb);
     count_launch(FAM_AUX);
     return check_launch("surface_shade");
+}
+
+extern "C" int p3d_surface_occlusion(const float* planes_cl, const float* decoder, const p3d_render_desc* d, const float* origin, const float* facing,
+                                     const uint8_t* active, const float* directions, int32_t n_directions, float ds, int32_t steps, float threshold,
+                                     float half_box, int32_t raster_width, uint8_t* open, uint8_t* total, p3d_stream_t stream)
+{
+    int rc = cast_check_desc(d);
+    if (rc != P3D_OK) return rc;
+    if (n_directions < 1 || n_directions > kMaxDirections || steps < 1 || steps > 4096)
+        return fail(P3D_ERR_UNSUPPORTED, "surface_occlusion: needs 1 <= directions <= %d and 1 <= steps <= 4096 (got %d, %d)", kMaxDirections, n_directions,
+                    steps);
+    P3D_REQUIRE(planes_cl && decoder && origin && facing && active && directions && open && total, "surface_occlusion: null pointer");
+    const int64_t M = d->rays_per_img;
+    P3D_REQUIRE(raster_width >= 0 && (raster_width == 0 || (raster_width % 8 == 0 && (int64_t)raster_width * raster_width == M)),
+                "surface_occlusion: raster_width %d must be 0, or a multiple of 8 whose square is rays_per_img (%d)", raster_width, d->rays_per_img);
+    if (M > (int64_t)INT32_MAX - 31)
+        return fail(P3D_ERR_UNSUPPORTED, "surface_occlusion: %lld points per set do not fit the kernel's 32-bit in-set index", (long long)M);
+    if (d->n_img == 0) return P3D_OK;
+    const RenderArgs a = cast_render_args(d, planes_cl, decoder, origin, facing);
+    OcclusionArgs c{};
+    c.ds = ds; c.threshold = threshold; c.half_box = half_box;
+    c.n_dirs = n_directions; c.steps = steps; c.raster = raster_width; c.points_per_set = (unsigned)M;
+    c.active = active; c.directions = directions; c.open = open; c.total = total;
+    const int64_t tiles = (M + 31) / 32;
+    int64_t bx = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
+    const int64_t cap = (kNumCU * 2 + d->n_img - 1) / d->n_img;     // about two blocks per CU over the whole launch
+    if (bx > cap) bx = cap;
+    const size_t lds_bytes = (size_t)(kDecoderFloats + kMaxDirections * 3) * sizeof(float);
+    const dim3 grid((unsigned)bx, (unsigned)d->n_img);
+    hipStream_t s = (hipStream_t)stream;
+    if (d->n_nets == 1) hipLaunchKernelGGL(surface_occlusion_kernel<1>, grid, dim3(kWavesPerBlock * 64), lds_bytes, s, a, c);
+    else                hipLaunchKernelGGL(surface_occlusion_kernel<2>, grid, dim3(kWavesPerBlock * 64), lds_bytes, s, a, c);
+    count_launch(FAM_RENDER);
+    return check_launch("surface_occlusion");
+}
+
+extern "C" int p3d_surface_shade_lit(const uint8_t* hit, const float* grad, const uint8_t* albedo, const float* cam2world, const float* light,
+                                     const uint8_t* ao_open, const uint8_t* ao_total, const uint8_t* sh_open, const uint8_t* sh_total, int32_t n_frames,
+                                     int32_t height, int32_t width, float ambient, int32_t bg_r, int32_t bg_g, int32_t bg_b, uint8_t* rgb,
+                                     p3d_stream_t stream)
+{
+    P3D_REQUIRE(n_frames >= 0 && height >= 1 && width >= 1, "surface_shade_lit: bad frame size %d x %d x %d", n_frames, height, width);
+    P3D_REQUIRE(!ao_open == !ao_total && !sh_open == !sh_total, "surface_shade_lit: an open count and its total come as a pair");
+    if (n_frames == 0) return P3D_OK;
+    P3D_REQUIRE(hit && grad && cam2world && rgb, "surface_shade_lit: null pointer");
+    const int64_t per_frame = (int64_t)height * width, total = per_frame * n_frames;
+    const int64_t blocks = (total + 255) / 256;
+    if (blocks > INT32_MAX)
+        return fail(P3D_ERR_UNSUPPORTED, "surface_shade_lit: %lld pixels are more than one launch takes", (long long)total);
+    hipLaunchKernelGGL(surface_shade_lit_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, hit, grad, albedo, cam2world, light, ao_open,
+                       ao_total, sh_open, sh_total, total, per_frame, ambient, bg_r & 255, bg_g & 255, bg_b & 255, rgb);
+    count_launch(FAM_AUX);
+    return check_launch("surface_shade_lit");
 }

@@ -77,6 +77,7 @@ _lib.register('p3d_render_forward_dual', ctypes.c_int, [_vp] * 9 + [ctypes.POINT
 _lib.register('p3d_sample_points_dual', ctypes.c_int, [_vp] * 4 + [ctypes.POINTER(_RenderDesc), _i32, _vp, _vp, _vp])
 _lib.register('p3d_sample_lattice', ctypes.c_int, [_vp, _vp, ctypes.POINTER(_RenderDesc), _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp])
 _lib.register('p3d_surface_cast', ctypes.c_int, [_vp, _vp, ctypes.POINTER(_RenderDesc), _vp, _vp, _f32, _f32, _i32, _i32, _f32, _f32, _f32, _i32] + [_vp] * 5)
+_lib.register('p3d_surface_occlusion', ctypes.c_int, [_vp, _vp, ctypes.POINTER(_RenderDesc), _vp, _vp, _vp, _vp, _i32, _f32, _i32, _f32, _f32, _i32, _vp, _vp, _vp])
 
 
 def generate_planes():
@@ -675,6 +676,36 @@ def fused_surface_cast(planes, decoder, ray_o, ray_d, opt, near, far, steps, ref
                                        _lib.ptr(hit), _lib.ptr(depth), _lib.ptr(position), _lib.ptr(grad), _lib.stream_of(hit))
     _lib.check(code, 'surface_cast')
     return hit, depth, position, grad
+
+
+def fused_surface_occlusion(planes, decoder, origin, facing, active, directions, opt, reach, steps, threshold, half_box=0.0, raster_width=0):
+    """One launch of p3d_surface_occlusion (csrc/surface.hip; the contract is include/p3d_hip.h's): points ``origin`` [N, M, 3] with the directions
+    ``facing`` [N, M, 3] their surface faces and the flags ``active`` uint8 [N, M], rays of ``steps`` samples up to ``reach`` along each of
+    ``directions`` [N, K, 3], against planes of batch N or of batch 1 for every point set -> (open, total) uint8 [N, M]: per point the directions it
+    uses (facing . d > 0) and those of them no sample of which is denser than ``threshold``.  ``half_box`` and ``raster_width`` as for
+    ``fused_surface_cast``."""
+    n, m, _ = origin.shape
+    shared = shared_planes(planes.shape[0], n, 'fused_surface_occlusion')
+    dev = planes.device
+    o, f, dirs = _f32c(origin), _f32c(facing), _f32c(directions).to(dev)
+    act = active.detach().to(device=dev, dtype=torch.uint8).contiguous()
+    if tuple(f.shape) != (n, m, 3) or tuple(act.shape) != (n, m) or dirs.ndim != 3 or dirs.shape[0] != n or dirs.shape[2] != 3:
+        raise ValueError(f'fused_surface_occlusion: origin {tuple(o.shape)} needs facing [{n}, {m}, 3], active [{n}, {m}] and directions [{n}, K, 3] '
+                         f'(got {tuple(f.shape)}, {tuple(act.shape)}, {tuple(dirs.shape)})')
+    # the entry point's own limits, checked here as well: preparing its operands (the planes' re-layout, the decoder stream) already launches
+    k, steps, raster_width = int(dirs.shape[1]), int(steps), int(raster_width)
+    if not (1 <= k <= 255 and 1 <= steps <= 4096):
+        raise RuntimeError(f'fused_surface_occlusion: needs 1 <= directions <= 255 and 1 <= steps <= 4096 (got {k}, {steps})')
+    if raster_width < 0 or (raster_width > 0 and (raster_width % 8 != 0 or raster_width * raster_width != m)):
+        raise RuntimeError(f'fused_surface_occlusion: raster_width {raster_width} must be 0, or a multiple of 8 whose square is the number of points ({m})')
+    ctx = _FusedContext(planes, _decoder_nets(decoder))
+    open_, total = torch.empty([n, m], dtype=torch.uint8, device=dev), torch.empty([n, m], dtype=torch.uint8, device=dev)
+    desc = ctx.desc(opt, rays_per_img=m, raster=2 if shared else 0, n_img=n)             # P3D_RENDER_SHARED_PLANES (2), as the cast
+    code = _lib.lib().p3d_surface_occlusion(_lib.ptr(ctx.planes_cl), _lib.ptr(ctx.packed), ctypes.byref(desc), _lib.ptr(o), _lib.ptr(f), _lib.ptr(act),
+                                            _lib.ptr(dirs), k, float(reach) / steps, steps, float(threshold), float(half_box), raster_width,
+                                            _lib.ptr(open_), _lib.ptr(total), _lib.stream_of(open_))
+    _lib.check(code, 'surface_occlusion')
+    return open_, total
 
 
 def _decoder_param_grads(decoder, nets, d_dec):
