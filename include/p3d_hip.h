@@ -144,7 +144,8 @@ typedef struct p3d_render_desc {
     int64_t image_stride, plane_stride, pixel_stride;
     int32_t raster_order;                 /* != 0: ray m of an image is pixel (m / R, m % R) of an R x R raster (R*R = rays_per_img):
                                              lets the kernel assign 16 x 16 pixel blocks to workgroups for L2 locality.
-                                             Bit 1 (P3D_RENDER_SHARED_PLANES; p3d_render_forward / _dual / _debug only): the plane tensor holds ONE
+                                             Bit 1 (P3D_RENDER_SHARED_PLANES; p3d_render_forward / _dual / _debug, p3d_surface_cast and p3d_surface_occlusion;
+                                             every other entry point ignores it): the plane tensor holds ONE
                                              image that all n_img ray sets read (many cameras of one latent) — the strides describe that one image  */
     int32_t mlp_bf16x3;                   /* p3d_render_forward only, != 0: the decoder stream comes from p3d_pack_decoder_bf16x3 and the MLPs run
                                              as three bf16 MFMAs per fp32 product (hi/lo splits, fp32 accumulation: ~5e-6 of the hidden range per

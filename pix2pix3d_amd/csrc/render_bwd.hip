@@ -20,7 +20,7 @@
 //                                            61 of the 64 ms at 4 x 128^2 rays x 96 samples; everything else takes 3 ms.
 //      The 128 accumulator registers of the four weight-gradient tiles per net pin the kernel at one wave per SIMD (512-register
 //      budget); weight gradients leave through atomics once per wave.
-#include "render_device.h"
+#include "render_host.h"
 
 namespace p3d {
 // Ablation builds (measurement only, never the shipped library: tests/gpu_probe_rbwd.sh compiles this file with -DP3D_RBWD_DEBUG=<bits>):
@@ -447,12 +447,12 @@ extern "C" int p3d_render_backward(const float* planes_cl, const float* decoder,
                                    const p3d_render_desc* d, const float* g_feat, const float* g_wsum, float* tape_intervals, float* tape_samples,
                                    float* d_planes_cl, float* d_decoder, p3d_stream_t stream)
 {
-    P3D_REQUIRE(d, "render_backward: null descriptor");
-    P3D_REQUIRE(d->n_nets == 1 || d->n_nets == 2, "render_backward: n_nets must be 1 or 2");
+    int rc = check_plane_desc(d, "render_backward", false);
+    if (rc != P3D_OK) return rc;
     P3D_REQUIRE(planes_cl && decoder && decoder_bwd && ray_o && ray_d && u_coarse && u_fine && g_feat && tape_intervals && tape_samples && d_planes_cl && d_decoder,
                 "render_backward: null pointer");
     P3D_REQUIRE((t_start == nullptr) == (t_end == nullptr), "render_backward: t_start/t_end must be given together");
-    P3D_REQUIRE(d->plane_h >= 1 && d->plane_w >= 1 && d->box_warp != 0.f && d->rays_per_img >= 1 && d->n_img >= 0, "render_backward: bad sizes");
+    P3D_REQUIRE(d->rays_per_img >= 1 && d->n_img >= 0, "render_backward: bad sizes");
     if (d->depth_resolution < 4 || d->depth_resolution > kMaxS || d->depth_resolution_importance < 1 || d->depth_resolution_importance > kMaxS)
         return fail(P3D_ERR_UNSUPPORTED, "render_backward: needs 4 <= depth_resolution <= %d and 1 <= depth_resolution_importance <= %d", kMaxS, kMaxS);
     const int64_t total = (int64_t)d->n_img * d->rays_per_img;
@@ -463,19 +463,10 @@ extern "C" int p3d_render_backward(const float* planes_cl, const float* decoder,
         return fail(P3D_ERR_LAUNCH, "render_backward: memset failed");
     if (total == 0) return P3D_OK;
     RenderArgs a{};
-    a.H = d->plane_h; a.W = d->plane_w; a.Sc = d->depth_resolution; a.Sf = d->depth_resolution_importance;
-    a.ray_start = d->ray_start; a.ray_end = d->ray_end; a.coord_scale = 2.f / d->box_warp;
-    a.lin_step = a.Sc > 1 ? (d->ray_end - d->ray_start) / (float)(a.Sc - 1) : 0.f;
-    a.disparity = d->disparity_space_sampling; a.white_back = d->white_back; a.sem_sigmoid = d->semantic_sigmoid;
-    if (d->pixel_stride > 0) { a.plane_stride = d->plane_stride; a.pix_stride = d->pixel_stride; a.img_stride = d->image_stride; }
-    else { a.plane_stride = (int64_t)a.H * a.W * 32; a.pix_stride = 32; a.img_stride = 3 * a.plane_stride; }
-    a.plane_bytes = (unsigned)(a.plane_stride * 4); a.pix_bytes = (unsigned)(a.pix_stride * 4); a.img_bytes = (unsigned)(a.img_stride * 4);
-    if ((int64_t)d->n_img * a.img_stride * 4 >= ((int64_t)1 << 31)) return fail(P3D_ERR_UNSUPPORTED, "render_backward: plane tensor too large for 32-bit buffer addressing");
-    a.planes_total_bytes = (unsigned)((int64_t)d->n_img * a.img_stride * 4);
+    fill_plane_args(a, d, false);
+    fill_ray_args(a, d);
     a.planes = planes_cl; a.decoder = decoder; a.ray_o = ray_o; a.ray_d = ray_d; a.u_coarse = u_coarse; a.u_fine = u_fine;
     a.t_start = t_start; a.t_end = t_end; a.g_feat = g_feat; a.g_wsum = g_wsum; a.tape_i = tape_intervals; a.tape_s = tape_samples;
-    a.total_rays = (int)total; a.rays_per_img = d->rays_per_img;
-    { int r = 1; while (r * r < d->rays_per_img) ++r; a.res = (r * r == d->rays_per_img && d->raster_order) ? r : 0; }
 
     // 1. the forward sweep with tape
     {
@@ -483,17 +474,10 @@ extern "C" int p3d_render_backward(const float* planes_cl, const float* decoder,
         int wpb = kWavesPerBlock;
         while (wpb > 2 && (total + wpb * 32 - 1) / (wpb * 32) < kNumCU) wpb >>= 1;
         const size_t lds_bytes = (size_t)(kDecoderFloats + kWavesPerBlock * (kWaveTile + kFeatTile + kTapTile)) * sizeof(float);
-        const int blocks = (int)((total + wpb * 32 - 1) / (wpb * 32));
-        if (d->n_nets == 1) {
-            static std::atomic<uint64_t> once1_devs{0}; const hipError_t once1 = reserve_lds_once((const void*)render_forward_kernel<1, true>, (int)lds_bytes, once1_devs);
-            if (once1 != hipSuccess) return fail(P3D_ERR_LAUNCH, "render_backward: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(once1));
-            hipLaunchKernelGGL((render_forward_kernel<1, true>), dim3(blocks), dim3(wpb * 64), lds_bytes, s, a);
-        } else {
-            static std::atomic<uint64_t> once2_devs{0}; const hipError_t once2 = reserve_lds_once((const void*)render_forward_kernel<2, true>, (int)lds_bytes, once2_devs);
-            if (once2 != hipSuccess) return fail(P3D_ERR_LAUNCH, "render_backward: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(once2));
-            hipLaunchKernelGGL((render_forward_kernel<2, true>), dim3(blocks), dim3(wpb * 64), lds_bytes, s, a);
-        }
-        int rc = check_launch("render_backward (tape sweep)");
+        const dim3 grid((unsigned)((total + wpb * 32 - 1) / (wpb * 32))), block(wpb * 64);
+        rc = d->n_nets == 1 ? launch_lds_opt_in<render_forward_kernel<1, true>>("render_backward", grid, block, lds_bytes, s, a)
+                            : launch_lds_opt_in<render_forward_kernel<2, true>>("render_backward", grid, block, lds_bytes, s, a);
+        if (rc == P3D_OK) rc = check_launch("render_backward (tape sweep)");
         if (rc != P3D_OK) return rc;
     }
     // 2. point-wise backward
@@ -505,17 +489,11 @@ extern "C" int p3d_render_backward(const float* planes_cl, const float* decoder,
         const int64_t n_tiles = total * ((S_all + 31) / 32);
         int tpw = (int)(n_tiles / ((int64_t)kBwdWaves * 2 * kNumCU));
         tpw = tpw < 1 ? 1 : (tpw > 96 ? 96 : tpw);
-        const int blocks = (int)((n_tiles + (int64_t)kBwdWaves * tpw - 1) / ((int64_t)kBwdWaves * tpw));
+        const dim3 grid((unsigned)((n_tiles + (int64_t)kBwdWaves * tpw - 1) / ((int64_t)kBwdWaves * tpw))), block(kBwdWaves * 64);
         PointArgs pa{}; pa.tiles_per_wave = tpw;
-        if (d->n_nets == 1) {
-            static std::atomic<uint64_t> once1_devs{0}; const hipError_t once1 = reserve_lds_once((const void*)render_backward_kernel<1>, (int)lds_bytes, once1_devs);
-            if (once1 != hipSuccess) return fail(P3D_ERR_LAUNCH, "render_backward: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(once1));
-            hipLaunchKernelGGL(render_backward_kernel<1>, dim3(blocks), dim3(kBwdWaves * 64), lds_bytes, s, a, decoder_bwd, d_planes_cl, d_decoder, pa);
-        } else {
-            static std::atomic<uint64_t> once2_devs{0}; const hipError_t once2 = reserve_lds_once((const void*)render_backward_kernel<2>, (int)lds_bytes, once2_devs);
-            if (once2 != hipSuccess) return fail(P3D_ERR_LAUNCH, "render_backward: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(once2));
-            hipLaunchKernelGGL(render_backward_kernel<2>, dim3(blocks), dim3(kBwdWaves * 64), lds_bytes, s, a, decoder_bwd, d_planes_cl, d_decoder, pa);
-        }
+        rc = d->n_nets == 1 ? launch_lds_opt_in<render_backward_kernel<1>>("render_backward", grid, block, lds_bytes, s, a, decoder_bwd, d_planes_cl, d_decoder, pa)
+                            : launch_lds_opt_in<render_backward_kernel<2>>("render_backward", grid, block, lds_bytes, s, a, decoder_bwd, d_planes_cl, d_decoder, pa);
+        if (rc != P3D_OK) return rc;
     }
     count_launch(FAM_RENDER);
     return check_launch("render_backward");
@@ -529,10 +507,10 @@ extern "C" int p3d_sample_points_backward(const float* planes_cl, const float* d
                                           const p3d_render_desc* d, int32_t pts_per_img, const float* g_rgb, const float* g_sigma,
                                           float* d_planes_cl, float* d_decoder, p3d_stream_t stream)
 {
-    P3D_REQUIRE(d, "sample_points_backward: null descriptor");
-    P3D_REQUIRE(d->n_nets == 1 || d->n_nets == 2, "sample_points_backward: n_nets must be 1 or 2");
+    int rc = check_plane_desc(d, "sample_points_backward", false);
+    if (rc != P3D_OK) return rc;
     P3D_REQUIRE(planes_cl && decoder && decoder_bwd && coords && d_planes_cl && d_decoder, "sample_points_backward: null pointer");
-    P3D_REQUIRE(d->plane_h >= 1 && d->plane_w >= 1 && d->box_warp != 0.f && pts_per_img >= 1 && d->n_img >= 0, "sample_points_backward: bad sizes");
+    P3D_REQUIRE(pts_per_img >= 1 && d->n_img >= 0, "sample_points_backward: bad sizes");
     const int64_t total = (int64_t)d->n_img * pts_per_img;
     P3D_REQUIRE(total <= INT32_MAX / 64, "sample_points_backward: too many points");
     hipStream_t s = (hipStream_t)stream;
@@ -541,28 +519,18 @@ extern "C" int p3d_sample_points_backward(const float* planes_cl, const float* d
         return fail(P3D_ERR_LAUNCH, "sample_points_backward: memset failed");
     if (total == 0 || (!g_rgb && !g_sigma)) return P3D_OK;
     RenderArgs a{};
-    a.H = d->plane_h; a.W = d->plane_w; a.coord_scale = 2.f / d->box_warp; a.sem_sigmoid = d->semantic_sigmoid;
-    if (d->pixel_stride > 0) { a.plane_stride = d->plane_stride; a.pix_stride = d->pixel_stride; a.img_stride = d->image_stride; }
-    else { a.plane_stride = (int64_t)a.H * a.W * 32; a.pix_stride = 32; a.img_stride = 3 * a.plane_stride; }
-    a.plane_bytes = (unsigned)(a.plane_stride * 4); a.pix_bytes = (unsigned)(a.pix_stride * 4); a.img_bytes = (unsigned)(a.img_stride * 4);
-    if ((int64_t)d->n_img * a.img_stride * 4 >= ((int64_t)1 << 31) || (int64_t)d->plane_h * d->plane_w >= (1 << 24) || d->pixel_stride * 4 >= (1 << 16))
-        return fail(P3D_ERR_UNSUPPORTED, "sample_points_backward: plane tensor too large for 32-bit buffer addressing");
-    a.planes_total_bytes = (unsigned)((int64_t)d->n_img * a.img_stride * 4);
+    fill_plane_args(a, d, false);
+    a.sem_sigmoid = d->semantic_sigmoid;
     a.planes = planes_cl; a.decoder = decoder;
     PointArgs pa{coords, g_rgb, g_sigma, pts_per_img, (int)total, 0};
     const size_t lds_bytes = (size_t)(kDecoderFloats + kBwdFloats + kBwdWaves * kBwdWaveLds) * sizeof(float);
     const int64_t tiles = (total + 31) / 32;
     int blocks = (int)((tiles + kBwdWaves - 1) / kBwdWaves);
     if (blocks > kNumCU) blocks = kNumCU;                                 // one block per CU (LDS); waves take further tiles grid-stride
-    if (d->n_nets == 1) {
-        static std::atomic<uint64_t> once1_devs{0}; const hipError_t once1 = reserve_lds_once((const void*)render_backward_kernel<1, true>, (int)lds_bytes, once1_devs);
-        if (once1 != hipSuccess) return fail(P3D_ERR_LAUNCH, "sample_points_backward: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(once1));
-        hipLaunchKernelGGL((render_backward_kernel<1, true>), dim3(blocks), dim3(kBwdWaves * 64), lds_bytes, s, a, decoder_bwd, d_planes_cl, d_decoder, pa);
-    } else {
-        static std::atomic<uint64_t> once2_devs{0}; const hipError_t once2 = reserve_lds_once((const void*)render_backward_kernel<2, true>, (int)lds_bytes, once2_devs);
-        if (once2 != hipSuccess) return fail(P3D_ERR_LAUNCH, "sample_points_backward: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(once2));
-        hipLaunchKernelGGL((render_backward_kernel<2, true>), dim3(blocks), dim3(kBwdWaves * 64), lds_bytes, s, a, decoder_bwd, d_planes_cl, d_decoder, pa);
-    }
+    const dim3 grid(blocks), block(kBwdWaves * 64);
+    rc = d->n_nets == 1 ? launch_lds_opt_in<render_backward_kernel<1, true>>("sample_points_backward", grid, block, lds_bytes, s, a, decoder_bwd, d_planes_cl, d_decoder, pa)
+                        : launch_lds_opt_in<render_backward_kernel<2, true>>("sample_points_backward", grid, block, lds_bytes, s, a, decoder_bwd, d_planes_cl, d_decoder, pa);
+    if (rc != P3D_OK) return rc;
     count_launch(FAM_RENDER);
     return check_launch("sample_points_backward");
 }

@@ -11,7 +11,8 @@
 // totals.  The caller scans the block totals (exclusive) and allocates the outputs from the grand totals.  emit: two launches that
 // redo the in-block scan (wave scan + LDS): the first writes the vertices and each corner's first vertex id, the second the faces,
 // whose vertices belong to corners of other blocks as well.
-#include "render_device.h"
+#include "density_device.h"
+#include "render_host.h"
 #include "mc_tables.h"
 
 namespace p3d {
@@ -23,56 +24,23 @@ lattice_sigma_kernel(RenderArgs a, const float* __restrict__ xs, const float* __
                      unsigned ny, unsigned nz, unsigned pts_per_img, float* __restrict__ sigma_out)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 31, h = lane >> 5;
-    for (int i = tid; i < kDecoderFloats / 4; i += blockDim.x) ((f32x4*)lds)[i] = ((const f32x4*)a.decoder)[i];
+    stage_decoder(lds, a.decoder);
     __syncthreads();
-    constexpr int SN = NNETS - 1;
-    const rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.planes, 0, a.planes_total_bytes, 0x00020000);
+    const rsrc_t rsrc = plane_rsrc(a);
     const unsigned img = blockIdx.y;                                 // one image per grid row: the in-image index stays 32-bit
     const unsigned img_off = img * a.img_bytes;
     float* out = sigma_out + (size_t)img * pts_per_img;
     const unsigned tiles = (pts_per_img + 31) / 32, nyz = ny * nz;
-    const float cs = a.coord_scale;
     for (unsigned t = blockIdx.x * kWavesPerBlock + wave; t < tiles; t += gridDim.x * kWavesPerBlock) {
-        const unsigned q = t * 32 + j;
+        const unsigned q = tile_point(t, j, 0, 1);
         const bool live = q < pts_per_img;
         const unsigned p = live ? q : pts_per_img - 1;
         const unsigned ix = p / nyz, r = p - ix * nyz, iy = r / nz, iz = r - iy * nz;
-        float feat[16];
-        gather_features<true>(a, rsrc, img_off, h, cs * xs[ix], cs * ys[iy], cs * zs[iz], feat);
-        f32x16 h0, h1;
-        mlp_layer1(lds, SN, lane, h, feat, h0, h1);
-        const float s = mlp_sigma(lds, h, h0, h1);
+        const float s = sigma_at<NNETS - 1>(a, rsrc, img_off, lds, lane, h, xs[ix], ys[iy], zs[iz]);
         if (live && h == 0) out[p] = s;
     }
-}
-
-// render.hip's descriptor checks and argument fill (file-local there), restated for the lattice
-static int lattice_check_desc(const p3d_render_desc* d)
-{
-    P3D_REQUIRE(d, "sample_lattice: null descriptor");
-    P3D_REQUIRE(d->n_nets == 1 || d->n_nets == 2, "sample_lattice: n_nets must be 1 or 2 (got %d)", d->n_nets);
-    P3D_REQUIRE(d->plane_h >= 1 && d->plane_w >= 1, "sample_lattice: bad plane size");
-    P3D_REQUIRE(d->box_warp != 0.f, "sample_lattice: box_warp must be non-zero");
-    P3D_REQUIRE(d->n_img >= 0 && d->n_img <= 65535, "sample_lattice: n_img must be in [0, 65535] (got %d)", d->n_img);
-    {   // the planes are read through one buffer descriptor with 32-bit byte offsets (24-bit multiplies for texel indices and strides)
-        const int64_t istr = d->pixel_stride > 0 ? d->image_stride : (int64_t)3 * d->plane_h * d->plane_w * 32;
-        if ((int64_t)d->n_img * istr * 4 >= ((int64_t)1 << 31) || (int64_t)d->plane_h * d->plane_w >= (1 << 24) || d->pixel_stride * 4 >= (1 << 16))
-            return fail(P3D_ERR_UNSUPPORTED, "sample_lattice: plane tensor too large for 32-bit buffer addressing (%d images)", d->n_img);
-    }
-    P3D_REQUIRE(d->pixel_stride == 0 || (d->pixel_stride % 4 == 0 && d->plane_stride % 4 == 0 && d->image_stride % 4 == 0),
-                "sample_lattice: plane strides must keep texels 16-byte aligned");
-    return P3D_OK;
-}
-
-static void lattice_fill_args(RenderArgs& a, const p3d_render_desc* d)
-{
-    a.H = d->plane_h; a.W = d->plane_w; a.coord_scale = 2.f / d->box_warp;
-    if (d->pixel_stride > 0) { a.plane_stride = d->plane_stride; a.pix_stride = d->pixel_stride; a.img_stride = d->image_stride; }
-    else { a.plane_stride = (int64_t)a.H * a.W * 32; a.pix_stride = 32; a.img_stride = 3 * a.plane_stride; }
-    a.plane_bytes = (unsigned)(a.plane_stride * 4); a.pix_bytes = (unsigned)(a.pix_stride * 4); a.img_bytes = (unsigned)(a.img_stride * 4);
-    a.planes_total_bytes = (unsigned)((int64_t)d->n_img * a.img_stride * 4);
 }
 
 // ---- marching cubes ---------------------------------------------------------------------------------------
@@ -204,7 +172,7 @@ using namespace p3d;
 extern "C" int p3d_sample_lattice(const float* planes_cl, const float* decoder, const p3d_render_desc* d, const float* xs, const float* ys,
                                   const float* zs, int32_t nx, int32_t ny, int32_t nz, float* sigma, p3d_stream_t stream)
 {
-    int rc = lattice_check_desc(d);
+    int rc = check_plane_desc(d, "sample_lattice", false, true);
     if (rc != P3D_OK) return rc;
     P3D_REQUIRE(planes_cl && decoder && xs && ys && zs && sigma, "sample_lattice: null pointer");
     P3D_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1, "sample_lattice: bad lattice size %d x %d x %d", nx, ny, nz);
@@ -213,15 +181,11 @@ extern "C" int p3d_sample_lattice(const float* planes_cl, const float* decoder, 
         return fail(P3D_ERR_UNSUPPORTED, "sample_lattice: %lld points per image do not fit the kernel's 32-bit in-image index", (long long)per_img);
     if (d->n_img == 0) return P3D_OK;
     RenderArgs a{};
-    lattice_fill_args(a, d);
+    fill_plane_args(a, d, false);
     a.planes = planes_cl; a.decoder = decoder;
-    const int64_t tiles = (per_img + 31) / 32;
-    int64_t bx = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    const int64_t cap = (kNumCU * 2 + d->n_img - 1) / d->n_img;     // about two blocks per CU over the whole launch
-    if (bx > cap) bx = cap;
     const size_t lds_bytes = (size_t)kDecoderFloats * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)bx, (unsigned)d->n_img);
+    const dim3 grid = set_row_grid(per_img, d->n_img);
     if (d->n_nets == 1) hipLaunchKernelGGL(lattice_sigma_kernel<1>, grid, dim3(kWavesPerBlock * 64), lds_bytes, s, a, xs, ys, zs, (unsigned)ny, (unsigned)nz, (unsigned)per_img, sigma);
     else                hipLaunchKernelGGL(lattice_sigma_kernel<2>, grid, dim3(kWavesPerBlock * 64), lds_bytes, s, a, xs, ys, zs, (unsigned)ny, (unsigned)nz, (unsigned)per_img, sigma);
     count_launch(FAM_RENDER);

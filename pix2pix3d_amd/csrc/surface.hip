@@ -25,7 +25,8 @@
 // No lane sits through a direction it does not use, neighbours whose hemispheres differ do not stall each other; the wave runs for as
 // long as its busiest lane.  The set's direction table sits in LDS behind the decoder copy.
 // p3d_surface_shade_lit: the shade with a directional light, an ambient-occlusion pair and a shadow pair, each optional.
-#include "render_device.h"
+#include "density_device.h"
+#include "render_host.h"
 
 namespace p3d {
 
@@ -64,41 +65,24 @@ __device__ __forceinline__ bool outside_box(float half_box, float x, float y, fl
     return half_box > 0.f && (fabsf(x) > half_box || fabsf(y) > half_box || fabsf(z) > half_box);
 }
 
-// The density at (x, y, z): the lattice kernel's three calls.  Every lane of the wave must get here.
-template <int SN>
-__device__ __forceinline__ float sigma_at(const RenderArgs& a, rsrc_t rsrc, unsigned img_off, const float* lds, int lane, int h, float x, float y, float z)
-{
-    const float cs = a.coord_scale;
-    float feat[16];
-    gather_features<true>(a, rsrc, img_off, h, cs * x, cs * y, cs * z, feat);
-    f32x16 h0, h1;
-    mlp_layer1(lds, SN, lane, h, feat, h0, h1);
-    return mlp_sigma(lds, h, h0, h1);
-}
-
 template <int NNETS>
 __global__ void __launch_bounds__(kWavesPerBlock * 64, 2)
 surface_cast_kernel(RenderArgs a, CastArgs c)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 31, h = lane >> 5;
-    for (int i = tid; i < kDecoderFloats / 4; i += blockDim.x) ((f32x4*)lds)[i] = ((const f32x4*)a.decoder)[i];
+    stage_decoder(lds, a.decoder);
     __syncthreads();
     constexpr int SN = NNETS - 1;
-    const rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.planes, 0, a.planes_total_bytes, 0x00020000);
+    const rsrc_t rsrc = plane_rsrc(a);
     const unsigned set = blockIdx.y;                                 // one ray set per grid row
     const unsigned img_off = set * a.img_bytes;                      // (0 for every set when the planes are shared)
     const unsigned M = c.rays_per_set, tiles = (M + 31) / 32;
     const size_t base = (size_t)set * M;
     const unsigned tiles_x = c.raster > 0 ? (unsigned)c.raster / 4u : 1u;
     for (unsigned t = blockIdx.x * kWavesPerBlock + wave; t < tiles; t += gridDim.x * kWavesPerBlock) {
-        unsigned q;
-        if (c.raster > 0) {                                          // 8 rows x 4 columns of the image
-            const unsigned ty = t / tiles_x, tx = t - ty * tiles_x;
-            q = (ty * 8u + (unsigned)(j & 7)) * (unsigned)c.raster + tx * 4u + (unsigned)(j >> 3);
-        } else
-            q = t * 32u + (unsigned)j;
+        const unsigned q = tile_point(t, j, c.raster, tiles_x);
         const bool live = q < M;
         const size_t g = base + (live ? q : M - 1);
         const float ox = a.ray_o[g * 3], oy = a.ray_o[g * 3 + 1], oz = a.ray_o[g * 3 + 2];
@@ -177,27 +161,22 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64, 2)
 surface_occlusion_kernel(RenderArgs a, OcclusionArgs c)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 31, h = lane >> 5;
     const unsigned set = blockIdx.y;                                 // one point set, and its direction table, per grid row
     float* dirs = lds + kDecoderFloats;
-    for (int i = tid; i < kDecoderFloats / 4; i += blockDim.x) ((f32x4*)lds)[i] = ((const f32x4*)a.decoder)[i];
-    for (int i = tid; i < c.n_dirs * 3; i += blockDim.x) dirs[i] = c.directions[(size_t)set * c.n_dirs * 3 + i];
+    stage_decoder(lds, a.decoder);
+    for (int i = threadIdx.x; i < c.n_dirs * 3; i += blockDim.x) dirs[i] = c.directions[(size_t)set * c.n_dirs * 3 + i];
     __syncthreads();
     constexpr int SN = NNETS - 1;
-    const rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.planes, 0, a.planes_total_bytes, 0x00020000);
+    const rsrc_t rsrc = plane_rsrc(a);
     const unsigned img_off = set * a.img_bytes;                      // (0 for every set when the planes are shared)
     const unsigned M = c.points_per_set, tiles = (M + 31) / 32;
     const size_t base = (size_t)set * M;
     const unsigned tiles_x = c.raster > 0 ? (unsigned)c.raster / 4u : 1u;
     const int K = c.n_dirs, last = c.steps - 1;
     for (unsigned t = blockIdx.x * kWavesPerBlock + wave; t < tiles; t += gridDim.x * kWavesPerBlock) {
-        unsigned q;
-        if (c.raster > 0) {                                          // 8 rows x 4 columns of the image
-            const unsigned ty = t / tiles_x, tx = t - ty * tiles_x;
-            q = (ty * 8u + (unsigned)(j & 7)) * (unsigned)c.raster + tx * 4u + (unsigned)(j >> 3);
-        } else
-            q = t * 32u + (unsigned)j;
+        const unsigned q = tile_point(t, j, c.raster, tiles_x);
         const bool live = q < M;
         const size_t g = base + (live ? q : M - 1);
         const float ox = a.ray_o[g * 3], oy = a.ray_o[g * 3 + 1], oz = a.ray_o[g * 3 + 2];
@@ -239,40 +218,40 @@ surface_occlusion_kernel(RenderArgs a, OcclusionArgs c)
     }
 }
 
-// shape.hip's descriptor checks (file-local there), restated for the cast
-static int cast_check_desc(const p3d_render_desc* d)
+// ---- what the two ray stages' entry points share ---------------------------------------------------------------------------------
+// The descriptor of a ray (or point) stage: one set of rays_per_img per grid row, shared planes honoured.
+static int stage_check_desc(const p3d_render_desc* d, const char* who)
 {
-    P3D_REQUIRE(d, "surface_cast: null descriptor");
-    P3D_REQUIRE(d->n_nets == 1 || d->n_nets == 2, "surface_cast: n_nets must be 1 or 2 (got %d)", d->n_nets);
-    P3D_REQUIRE(d->plane_h >= 1 && d->plane_w >= 1, "surface_cast: bad plane size");
-    P3D_REQUIRE(d->box_warp != 0.f, "surface_cast: box_warp must be non-zero");
-    P3D_REQUIRE(d->n_img >= 0 && d->n_img <= 65535, "surface_cast: n_img must be in [0, 65535] (got %d)", d->n_img);
-    P3D_REQUIRE(d->rays_per_img >= 1, "surface_cast: rays_per_img must be >= 1 (got %d)", d->rays_per_img);
-    {   // the planes are read through one buffer descriptor with 32-bit byte offsets (24-bit multiplies for texel indices and strides)
-        const int64_t istr = d->pixel_stride > 0 ? d->image_stride : (int64_t)3 * d->plane_h * d->plane_w * 32;
-        const int64_t sets = (d->raster_order & P3D_RENDER_SHARED_PLANES) ? 1 : d->n_img;
-        if (sets * istr * 4 >= ((int64_t)1 << 31) || (int64_t)d->plane_h * d->plane_w >= (1 << 24) || d->pixel_stride * 4 >= (1 << 16))
-            return fail(P3D_ERR_UNSUPPORTED, "surface_cast: plane tensor too large for 32-bit buffer addressing (%d images)", d->n_img);
-    }
-    P3D_REQUIRE(d->pixel_stride == 0 || (d->pixel_stride % 4 == 0 && d->plane_stride % 4 == 0 && d->image_stride % 4 == 0),
-                "surface_cast: plane strides must keep texels 16-byte aligned");
+    const int rc = check_plane_desc(d, who, true, true);
+    if (rc != P3D_OK) return rc;
+    P3D_REQUIRE(d->rays_per_img >= 1, "%s: rays_per_img must be >= 1 (got %d)", who, d->rays_per_img);
     return P3D_OK;
 }
 
-// What the kernels of this file read of a checked descriptor: the planes' sizes and strides, the decoder, one ray (or point) set per image.
-static RenderArgs cast_render_args(const p3d_render_desc* d, const float* planes_cl, const float* decoder, const float* ray_o, const float* ray_d)
+// The tile mapping's limits (`what` a set holds: rays, points).
+static int stage_check_tiles(const p3d_render_desc* d, int32_t raster_width, const char* who, const char* what)
+{
+    const int64_t M = d->rays_per_img;
+    P3D_REQUIRE(raster_width >= 0 && (raster_width == 0 || (raster_width % 8 == 0 && (int64_t)raster_width * raster_width == M)),
+                "%s: raster_width %d must be 0, or a multiple of 8 whose square is rays_per_img (%d)", who, raster_width, d->rays_per_img);
+    if (M > (int64_t)INT32_MAX - 31)
+        return fail(P3D_ERR_UNSUPPORTED, "%s: %lld %s per set do not fit the kernel's 32-bit in-set index", who, (long long)M, what);
+    return P3D_OK;
+}
+
+// One launch over all sets of a checked descriptor (n_img >= 1); origins and directions (or facings) travel as RenderArgs' ray_o, ray_d.
+template <class StageArgs>
+static int stage_launch(void (*one_net)(RenderArgs, StageArgs), void (*two_nets)(RenderArgs, StageArgs), const p3d_render_desc* d, const float* planes_cl,
+                        const float* decoder, const float* ray_o, const float* ray_d, const StageArgs& c, size_t lds_floats, p3d_stream_t stream,
+                        const char* who)
 {
     RenderArgs a{};
-    a.H = d->plane_h; a.W = d->plane_w; a.coord_scale = 2.f / d->box_warp;
-    if (d->pixel_stride > 0) { a.plane_stride = d->plane_stride; a.pix_stride = d->pixel_stride; a.img_stride = d->image_stride; }
-    else { a.plane_stride = (int64_t)a.H * a.W * 32; a.pix_stride = 32; a.img_stride = 3 * a.plane_stride; }
-    a.plane_bytes = (unsigned)(a.plane_stride * 4); a.pix_bytes = (unsigned)(a.pix_stride * 4); a.img_bytes = (unsigned)(a.img_stride * 4);
-    a.planes_total_bytes = (unsigned)((int64_t)d->n_img * a.img_stride * 4);
-    if (d->raster_order & P3D_RENDER_SHARED_PLANES) {      // one plane set for all n_img ray sets: a zero image stride, and the buffer bound is that one set's
-        a.planes_total_bytes = a.img_bytes; a.img_bytes = 0; a.img_stride = 0;
-    }
+    fill_plane_args(a, d, true);
     a.planes = planes_cl; a.decoder = decoder; a.ray_o = ray_o; a.ray_d = ray_d;
-    return a;
+    hipLaunchKernelGGL(d->n_nets == 1 ? one_net : two_nets, set_row_grid(d->rays_per_img, d->n_img), dim3(kWavesPerBlock * 64), lds_floats * sizeof(float),
+                       (hipStream_t)stream, a, c);
+    count_launch(FAM_RENDER);
+    return check_launch(who);
 }
 
 // ---- shading ----------------------------------------------------------------------------------------------------------------
@@ -283,9 +262,13 @@ __device__ __forceinline__ uint8_t byte_of(double v)
     return (uint8_t)(v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v));
 }
 
+// One thread per pixel.  mode 1: the normal map.  mode 0: light [F][3] (null: the headlight), ao_* and sh_* [F*H*W] counts (null pairs: 1);
+// with all three null this is the plain lambert shade: amb * 1.0 and b * 1.0 are exact.
 __global__ void __launch_bounds__(256) surface_shade_kernel(const uint8_t* __restrict__ hit, const float* __restrict__ grad, const uint8_t* __restrict__ albedo,
-                                                            const float* __restrict__ cam2world, int64_t total, int64_t per_frame, float ambient, int mode,
-                                                            int bg_r, int bg_g, int bg_b, uint8_t* __restrict__ rgb)
+                                                            const float* __restrict__ cam2world, const float* __restrict__ light,
+                                                            const uint8_t* __restrict__ ao_open, const uint8_t* __restrict__ ao_total,
+                                                            const uint8_t* __restrict__ sh_open, const uint8_t* __restrict__ sh_total, int64_t total,
+                                                            int64_t per_frame, float ambient, int mode, int bg_r, int bg_g, int bg_b, uint8_t* __restrict__ rgb)
 {
 #pragma clang fp contract(off)
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -305,37 +288,6 @@ __global__ void __launch_bounds__(256) surface_shade_kernel(const uint8_t* __res
         }
         return;
     }
-    const float* cam = cam2world + (p / per_frame) * 16;
-    const double f0 = (double)cam[2], f1 = (double)cam[6], f2 = (double)cam[10];
-    double ff = f0 * f0; ff = ff + f1 * f1; ff = ff + f2 * f2;
-    double dot = g0 * f0; dot = dot + g1 * f1; dot = dot + g2 * f2;
-    const double den = sqrt(nn) * sqrt(ff);
-    const double cosv = den > 0.0 ? fabs(dot) / den : 0.0;
-    const double amb = (double)ambient;
-    const double shade = amb + (1.0 - amb) * cosv;
-    for (int k = 0; k < 3; ++k) {
-        const double alb = albedo ? (double)albedo[p * 3 + k] : kSurfaceGrey;
-        dst[k] = byte_of(floor(alb * shade + 0.5));
-    }
-}
-
-// The lit shade.  light [F][3] (null: the headlight), ao_* and sh_* [F*H*W] counts (null pairs: 1).  With all three null the operations
-// and their order are surface_shade_kernel's mode 0: amb * 1.0 and b * 1.0 are exact.
-__global__ void __launch_bounds__(256) surface_shade_lit_kernel(const uint8_t* __restrict__ hit, const float* __restrict__ grad, const uint8_t* __restrict__ albedo,
-                                                                const float* __restrict__ cam2world, const float* __restrict__ light,
-                                                                const uint8_t* __restrict__ ao_open, const uint8_t* __restrict__ ao_total,
-                                                                const uint8_t* __restrict__ sh_open, const uint8_t* __restrict__ sh_total, int64_t total,
-                                                                int64_t per_frame, float ambient, int bg_r, int bg_g, int bg_b, uint8_t* __restrict__ rgb)
-{
-#pragma clang fp contract(off)
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= total) return;
-    uint8_t* dst = rgb + p * 3;
-    if (!hit[p]) { dst[0] = (uint8_t)bg_r; dst[1] = (uint8_t)bg_g; dst[2] = (uint8_t)bg_b; return; }
-    const float g32[3] = {grad[p * 3], grad[p * 3 + 1], grad[p * 3 + 2]};
-    const bool finite = isfinite(g32[0]) && isfinite(g32[1]) && isfinite(g32[2]);
-    const double g0 = finite ? (double)g32[0] : 0.0, g1 = finite ? (double)g32[1] : 0.0, g2 = finite ? (double)g32[2] : 0.0;
-    double nn = g0 * g0; nn = nn + g1 * g1; nn = nn + g2 * g2;
     const int64_t frame = p / per_frame;
     const float* v = light ? light + frame * 3 : nullptr;            // the light, or the camera's forward axis
     const float* cam = cam2world + frame * 16;
@@ -361,6 +313,23 @@ __global__ void __launch_bounds__(256) surface_shade_lit_kernel(const uint8_t* _
     }
 }
 
+// The launch behind p3d_surface_shade and p3d_surface_shade_lit, whose frame sizes and required pointers are checked the same way.
+static int shade_launch(const char* who, const uint8_t* hit, const float* grad, const uint8_t* albedo, const float* cam2world, const float* light,
+                        const uint8_t* ao_open, const uint8_t* ao_total, const uint8_t* sh_open, const uint8_t* sh_total, int32_t n_frames, int32_t height,
+                        int32_t width, float ambient, int32_t mode, int32_t bg_r, int32_t bg_g, int32_t bg_b, uint8_t* rgb, p3d_stream_t stream)
+{
+    if (n_frames == 0) return P3D_OK;
+    P3D_REQUIRE(hit && grad && cam2world && rgb, "%s: null pointer", who);
+    const int64_t per_frame = (int64_t)height * width, total = per_frame * n_frames;
+    const int64_t blocks = (total + 255) / 256;
+    if (blocks > INT32_MAX)
+        return fail(P3D_ERR_UNSUPPORTED, "%s: %lld pixels are more than one launch takes", who, (long long)total);
+    hipLaunchKernelGGL(surface_shade_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, hit, grad, albedo, cam2world, light, ao_open,
+                       ao_total, sh_open, sh_total, total, per_frame, ambient, mode, bg_r & 255, bg_g & 255, bg_b & 255, rgb);
+    count_launch(FAM_AUX);
+    return check_launch(who);
+}
+
 } // namespace p3d
 
 using namespace p3d;
@@ -369,33 +338,18 @@ extern "C" int p3d_surface_cast(const float* planes_cl, const float* decoder, co
                                 float near, float dt, int32_t steps, int32_t refine, float threshold, float eps, float half_box, int32_t raster_width,
                                 uint8_t* hit, float* depth, float* position, float* grad, p3d_stream_t stream)
 {
-    int rc = cast_check_desc(d);
+    int rc = stage_check_desc(d, "surface_cast");
     if (rc != P3D_OK) return rc;
     P3D_REQUIRE(planes_cl && decoder && ray_o && ray_d && hit && depth, "surface_cast: null pointer");
     if (steps < 2 || steps > 4096 || refine < 0 || refine > 24)
         return fail(P3D_ERR_UNSUPPORTED, "surface_cast: needs 2 <= steps <= 4096 and 0 <= refine <= 24 (got %d, %d)", steps, refine);
-    const int64_t M = d->rays_per_img;
-    P3D_REQUIRE(raster_width >= 0 && (raster_width == 0 || (raster_width % 8 == 0 && (int64_t)raster_width * raster_width == M)),
-                "surface_cast: raster_width %d must be 0, or a multiple of 8 whose square is rays_per_img (%d)", raster_width, d->rays_per_img);
-    if (M > (int64_t)INT32_MAX - 31)
-        return fail(P3D_ERR_UNSUPPORTED, "surface_cast: %lld rays per set do not fit the kernel's 32-bit in-set index", (long long)M);
-    if (d->n_img == 0) return P3D_OK;
-    const RenderArgs a = cast_render_args(d, planes_cl, decoder, ray_o, ray_d);
+    rc = stage_check_tiles(d, raster_width, "surface_cast", "rays");
+    if (rc != P3D_OK || d->n_img == 0) return rc;
     CastArgs c{};
     c.near = near; c.dt = dt; c.threshold = threshold; c.eps = eps; c.half_box = half_box;
-    c.steps = steps; c.refine = refine; c.raster = raster_width; c.rays_per_set = (unsigned)M;
+    c.steps = steps; c.refine = refine; c.raster = raster_width; c.rays_per_set = (unsigned)d->rays_per_img;
     c.hit = hit; c.depth = depth; c.position = position; c.grad = grad;
-    const int64_t tiles = (M + 31) / 32;
-    int64_t bx = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    const int64_t cap = (kNumCU * 2 + d->n_img - 1) / d->n_img;     // about two blocks per CU over the whole launch
-    if (bx > cap) bx = cap;
-    const size_t lds_bytes = (size_t)kDecoderFloats * sizeof(float);
-    const dim3 grid((unsigned)bx, (unsigned)d->n_img);
-    hipStream_t s = (hipStream_t)stream;
-    if (d->n_nets == 1) hipLaunchKernelGGL(surface_cast_kernel<1>, grid, dim3(kWavesPerBlock * 64), lds_bytes, s, a, c);
-    else                hipLaunchKernelGGL(surface_cast_kernel<2>, grid, dim3(kWavesPerBlock * 64), lds_bytes, s, a, c);
-    count_launch(FAM_RENDER);
-    return check_launch("surface_cast");
+    return stage_launch(surface_cast_kernel<1>, surface_cast_kernel<2>, d, planes_cl, decoder, ray_o, ray_d, c, kDecoderFloats, stream, "surface_cast");
 }
 
 extern "C" int p3d_surface_shade(const uint8_t* hit, const float* grad, const uint8_t* albedo, const float* cam2world, int32_t n_frames, int32_t height,
@@ -403,50 +357,28 @@ extern "C" int p3d_surface_shade(const uint8_t* hit, const float* grad, const ui
 {
     P3D_REQUIRE(n_frames >= 0 && height >= 1 && width >= 1, "surface_shade: bad frame size %d x %d x %d", n_frames, height, width);
     P3D_REQUIRE(mode == 0 || mode == 1, "surface_shade: mode must be 0 (lambert) or 1 (normal), got %d", mode);
-    if (n_frames == 0) return P3D_OK;
-    P3D_REQUIRE(hit && grad && cam2world && rgb, "surface_shade: null pointer");
-    const int64_t per_frame = (int64_t)height * width, total = per_frame * n_frames;
-    const int64_t blocks = (total + 255) / 256;
-    if (blocks > INT32_MAX)
-        return fail(P3D_ERR_UNSUPPORTED, "surface_shade: %lld pixels are more than one launch takes", (long long)total);
-    hipLaunchKernelGGL(surface_shade_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, hit, grad, albedo, cam2world, total, per_frame,
-                       ambient, mode, bg_r & 255, bg_g & 255, bg_b & 255, rgb);
-    count_launch(FAM_AUX);
-    return check_launch("surface_shade");
+    return shade_launch("surface_shade", hit, grad, albedo, cam2world, nullptr, nullptr, nullptr, nullptr, nullptr, n_frames, height, width, ambient, mode,
+                        bg_r, bg_g, bg_b, rgb, stream);
 }
 
 extern "C" int p3d_surface_occlusion(const float* planes_cl, const float* decoder, const p3d_render_desc* d, const float* origin, const float* facing,
                                      const uint8_t* active, const float* directions, int32_t n_directions, float ds, int32_t steps, float threshold,
                                      float half_box, int32_t raster_width, uint8_t* open, uint8_t* total, p3d_stream_t stream)
 {
-    int rc = cast_check_desc(d);
+    int rc = stage_check_desc(d, "surface_occlusion");
     if (rc != P3D_OK) return rc;
     if (n_directions < 1 || n_directions > kMaxDirections || steps < 1 || steps > 4096)
         return fail(P3D_ERR_UNSUPPORTED, "surface_occlusion: needs 1 <= directions <= %d and 1 <= steps <= 4096 (got %d, %d)", kMaxDirections, n_directions,
                     steps);
     P3D_REQUIRE(planes_cl && decoder && origin && facing && active && directions && open && total, "surface_occlusion: null pointer");
-    const int64_t M = d->rays_per_img;
-    P3D_REQUIRE(raster_width >= 0 && (raster_width == 0 || (raster_width % 8 == 0 && (int64_t)raster_width * raster_width == M)),
-                "surface_occlusion: raster_width %d must be 0, or a multiple of 8 whose square is rays_per_img (%d)", raster_width, d->rays_per_img);
-    if (M > (int64_t)INT32_MAX - 31)
-        return fail(P3D_ERR_UNSUPPORTED, "surface_occlusion: %lld points per set do not fit the kernel's 32-bit in-set index", (long long)M);
-    if (d->n_img == 0) return P3D_OK;
-    const RenderArgs a = cast_render_args(d, planes_cl, decoder, origin, facing);
+    rc = stage_check_tiles(d, raster_width, "surface_occlusion", "points");
+    if (rc != P3D_OK || d->n_img == 0) return rc;
     OcclusionArgs c{};
     c.ds = ds; c.threshold = threshold; c.half_box = half_box;
-    c.n_dirs = n_directions; c.steps = steps; c.raster = raster_width; c.points_per_set = (unsigned)M;
+    c.n_dirs = n_directions; c.steps = steps; c.raster = raster_width; c.points_per_set = (unsigned)d->rays_per_img;
     c.active = active; c.directions = directions; c.open = open; c.total = total;
-    const int64_t tiles = (M + 31) / 32;
-    int64_t bx = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    const int64_t cap = (kNumCU * 2 + d->n_img - 1) / d->n_img;     // about two blocks per CU over the whole launch
-    if (bx > cap) bx = cap;
-    const size_t lds_bytes = (size_t)(kDecoderFloats + kMaxDirections * 3) * sizeof(float);
-    const dim3 grid((unsigned)bx, (unsigned)d->n_img);
-    hipStream_t s = (hipStream_t)stream;
-    if (d->n_nets == 1) hipLaunchKernelGGL(surface_occlusion_kernel<1>, grid, dim3(kWavesPerBlock * 64), lds_bytes, s, a, c);
-    else                hipLaunchKernelGGL(surface_occlusion_kernel<2>, grid, dim3(kWavesPerBlock * 64), lds_bytes, s, a, c);
-    count_launch(FAM_RENDER);
-    return check_launch("surface_occlusion");
+    return stage_launch(surface_occlusion_kernel<1>, surface_occlusion_kernel<2>, d, planes_cl, decoder, origin, facing, c, kDecoderFloats + kMaxDirections * 3,
+                        stream, "surface_occlusion");
 }
 
 extern "C" int p3d_surface_shade_lit(const uint8_t* hit, const float* grad, const uint8_t* albedo, const float* cam2world, const float* light,
@@ -456,14 +388,6 @@ extern "C" int p3d_surface_shade_lit(const uint8_t* hit, const float* grad, cons
 {
     P3D_REQUIRE(n_frames >= 0 && height >= 1 && width >= 1, "surface_shade_lit: bad frame size %d x %d x %d", n_frames, height, width);
     P3D_REQUIRE(!ao_open == !ao_total && !sh_open == !sh_total, "surface_shade_lit: an open count and its total come as a pair");
-    if (n_frames == 0) return P3D_OK;
-    P3D_REQUIRE(hit && grad && cam2world && rgb, "surface_shade_lit: null pointer");
-    const int64_t per_frame = (int64_t)height * width, total = per_frame * n_frames;
-    const int64_t blocks = (total + 255) / 256;
-    if (blocks > INT32_MAX)
-        return fail(P3D_ERR_UNSUPPORTED, "surface_shade_lit: %lld pixels are more than one launch takes", (long long)total);
-    hipLaunchKernelGGL(surface_shade_lit_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, hit, grad, albedo, cam2world, light, ao_open,
-                       ao_total, sh_open, sh_total, total, per_frame, ambient, bg_r & 255, bg_g & 255, bg_b & 255, rgb);
-    count_launch(FAM_AUX);
-    return check_launch("surface_shade_lit");
+    return shade_launch("surface_shade_lit", hit, grad, albedo, cam2world, light, ao_open, ao_total, sh_open, sh_total, n_frames, height, width, ambient, 0,
+                        bg_r, bg_g, bg_b, rgb, stream);
 }

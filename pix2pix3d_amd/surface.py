@@ -39,8 +39,6 @@ MAX_DIRECTIONS = 255                                     # p3d_surface_occlusion
 _MODES = {'lambert': 0, 'normal': 1}
 _RAY_BYTES = 1024                                        # what one ray of a chunk is budgeted at: its points, the features and hidden units behind them
 
-# (renderer.fused_surface_cast, which makes the cast's call, declares the same signature)
-_lib.register('p3d_surface_cast', ctypes.c_int, [_vp, _vp, ctypes.POINTER(_rmod._RenderDesc), _vp, _vp, _f32, _f32, _i32, _i32, _f32, _f32, _f32, _i32] + [_vp] * 5)
 _lib.register('p3d_surface_shade', ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _i32, _i32, _i32, _vp, _vp])      # csrc/surface.hip
 _lib.register('p3d_surface_shade_lit', ctypes.c_int, [_vp] * 9 + [_i32, _i32, _i32, _f32, _i32, _i32, _i32, _vp, _vp])
 

@@ -153,6 +153,83 @@ def test_entry_points_reject_what_their_index_types_cannot_hold():
     assert b'32-bit in-image index' in h.p3d_last_error()
 
 
+def _plane_desc_callers():
+    """name -> (call(descriptor or None, missing=False), honours shared planes, one grid row per set): every entry point that reads the tri-plane
+    features through a p3d_render_desc, with dummy non-null pointers and otherwise valid arguments.  ``missing`` nulls one required output."""
+    import ctypes
+    from pix2pix3d_amd import _lib
+    h = _lib.lib()
+    p = ctypes.c_void_p(16)
+    return {
+        'p3d_sample_points': (lambda d, missing=False: h.p3d_sample_points(p, p, p, d, 64, p, p, None), False, False),      # csrc/render.hip: the yardstick
+        'p3d_sample_lattice': (lambda d, missing=False: h.p3d_sample_lattice(p, p, d, p, p, p, 4, 4, 4, p, None), False, True),
+        'p3d_surface_cast': (lambda d, missing=False: h.p3d_surface_cast(p, p, d, p, p, 0.1, 0.1, 8, 2, 10.0, 0.01, 0.5, 0, None if missing else p, p, p, p,
+                                                                         None), True, True),
+        'p3d_surface_occlusion': (lambda d, missing=False: h.p3d_surface_occlusion(p, p, d, p, p, p, p, 3, 0.1, 4, 10.0, 0.5, 0, None if missing else p, p,
+                                                                                   None), True, True),
+        'p3d_render_backward': (lambda d, missing=False: h.p3d_render_backward(p, p, p, p, p, p, p, None, None, d, p, p, p, p, p, p, None), False, False),
+        'p3d_sample_points_backward': (lambda d, missing=False: h.p3d_sample_points_backward(p, p, p, p, d, 64, p, p, p, p, None), False, False),
+    }
+
+
+def _plane_desc(**over):
+    from pix2pix3d_amd.training.volumetric_rendering import renderer as rmod
+    fields = dict(n_img=1, rays_per_img=64, plane_h=16, plane_w=16, n_nets=2, semantic_sigmoid=0, depth_resolution=8, depth_resolution_importance=8,
+                  disparity_space_sampling=0, white_back=0, ray_start=0.1, ray_end=1.0, box_warp=1.0, image_stride=0, plane_stride=0, pixel_stride=0,
+                  raster_order=0, mlp_bf16x3=0)
+    fields.update(over)
+    return rmod._RenderDesc(**fields)
+
+
+def _strided(pixel_stride):      # the [N][H][W][C] view: the three planes interleaved in a pixel's channels
+    return dict(pixel_stride=pixel_stride, plane_stride=32, image_stride=pixel_stride * 16 * 16)
+
+
+# (row, descriptor fields or None for a null descriptor, return code, what the message says)
+_BAD_PLANE_DESCS = [
+    ('null', None, -2, b'null descriptor'),
+    ('n_nets_3', dict(n_nets=3), -2, b'n_nets must be 1 or 2'),
+    ('plane_h_0', dict(plane_h=0), -2, b'bad plane size'),
+    ('box_warp_0', dict(box_warp=0.0), -2, b'box_warp must be non-zero'),
+    ('over_2GiB', dict(n_img=86, plane_h=256, plane_w=256), -1, b'32-bit buffer addressing'),      # 86 x 3 x 256^2 x 32 floats: > 2^31 bytes
+    ('pixel_stride_16384', _strided(16384), -1, b'32-bit buffer addressing'),                      # 65536 bytes: past the 24-bit multiply's 16-bit factor
+    ('pixel_stride_98', _strided(98), -2, b'16-byte aligned'),
+]
+
+
+@pytest.mark.parametrize('entry', ['p3d_sample_lattice', 'p3d_surface_cast', 'p3d_surface_occlusion', 'p3d_render_backward', 'p3d_sample_points_backward'])
+def test_every_plane_reader_rejects_what_the_point_kernel_rejects(entry):
+    """csrc/render_host.h's check_plane_desc behind every entry point that reads the planes: the codes of p3d_sample_points (csrc/render.hip, which keeps
+    its own copy of the checks) and, after the ``who:`` prefix, its messages — all returned before any launch (no GPU needed)."""
+    import ctypes
+    from pix2pix3d_amd import _lib
+    h = _lib.lib()
+    callers = _plane_desc_callers()
+    call, shared, set_rows = callers[entry]
+    yardstick = callers['p3d_sample_points'][0]
+
+    def message():
+        return h.p3d_last_error().split(b': ', 1)[1]
+
+    for row, fields, code, says in _BAD_PLANE_DESCS:
+        d = None if fields is None else ctypes.byref(_plane_desc(**fields))
+        assert yardstick(d) == code, row
+        want = message()
+        assert says in want, (row, want)
+        assert call(d) == code, row
+        assert message() == want, row
+    if set_rows:
+        assert call(ctypes.byref(_plane_desc(n_img=65536))) == -2
+        assert b'n_img must be in [0, 65535]' in message()
+    over = dict(n_img=86, plane_h=256, plane_w=256, raster_order=2)      # P3D_RENDER_SHARED_PLANES: one 256^2 set under 86 ray sets
+    if shared:      # the span is the one set's: the descriptor passes, the next bad argument is reported
+        assert call(ctypes.byref(_plane_desc(**over)), missing=True) == -2
+        assert message() == b'null pointer'
+    else:           # the bit is ignored: 86 sets
+        assert call(ctypes.byref(_plane_desc(**over))) == -1
+        assert b'32-bit buffer addressing' in message()
+
+
 def script_sigma_field(G, ws, resolution, block_resolution=64):
     """get_sigma_field_np (extract_mesh.py:60-81) restated for one image."""
     bound = G.rendering_kwargs['box_warp'] * 0.5

@@ -11,7 +11,7 @@ from edit_cases import demo_pose, random_mask
 from pix2pix3d_amd import _lib, surface
 from pix2pix3d_amd.training.volumetric_rendering import renderer as rmod
 from test_shape_gpu import _decoder
-from test_surface_gpu import EPS, HALF_BOX, OPT, _generator_case, _point_sigma, _ray_max, _rays, planes  # noqa: F401  (planes: the module's fixture)
+from test_surface_gpu import EPS, HALF_BOX, OPT, _generator_case, _point_sigma, _ray_max, _rays, _same_bytes, planes  # noqa: F401  (planes: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -83,6 +83,32 @@ def test_occlusion_equals_the_composition_over_the_point_kernel(hip_lib, planes,
     assert torch.equal(torch.stack([r[0] for r in ref]), want_open) and torch.equal(torch.stack([r[1] for r in ref]), want_total)
     assert torch.equal(total, want_total)
     assert torch.equal(open_, want_open)
+
+
+@pytest.mark.parametrize('nets', [1, 2])
+def test_planes_read_in_place_give_the_bytes_of_the_relayout_pass(hip_lib, nets):
+    """csrc/render_host.h's one argument fill serves both layouts ``_plane_set_cl`` hands the density kernels: a channels-last [N, 96, H, W] tensor read
+    in place through its strides, and the same values through the re-layout pass to [N][3][H][W][32]."""
+    cl = (torch.randn([2, 96, 16, 16], generator=torch.Generator().manual_seed(23)) * 2).cuda().contiguous(memory_format=torch.channels_last)
+    in_place = cl.view(2, 3, 32, 16, 16)
+    copied = in_place.contiguous()
+    assert rmod._plane_set_cl(in_place)[1] == (96 * 256, 32, 96) and rmod._plane_set_cl(copied)[1] == (0, 0, 0)
+    dec = _decoder(nets, seed=nets).cuda()
+    xs, ys, zs = (torch.linspace(-0.5, 0.5, n) for n in (5, 6, 7))                 # 210 points: six tiles and a partial one
+    o, d = (t[:, :72].contiguous() for t in _rays(9))                              # 72 rays: two tiles and a quarter
+    dirs = surface.sphere_directions(3).cuda()[None].expand(2, -1, -1).contiguous()
+    with torch.no_grad():
+        lattice = [rmod.fused_sample_lattice(p, dec, xs, ys, zs, OPT) for p in (in_place, copied)]
+        assert tuple(lattice[0].shape) == (2, 5, 6, 7) and torch.equal(lattice[0], lattice[1])
+        thr = float(lattice[1].flatten().quantile(0.75))
+        for first in (2, 1):                                                       # per-set planes; set 0 shared over the two ray sets
+            cast = [rmod.fused_surface_cast(p[:first], dec, o, d, OPT, NEAR, FAR, 8, 2, thr, EPS, HALF_BOX) for p in (in_place, copied)]
+            assert all(_same_bytes(a, b) for a, b in zip(*cast))
+            hit, _, position, grad = cast[1]
+            assert bool(hit.any()) and not bool(hit.all())
+            counts = [rmod.fused_surface_occlusion(p[:first], dec, position, -grad, hit, dirs, OPT, REACH, 4, thr, HALF_BOX) for p in (in_place, copied)]
+            assert all(torch.equal(a, b) for a, b in zip(*counts))
+            assert int(counts[1][1].sum()) > 0
 
 
 # ---- 2. scheduling does not change a count; the limits -----------------------------------------------------------------------------
