@@ -698,6 +698,24 @@ int p3d_demod_coefs_backward(const float* gd, const float* d, const float* style
 int64_t p3d_conv2d_nhwc_workspace(int dtype, int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int64_t w_img_stride, int32_t kernel_size,
                                   int32_t resample);
 
+/* The kernel family a p3d_conv2d_nhwc* call with these sizes and operand facts would run, without launching anything (read-only: tests pin the
+ * host path's route decision with it).  Returns a p3d_conv_route code, or a negative p3d_status exactly as the call itself would for these sizes
+ * (pointer checks excepted: there are no pointers here); *scratch_bytes (optional) = the split-K scratch that route would like, granted or not.
+ * flags: P3D_CONV_* bits below — which per-image scales the call brings, whether it brings a workspace (taken to be aligned and as large as
+ * wanted), whether y is 16-byte aligned.  x_split / y_split: as p3d_conv2d_nhwc_bf16x3_io.                                                    */
+enum p3d_conv_route {
+    P3D_CONV_ROUTE_GENERIC        = 0,   /* conv2d_nhwc_kernel: any size, any resample mode, the per-image scales                            */
+    P3D_CONV_ROUTE_GENERIC_SPLITK = 1,   /* ... with its K loop dealt out over the workspace, + splitk_epilogue_kernel (two launches)        */
+    P3D_CONV_ROUTE_HALO           = 2,   /* conv3x3_halo_kernel: 3x3 "same" on 8 x 16 pixel slabs                                            */
+    P3D_CONV_ROUTE_HALO_X6P       = 3,   /* conv3x3_halo_x6p_kernel: the same for bf16x6 with operands split once per work-group             */
+    P3D_CONV_ROUTE_H2_F16         = 4,   /* conv3x3_h2_f16_kernel: fp16 3x3 "same" on 16 x 16 patches                                        */
+    P3D_CONV_ROUTE_R2_BF16X3      = 5,   /* conv3x3_r2_bf16x3_kernel: bf16x3 3x3 "same" on split activations                                 */
+    P3D_CONV_ROUTE_CONVT_H2_F16   = 6    /* convT_h2_f16_kernel: fp16 transposed stride-2 form                                               */
+};
+enum { P3D_CONV_HAS_OUT_SCALE = 1, P3D_CONV_HAS_IN_SCALE = 2, P3D_CONV_HAS_WORKSPACE = 4, P3D_CONV_Y_ALIGNED = 8 };
+int p3d_conv2d_nhwc_route(int dtype, int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int64_t w_img_stride, int32_t kernel_size,
+                          int32_t resample, int32_t x_split, int32_t y_split, uint32_t flags, int64_t* scratch_bytes);
+
 /* x [N][HW][Ci] fp16 channels-last, weight [Co][Ci] fp32, styles [N][Ci] fp32 (weight gain already applied),
  * bias [Co] or null -> y [N][Co][HW] fp32 (NCHW); accumulate != 0 adds into y (the skip-image sum).
  * Ci in {64, 128, 256}, Co <= 32, HW a multiple of 4, else P3D_ERR_UNSUPPORTED (wide outputs: p3d_conv2d_nhwc, k = 1). */

@@ -90,8 +90,6 @@ struct ConvArgs {
                            // the same 128 bytes as 32 floats — which the next bf16x3 layer reads without splitting anything (XS below)
 };
 
-static thread_local const float* tl_in_scale = nullptr;      // ConvArgs::iscale of the call in flight on this thread (p3d_conv2d_nhwc_scaled_in)
-
 // 16-B slot of (row, chunk).  Two 128-byte tile rows share one 256-byte LDS bank row, so the XOR key is (row >> 1) & 7:
 // the 16 rows a ds_read_b128 lane group touches then land on 16 distinct slots (row & 7 would leave a 2-way conflict).
 __device__ __forceinline__ int swz(int row, int chunk) { return row * 8 + (chunk ^ ((row >> 1) & 7)); }
@@ -2173,6 +2171,81 @@ extern "C" int p3d_modulate_weights(const float* weight, const float* styles, vo
     return check_launch("modulate_weights");
 }
 
+// ---- forward convolution host path: one request (ConvRequest), one plan (plan_conv), one launch switch (launch_conv_plan) --------------------
+// Template instantiation within a route's kernel family: the generic kernel has the first nine, the 8 x 16 halo kernel the first five, its pre-split form the last two.
+enum ConvVariant { CV_F16 = 0, CV_F32, CV_BF3, CV_BF3_XS, CV_X6, CV_BF3_ISC, CV_F16_CO64, CV_F32_CO64, CV_X6_CO64, CV_X6P, CV_X6P_CO64 };
+
+// Every P3D_* switch of this host path, read once per process — except P3D_X6_PRESPLIT, which x6_presplit_mode() reads at every call that asks.
+static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static int env_within(const char* name, int dflt, int lo, int hi) { const int v = env_int(name, dflt); return v >= lo && v <= hi ? v : dflt; }
+struct ConvSwitches {
+    bool no_h2 = getenv("P3D_CONV_NO_H2") != nullptr;              // the h2 kernels (3x3 and transposed) off
+    bool no_halo = getenv("P3D_CONV_NO_HALO") != nullptr;          // every 3x3 halo kernel off
+    bool no_r2 = getenv("P3D_CONV_NO_R2") != nullptr;              // the ring kernel off
+    bool no_co64 = getenv("P3D_CONV_NO_CO64") != nullptr;          // (A/B switch of the measurement scripts) the generic kernel's 64-column form off
+    bool no_cls_major = env_int("P3D_CONV_CLASS_MAJOR", 1) == 0;   // (A/B switch) image-major block order for the transposed form
+    bool r2_store2 = env_int("P3D_R2_STORE2", 0) != 0;             // (A/B only) the ring kernel's split result with the 2-byte stores of the lane = channel layout
+    bool store_narrow = env_int("P3D_CONV_STORE4", 0) != 0;        // (A/B only) ConvArgs::store_narrow
+    bool torgb_no_tr = env_int("P3D_TORGB_NO_TR", 0) != 0;         // (A/B switch) p3d_conv3x3_torgb_f16: the LDS-image epilogue without the store
+    // tuning switches of tests/gpu_probe_splitk.sh (defaults = the values the sweep kept): work-groups per CU aimed at, fewest K steps per split
+    int splitk_per_cu = env_within("P3D_SPLITK_PER_CU", 2, 1, 8), splitk_min_steps = env_within("P3D_SPLITK_MIN_STEPS", 4, 1, 64);
+};
+static const ConvSwitches& conv_switches() { static const ConvSwitches once; return once; }
+// P3D_X6_PRESPLIT: 0 never, 1 (default) where the grid is large enough, 2 always — read at every call, so that one test process can put small geometries through either kernel
+static int x6_presplit_mode() { const char* e = getenv("P3D_X6_PRESPLIT"); return e ? atoi(e) : 1; }
+
+// The halo kernels (8 x 16, h2, ring) have no split-K: they take the layers whose own grid fills the chip (or every layer when the caller brought no scratch).
+// Below kMinOwnBlocks work-groups a layer with a long K loop goes to the generic kernel with its K steps dealt out: a 512-channel layer at 16^2 / 32^2 is
+// 32 / 128 work-groups with a 144-step K loop.  The ring kernel is not taken below it at all (smaller grids: the 8 x 16 halo kernel, then split-K).
+constexpr int kMinOwnBlocks = 192;
+constexpr int kSplitWorthSteps = 16;       // ... "long": K steps (channel blocks x taps) from which that hand-over pays
+// bf16x6: operands split once per work-group (conv3x3_halo_x6p_kernel) where the grid gives every CU its two work-groups — one alone has nobody to hide its per-tap
+// rendezvous behind (512 -> 512 at 32^2 x 4, 128 work-groups: 0.149 ms against 0.135 for the in-register kernel, profiles/round6_m_*)
+constexpr int kX6PresplitBlocks = 256;
+constexpr int kSplitKMinLoop = 8;          // split-K of the generic kernel: K loops shorter than this stay whole
+
+// Work-groups of a 3x3 kernel that gives each one a ph x pw pixel patch of one image and one block of 128 output channels
+static int64_t patch_count(int h, int wdt, int ph, int pw, int channel_blocks, int n_img)
+{
+    return (int64_t)((h + ph - 1) / ph) * ((wdt + pw - 1) / pw) * channel_blocks * n_img;
+}
+
+// The sizes and the tap set of a k x k "same" convolution (correlation, input offset = tap - k/2), one class, nothing split: what the 3x3 layers and the fused
+// ToRGB entry points run as it stands, and what conv_geometry starts the resampling forms from.
+static void fill_same_conv(ConvArgs& a, int n_img, int h, int wdt, int ci, int co, int k, int64_t w_img_stride, int act, float gain, float clamp)
+{
+    a.N = n_img; a.H = h; a.W = wdt; a.Ci = ci; a.Co = co; a.KT = k * k; a.w_img_stride = w_img_stride;
+    a.act = act; a.gain = gain; a.clamp = clamp; a.isy = a.isx = 1; a.OH = h; a.OW = wdt; a.osy = a.osx = 1; a.ncls = 1; a.ksplit = 1;
+    a.cls[0].SH = h; a.cls[0].SW = wdt; a.cls[0].ntaps = a.KT;
+    for (int t = 0; t < a.KT; ++t) a.cls[0].taps[t] = ConvTap{t / k - k / 2, t % k - k / 2, t};
+}
+
+// Everything in ConvArgs that follows from the request's sizes (no pointer, no plan field).  The request has passed plan_conv's checks.
+static void conv_geometry(const ConvRequest& r, ConvArgs& a)
+{
+    const int k = r.kernel_size;
+    fill_same_conv(a, r.n_img, r.h, r.wdt, r.ci, r.co, k, r.w_img_stride, r.act, r.gain, r.clamp);
+    if (r.resample == 2) {                                           // valid (unpadded) correlation at stride 2: conv2d_resample.py:108-111 after its FIR
+        a.OH = (r.h - k) / 2 + 1; a.OW = (r.wdt - k) / 2 + 1; a.isy = a.isx = 2;
+        a.cls[0].SH = a.OH; a.cls[0].SW = a.OW;
+        for (int t = 0; t < a.KT; ++t) a.cls[0].taps[t] = ConvTap{t / k, t % k, t};
+    } else if (r.resample == 1) {
+        // conv_transpose2d(stride 2, no padding): out[(2i+py), (2j+px)] = sum_{ky = py (mod 2), kx = px (mod 2)} x[i - (ky-py)/2, j - (kx-px)/2] w[ky, kx]
+        // -> four dense sub-problems (4 / 2 / 2 / 1 taps), all in ONE launch so the grid fills the chip
+        a.OH = r.out_h > 0 ? r.out_h : 2 * r.h + 1; a.OW = r.out_w > 0 ? r.out_w : 2 * r.wdt + 1; a.osy = a.osx = 2; a.ncls = 4;
+        for (int py = 0; py < 2; ++py)
+            for (int px = 0; px < 2; ++px) {
+                ConvArgs::Cls& c = a.cls[py * 2 + px];
+                c.ooy = py; c.oox = px;
+                c.SH = (a.OH - py + 1) / 2; c.SW = (a.OW - px + 1) / 2;                // output rows py, py + 2, ... < OH
+                c.ntaps = 0;
+                for (int ky = py; ky < 3; ky += 2)
+                    for (int kx = px; kx < 3; kx += 2)
+                        c.taps[c.ntaps++] = ConvTap{-(ky - py) / 2, -(kx - px) / 2, ky * 3 + kx};
+            }
+    }
+}
+
 // Fold the batch into the GEMM rows when the weights are shared and one image cannot fill a 128-row tile (training-mode and
 // plain Conv2dLayer calls on the low-resolution blocks): N x H x W rows instead of N launches' worth of mostly empty tiles.
 static int fold_batch(const ConvArgs& a, int dtype)
@@ -2184,50 +2257,39 @@ static int fold_batch(const ConvArgs& a, int dtype)
 
 // Split-K plan of the generic kernel for a launch of `blocks` work-groups whose longest K loop has `nsteps` steps: 1 when the
 // launch already fills the chip or the loop is short; otherwise enough splits for ~2 work-groups per CU with >= 4 steps each.
-static int splitk_plan(int64_t blocks, int nsteps)
+static int splitk_plan(int64_t blocks, int nsteps, const ConvSwitches& sw)
 {
-    // tuning switches of tests/gpu_probe_splitk.sh (defaults = the values the sweep kept): work-groups per CU aimed at, fewest K steps per split
-    static const int per_cu = [] { const char* e = getenv("P3D_SPLITK_PER_CU"); const int v = e ? atoi(e) : 2; return v >= 1 && v <= 8 ? v : 2; }();
-    static const int min_steps = [] { const char* e = getenv("P3D_SPLITK_MIN_STEPS"); const int v = e ? atoi(e) : 4; return v >= 1 && v <= 64 ? v : 4; }();
-    if (blocks >= kNumCU || nsteps < 8) return 1;
-    int64_t want = (per_cu * kNumCU + blocks - 1) / blocks;
-    if (want > nsteps / min_steps) want = nsteps / min_steps;
+    if (blocks >= kNumCU || nsteps < kSplitKMinLoop) return 1;
+    int64_t want = (sw.splitk_per_cu * kNumCU + blocks - 1) / blocks;
+    if (want > nsteps / sw.splitk_min_steps) want = nsteps / sw.splitk_min_steps;
     if (want < 2) return 1;
     const int per = (int)((nsteps + want - 1) / want);
     return (nsteps + per - 1) / per;
 }
 
-static void conv_launch_shape(const ConvArgs& a, int* M, int* z, int* nsteps)
+// The generic kernel's part of the plan: batch fold, grid, split-K and its scratch, block order, template variant
+static int plan_generic(const ConvRequest& r, ConvArgs& a, const ConvSwitches& sw, ConvPlan* p)
 {
+    const int dtype = r.dtype;
+    p->route = P3D_CONV_ROUTE_GENERIC;
+    p->fold = a.fold = fold_batch(a, dtype);                         // (never the transposed form: four classes)
     int m = 0, taps = 0;
     for (int c = 0; c < a.ncls; ++c) {
         m = a.cls[c].SH * a.cls[c].SW > m ? a.cls[c].SH * a.cls[c].SW : m;
         taps = a.cls[c].ntaps > taps ? a.cls[c].ntaps : taps;
     }
-    *M = a.fold ? m * a.N : m;
-    *z = a.fold ? 1 : a.N * a.ncls;
-    *nsteps = taps;
-}
-
-static int launch_conv(ConvArgs& a, int dtype, hipStream_t s, void* workspace, int64_t workspace_bytes, int64_t* query, bool x_split = false)
-{
-    int M, z, taps;
-    conv_launch_shape(a, &M, &z, &taps);
-    if (M <= 0) return P3D_OK;
+    const int M = a.fold ? m * a.N : m, z = a.fold ? 1 : a.N * a.ncls;
+    if (M <= 0) return P3D_OK;                                       // (grid 0: nothing to launch)
     const int gx = (M + BM - 1) / BM, gy = (a.Co + BN - 1) / BN;
     const int nsteps = taps * (a.Ci / (dtype == P3D_F16 ? 64 : 32));
-    a.ksplit = 1; a.partial = nullptr;
-    const int want = splitk_plan((int64_t)gx * gy * z, nsteps);
-    const int64_t need = want > 1 ? (int64_t)want * z * gx * BM * gy * BN * 4 : 0;
-    if (query) { *query = need; return P3D_OK; }
-    if (want > 1 && workspace && workspace_bytes >= need && (((uintptr_t)workspace) & 15u) == 0) { a.ksplit = want; a.partial = (float*)workspace; }
-    dim3 grid(gx, gy, z * a.ksplit);
-    static const bool no_co64 = getenv("P3D_CONV_NO_CO64") != nullptr;          // (A/B switch of the measurement scripts)
-    const bool co64 = !no_co64 && a.Co <= 64;
-    static const bool no_cls_major = [] { const char* e = getenv("P3D_CONV_CLASS_MAJOR"); return e && atoi(e) == 0; }();      // (A/B switch)
-    a.cls_major = (a.ncls > 1 && !a.fold && !no_cls_major) ? 1 : 0;
-    if (a.iscale) {                                                             // the table of conv2d_nhwc_kernel<.., ISC>: the scale rows of every image a 128-row tile touches
-        if (dtype != P3D_F32_BF16X3 || x_split) return fail(P3D_ERR_UNSUPPORTED, "conv2d_nhwc: the input scale is implemented for bf16x3 on plain fp32 activations");
+    const int want = splitk_plan((int64_t)gx * gy * z, nsteps, sw);
+    p->scratch_bytes = want > 1 ? (int64_t)want * z * gx * BM * gy * BN * 4 : 0;
+    if (want > 1 && r.ws_usable_bytes >= p->scratch_bytes) { p->ksplit = want; p->route = P3D_CONV_ROUTE_GENERIC_SPLITK; }
+    p->grid[0] = gx; p->grid[1] = gy; p->grid[2] = z * p->ksplit;
+    p->co64 = !sw.no_co64 && a.Co <= 64;
+    p->cls_major = (a.ncls > 1 && !a.fold && !sw.no_cls_major) ? 1 : 0;
+    if (r.has_in_scale) {                                            // the table of conv2d_nhwc_kernel<.., ISC>: the scale rows of every image a 128-row tile touches
+        if (dtype != P3D_F32_BF16X3 || r.x_split) return fail(P3D_ERR_UNSUPPORTED, "conv2d_nhwc: the input scale is implemented for bf16x3 on plain fp32 activations");
         int worst = 1;
         if (a.fold) {
             const int MI = a.cls[0].SH * a.cls[0].SW;
@@ -2240,32 +2302,115 @@ static int launch_conv(ConvArgs& a, int dtype, hipStream_t s, void* workspace, i
         }
         if ((int64_t)worst * a.Ci > kIscaleFloats) return fail(P3D_ERR_UNSUPPORTED, "conv2d_nhwc: %d images x %d channels of input scales exceed the kernel's table", worst, a.Ci);
     }
-    if (dtype == P3D_F16 && co64)     hipLaunchKernelGGL((conv2d_nhwc_kernel<__half, false, false, true>), grid, dim3(256), 0, s, a);
-    else if (dtype == P3D_F32 && co64) hipLaunchKernelGGL((conv2d_nhwc_kernel<float, false, false, true>), grid, dim3(256), 0, s, a);
-    else if (dtype == P3D_F32_BF16X6 && co64) hipLaunchKernelGGL((conv2d_nhwc_kernel<float, false, false, true, false, true>), grid, dim3(256), 0, s, a);
-    else if (dtype == P3D_F32_BF16X6) hipLaunchKernelGGL((conv2d_nhwc_kernel<float, false, false, false, false, true>), grid, dim3(256), 0, s, a);
-    else if (dtype == P3D_F16)        hipLaunchKernelGGL(conv2d_nhwc_kernel<__half>, grid, dim3(256), 0, s, a);
-    else if (dtype == P3D_F32_BF16X3 && x_split) hipLaunchKernelGGL((conv2d_nhwc_kernel<float, true, true>), grid, dim3(256), 0, s, a);
-    else if (dtype == P3D_F32_BF16X3 && a.iscale) hipLaunchKernelGGL((conv2d_nhwc_kernel<float, true, false, false, true>), grid, dim3(256), 0, s, a);
-    else if (dtype == P3D_F32_BF16X3) hipLaunchKernelGGL((conv2d_nhwc_kernel<float, true>), grid, dim3(256), 0, s, a);
-    else                              hipLaunchKernelGGL(conv2d_nhwc_kernel<float>, grid, dim3(256), 0, s, a);
+    if (dtype == P3D_F32_BF16X3) p->variant = r.x_split ? CV_BF3_XS : (r.has_in_scale ? CV_BF3_ISC : CV_BF3);      // (no 64-column form)
+    else if (dtype == P3D_F32_BF16X6) p->variant = p->co64 ? CV_X6_CO64 : CV_X6;
+    else if (dtype == P3D_F16) p->variant = p->co64 ? CV_F16_CO64 : CV_F16;
+    else p->variant = p->co64 ? CV_F32_CO64 : CV_F32;
+    return P3D_OK;
+}
+
+static int plan_patches(ConvPlan* p, int route, int variant, int patches, int channel_blocks, int z, int y_split = 0)
+{
+    p->route = route; p->variant = variant; p->grid[0] = patches; p->grid[1] = channel_blocks; p->grid[2] = z; p->y_split = y_split;
+    return P3D_OK;
+}
+
+int p3d::plan_conv(const ConvRequest& r, ConvPlan* p)
+{
+    *p = ConvPlan{};
+    const int dtype = r.dtype, n_img = r.n_img, h = r.h, wdt = r.wdt, ci = r.ci, co = r.co, k = r.kernel_size;
+    P3D_REQUIRE(!(r.x_split || r.y_split) || dtype == P3D_F32_BF16X3, "conv2d_nhwc: pre-split activations are a bf16x3 format");
+    P3D_REQUIRE(!r.y_split || co % 32 == 0, "conv2d_nhwc: a split result needs whole 32-channel rows");
+    P3D_REQUIRE(r.resample >= 0 && r.resample <= 2, "conv2d_nhwc: resample must be 0 (same), 1 (transposed x2) or 2 (valid, stride 2)");
+    P3D_REQUIRE(n_img >= 1 && h >= 1 && wdt >= 1 && co >= 1, "conv2d_nhwc: bad sizes");
+    P3D_REQUIRE(dtype == P3D_F16 || dtype == P3D_F32 || dtype == P3D_F32_BF16X3 || dtype == P3D_F32_BF16X6, "conv2d_nhwc: dtype must be fp16, fp32, fp32-as-bf16x3 or fp32-as-bf16x6");
+    P3D_REQUIRE(k == 3 || (k == 1 && r.resample != 1), "conv2d_nhwc: kernel 3x3, or 1x1 without upsampling");
+    P3D_REQUIRE(!r.has_out_scale || dtype != P3D_F16, "conv2d_nhwc: the per-image output scale is implemented for fp32 tensors");
+    const ConvSwitches& sw = conv_switches();
+    const bool big = h >= 32 && wdt >= 32;                           // what the 16 x 16 patch kernels (h2, ring, transposed h2) ask of the image
+    const bool h2t = !sw.no_h2 && r.resample == 1 && dtype == P3D_F16 && big && ci % 32 == 0 && co % BN == 0 && r.y_aligned;   // convT_h2_f16_kernel: 64-byte K rows
+    const int bk = dtype == P3D_F16 ? 64 : 32;
+    if (ci % bk != 0 && !h2t) return fail(P3D_ERR_UNSUPPORTED, "conv2d_nhwc: Ci=%d must be a multiple of %d", ci, bk);
+    P3D_REQUIRE(r.resample != 2 || (h >= k && wdt >= k), "conv2d_nhwc: image smaller than the kernel");
+    ConvArgs a{};
+    conv_geometry(r, a);
+    P3D_REQUIRE(r.resample != 1 || (a.OH >= 2 * h + 1 && a.OH <= 2 * h + 2 && a.OW >= 2 * wdt + 1 && a.OW <= 2 * wdt + 2), "conv2d_nhwc: transposed output must be 2h+1 or 2h+2");
+    if (r.resample == 0 && k == 3 && !sw.no_halo) {                  // the 3x3 "same" layers: h2 (fp16), ring (bf16x3 on split activations), 8 x 16 halo slab
+        const bool h2_ok = !sw.no_h2 && dtype == P3D_F16 && big && ci % 64 == 0 && co % BN == 0 && r.y_aligned;
+        const bool halo_ok = h >= PH && wdt >= PW && !r.has_out_scale && !r.has_in_scale;      // (the per-image scales live in the generic kernel)
+        const int64_t q_blocks = patch_count(h, wdt, QH, QW, co / BN, n_img);
+        const int64_t own_blocks = h2_ok ? q_blocks : patch_count(h, wdt, PH, PW, (co + BN - 1) / BN, n_img);
+        const bool prefer_split = r.have_ws && (h2_ok || halo_ok) && own_blocks < kMinOwnBlocks && ci / bk * a.KT >= kSplitWorthSteps;
+        if (h2_ok && !prefer_split)
+            return plan_patches(p, P3D_CONV_ROUTE_H2_F16, CV_F16, (int)patch_count(h, wdt, QH, QW, 1, 1), co / BN, n_img);
+        const bool r2_ok = !sw.no_r2 && dtype == P3D_F32_BF16X3 && r.x_split && big && co % BN == 0 && !r.has_out_scale;
+        if (r2_ok && q_blocks >= kMinOwnBlocks)                      // split activations in: the ring pipeline on 16-channel half rows
+            return plan_patches(p, P3D_CONV_ROUTE_R2_BF16X3, CV_BF3_XS, (int)patch_count(h, wdt, QH, QW, 1, 1), co / BN, n_img, (r.y_split && sw.r2_store2) ? 2 : r.y_split);
+        if (halo_ok && !prefer_split) {                              // halo-reuse kernel for the plain 3x3 layers
+            const int patches = (int)patch_count(h, wdt, PH, PW, 1, 1), cbs = (co + BN - 1) / BN;
+            const int x6p_mode = dtype == P3D_F32_BF16X6 ? x6_presplit_mode() : 0;
+            if (x6p_mode == 2 || (x6p_mode == 1 && own_blocks >= kX6PresplitBlocks))
+                return plan_patches(p, P3D_CONV_ROUTE_HALO_X6P, co <= 64 ? CV_X6P_CO64 : CV_X6P, patches, cbs, n_img);
+            const int variant = dtype == P3D_F16 ? CV_F16 : dtype == P3D_F32_BF16X3 ? (r.x_split ? CV_BF3_XS : CV_BF3) : dtype == P3D_F32_BF16X6 ? CV_X6 : CV_F32;
+            return plan_patches(p, P3D_CONV_ROUTE_HALO, variant, patches, cbs, n_img, r.y_split);
+        }
+    }
+    if (h2t)                                                         // class (0, 0) is the largest: (H + 1) x (W + 1) positions
+        return plan_patches(p, P3D_CONV_ROUTE_CONVT_H2_F16, CV_F16, (int)patch_count(h + 1, wdt + 1, QH, QW, 1, 1), co / BN, n_img * 4);
+    if (r.y_split) return fail(P3D_ERR_UNSUPPORTED, "conv2d_nhwc: a split result is produced by the 3x3 halo kernel only");
+    return plan_generic(r, a, sw, p);
+}
+
+// The generic kernel, and the pass over the split-K partial tiles where the plan dealt the K loop out
+static int launch_generic(const ConvPlan& p, const ConvArgs& a, int dtype, hipStream_t s)
+{
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]), block(256);
+    switch (p.variant) {
+    case CV_F16_CO64: hipLaunchKernelGGL((conv2d_nhwc_kernel<__half, false, false, true>), grid, block, 0, s, a); break;
+    case CV_F32_CO64: hipLaunchKernelGGL((conv2d_nhwc_kernel<float, false, false, true>), grid, block, 0, s, a); break;
+    case CV_X6_CO64:  hipLaunchKernelGGL((conv2d_nhwc_kernel<float, false, false, true, false, true>), grid, block, 0, s, a); break;
+    case CV_X6:       hipLaunchKernelGGL((conv2d_nhwc_kernel<float, false, false, false, false, true>), grid, block, 0, s, a); break;
+    case CV_F16:      hipLaunchKernelGGL(conv2d_nhwc_kernel<__half>, grid, block, 0, s, a); break;
+    case CV_BF3_XS:   hipLaunchKernelGGL((conv2d_nhwc_kernel<float, true, true>), grid, block, 0, s, a); break;
+    case CV_BF3_ISC:  hipLaunchKernelGGL((conv2d_nhwc_kernel<float, true, false, false, true>), grid, block, 0, s, a); break;
+    case CV_BF3:      hipLaunchKernelGGL((conv2d_nhwc_kernel<float, true>), grid, block, 0, s, a); break;
+    default:          hipLaunchKernelGGL(conv2d_nhwc_kernel<float>, grid, block, 0, s, a); break;
+    }
     count_launch(FAM_CONV);
-    int rc = check_launch("conv2d_nhwc");
-    if (rc != P3D_OK || a.ksplit == 1) return rc;
+    const int rc = check_launch("conv2d_nhwc");
+    if (rc != P3D_OK || p.ksplit == 1) return rc;
+    const int gx = p.grid[0], gy = p.grid[1], z = p.grid[2] / p.ksplit;
     const int64_t total = (int64_t)z * gx * BM * ((a.Co + 3) / 4);
     const int blocks = (int)((total + 255) / 256 < 8 * kNumCU ? (total + 255) / 256 : 8 * kNumCU);
-    if (dtype == P3D_F16) hipLaunchKernelGGL(splitk_epilogue_kernel<__half>, dim3(blocks), dim3(256), 0, s, a, gx * BM, gy * BN, z);   // (P3D_F32_BF16X3: fp32 tensors)
-    else                  hipLaunchKernelGGL(splitk_epilogue_kernel<float>, dim3(blocks), dim3(256), 0, s, a, gx * BM, gy * BN, z);
+    if (dtype == P3D_F16) hipLaunchKernelGGL(splitk_epilogue_kernel<__half>, dim3(blocks), block, 0, s, a, gx * BM, gy * BN, z);   // (P3D_F32_BF16X3: fp32 tensors)
+    else                  hipLaunchKernelGGL(splitk_epilogue_kernel<float>, dim3(blocks), block, 0, s, a, gx * BM, gy * BN, z);
     count_launch(FAM_CONV);
     return check_launch("conv2d_nhwc split-K epilogue");
+}
+
+// The operands and sizes every p3d_conv2d_nhwc* entry point shares, by name (the macro only spares five copies of these lines)
+#define P3D_NHWC_REQUEST(r)                                                                                                                         \
+    ConvRequest r;                                                                                                                                  \
+    r.x = x; r.w = w; r.y = y; r.bias = bias; r.noise = noise; r.noise_strength = noise_strength; r.zeros128 = zeros128; r.stream = stream;         \
+    r.n_img = n_img; r.h = h; r.wdt = wdt; r.ci = ci; r.co = co; r.w_img_stride = w_img_stride; r.kernel_size = kernel_size; r.resample = resample; \
+    r.act = act; r.gain = gain; r.clamp = clamp
+
+// The request of the sizing entry points and of p3d_conv2d_nhwc_route: sizes alone, plain operands assumed
+static ConvRequest sized_request(int dtype, int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int64_t w_img_stride, int32_t kernel_size, int32_t resample)
+{
+    ConvRequest r;
+    r.dtype = dtype; r.n_img = n_img; r.h = h; r.wdt = wdt; r.ci = ci; r.co = co; r.w_img_stride = w_img_stride; r.kernel_size = kernel_size; r.resample = resample;
+    r.assume_plain_operands();
+    return r;
 }
 
 extern "C" int p3d_conv2d_nhwc(const void* x, const void* w, void* y, int dtype, const float* bias, const float* noise, const float* noise_strength,
                                const void* zeros128, int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int64_t w_img_stride,
                                int32_t kernel_size, int32_t resample, int32_t act, float gain, float clamp, p3d_stream_t stream)
 {
-    return p3d::conv2d_nhwc_run(x, w, y, dtype, bias, noise, noise_strength, zeros128, n_img, h, wdt, ci, co, w_img_stride, kernel_size, resample, act, gain, clamp,
-                                0, 0, nullptr, 0, nullptr, nullptr, stream);
+    P3D_NHWC_REQUEST(r);
+    r.dtype = dtype;
+    return run_conv(r);
 }
 
 extern "C" int p3d_conv2d_nhwc_ws(const void* x, const void* w, void* y, int dtype, const float* bias, const float* noise, const float* noise_strength,
@@ -2273,15 +2418,16 @@ extern "C" int p3d_conv2d_nhwc_ws(const void* x, const void* w, void* y, int dty
                                   int32_t kernel_size, int32_t resample, int32_t act, float gain, float clamp, void* workspace, int64_t workspace_bytes,
                                   p3d_stream_t stream)
 {
-    return p3d::conv2d_nhwc_run(x, w, y, dtype, bias, noise, noise_strength, zeros128, n_img, h, wdt, ci, co, w_img_stride, kernel_size, resample, act, gain, clamp,
-                                0, 0, workspace, workspace_bytes, nullptr, nullptr, stream);
+    P3D_NHWC_REQUEST(r);
+    r.dtype = dtype; r.workspace = workspace; r.workspace_bytes = workspace_bytes;
+    return run_conv(r);
 }
 
+// ---- 3x3 layer + ToRGB in one launch: their own checks and launches, the "same" geometry of fill_same_conv ----------------------------------
 extern "C" int p3d_conv3x3_torgb_f16(const void* x, const void* w, void* y, const float* bias, const void* zeros128, const float* rgb_w, const float* rgb_bias,
                                      float* rgb_out, int32_t rgb_co, float rgb_clamp, int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co,
                                      int64_t w_img_stride, int32_t act, float gain, float clamp, p3d_stream_t stream)
 {
-    using namespace p3d;
     P3D_REQUIRE(x && w && zeros128 && rgb_w && rgb_out, "conv3x3_torgb_f16: null pointer");      // y may be null: the layer's activations have no other consumer
     P3D_REQUIRE(rgb_co >= 1 && rgb_co <= 8, "conv3x3_torgb_f16: 1 .. 8 image channels");
     P3D_REQUIRE(act == 0 || act == 1, "conv3x3_torgb_f16: act must be 0 (linear) or 1 (lrelu)");
@@ -2289,17 +2435,13 @@ extern "C" int p3d_conv3x3_torgb_f16(const void* x, const void* w, void* y, cons
         return fail(P3D_ERR_UNSUPPORTED, "conv3x3_torgb_f16: needs Co = 128 or 256, Ci %% 64 = 0, an image of 32 x 32 or more (got %d, %d, %d x %d)", co, ci, h, wdt);
     P3D_REQUIRE((((uintptr_t)x) & 15u) == 0 && (((uintptr_t)w) & 15u) == 0 && (((uintptr_t)zeros128) & 15u) == 0, "conv3x3_torgb_f16: x, w and zeros128 must be 16-byte aligned");
     ConvArgs a{};
+    fill_same_conv(a, n_img, h, wdt, ci, co, 3, w_img_stride, act, gain, clamp);
     a.x = x; a.w = w; a.y = y; a.bias = bias; a.zeros = zeros128;
-    a.N = n_img; a.H = h; a.W = wdt; a.Ci = ci; a.Co = co; a.KT = 9; a.w_img_stride = w_img_stride;
-    a.act = act; a.gain = gain; a.clamp = clamp; a.isy = a.isx = 1; a.OH = h; a.OW = wdt; a.osy = a.osx = 1; a.ncls = 1; a.ksplit = 1;
-    a.cls[0].SH = h; a.cls[0].SW = wdt; a.cls[0].ntaps = 9;
-    for (int t = 0; t < 9; ++t) a.cls[0].taps[t] = ConvTap{t / 3 - 1, t % 3 - 1, t};
     a.rgb_w = rgb_w; a.rgb_bias = rgb_bias; a.rgb_out = rgb_out; a.rgb_co = rgb_co; a.rgb_clamp = rgb_clamp;
-    dim3 grid(((h + QH - 1) / QH) * ((wdt + QW - 1) / QW), 1, n_img);
-    static const bool no_tr = [] { const char* d = getenv("P3D_TORGB_NO_TR"); return d && atoi(d) != 0; }();      // A/B switch: the LDS-image epilogue without the store
+    dim3 grid((int)patch_count(h, wdt, QH, QW, 1, 1), 1, n_img);
     a.cb_loop = co / BN;                                                        // Co = 256: each work-group walks both channel blocks of its patch (the contraction runs over all of them)
     if (a.cb_loop > 1)     hipLaunchKernelGGL((conv3x3_h2_f16_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    else if (!y && !no_tr) hipLaunchKernelGGL(conv3x3_h2_f16_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    else if (!y && !conv_switches().torgb_no_tr) hipLaunchKernelGGL(conv3x3_h2_f16_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
     else                   hipLaunchKernelGGL(conv3x3_h2_f16_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
     count_launch(FAM_CONV);
     return check_launch("conv3x3_torgb_f16");
@@ -2310,43 +2452,40 @@ extern "C" int p3d_conv3x3_torgb_split(const void* x_split, const void* w_split,
                                        int32_t rgb_co, float rgb_clamp, int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int64_t w_img_stride,
                                        int32_t act, float gain, float clamp, p3d_stream_t stream)
 {
-    using namespace p3d;
     P3D_REQUIRE(x_split && w_split && zeros128 && rgb_wmod_split && img_nhwc, "conv3x3_torgb_split: null pointer");
     P3D_REQUIRE(!prev_nhwc || f4x4_host, "conv3x3_torgb_split: the skip image needs its upsampling filter");
     P3D_REQUIRE(!noise || noise_strength, "conv3x3_torgb_split: noise without its strength");
     P3D_REQUIRE(act == 0 || act == 1, "conv3x3_torgb_split: act must be 0 (linear) or 1 (lrelu)");
     P3D_REQUIRE(n_img >= 1 && n_img < 65536 && h >= 1 && wdt >= 1, "conv3x3_torgb_split: bad sizes");
-    const int64_t blocks = (int64_t)((h + QH - 1) / QH) * ((wdt + QW - 1) / QW) * n_img;
-    if (co != BN || ci % 32 != 0 || h < 32 || wdt < 32 || rgb_co % 32 != 0 || rgb_co < 32 || rgb_co > 96 || (prev_nhwc && ((h | wdt) & 1)) || blocks < 192)
+    if (co != BN || ci % 32 != 0 || h < 32 || wdt < 32 || rgb_co % 32 != 0 || rgb_co < 32 || rgb_co > 96 || (prev_nhwc && ((h | wdt) & 1)) || patch_count(h, wdt, QH, QW, 1, n_img) < kMinOwnBlocks)
         return fail(P3D_ERR_UNSUPPORTED, "conv3x3_torgb_split: needs Co = 128, Ci %% 32 = 0, rgb_co in {32, 64, 96}, an even image of 32 x 32 or more and >= 192 patches (got %d, %d, %d, %d x %d x %d)",
                     co, ci, rgb_co, n_img, h, wdt);
     P3D_REQUIRE(((((uintptr_t)x_split) | ((uintptr_t)w_split) | ((uintptr_t)zeros128) | ((uintptr_t)rgb_wmod_split) | ((uintptr_t)img_nhwc) | ((uintptr_t)prev_nhwc) | ((uintptr_t)bias)
                   | ((uintptr_t)rgb_bias)) & 15u) == 0, "conv3x3_torgb_split: pointers must be 16-byte aligned");
     ConvArgs a{};
+    fill_same_conv(a, n_img, h, wdt, ci, co, 3, w_img_stride, act, gain, clamp);
     a.x = x_split; a.w = w_split; a.bias = bias; a.noise = noise; a.noise_strength = noise_strength; a.zeros = zeros128;
-    a.N = n_img; a.H = h; a.W = wdt; a.Ci = ci; a.Co = co; a.KT = 9; a.w_img_stride = w_img_stride;
-    a.act = act; a.gain = gain; a.clamp = clamp; a.isy = a.isx = 1; a.OH = h; a.OW = wdt; a.osy = a.osx = 1; a.ncls = 1; a.ksplit = 1;
-    a.cls[0].SH = h; a.cls[0].SW = wdt; a.cls[0].ntaps = 9;
-    for (int t = 0; t < 9; ++t) a.cls[0].taps[t] = ConvTap{t / 3 - 1, t % 3 - 1, t};
     a.rgb_w = (const float*)rgb_wmod_split; a.rgb_bias = rgb_bias; a.rgb_out = img_nhwc; a.rgb_co = rgb_co; a.rgb_clamp = rgb_clamp;
     WideRgbTail tail{};
     tail.prev = prev_nhwc;
     if (prev_nhwc)
         for (int ky = 0; ky < 4; ++ky)                                            // (f4x4_host: sixteen floats in HOST memory, row-major; as p3d_torgb_wide_split builds them)
             for (int kx = 0; kx < 4; ++kx) tail.fr[ky][kx] = f4x4_host[(3 - kx) + (3 - ky) * 4] * 4.f;
-    dim3 grid(((h + QH - 1) / QH) * ((wdt + QW - 1) / QW), 1, n_img);
+    dim3 grid((int)patch_count(h, wdt, QH, QW, 1, 1), 1, n_img);
     hipLaunchKernelGGL(conv3x3_r2_bf16x3_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a, tail);
     count_launch(FAM_CONV);
     return check_launch("conv3x3_torgb_split");
 }
+
 
 extern "C" int p3d_conv2d_nhwc_bf16x3_io(const void* x, const void* w, void* y, const float* bias, const float* noise, const float* noise_strength,
                                          const void* zeros128, int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int64_t w_img_stride,
                                          int32_t kernel_size, int32_t resample, int32_t act, float gain, float clamp, int32_t x_split, int32_t y_split,
                                          void* workspace, int64_t workspace_bytes, p3d_stream_t stream)
 {
-    return p3d::conv2d_nhwc_run_io(x, w, y, P3D_F32_BF16X3, bias, noise, noise_strength, zeros128, n_img, h, wdt, ci, co, w_img_stride, kernel_size, resample, act, gain,
-                                   clamp, 0, 0, workspace, workspace_bytes, nullptr, nullptr, x_split, y_split, stream);
+    P3D_NHWC_REQUEST(r);
+    r.dtype = P3D_F32_BF16X3; r.x_split = x_split; r.y_split = y_split; r.workspace = workspace; r.workspace_bytes = workspace_bytes;
+    return run_conv(r);
 }
 
 // The route p3d_conv2d_nhwc_bf16x3_io would take, without launching: returns 1 when a split result (y_split) would be granted for these sizes,
@@ -2356,11 +2495,13 @@ extern "C" int p3d_conv2d_nhwc_bf16x3_io_plan(int32_t n_img, int32_t h, int32_t 
 {
     P3D_REQUIRE(workspace_bytes, "conv2d_nhwc_bf16x3_io_plan: null pointer");
     *workspace_bytes = 0;
+    ConvRequest r = sized_request(P3D_F32_BF16X3, n_img, h, wdt, ci, co, w_img_stride, kernel_size, resample);
+    r.x_split = x_split;
     for (int ys = (want_y_split && co % 32 == 0) ? 1 : 0; ys >= 0; --ys) {
-        int64_t bytes = 0;
-        const int rc = p3d::conv2d_nhwc_run_io(nullptr, nullptr, nullptr, P3D_F32_BF16X3, nullptr, nullptr, nullptr, nullptr, n_img, h, wdt, ci, co, w_img_stride, kernel_size,
-                                               resample, 0, 1.f, -1.f, 0, 0, nullptr, 0, &bytes, nullptr, x_split, ys, nullptr);
-        if (rc == P3D_OK) { *workspace_bytes = bytes; return ys; }
+        ConvPlan plan;
+        r.y_split = ys;
+        const int rc = plan_conv(r, &plan);
+        if (rc == P3D_OK) { *workspace_bytes = plan.scratch_bytes; return ys; }
         if (rc != P3D_ERR_UNSUPPORTED || ys == 0) return rc < 0 ? rc : -rc;
     }
     return 0;
@@ -2371,8 +2512,9 @@ extern "C" int p3d_conv2d_nhwc_scaled(const void* x, const void* w, void* y, int
                                       int64_t w_img_stride, int32_t kernel_size, int32_t resample, int32_t act, float gain, float clamp, void* workspace,
                                       int64_t workspace_bytes, p3d_stream_t stream)
 {
-    return p3d::conv2d_nhwc_run(x, w, y, dtype, bias, noise, noise_strength, zeros128, n_img, h, wdt, ci, co, w_img_stride, kernel_size, resample, act, gain, clamp,
-                                0, 0, workspace, workspace_bytes, nullptr, out_scale, stream);
+    P3D_NHWC_REQUEST(r);
+    r.dtype = dtype; r.out_scale = out_scale; r.workspace = workspace; r.workspace_bytes = workspace_bytes;
+    return run_conv(r);
 }
 
 extern "C" int p3d_conv2d_nhwc_scaled_in(const void* x, const void* w, void* y, int dtype, const float* in_scale, const float* out_scale, const float* bias,
@@ -2380,162 +2522,86 @@ extern "C" int p3d_conv2d_nhwc_scaled_in(const void* x, const void* w, void* y, 
                                          int32_t co, int64_t w_img_stride, int32_t kernel_size, int32_t resample, int32_t act, float gain, float clamp,
                                          void* workspace, int64_t workspace_bytes, p3d_stream_t stream)
 {
-    using namespace p3d;
     P3D_REQUIRE(in_scale && out_scale, "conv2d_nhwc_scaled_in: both scales are required (the shared-weight form of the modulated convolution)");
     if (dtype != P3D_F32_BF16X3) return fail(P3D_ERR_UNSUPPORTED, "conv2d_nhwc_scaled_in: implemented for dtype P3D_F32_BF16X3");
     P3D_REQUIRE((((uintptr_t)in_scale) & 15u) == 0, "conv2d_nhwc_scaled_in: in_scale must be 16-byte aligned");
-    tl_in_scale = in_scale;
-    const int rc = conv2d_nhwc_run(x, w, y, dtype, bias, noise, noise_strength, zeros128, n_img, h, wdt, ci, co, w_img_stride, kernel_size, resample, act, gain, clamp,
-                                   0, 0, workspace, workspace_bytes, nullptr, out_scale, stream);
-    tl_in_scale = nullptr;
-    return rc;
+    P3D_NHWC_REQUEST(r);
+    r.dtype = dtype; r.in_scale = in_scale; r.out_scale = out_scale; r.workspace = workspace; r.workspace_bytes = workspace_bytes;
+    return run_conv(r);
 }
+
+#undef P3D_NHWC_REQUEST
 
 extern "C" int64_t p3d_conv2d_nhwc_workspace(int dtype, int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int64_t w_img_stride, int32_t kernel_size,
                                              int32_t resample)
 {
-    int64_t bytes = 0;
-    const int rc = p3d::conv2d_nhwc_run(nullptr, nullptr, nullptr, dtype, nullptr, nullptr, nullptr, nullptr, n_img, h, wdt, ci, co, w_img_stride, kernel_size, resample, 0, 1.f, -1.f,
-                                        0, 0, nullptr, 0, &bytes, nullptr, nullptr);
-    return rc == P3D_OK ? bytes : 0;
+    ConvPlan plan;
+    return plan_conv(sized_request(dtype, n_img, h, wdt, ci, co, w_img_stride, kernel_size, resample), &plan) == P3D_OK ? plan.scratch_bytes : 0;
 }
 
-// out_h / out_w (transposed form only, 0 = 2h+1 / 2w+1): the output size conv_transpose2d's output_padding asks for (2h+1 or 2h+2);
-// the extra row / column only sees taps that fall outside the input, i.e. comes out as zeros, as in the reference's op.
-int p3d::conv2d_nhwc_run(const void* x, const void* w, void* y, int dtype, const float* bias, const float* noise, const float* noise_strength,
-                         const void* zeros128, int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int64_t w_img_stride,
-                         int32_t kernel_size, int32_t resample, int32_t act, float gain, float clamp, int32_t out_h, int32_t out_w,
-                         void* workspace, int64_t workspace_bytes, int64_t* query, const float* out_scale, p3d_stream_t stream)
+extern "C" int p3d_conv2d_nhwc_route(int dtype, int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int64_t w_img_stride, int32_t kernel_size,
+                                     int32_t resample, int32_t x_split, int32_t y_split, uint32_t flags, int64_t* scratch_bytes)
 {
-    return conv2d_nhwc_run_io(x, w, y, dtype, bias, noise, noise_strength, zeros128, n_img, h, wdt, ci, co, w_img_stride, kernel_size, resample, act, gain, clamp,
-                              out_h, out_w, workspace, workspace_bytes, query, out_scale, 0, 0, stream);
+    ConvRequest r = sized_request(dtype, n_img, h, wdt, ci, co, w_img_stride, kernel_size, resample);
+    r.x_split = x_split; r.y_split = y_split;
+    r.has_out_scale = (flags & P3D_CONV_HAS_OUT_SCALE) != 0; r.has_in_scale = (flags & P3D_CONV_HAS_IN_SCALE) != 0; r.y_aligned = (flags & P3D_CONV_Y_ALIGNED) != 0;
+    r.have_ws = (flags & P3D_CONV_HAS_WORKSPACE) != 0;
+    if (!r.have_ws) r.ws_usable_bytes = 0;
+    if (scratch_bytes) *scratch_bytes = 0;
+    ConvPlan plan;
+    const int rc = plan_conv(r, &plan);
+    if (rc != P3D_OK) return rc;
+    if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
+    return plan.route;
 }
 
-// x_split / y_split (dtype P3D_F32_BF16X3 only): the activations are / the result is to be in the bf16x3 K-row layout — per pixel and 32 channels
-// [32 x bf16 hi | 32 x bf16 lo] in the 128 bytes of 32 floats.  Every route takes x_split; y_split needs the halo-slab 3x3 kernel (anything else:
-// P3D_ERR_UNSUPPORTED before a launch, the caller asks again for a plain result).
-int p3d::conv2d_nhwc_run_io(const void* x, const void* w, void* y, int dtype, const float* bias, const float* noise, const float* noise_strength,
-                            const void* zeros128, int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int64_t w_img_stride,
-                            int32_t kernel_size, int32_t resample, int32_t act, float gain, float clamp, int32_t out_h, int32_t out_w,
-                            void* workspace, int64_t workspace_bytes, int64_t* query, const float* out_scale, int32_t x_split, int32_t y_split,
-                            p3d_stream_t stream)
+int p3d::launch_conv_plan(const ConvRequest& r, const ConvPlan& p)
 {
-    P3D_REQUIRE(!(x_split || y_split) || dtype == P3D_F32_BF16X3, "conv2d_nhwc: pre-split activations are a bf16x3 format");
-    P3D_REQUIRE(!y_split || co % 32 == 0, "conv2d_nhwc: a split result needs whole 32-channel rows");
-    // query != null: dry run — *query = bytes of split-K scratch this call would like (0: none); nothing is launched
-    const bool dry = query != nullptr;
-    if (dry) { *query = 0; x = w = zeros128 = (const void*)(uintptr_t)16; y = (void*)(uintptr_t)16; }
-    const bool transposed_stride2 = (resample == 1), down2 = (resample == 2);
-    P3D_REQUIRE(resample >= 0 && resample <= 2, "conv2d_nhwc: resample must be 0 (same), 1 (transposed x2) or 2 (valid, stride 2)");
-    P3D_REQUIRE(x && w && y && zeros128, "conv2d_nhwc: null pointer");
-    P3D_REQUIRE(n_img >= 1 && h >= 1 && wdt >= 1 && co >= 1, "conv2d_nhwc: bad sizes");
-    P3D_REQUIRE(dtype == P3D_F16 || dtype == P3D_F32 || dtype == P3D_F32_BF16X3 || dtype == P3D_F32_BF16X6, "conv2d_nhwc: dtype must be fp16, fp32, fp32-as-bf16x3 or fp32-as-bf16x6");
-    P3D_REQUIRE(kernel_size == 3 || (kernel_size == 1 && !transposed_stride2), "conv2d_nhwc: kernel 3x3, or 1x1 without upsampling");
-    P3D_REQUIRE(!out_scale || dtype != P3D_F16, "conv2d_nhwc: the per-image output scale is implemented for fp32 tensors");
-    static const bool no_h2t = getenv("P3D_CONV_NO_H2") != nullptr;
-    const bool h2t = !no_h2t && resample == 1 && dtype == P3D_F16 && h >= 32 && wdt >= 32 && ci % 32 == 0 && co % BN == 0 && (((uintptr_t)y) & 15u) == 0;   // convT_h2_f16_kernel: 64-byte K rows
-    const int bk = dtype == P3D_F16 ? 64 : 32;
-    if (ci % bk != 0 && !h2t) return fail(P3D_ERR_UNSUPPORTED, "conv2d_nhwc: Ci=%d must be a multiple of %d", ci, bk);
-    P3D_REQUIRE((((uintptr_t)x) & 15u) == 0 && (((uintptr_t)w) & 15u) == 0 && (((uintptr_t)zeros128) & 15u) == 0, "conv2d_nhwc: x, w and zeros128 must be 16-byte aligned");
+    P3D_REQUIRE(r.x && r.w && r.y && r.zeros128, "conv2d_nhwc: null pointer");
+    P3D_REQUIRE((((uintptr_t)r.x) & 15u) == 0 && (((uintptr_t)r.w) & 15u) == 0 && (((uintptr_t)r.zeros128) & 15u) == 0, "conv2d_nhwc: x, w and zeros128 must be 16-byte aligned");
+    P3D_REQUIRE(r.resample != 1 || (!r.noise && !r.bias && r.act == 0), "conv2d_nhwc: the transposed form has no epilogue (the FIR runs next)");
+    if (p.grid[0] <= 0) return P3D_OK;
     ConvArgs a{};
-    a.x = x; a.w = w; a.y = y; a.bias = bias; a.noise = noise; a.noise_strength = noise_strength; a.zeros = zeros128;
-    a.N = n_img; a.H = h; a.W = wdt; a.Ci = ci; a.Co = co; a.KT = kernel_size * kernel_size; a.w_img_stride = w_img_stride;
-    a.act = act; a.gain = gain; a.clamp = clamp; a.isy = a.isx = 1; a.oscale = out_scale;
-    a.iscale = tl_in_scale;                                          // (set by p3d_conv2d_nhwc_scaled_in for the duration of its call)
-    { static const bool narrow = [] { const char* d = getenv("P3D_CONV_STORE4"); return d && atoi(d) != 0; }(); a.store_narrow = narrow; }
-    hipStream_t s = (hipStream_t)stream;
-    if (down2) {                                                     // valid (unpadded) correlation at stride 2: conv2d_resample.py:108-111 after its FIR
-        P3D_REQUIRE(h >= kernel_size && wdt >= kernel_size, "conv2d_nhwc: image smaller than the kernel");
-        a.OH = (h - kernel_size) / 2 + 1; a.OW = (wdt - kernel_size) / 2 + 1; a.osy = a.osx = 1; a.isy = a.isx = 2; a.ncls = 1;
-        a.cls[0].SH = a.OH; a.cls[0].SW = a.OW; a.cls[0].ooy = a.cls[0].oox = 0; a.cls[0].ntaps = a.KT;
-        for (int t = 0; t < a.KT; ++t) a.cls[0].taps[t] = ConvTap{t / kernel_size, t % kernel_size, t};
-        if (y_split) return dry ? (int)P3D_ERR_UNSUPPORTED : fail(P3D_ERR_UNSUPPORTED, "conv2d_nhwc: a split result is produced by the 3x3 halo kernel only");
-        a.fold = fold_batch(a, dtype);
-        return launch_conv(a, dtype, s, workspace, workspace_bytes, query, x_split != 0);
+    conv_geometry(r, a);
+    a.x = r.x; a.w = r.w; a.y = r.y; a.bias = r.bias; a.noise = r.noise; a.noise_strength = r.noise_strength; a.zeros = r.zeros128;
+    a.oscale = r.out_scale; a.iscale = r.in_scale; a.store_narrow = conv_switches().store_narrow;
+    a.fold = p.fold; a.cls_major = p.cls_major; a.ksplit = p.ksplit; a.y_split = p.y_split;
+    a.partial = p.ksplit > 1 ? (float*)r.workspace : nullptr;
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]), block(256);
+    hipStream_t s = (hipStream_t)r.stream;
+    const char* what = "conv3x3_halo";
+    switch (p.route) {
+    case P3D_CONV_ROUTE_GENERIC:
+    case P3D_CONV_ROUTE_GENERIC_SPLITK:
+        return launch_generic(p, a, r.dtype, s);
+    case P3D_CONV_ROUTE_H2_F16:
+        what = "conv3x3_h2_f16";
+        hipLaunchKernelGGL(conv3x3_h2_f16_kernel<false>, grid, block, 0, s, a);
+        break;
+    case P3D_CONV_ROUTE_R2_BF16X3:
+        what = "conv3x3_r2_bf16x3";
+        hipLaunchKernelGGL(conv3x3_r2_bf16x3_kernel<false>, grid, block, 0, s, a, WideRgbTail{});
+        break;
+    case P3D_CONV_ROUTE_HALO:
+    case P3D_CONV_ROUTE_HALO_X6P:
+        switch (p.variant) {
+        case CV_F16:      hipLaunchKernelGGL(conv3x3_halo_kernel<__half>, grid, block, 0, s, a); break;
+        case CV_BF3_XS:   hipLaunchKernelGGL((conv3x3_halo_kernel<float, true, true>), grid, block, 0, s, a); break;
+        case CV_BF3:      hipLaunchKernelGGL((conv3x3_halo_kernel<float, true>), grid, block, 0, s, a); break;
+        case CV_X6P_CO64: hipLaunchKernelGGL(conv3x3_halo_x6p_kernel<true>, grid, block, 0, s, a); break;
+        case CV_X6P:      hipLaunchKernelGGL(conv3x3_halo_x6p_kernel<false>, grid, block, 0, s, a); break;
+        case CV_X6:       hipLaunchKernelGGL((conv3x3_halo_kernel<float, false, false, true>), grid, block, 0, s, a); break;
+        default:          hipLaunchKernelGGL(conv3x3_halo_kernel<float>, grid, block, 0, s, a); break;
+        }
+        break;
+    case P3D_CONV_ROUTE_CONVT_H2_F16:
+        what = "convT_h2_f16";
+        hipLaunchKernelGGL(convT_h2_f16_kernel, grid, block, 0, s, a);
+        break;
+    default: return fail(P3D_ERR_ARGUMENT, "conv2d_nhwc: unknown route %d", p.route);
     }
-    if (!transposed_stride2) {                                       // correlation, "same" padding: input offset = tap - k/2
-        a.OH = h; a.OW = wdt; a.osy = a.osx = 1; a.ncls = 1;
-        a.cls[0].SH = h; a.cls[0].SW = wdt; a.cls[0].ooy = a.cls[0].oox = 0; a.cls[0].ntaps = a.KT;
-        for (int t = 0; t < a.KT; ++t) a.cls[0].taps[t] = ConvTap{t / kernel_size - kernel_size / 2, t % kernel_size - kernel_size / 2, t};
-        static const bool no_halo = getenv("P3D_CONV_NO_HALO") != nullptr;
-        static const bool no_h2 = getenv("P3D_CONV_NO_H2") != nullptr;
-        // the halo kernels have no split-K: they take the layers whose own grid fills the chip (or every layer when the caller brought
-        // no scratch); a 512-channel layer at 16^2 / 32^2 is 32 / 128 work-groups with a 144-step K loop — that goes to the generic
-        // kernel with its K steps dealt out
-        const bool h2_ok = !no_h2 && !no_halo && kernel_size == 3 && dtype == P3D_F16 && h >= 32 && wdt >= 32 && ci % 64 == 0 && co % BN == 0 && (((uintptr_t)y) & 15u) == 0;
-        const bool halo_ok = kernel_size == 3 && h >= PH && wdt >= PW && !no_halo && !out_scale && !a.iscale;      // (the per-image scales live in the generic kernel)
-        const int64_t own_blocks = h2_ok ? (int64_t)((h + QH - 1) / QH) * ((wdt + QW - 1) / QW) * (co / BN) * n_img
-                                         : (int64_t)((h + PH - 1) / PH) * ((wdt + PW - 1) / PW) * ((co + BN - 1) / BN) * n_img;
-        const bool have_ws = dry || (workspace != nullptr && workspace_bytes > 0);
-        const bool prefer_split = have_ws && (h2_ok || halo_ok) && own_blocks < 192 && ci / bk * a.KT >= 16;
-        if (h2_ok && !prefer_split) {
-            if (dry) return P3D_OK;
-            dim3 grid(((h + QH - 1) / QH) * ((wdt + QW - 1) / QW), co / BN, n_img);
-            hipLaunchKernelGGL(conv3x3_h2_f16_kernel<false>, grid, dim3(256), 0, s, a);
-            count_launch(FAM_CONV);
-            return check_launch("conv3x3_h2_f16");
-        }
-        static const bool no_r2 = getenv("P3D_CONV_NO_R2") != nullptr;
-        const bool r2_ok = !no_r2 && !no_halo && kernel_size == 3 && dtype == P3D_F32_BF16X3 && x_split && h >= 32 && wdt >= 32 && ci % 32 == 0 && co % BN == 0 && !out_scale;
-        if (r2_ok && (int64_t)((h + QH - 1) / QH) * ((wdt + QW - 1) / QW) * (co / BN) * n_img >= 192) {      // (smaller grids: the 8 x 16 halo kernel, then split-K)
-            if (dry) return P3D_OK;                                       // split activations in: the ring pipeline on 16-channel half rows
-            static const bool store2 = [] { const char* d = getenv("P3D_R2_STORE2"); return d && atoi(d) != 0; }();      // (A/B only: the 2-byte stores of the lane = channel layout)
-            a.y_split = (y_split && store2) ? 2 : y_split;
-            dim3 grid(((h + QH - 1) / QH) * ((wdt + QW - 1) / QW), co / BN, n_img);
-            hipLaunchKernelGGL(conv3x3_r2_bf16x3_kernel<false>, grid, dim3(256), 0, s, a, WideRgbTail{});
-            count_launch(FAM_CONV);
-            return check_launch("conv3x3_r2_bf16x3");
-        }
-        if (halo_ok && !prefer_split) {                                   // halo-reuse kernel for the plain 3x3 layers
-            if (dry) return P3D_OK;
-            dim3 grid(((h + PH - 1) / PH) * ((wdt + PW - 1) / PW), (co + BN - 1) / BN, n_img);
-            a.y_split = y_split;
-            // bf16x6: operands split once per work-group (conv3x3_halo_x6p_kernel) where the grid gives every CU its two work-groups — one alone has nobody to hide its
-            // per-tap rendezvous behind (512 -> 512 at 32^2 x 4, 128 work-groups: 0.149 ms against 0.135 for the in-register kernel, profiles/round6_m_*).  P3D_X6_PRESPLIT=0: never
-            // (2: always — read at every call, so that one test process can put small geometries through either kernel)
-            const char* const x6p_env = dtype == P3D_F32_BF16X6 ? getenv("P3D_X6_PRESPLIT") : nullptr;
-            const int x6p_mode = x6p_env ? atoi(x6p_env) : 1;
-            const bool x6p = x6p_mode == 2 || (x6p_mode == 1 && own_blocks >= 256);
-            if (dtype == P3D_F16)             hipLaunchKernelGGL(conv3x3_halo_kernel<__half>, grid, dim3(256), 0, s, a);
-            else if (dtype == P3D_F32_BF16X3 && x_split) hipLaunchKernelGGL((conv3x3_halo_kernel<float, true, true>), grid, dim3(256), 0, s, a);
-            else if (dtype == P3D_F32_BF16X3) hipLaunchKernelGGL((conv3x3_halo_kernel<float, true>), grid, dim3(256), 0, s, a);
-            else if (dtype == P3D_F32_BF16X6 && x6p && ci % 32 == 0 && co <= 64) hipLaunchKernelGGL(conv3x3_halo_x6p_kernel<true>, grid, dim3(256), 0, s, a);
-            else if (dtype == P3D_F32_BF16X6 && x6p && ci % 32 == 0) hipLaunchKernelGGL(conv3x3_halo_x6p_kernel<false>, grid, dim3(256), 0, s, a);
-            else if (dtype == P3D_F32_BF16X6) hipLaunchKernelGGL((conv3x3_halo_kernel<float, false, false, true>), grid, dim3(256), 0, s, a);
-            else                              hipLaunchKernelGGL(conv3x3_halo_kernel<float>, grid, dim3(256), 0, s, a);
-            count_launch(FAM_CONV);
-            return check_launch("conv3x3_halo");
-        }
-        if (y_split) return dry ? (int)P3D_ERR_UNSUPPORTED : fail(P3D_ERR_UNSUPPORTED, "conv2d_nhwc: a split result is produced by the 3x3 halo kernel only");
-        a.fold = fold_batch(a, dtype);
-        return launch_conv(a, dtype, s, workspace, workspace_bytes, query, x_split != 0);
-    }
-    // conv_transpose2d(stride 2, no padding): out[(2i+py), (2j+px)] = sum_{ky = py (mod 2), kx = px (mod 2)} x[i - (ky-py)/2, j - (kx-px)/2] w[ky, kx]
-    // -> four dense sub-problems (4 / 2 / 2 / 1 taps), all in ONE launch so the grid fills the chip
-    P3D_REQUIRE(!noise && !bias && act == 0, "conv2d_nhwc: the transposed form has no epilogue (the FIR runs next)");
-    a.OH = out_h > 0 ? out_h : 2 * h + 1; a.OW = out_w > 0 ? out_w : 2 * wdt + 1; a.osy = a.osx = 2; a.ncls = 4;
-    P3D_REQUIRE(a.OH >= 2 * h + 1 && a.OH <= 2 * h + 2 && a.OW >= 2 * wdt + 1 && a.OW <= 2 * wdt + 2, "conv2d_nhwc: transposed output must be 2h+1 or 2h+2");
-    for (int py = 0; py < 2; ++py)
-        for (int px = 0; px < 2; ++px) {
-            ConvArgs::Cls& c = a.cls[py * 2 + px];
-            c.ooy = py; c.oox = px;
-            c.SH = (a.OH - py + 1) / 2; c.SW = (a.OW - px + 1) / 2;                // output rows py, py + 2, ... < OH
-            c.ntaps = 0;
-            for (int ky = py; ky < 3; ky += 2)
-                for (int kx = px; kx < 3; kx += 2)
-                    c.taps[c.ntaps++] = ConvTap{-(ky - py) / 2, -(kx - px) / 2, ky * 3 + kx};
-        }
-    {
-        if (h2t) {
-            if (dry) return P3D_OK;
-            const int tiles = ((h + 1 + QH - 1) / QH) * ((wdt + 1 + QW - 1) / QW);          // class (0, 0) is the largest: (H + 1) x (W + 1) positions
-            hipLaunchKernelGGL(convT_h2_f16_kernel, dim3(tiles, co / BN, n_img * 4), dim3(256), 0, s, a);
-            count_launch(FAM_CONV);
-            return check_launch("convT_h2_f16");
-        }
-    }
-    if (y_split) return dry ? (int)P3D_ERR_UNSUPPORTED : fail(P3D_ERR_UNSUPPORTED, "conv2d_nhwc: a split result is produced by the 3x3 halo kernel only");
-    return launch_conv(a, dtype, s, workspace, workspace_bytes, query, x_split != 0);
+    count_launch(FAM_CONV);
+    return check_launch(what);
 }
 
 extern "C" int p3d_torgb_nhwc_f16(const void* x, const float* weight, const float* styles, const float* bias, float* y_nchw,

@@ -825,79 +825,91 @@ static int relayout(const void* w, void* dst, int dtype, int A, int B, int taps,
 
 static bool mfma_channels_ok(int dtype, int ci) { return ci % (dtype == P3D_F16 ? 64 : 32) == 0; }      // (P3D_F32_BF16X3: fp32 tensors, 32)
 
-static int conv_forward_impl(const void* x, const void* weight, void* y, void* w_scratch, const void* zeros128, int dtype,
-                             int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int32_t kernel_size, int32_t stride,
-                             int32_t transposed, int32_t out_h, int32_t out_w, void* workspace, int64_t workspace_bytes, int64_t* query, p3d_stream_t stream)
+// What p3d_conv2d_forward / _bwd_data run for these sizes.  *skinny: the 1x1 VALU kernels below take the call (no weight relayout, no request);
+// otherwise *r is the channels-last request over the relaid weights — operands not filled in.
+static int forward_request(int dtype, int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int32_t kernel_size, int32_t stride, int32_t transposed,
+                           int32_t out_h, int32_t out_w, bool have_scratch, bool* skinny, ConvRequest* r)
 {
-    const bool dry = query != nullptr;
-    if (dry) { *query = 0; x = weight = zeros128 = (const void*)(uintptr_t)16; y = w_scratch = (void*)(uintptr_t)16; }
-    P3D_REQUIRE(x && weight && y, "conv2d_forward: null pointer");
     P3D_REQUIRE(dtype == P3D_F16 || dtype == P3D_F32 || dtype == P3D_F32_BF16X3 || dtype == P3D_F32_BF16X6, "conv2d_forward: dtype must be fp16, fp32, fp32-as-bf16x3 or fp32-as-bf16x6");
     P3D_REQUIRE(n_img >= 1 && h >= 1 && wdt >= 1 && ci >= 1 && co >= 1, "conv2d_forward: bad sizes");
     P3D_REQUIRE((kernel_size == 3 && (stride == 1 || stride == 2)) || (kernel_size == 1 && stride == 1), "conv2d_forward: 3x3 at stride 1 / 2 or 1x1 at stride 1");
-    hipStream_t s = (hipStream_t)stream;
-    const int taps = kernel_size * kernel_size;
-    if (kernel_size == 1 && (!mfma_channels_ok(dtype, ci) || co < 32)) {
-        if (dtype == P3D_F32_BF16X3 || dtype == P3D_F32_BF16X6) dtype = P3D_F32;      // the skinny kernels are plain fp32 VALU
-        // skinny 1x1 (either direction: a transposed 1x1 is the same product with the weight read transposed), channels-last
-        if (dry) return P3D_OK;
-        const int64_t npix = (int64_t)n_img * h * wdt;
-        const int64_t w_so = transposed ? 1 : ci, w_si = transposed ? co : 1;   // conv2d: w[o][i]; conv_transpose2d: w[i][o]
-        const int epc = dtype == P3D_F16 ? 8 : 4;
-        P3D_REQUIRE((int64_t)ci * ((co + 7) & ~7) * 4 <= 64 * 1024, "conv2d_forward: skinny 1x1 weights must fit 64 KB of LDS");
-        if (co <= ci && ci % epc == 0 && (((uintptr_t)x) & 15u) == 0) {                            // many -> few
-            int lpp = 1;
-            while (lpp < 64 && lpp * 2 <= ci / epc) lpp *= 2;
-            const int ppw = 64 / lpp;
-            int64_t blocks = (npix + 4 * ppw - 1) / (4 * ppw);
-            if (blocks > 8 * kNumCU) blocks = 8 * kNumCU;
-            const size_t lds = (size_t)ci * co * 4;
-            if (dtype == P3D_F16) hipLaunchKernelGGL(skinny_contract_kernel<__half>, dim3((int)blocks), dim3(256), lds, s, (const __half*)x, (const __half*)weight, (__half*)y, npix, ci, co, w_so, w_si, lpp);
-            else                  hipLaunchKernelGGL(skinny_contract_kernel<float>, dim3((int)blocks), dim3(256), lds, s, (const float*)x, (const float*)weight, (float*)y, npix, ci, co, w_so, w_si, lpp);
-            count_launch(FAM_CONV);
-            return check_launch("skinny_contract");
-        }
-        const int64_t total = npix * ((co + 7) / 8);
-        int64_t blocks = (total + 255) / 256;
-        if (blocks > 16 * kNumCU) blocks = 16 * kNumCU;
-        const size_t lds = (size_t)ci * ((co + 7) & ~7) * 4;
-        if (dtype == P3D_F16) hipLaunchKernelGGL(skinny_expand_kernel<__half>, dim3((int)blocks), dim3(256), lds, s, (const __half*)x, (const __half*)weight, (__half*)y, npix, ci, co, w_so, w_si);
-        else                  hipLaunchKernelGGL(skinny_expand_kernel<float>, dim3((int)blocks), dim3(256), lds, s, (const float*)x, (const float*)weight, (float*)y, npix, ci, co, w_so, w_si);
-        count_launch(FAM_CONV);
-        return check_launch("skinny_expand");
-    }
-    P3D_REQUIRE(w_scratch && zeros128, "conv2d_forward: the MFMA route needs w_scratch (Co*Ci*k*k elements) and zeros128");
+    *skinny = kernel_size == 1 && (!mfma_channels_ok(dtype, ci) || co < 32);
+    if (*skinny) return P3D_OK;
+    P3D_REQUIRE(have_scratch, "conv2d_forward: the MFMA route needs w_scratch (Co*Ci*k*k elements) and zeros128");
     if (!mfma_channels_ok(dtype, ci) && !(dtype == P3D_F16 && transposed && stride == 2 && ci % 32 == 0 && co % 128 == 0 && h >= 32 && wdt >= 32))
         return fail(P3D_ERR_UNSUPPORTED, "conv2d_forward: Ci=%d must be a multiple of %d (pad the channels)", ci, dtype == P3D_F16 ? 64 : 32);
-    int rc;
-    if (!transposed) {
-        rc = dry ? P3D_OK : relayout(weight, w_scratch, dtype, co, ci, taps, 0, 0, s);           // wm[o][t][i] = w[o][i][t]
-        if (rc != P3D_OK) return rc;
-        return conv2d_nhwc_run(x, w_scratch, y, dtype, nullptr, nullptr, nullptr, zeros128, n_img, h, wdt, ci, co, 0, kernel_size, stride == 2 ? 2 : 0, 0, 1.f, -1.f, 0, 0, workspace, workspace_bytes, query, nullptr, stream);
+    r->dtype = dtype; r->n_img = n_img; r->h = h; r->wdt = wdt; r->ci = ci; r->co = co; r->kernel_size = kernel_size;
+    if (!transposed) r->resample = stride == 2 ? 2 : 0;
+    else if (stride == 1) r->resample = 0;                                                        // = correlation with mirrored taps and swapped channel axes
+    else { r->resample = 1; r->out_h = out_h; r->out_w = out_w; }
+    return P3D_OK;
+}
+
+// skinny 1x1 (either direction: a transposed 1x1 is the same product with the weight read transposed), channels-last
+static int launch_skinny_1x1(const void* x, const void* weight, void* y, int dtype, int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int32_t transposed, hipStream_t s)
+{
+    if (dtype == P3D_F32_BF16X3 || dtype == P3D_F32_BF16X6) dtype = P3D_F32;      // the skinny kernels are plain fp32 VALU
+    const int64_t npix = (int64_t)n_img * h * wdt;
+    const int64_t w_so = transposed ? 1 : ci, w_si = transposed ? co : 1;   // conv2d: w[o][i]; conv_transpose2d: w[i][o]
+    const int epc = dtype == P3D_F16 ? 8 : 4;
+    P3D_REQUIRE((int64_t)ci * ((co + 7) & ~7) * 4 <= 64 * 1024, "conv2d_forward: skinny 1x1 weights must fit 64 KB of LDS");
+    if (co <= ci && ci % epc == 0 && (((uintptr_t)x) & 15u) == 0) {                            // many -> few
+        int lpp = 1;
+        while (lpp < 64 && lpp * 2 <= ci / epc) lpp *= 2;
+        const int ppw = 64 / lpp;
+        int64_t blocks = (npix + 4 * ppw - 1) / (4 * ppw);
+        if (blocks > 8 * kNumCU) blocks = 8 * kNumCU;
+        const size_t lds = (size_t)ci * co * 4;
+        if (dtype == P3D_F16) hipLaunchKernelGGL(skinny_contract_kernel<__half>, dim3((int)blocks), dim3(256), lds, s, (const __half*)x, (const __half*)weight, (__half*)y, npix, ci, co, w_so, w_si, lpp);
+        else                  hipLaunchKernelGGL(skinny_contract_kernel<float>, dim3((int)blocks), dim3(256), lds, s, (const float*)x, (const float*)weight, (float*)y, npix, ci, co, w_so, w_si, lpp);
+        count_launch(FAM_CONV);
+        return check_launch("skinny_contract");
     }
-    if (stride == 1) {                                                                            // = correlation with mirrored taps and swapped channel axes
-        rc = dry ? P3D_OK : relayout(weight, w_scratch, dtype, ci, co, taps, 1, 1, s);           // wm[o][t][i] = w[i][o][taps-1-t]
-        if (rc != P3D_OK) return rc;
-        return conv2d_nhwc_run(x, w_scratch, y, dtype, nullptr, nullptr, nullptr, zeros128, n_img, h, wdt, ci, co, 0, kernel_size, 0, 0, 1.f, -1.f, 0, 0, workspace, workspace_bytes, query, nullptr, stream);
-    }
-    rc = dry ? P3D_OK : relayout(weight, w_scratch, dtype, ci, co, taps, 1, 0, s);               // wm[o][t][i] = w[i][o][t]
+    const int64_t total = npix * ((co + 7) / 8);
+    int64_t blocks = (total + 255) / 256;
+    if (blocks > 16 * kNumCU) blocks = 16 * kNumCU;
+    const size_t lds = (size_t)ci * ((co + 7) & ~7) * 4;
+    if (dtype == P3D_F16) hipLaunchKernelGGL(skinny_expand_kernel<__half>, dim3((int)blocks), dim3(256), lds, s, (const __half*)x, (const __half*)weight, (__half*)y, npix, ci, co, w_so, w_si);
+    else                  hipLaunchKernelGGL(skinny_expand_kernel<float>, dim3((int)blocks), dim3(256), lds, s, (const float*)x, (const float*)weight, (float*)y, npix, ci, co, w_so, w_si);
+    count_launch(FAM_CONV);
+    return check_launch("skinny_expand");
+}
+
+static int conv_forward_impl(const void* x, const void* weight, void* y, void* w_scratch, const void* zeros128, int dtype,
+                             int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int32_t kernel_size, int32_t stride,
+                             int32_t transposed, int32_t out_h, int32_t out_w, void* workspace, int64_t workspace_bytes, p3d_stream_t stream)
+{
+    P3D_REQUIRE(x && weight && y, "conv2d_forward: null pointer");
+    ConvRequest r;
+    bool skinny = false;
+    int rc = forward_request(dtype, n_img, h, wdt, ci, co, kernel_size, stride, transposed, out_h, out_w, w_scratch && zeros128, &skinny, &r);
     if (rc != P3D_OK) return rc;
-    return conv2d_nhwc_run(x, w_scratch, y, dtype, nullptr, nullptr, nullptr, zeros128, n_img, h, wdt, ci, co, 0, kernel_size, 1, 0, 1.f, -1.f, out_h, out_w, workspace, workspace_bytes, query, nullptr, stream);
+    if (skinny) return launch_skinny_1x1(x, weight, y, dtype, n_img, h, wdt, ci, co, transposed, (hipStream_t)stream);
+    r.x = x; r.w = w_scratch; r.y = y; r.zeros128 = zeros128; r.workspace = workspace; r.workspace_bytes = workspace_bytes; r.stream = stream;
+    r.note_operands();
+    ConvPlan plan;
+    if ((rc = plan_conv(r, &plan)) != P3D_OK) return rc;
+    // the weights in the kernels' [o][tap][i] order: wm[o][t][i] = w[o][i][t]; transposed: = w[i][o][t], with mirrored taps (taps-1-t) at stride 1
+    rc = relayout(weight, w_scratch, dtype, transposed ? ci : co, transposed ? co : ci, kernel_size * kernel_size, transposed ? 1 : 0, transposed && stride == 1, (hipStream_t)stream);
+    return rc != P3D_OK ? rc : launch_conv_plan(r, plan);
 }
 
 extern "C" int p3d_conv2d_forward(const void* x, const void* weight, void* y, void* w_scratch, const void* zeros128, int dtype,
                                   int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int32_t kernel_size, int32_t stride,
                                   int32_t transposed, int32_t out_h, int32_t out_w, void* workspace, int64_t workspace_bytes, p3d_stream_t stream)
 {
-    return conv_forward_impl(x, weight, y, w_scratch, zeros128, dtype, n_img, h, wdt, ci, co, kernel_size, stride, transposed, out_h, out_w, workspace, workspace_bytes, nullptr, stream);
+    return conv_forward_impl(x, weight, y, w_scratch, zeros128, dtype, n_img, h, wdt, ci, co, kernel_size, stride, transposed, out_h, out_w, workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t p3d_conv2d_forward_workspace(int dtype, int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int32_t kernel_size, int32_t stride,
                                                 int32_t transposed)
 {
-    int64_t bytes = 0;
-    const int rc = conv_forward_impl(nullptr, nullptr, nullptr, nullptr, nullptr, dtype, n_img, h, wdt, ci, co, kernel_size, stride, transposed, 0, 0, nullptr, 0, &bytes, nullptr);
-    return rc == P3D_OK ? bytes : 0;
+    ConvRequest r;
+    ConvPlan plan;
+    bool skinny = false;
+    if (forward_request(dtype, n_img, h, wdt, ci, co, kernel_size, stride, transposed, 0, 0, true, &skinny, &r) != P3D_OK || skinny) return 0;
+    r.assume_plain_operands();
+    return plan_conv(r, &plan) == P3D_OK ? plan.scratch_bytes : 0;
 }
 
 extern "C" int p3d_conv2d_bwd_data(const void* gy, const void* weight, void* gx, void* w_scratch, const void* zeros128, int dtype,
@@ -906,7 +918,7 @@ extern "C" int p3d_conv2d_bwd_data(const void* gy, const void* weight, void* gx,
 {
     // d(input) of op(transposed) is op(!transposed) over the same weight tensor with input / output channels trading places
     // (conv2d_gradfix.py:139-143); x_h / x_w fix the output_padding when that op is the transposed one
-    return conv_forward_impl(gy, weight, gx, w_scratch, zeros128, dtype, n_img, gy_h, gy_w, co, ci, kernel_size, stride, !transposed, x_h, x_w, workspace, workspace_bytes, nullptr, stream);
+    return conv_forward_impl(gy, weight, gx, w_scratch, zeros128, dtype, n_img, gy_h, gy_w, co, ci, kernel_size, stride, !transposed, x_h, x_w, workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t p3d_conv2d_bwd_weight_workspace(int dtype, int32_t n_img, int32_t small_h, int32_t small_w, int32_t c_small, int32_t c_big, int32_t kernel_size)
