@@ -445,6 +445,42 @@ int p3d_mesh_cluster_means(const float* vertices, int32_t n_vertices, const int3
 int p3d_mesh_cluster_faces(const int32_t* faces, int32_t n_faces, int32_t n_vertices, const int32_t* cluster, int32_t* mapped,
                            int32_t* sorted, uint8_t* degenerate, p3d_stream_t stream);
 
+/* ---- mesh filtering: smoothing, label voting and smooth shading over vertex adjacency (csrc/mesh_filter.hip; pix2pix3d_amd/mesh.py) ----
+ * The caller builds the adjacency of the indexed mesh with sorts (mesh.adjacency): offsets int64 [V + 1] (offsets[0] = 0,
+ * offsets[V] = E) and neighbours int32 [E], the list of v being neighbours[offsets[v] .. offsets[v + 1]): the distinct vertices w != v
+ * that share a face with v, in ascending id.  V <= INT32_MAX - 1 (P3D_ERR_UNSUPPORTED beyond).  The kernels clamp a list to [0, E) and
+ * skip an entry outside [0, V); the DEGREE of v is the number of entries that are left.  pinned uint8 [V] or NULL: a vertex with a
+ * non-zero byte keeps its value.  The CPU formulation of mesh.py is the definition; the kernels' bytes equal it.
+ * p3d_mesh_smooth_step: one Jacobi step of Laplacian smoothing on x float32 [V][C], 1 <= C <= 256, into out float32 [V][C], which must
+ *   not overlap x (P3D_ERR_ARGUMENT).  A pinned vertex and a vertex of degree 0 copy their row bit for bit.  For every other vertex
+ *   and every channel c, in fp64 with no contraction:
+ *     acc = 0;  for w in list order: acc = acc + x[w][c];
+ *     m = acc / degree;  d = m - x[v][c];  p = factor * d;  y = x[v][c] + p;  out[v][c] = (float)y.
+ *   One thread per (vertex, channel) with the channel fastest, so that a wave reads a neighbour's row as one contiguous run; the sum
+ *   runs in list order in one thread, so the output is a pure function of the inputs.  Taubin smoothing is a step with factor
+ *   lambda > 0 followed by one with factor mu < -lambda, the caller alternating two buffers.
+ * p3d_mesh_label_vote: one synchronous majority step on labels uint8 [V] into out uint8 [V] (no overlap), 1 <= n_labels <= 256 and
+ *   every label < n_labels (the caller checks).  count[l] = the number of listed neighbours with label l, plus one if v itself has l.
+ *   v keeps its label when count[its label] equals the maximum count, else it takes the smallest label that reaches the maximum.
+ *   Pinned and degree-0 vertices keep theirs.  All integer: the result does not depend on any order.  One thread per vertex counts
+ *   in a private column of an LDS table while its list holds at most P3D_MESH_VOTE_THREAD_DEGREE entries (three walks of the list, never
+ *   degree^2 work); the longer lists of a work-group are then taken one by one by the whole group with LDS atomics on a 256-entry
+ *   histogram.  One launch.
+ * p3d_mesh_shade_smooth: p3d_mesh_shade with interpolated vertex normals, normals float32 [V][3] (need not be unit).  Everything up
+ *   to the barycentrics b is p3d_mesh_shade's.  Then, per component in fp64, products rounded one by one and summed left to right in
+ *   the weight order of the triangle setup, n = b0 n_0 + b1 n_1 + b2 n_2, and the factor is
+ *   ambient + (1 - ambient) |n . f| / (|n| |f|) with p3d_mesh_shade's dot products and square roots, 0 for the fraction when the
+ *   denominator is not > 0.  Albedo, rounding and background are p3d_mesh_shade's.                                                    */
+#define P3D_MESH_VOTE_THREAD_DEGREE 64
+int p3d_mesh_smooth_step(const float* x, int32_t n_vertices, int32_t channels, const int64_t* offsets, const int32_t* neighbours,
+                         int64_t n_entries, const uint8_t* pinned, double factor, float* out, p3d_stream_t stream);
+int p3d_mesh_label_vote(const uint8_t* labels, int32_t n_vertices, int32_t n_labels, const int64_t* offsets, const int32_t* neighbours,
+                        int64_t n_entries, const uint8_t* pinned, uint8_t* out, p3d_stream_t stream);
+int p3d_mesh_shade_smooth(const int32_t* face_id, const int32_t* proj, const float* vertices, int32_t n_vertices, const int32_t* faces,
+                          int32_t n_faces, const float* normals, const uint8_t* colors, const float* cameras, int32_t n_frames,
+                          int32_t orthographic, int32_t width, int32_t height, float ambient, int32_t bg_r, int32_t bg_g, int32_t bg_b,
+                          uint8_t* rgb, p3d_stream_t stream);
+
 /* ---- mesh baking: vertex normals and per-vertex colours from rendered views (csrc/mesh_bake.hip; pix2pix3d_amd/texture.py) ---------
  * One thread per vertex; every sum runs in fp64 in a fixed order and every product and sum below is rounded on its own (no
  * contraction), so the outputs are pure functions of the inputs.  The CPU formulation of pix2pix3d_amd/texture.py, written operation

@@ -12,7 +12,11 @@
 * ``components`` / ``clean`` / ``simplify``: what a trimesh user does between extraction and export (``mesh.split()``, keep the
   largest part, decimate), on the bare geometry: connected components by union-find, a keep-the-largest filter, vertex-clustering
   decimation (csrc/mesh_ops.hip on device tensors, a restatement on CPU tensors; the rules are include/p3d_hip.h's).
-* ``extract_mesh``: shape.extract_geometry, the optional clean-up, the labels and the turntable in one call.
+* ``adjacency`` / ``smooth`` / ``smooth_values`` / ``smooth_labels``: the filter stage a trimesh user runs next
+  (``trimesh.smoothing.filter_taubin``): neighbour lists and boundary flags from sorts, Taubin smoothing of positions or of any
+  per-vertex attribute, majority voting of labels, and smooth shading through ``shade(..., normals=)`` (csrc/mesh_filter.hip on device
+  tensors; the CPU formulation is the definition and the bytes are the same).
+* ``extract_mesh``: shape.extract_geometry, the optional clean-up and filters, the labels and the turntable in one call.
 """
 import ctypes
 import functools
@@ -23,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib, configs, shape
-from ._lib import _f32, _f64, _i32, _vp
+from ._lib import _c_i64 as _i64, _f32, _f64, _i32, _vp
 
 CAMERA_FLOATS = 24             # P3D_MESH_CAMERA_FLOATS
 GREY = 200                     # P3D_MESH_GREY: the albedo of a mesh without colours
@@ -43,6 +47,10 @@ _lib.register('p3d_mesh_components', ctypes.c_int, [_vp, _i32, _i32, _vp, _vp])
 _lib.register('p3d_mesh_cluster_keys', ctypes.c_int, [_vp, _i32, _f32, _f32, _f32, _f64, _i32, _i32, _i32, _vp, _vp])
 _lib.register('p3d_mesh_cluster_means', ctypes.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp])
 _lib.register('p3d_mesh_cluster_faces', ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp])
+_lib.register('p3d_mesh_smooth_step', ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _i64, _vp, _f64, _vp, _vp])         # (csrc/mesh_filter.hip)
+_lib.register('p3d_mesh_label_vote', ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp])
+_lib.register('p3d_mesh_shade_smooth', ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _i32,
+                                                  _i32, _vp, _vp])
 
 
 class Orthographic(NamedTuple):
@@ -302,9 +310,10 @@ def rasterize(proj, faces, resolution):
 
 
 # ---- shading ----------------------------------------------------------------------------------------------------------------
-def _shade_terms_cpu(f, face_id, proj, vertices, faces, cams, ambient):
+def _shade_terms_cpu(f, face_id, proj, vertices, faces, cams, ambient, normals=None):
     """What p3d_mesh_shade works out at every drawn pixel of frame f before the albedo: (pix, the flat pixel indices; t, their faces;
-    idx [N, 3], the vertex ids in weight order; b, the three barycentrics; the headlight factor)."""
+    idx [N, 3], the vertex ids in weight order; b, the three barycentrics; the headlight factor).  With ``normals`` float32 [V, 3] the
+    normal is p3d_mesh_shade_smooth's, the barycentric mix of the vertex normals, in place of the face's."""
     _, h, w = face_id.shape
     nf = faces.shape[0]
     verts = vertices.double()
@@ -327,11 +336,18 @@ def _shade_terms_cpu(f, face_id, proj, vertices, faces, cams, ambient):
         q = q0 + q1
         q = q + q2
         b = (q0 / q, q1 / q, q2 / q)
-    e1 = verts[idx[:, 1]] - verts[idx[:, 0]]
-    e2 = verts[idx[:, 2]] - verts[idx[:, 0]]
-    nx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
-    ny = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
-    nz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+    if normals is None:
+        e1 = verts[idx[:, 1]] - verts[idx[:, 0]]
+        e2 = verts[idx[:, 2]] - verts[idx[:, 0]]
+        nx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+        ny = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+        nz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+    else:
+        nrm = normals.double()
+        n = b[0][:, None] * nrm[idx[:, 0]]
+        n = n + b[1][:, None] * nrm[idx[:, 1]]
+        n = n + b[2][:, None] * nrm[idx[:, 2]]
+        nx, ny, nz = n.unbind(1)
     f0, f1, f2 = (float(cams[f, j].double()) for j in (2, 6, 10))
     nn = nx * nx
     nn = nn + ny * ny
@@ -352,14 +368,14 @@ def _shaded_bytes(albedo, shade_):
     return torch.floor(albedo * shade_ + 0.5).clamp(0, 255).to(torch.uint8)
 
 
-def _shade_cpu(face_id, proj, vertices, faces, cams, ambient, background, albedo):
+def _shade_cpu(face_id, proj, vertices, faces, cams, ambient, background, albedo, normals=None):
     """The CPU shade of every frame: ``albedo(t, idx, b)`` gives the float64 albedo [N, 3] (or [N, 1]) of the N drawn pixels from
-    ``_shade_terms_cpu``'s faces, vertex ids and barycentrics."""
+    ``_shade_terms_cpu``'s faces, vertex ids and barycentrics; ``normals`` as there."""
     n, h, w = face_id.shape
     out = torch.empty([n, h, w, 3], dtype=torch.uint8)
     out[:] = torch.tensor(background, dtype=torch.uint8)
     for f in range(n):
-        pix, t, idx, b, shade_ = _shade_terms_cpu(f, face_id, proj, vertices, faces, cams, ambient)
+        pix, t, idx, b, shade_ = _shade_terms_cpu(f, face_id, proj, vertices, faces, cams, ambient, normals)
         out[f].reshape(-1, 3)[pix] = _shaded_bytes(albedo(t, idx, b), shade_[:, None])
     return out
 
@@ -398,19 +414,32 @@ def _shade_operands(what, face_id, proj, vertices, faces, cam2world, background)
     return face_id, Projection(packed, proj.orthographic), vertices, faces32, cams.to(dev), tuple(int(v) & 255 for v in background)
 
 
-def shade(face_id, proj, vertices, faces, cam2world, colors=None, background=(255, 255, 255), ambient=0.3):
+def shade(face_id, proj, vertices, faces, cam2world, colors=None, background=(255, 255, 255), ambient=0.3, normals=None):
     """uint8 [F, H, W, 3] frames from the raster buffers: barycentric vertex colours (perspective-correct under a pinhole camera) times
     ambient + (1 - ambient) |n . f| (face normal, camera forward axis); colors uint8 [V, 3] or None for uniform grey; background where
-    face_id is -1.  cam2world as given to ``project``.  Every input is moved to face_id's device, which picks the path."""
+    face_id is -1.  cam2world as given to ``project``.  With ``normals`` float32 [V, 3] (``texture.vertex_normals``; need not be unit)
+    the shading is smooth: n is the barycentric mix of the three vertex normals (p3d_mesh_shade_smooth).  Every input is moved to
+    face_id's device, which picks the path."""
     face_id, proj, vertices, faces32, cams, bg = _shade_operands('shade', face_id, proj, vertices, faces, cam2world, background)
     if colors is not None:
         colors = torch.as_tensor(colors).detach().to(device=face_id.device, dtype=torch.uint8).contiguous()
         if tuple(colors.shape) != (vertices.shape[0], 3):
             raise ValueError(f'shade: colors must be uint8 [V, 3], got {tuple(colors.shape)}')
+    if normals is not None:
+        normals = torch.as_tensor(normals)
+        if normals.dtype != torch.float32 or tuple(normals.shape) != (vertices.shape[0], 3):
+            raise ValueError(f'shade: normals must be float32 [{vertices.shape[0]}, 3], got {normals.dtype} {tuple(normals.shape)}')
+        normals = normals.detach().to(face_id.device).contiguous()
     if not face_id.is_cuda:
-        return _shade_cpu(face_id, proj, vertices, faces32, cams, ambient, bg, _vertex_albedo(colors))
+        return _shade_cpu(face_id, proj, vertices, faces32, cams, ambient, bg, _vertex_albedo(colors), normals)
     n, h, w = face_id.shape
     rgb = torch.empty([n, h, w, 3], dtype=torch.uint8, device=face_id.device)
+    if normals is not None:
+        _lib.check(_lib.lib().p3d_mesh_shade_smooth(_lib.ptr(face_id), _lib.ptr(proj.packed), _lib.ptr(vertices), vertices.shape[0],
+                                                    _lib.ptr(faces32), faces32.shape[0], _lib.ptr(normals), _lib.ptr(colors), _lib.ptr(cams),
+                                                    n, int(proj.orthographic), w, h, float(ambient), *bg, _lib.ptr(rgb),
+                                                    _lib.stream_of(rgb)), 'mesh_shade_smooth')
+        return rgb
     _lib.check(_lib.lib().p3d_mesh_shade(_lib.ptr(face_id), _lib.ptr(proj.packed), _lib.ptr(vertices), vertices.shape[0],
                                          _lib.ptr(faces32), faces32.shape[0], _lib.ptr(colors), _lib.ptr(cams), n, int(proj.orthographic),
                                          w, h, float(ambient), *bg, _lib.ptr(rgb), _lib.stream_of(rgb)), 'mesh_shade')
@@ -470,14 +499,15 @@ def _render(what, vertices, faces, cam2world, camera, resolution, shade_stage, r
 
 @torch.no_grad()
 def render(vertices, faces, cam2world, camera, resolution=512, colors=None, background=(255, 255, 255), ambient=0.3, return_buffers=False,
-           max_bytes=1 << 30):
+           max_bytes=1 << 30, normals=None):
     """The role of pyrender.OffscreenRenderer.render for every pose of cam2world [F, 4, 4] (OpenCV convention): uint8 frames
     [F, H, W, 3] on the vertices' device.  ``camera`` is Orthographic(xmag, ymag) or Pinhole(intrinsics); faces int32 or int64 [T, 3];
-    colors uint8 [V, 3] or None (uniform grey).  With return_buffers=True also (face_id int32 [F, H, W], depth float32 [F, H, W]).
+    colors uint8 [V, 3] or None (uniform grey); normals float32 [V, 3] or None (flat shading), as for ``shade``.  With
+    return_buffers=True also (face_id int32 [F, H, W], depth float32 [F, H, W]).
     Frames go through project / rasterize / shade in groups whose projections take at most ``max_bytes``."""
     if colors is not None:
         colors = torch.as_tensor(colors).to(device=vertices.device, dtype=torch.uint8).contiguous()
-    stage = functools.partial(shade, colors=colors, background=background, ambient=ambient)
+    stage = functools.partial(shade, colors=colors, background=background, ambient=ambient, normals=normals)
     return _render('render', vertices, faces, cam2world, camera, resolution, stage, return_buffers, max_bytes)
 
 
@@ -717,6 +747,218 @@ def simplify(vertices, faces, cell):
     return means, mapped[keep].long()
 
 
+# ---- filtering: adjacency, Taubin smoothing, label voting -----------------------------------------------------------------------
+class Adjacency(NamedTuple):
+    """The vertex adjacency of an indexed mesh (``adjacency``): the list of v is neighbours[offsets[v]:offsets[v + 1]]."""
+    offsets: torch.Tensor          # int64 [V + 1]
+    neighbours: torch.Tensor       # int32 [E]
+    boundary: torch.Tensor         # bool [V]
+
+
+def adjacency(faces, n_vertices):
+    """``Adjacency`` of the mesh: the list of v holds the distinct vertices w != v that share a face with v, in ascending id;
+    boundary[v] says that v is an end of an undirected edge {a, b}, a != b, that exactly one face side uses (an edge three faces share
+    is not a boundary edge).  A face lists its three sides; a side a == b of a degenerate face is ignored, so that a face with a
+    repeated index adds no self entry and, using its one edge from both sides, no boundary flag of its own.  A pure function of
+    (faces, V): face order and corner order do not matter.  Sorts and uniques of int64 keys a * V + b in torch, the same on a device
+    and on the CPU: no kernel."""
+    faces = _mesh_faces('adjacency', faces, n_vertices)
+    nv, dev = int(n_vertices), faces.device
+    a = torch.cat([faces[:, 0], faces[:, 1], faces[:, 2]])                 # the three sides of every face
+    b = torch.cat([faces[:, 1], faces[:, 2], faces[:, 0]])
+    proper = a != b
+    a, b = a[proper], b[proper]
+    key = torch.unique(torch.cat([a * nv + b, b * nv + a]))                # sorted: by vertex, then by neighbour
+    source = torch.div(key, max(nv, 1), rounding_mode='floor')
+    offsets = torch.searchsorted(source, torch.arange(nv + 1, device=dev))
+    neighbours = (key - source * nv).to(torch.int32)
+    edge, uses = torch.unique(torch.minimum(a, b) * nv + torch.maximum(a, b), return_counts=True)
+    edge = edge[uses == 1]
+    low = torch.div(edge, max(nv, 1), rounding_mode='floor')
+    boundary = torch.zeros([nv], dtype=torch.bool, device=dev)
+    boundary[low] = True
+    boundary[edge - low * nv] = True
+    return Adjacency(offsets, neighbours, boundary)
+
+
+def _filter_adjacency(what, faces, n_vertices, given, device):
+    """The ``Adjacency`` a filter works on, on ``device``: ``given`` (checked for its shapes; the kernels skip what lies out of
+    range) or ``adjacency(faces, n_vertices)``."""
+    if given is None:
+        return adjacency(_mesh_faces(what, faces, n_vertices).to(device), n_vertices)
+    offsets, neighbours, boundary = given
+    if offsets.dtype != torch.int64 or tuple(offsets.shape) != (n_vertices + 1,) or neighbours.dtype != torch.int32 or neighbours.ndim != 1 \
+            or boundary.dtype != torch.bool or tuple(boundary.shape) != (n_vertices,):
+        raise ValueError(f'{what}: adjacency must be (int64 [{n_vertices + 1}], int32 [E], bool [{n_vertices}]) as mesh.adjacency returns it')
+    return Adjacency(offsets.to(device).contiguous(), neighbours.to(device).contiguous(), boundary.to(device))
+
+
+def _pinned(what, pinned, n_vertices, device, also=None):
+    """``pinned`` (bool [V] or None) ORed with ``also`` as the kernels' uint8 [V], or None when nothing is pinned by either."""
+    if pinned is not None:
+        pinned = torch.as_tensor(pinned)
+        if pinned.dtype != torch.bool or tuple(pinned.shape) != (n_vertices,):
+            raise ValueError(f'{what}: pinned must be bool [{n_vertices}], got {pinned.dtype} {tuple(pinned.shape)}')
+        pinned = pinned.to(device)
+        also = pinned if also is None else pinned | also
+    return None if also is None else also.to(torch.uint8).contiguous()
+
+
+def _iterations(what, iterations):
+    if isinstance(iterations, bool) or int(iterations) != iterations or iterations < 0:
+        raise ValueError(f'{what}: iterations must be a non-negative integer, got {iterations!r}')
+    return int(iterations)
+
+
+def _smooth_step_cpu(x, adj, pinned, factor):
+    """p3d_mesh_smooth_step's arithmetic exactly: per vertex the fp64 sum of its list in list order, one list position of every
+    vertex per pass (as ``_cluster_means_cpu``), then every rounding its own torch operation.  Once only a few long lists are left
+    (the hub of a fan), each is finished entry by entry in Python floats, which are the same fp64 additions in the same order."""
+    offsets, neighbours = adj.offsets, adj.neighbours.long()
+    counts = offsets[1:] - offsets[:-1]
+    x64 = x.double()
+    acc = torch.zeros_like(x64)
+    live = (counts > 0).nonzero()[:, 0]
+    j = 0
+    while len(live) > 16:
+        acc[live] += x64[neighbours[offsets[live] + j]]
+        j += 1
+        live = live[counts[live] > j]
+    for v in live.tolist():
+        total = acc[v].tolist()
+        for row in x64[neighbours[offsets[v] + j:offsets[v + 1]]].tolist():
+            total = [a + b for a, b in zip(total, row)]
+        acc[v] = torch.tensor(total, dtype=torch.float64)
+    m = acc / counts.clamp(min=1).double()[:, None]
+    d = m - x64
+    p = factor * d
+    y = x64 + p
+    moves = counts > 0
+    if pinned is not None:
+        moves &= pinned == 0
+    return torch.where(moves[:, None], y.float(), x)
+
+
+def _smooth_steps(x, adj, pinned, factors):
+    """One Jacobi step per entry of ``factors`` on x float32 [V, C], the input left as it is and two buffers taking turns (a step
+    must not write what it reads)."""
+    if not x.is_cuda:
+        for factor in factors:
+            x = _smooth_step_cpu(x, adj, pinned, float(factor))
+        return x
+    lib = _lib.lib()
+    spare = [torch.empty_like(x), torch.empty_like(x)] if len(factors) > 1 else [torch.empty_like(x)]
+    for k, factor in enumerate(factors):
+        out = spare[k % 2]
+        _lib.check(lib.p3d_mesh_smooth_step(_lib.ptr(x), x.shape[0], x.shape[1], _lib.ptr(adj.offsets), _lib.ptr(adj.neighbours),
+                                            adj.neighbours.shape[0], _lib.ptr(pinned), float(factor), _lib.ptr(out), _lib.stream_of(x)),
+                   'mesh_smooth_step')
+        x = out
+    return x
+
+
+def smooth(vertices, faces, iterations=10, lam=0.5, mu=-0.53, pin_boundary=True, pinned=None, adjacency=None):
+    """Taubin smoothing of the positions (the role of trimesh.smoothing.filter_taubin): float32 [V, 3].  Every iteration is a Jacobi
+    step x <- x + lam (mean of the neighbours - x) and then the same step with ``mu`` < -lam, which undoes the shrinkage of the
+    first; mu = 0 leaves the second step out (plain Laplacian smoothing, which shrinks).  Uniform weights over ``mesh.adjacency``.
+    ``pinned`` bool [V] vertices stay where they are, and with ``pin_boundary`` so do the boundary vertices: a mesh the box cut is
+    open, and a free rim shrinks.  The faces are untouched; ``adjacency`` spares building it again.  iterations = 0 returns the
+    input's bits.  Device vertices run p3d_mesh_smooth_step, one launch per step; CPU vertices the formulation, with the same bytes
+    (fp64 sums in list order, include/p3d_hip.h)."""
+    iterations = _iterations('smooth', iterations)
+    lam, mu = float(lam), float(mu)
+    if not 0.0 < lam <= 1.0:
+        raise ValueError(f'smooth: lam must be in (0, 1], got {lam}')
+    if not (mu == 0.0 or -math.inf < mu < -lam):
+        raise ValueError(f'smooth: mu must be 0 or below -lam = {-lam}, got {mu}')
+    vertices = _mesh_vertices('smooth', vertices)
+    nv, dev = vertices.shape[0], vertices.device
+    adj = _filter_adjacency('smooth', faces, nv, adjacency, dev)
+    pin = _pinned('smooth', pinned, nv, dev, adj.boundary if pin_boundary else None)
+    if iterations == 0 or nv == 0:
+        return vertices.clone()
+    return _smooth_steps(vertices, adj, pin, ([lam] if mu == 0.0 else [lam, mu]) * iterations)
+
+
+def smooth_values(values, faces, iterations=1, factor=0.5, pinned=None, adjacency=None):
+    """Laplacian smoothing of a per-vertex attribute [V, C], 1 <= C <= 256: ``iterations`` steps x <- x + factor (mean of the
+    neighbours - x).  float32 values come back as float32; uint8 colours are smoothed as float32 and come back as
+    floor(x + 0.5) clamped to uint8.  ``pinned`` and ``adjacency`` as for ``smooth``; nothing is pinned unless asked."""
+    iterations = _iterations('smooth_values', iterations)
+    factor = float(factor)
+    if not math.isfinite(factor):
+        raise ValueError(f'smooth_values: factor must be finite, got {factor}')
+    values = torch.as_tensor(values).detach()
+    if values.dtype not in (torch.float32, torch.uint8) or values.ndim != 2 or not 1 <= values.shape[1] <= 256 or values.shape[0] >= 2 ** 31 - 1:
+        raise ValueError(f'smooth_values: values must be float32 or uint8 [V, C] with 1 <= C <= 256, got {values.dtype} {tuple(values.shape)}')
+    nv, dev = values.shape[0], values.device
+    adj = _filter_adjacency('smooth_values', faces, nv, adjacency, dev)
+    pin = _pinned('smooth_values', pinned, nv, dev)
+    x = values.to(torch.float32).contiguous()
+    x = _smooth_steps(x, adj, pin, [factor] * iterations) if nv else x
+    if values.dtype == torch.uint8:
+        return torch.floor(x + 0.5).clamp(0, 255).to(torch.uint8)
+    return x.clone() if iterations == 0 or nv == 0 else x
+
+
+def _label_vote_cpu(labels, adj, pinned, n_labels):
+    """p3d_mesh_label_vote's rule on uint8 labels: the counts of the neighbours' labels and the vertex's own, the smallest label
+    that reaches the maximum unless the vertex's own does."""
+    nv = labels.shape[0]
+    counts = adj.offsets[1:] - adj.offsets[:-1]
+    own = labels.long()
+    source = torch.repeat_interleave(torch.arange(nv), counts)
+    tally = torch.zeros([nv * n_labels], dtype=torch.int64)
+    tally.index_add_(0, source * n_labels + own[adj.neighbours.long()], torch.ones_like(source))
+    tally.index_add_(0, torch.arange(nv) * n_labels + own, torch.ones([nv], dtype=torch.int64))
+    tally = tally.view(nv, n_labels)
+    most = tally.max(1).values
+    reaches = tally == most[:, None]
+    smallest = torch.where(reaches, torch.arange(n_labels), torch.tensor(n_labels)).min(1).values
+    new = torch.where(reaches.gather(1, own[:, None])[:, 0], own, smallest)
+    moves = counts > 0
+    if pinned is not None:
+        moves &= pinned == 0
+    return torch.where(moves, new, own).to(torch.uint8)
+
+
+def smooth_labels(labels, faces, iterations=1, n_labels=None, pinned=None, adjacency=None):
+    """Majority voting of per-vertex class labels (what removes the speckle an argmax leaves at part boundaries): int64 [V] on the
+    labels' device.  Every iteration is one synchronous step: a vertex counts the labels of its neighbours and its own, keeps its
+    label when that reaches the maximum count and otherwise takes the smallest label that does.  ``n_labels`` <= 256 (default: the
+    largest label + 1); a label outside [0, n_labels) is a ValueError.  ``pinned`` and ``adjacency`` as for ``smooth``; vertices
+    without neighbours keep their label.  Device labels run p3d_mesh_label_vote, one launch per step; CPU labels the same integer
+    rule."""
+    iterations = _iterations('smooth_labels', iterations)
+    labels = torch.as_tensor(labels).detach()
+    if labels.ndim != 1 or labels.dtype not in (torch.uint8, torch.int16, torch.int32, torch.int64) or labels.shape[0] >= 2 ** 31 - 1:
+        raise ValueError(f'smooth_labels: labels must be an integer tensor [V], got {labels.dtype} {tuple(labels.shape)}')
+    nv, dev = labels.shape[0], labels.device
+    lo, hi = torch.stack(torch.aminmax(labels)).tolist() if nv else (0, 0)  # (on a device: one device-to-host copy)
+    n_labels = hi + 1 if n_labels is None else int(n_labels)
+    if not 1 <= n_labels <= 256:
+        raise ValueError(f'smooth_labels: n_labels must be in [1, 256], got {n_labels}')
+    if lo < 0 or hi >= n_labels:
+        raise ValueError(f'smooth_labels: label outside [0, {n_labels}) (labels span [{lo}, {hi}])')
+    adj = _filter_adjacency('smooth_labels', faces, nv, adjacency, dev)
+    pin = _pinned('smooth_labels', pinned, nv, dev)
+    x = labels.to(torch.uint8).contiguous()
+    if nv == 0:
+        return x.long()
+    if not x.is_cuda:
+        for _ in range(iterations):
+            x = _label_vote_cpu(x, adj, pin, n_labels)
+        return x.long()
+    lib = _lib.lib()
+    spare = [torch.empty_like(x), torch.empty_like(x)]
+    for k in range(iterations):
+        out = spare[k % 2]
+        _lib.check(lib.p3d_mesh_label_vote(_lib.ptr(x), nv, n_labels, _lib.ptr(adj.offsets), _lib.ptr(adj.neighbours),
+                                           adj.neighbours.shape[0], _lib.ptr(pin), _lib.ptr(out), _lib.stream_of(x)), 'mesh_label_vote')
+        x = out
+    return x.long()
+
+
 # ---- labels and the whole script ---------------------------------------------------------------------------------------------
 def default_palette(n):
     """uint8 [n, 3]: class 0 grey, the others spread round the hue circle by the golden angle (this package's own colours)."""
@@ -755,6 +997,18 @@ def _clean_geometry(G, ws, resolution, threshold, keep, min_faces, cell, **synth
     return vertices, faces
 
 
+def _taubin(vertices, faces, iterations, lam, mu, adj):
+    """``smooth`` for ``extract_mesh``, whose arguments ``smooth`` and ``smooth_labels`` hide the functions of those names."""
+    return smooth(vertices, faces, iterations, lam, mu, adjacency=adj)
+
+
+def _voted_colors(labels, faces, iterations, n_labels, palette, adj):
+    """The palette colours (as ``vertex_labels`` picks them) of the labels after ``iterations`` voting steps."""
+    labels = smooth_labels(labels, faces, iterations, n_labels, adjacency=adj)
+    pal = default_palette(n_labels) if palette is None else torch.as_tensor(palette, dtype=torch.uint8)
+    return pal.to(labels.device)[labels]
+
+
 def script_turntable(G, n_frames=120):
     """(poses [n_frames, 4, 4], camera): the script's turntable for G, orthographic xmag = ymag = 0.3 at radius 1 about
     G.rendering_kwargs['avg_camera_pivot'] (an edge-map generator, the script's edge2car branch: 0.6 at 1.2, the full orbit)."""
@@ -767,7 +1021,7 @@ def script_turntable(G, n_frames=120):
 
 @torch.no_grad()
 def extract_mesh(G, ws, resolution=512, threshold=50., n_frames=120, image_size=512, palette=None, keep=None, min_faces=1, cell=None,
-                 **synthesis_kwargs):
+                 smooth=0, smooth_labels=0, smooth_shading=False, lam=0.5, mu=-0.53, **synthesis_kwargs):
     """applications/extract_mesh.py after its inputs: shape.extract_geometry, per-vertex label colours unless G is an edge-map
     generator (data_type 'edge') or has no label channels, and the script's turntable — orthographic xmag = ymag = 0.3 at radius 1 (edge2car: 0.6 at 1.2) about
     G.rendering_kwargs['avg_camera_pivot'], image_size^2 pixels.  Returns (vertices, faces, vertex_colors or None, frames uint8
@@ -775,11 +1029,26 @@ def extract_mesh(G, ws, resolution=512, threshold=50., n_frames=120, image_size=
     turntable: ``clean(keep, min_faces)`` when ``keep`` is given or ``min_faces`` exceeds 1, then ``simplify(cell)`` when ``cell``
     (world units) is given.  Clustering can pinch a thin neck into an edge, which no face carries, and so detach a crumb (and leaves
     the vertices of cells whose faces all collapsed): with both ``keep`` and ``cell`` the component count asked for is applied to the
-    simplified mesh once more, so that keep=1 hands over one component."""
+    simplified mesh once more, so that keep=1 hands over one component.  Filtering, off by default too, follows the clean-up and
+    leaves the faces alone: the labels are read at the unsmoothed vertices (the decoder's own level set), ``smooth_labels`` voting
+    steps (``mesh.smooth_labels``) go over them before they become colours, ``smooth`` Taubin iterations with ``lam`` and ``mu``
+    (``mesh.smooth``, boundary pinned) then move the vertices that are returned and rendered, and ``smooth_shading`` renders with
+    ``texture.vertex_normals`` of that mesh instead of face normals."""
     vertices, faces = _clean_geometry(G, ws, resolution, threshold, keep, min_faces, cell, **synthesis_kwargs)
     edge = getattr(G, 'data_type', None) == 'edge'                      # the script's edge2car branch; every other generator is seg-like
     labelled = not edge and int(getattr(G, 'semantic_channels', 0) or 0) > 1
-    colors = vertex_labels(G, ws, vertices, palette)[1] if labelled and len(vertices) else None
+    adj = adjacency(faces, len(vertices)) if (smooth or smooth_labels) and len(vertices) else None
+    colors = None
+    if labelled and len(vertices):
+        labels, colors = vertex_labels(G, ws, vertices, palette)
+        if smooth_labels:
+            colors = _voted_colors(labels, faces, smooth_labels, int(G.semantic_channels), palette, adj)
+    if smooth and len(vertices):
+        vertices = _taubin(vertices, faces, smooth, lam, mu, adj)
+    shading = {}
+    if smooth_shading and len(vertices):
+        from . import texture                                              # (texture imports this module)
+        shading['normals'] = texture.vertex_normals(vertices, faces)
     poses, camera = script_turntable(G, n_frames)
-    frames = render(vertices, faces, poses, camera, image_size, colors=colors)
+    frames = render(vertices, faces, poses, camera, image_size, colors=colors, **shading)
     return vertices, faces, colors, frames
