@@ -648,6 +648,30 @@ int p3d_conv2d_bwd_weight_scaled(const void* small_img, const void* big_img, flo
                                  int32_t n_img, int32_t small_h, int32_t small_w, int32_t c_small, int32_t big_h, int32_t big_w, int32_t c_big,
                                  int32_t kernel_size, int32_t stride, int32_t pad, float scale, p3d_stream_t stream);
 
+/* The kernel a p3d_conv2d_bwd_weight* call with these sizes and operand facts would run, without launching anything (read-only: tests pin the host
+ * path's route decision with it).  Returns a p3d_wgrad_route code, or a negative p3d_status exactly as the call itself would for these sizes (pointer
+ * checks excepted: there are no pointers here).  flags: P3D_WGRAD_* bits below — which of the two images sits on a 16-byte boundary.
+ * workspace_bytes: what the call brings (< 0: as much as wanted).  plan_out (optional, 8 ints): grid, ksplit, chunks, chunks_per_split, psplit,
+ * narrow_b, xcd_pad of the launch and the number of partial tiles its reduce launch sums.                                                          */
+enum p3d_wgrad_route {
+    P3D_WGRAD_ROUTE_SKINNY_F16    = 0,   /* skinny_wgrad_kernel<__half>: 1x1, a handful of channels on one side (memory pass)               */
+    P3D_WGRAD_ROUTE_SKINNY_F32    = 1,   /* skinny_wgrad_kernel<float>                                                                       */
+    P3D_WGRAD_ROUTE_TR_SMALL_ROWK = 2,   /* conv_wgrad_tr_f16_kernel<true, true>: both sides <= 64 channels, rows of 128 pixels              */
+    P3D_WGRAD_ROUTE_TR_SMALL      = 3,   /* conv_wgrad_tr_f16_kernel<false, true>: both sides <= 64 channels                                 */
+    P3D_WGRAD_ROUTE_TR_ROWK       = 4,   /* conv_wgrad_tr_f16_kernel<true, false>: rows of 64 pixels                                         */
+    P3D_WGRAD_ROUTE_TR            = 5,   /* conv_wgrad_tr_f16_kernel<false, false>: fp16, aligned whole channel groups                       */
+    P3D_WGRAD_ROUTE_F16_SMALL     = 6,   /* conv_wgrad_kernel<__half, 128, true, true>: only with P3D_WGRAD_NO_TR / _NO_TR_SMALL             */
+    P3D_WGRAD_ROUTE_F16_FAST      = 7,   /* conv_wgrad_kernel<__half, 64, true>: only with P3D_WGRAD_NO_TR (/ _NO_SMALL at <= 64 channels)  */
+    P3D_WGRAD_ROUTE_F16_GENERAL   = 8,   /* conv_wgrad_kernel<__half, 64, false>: any fp16 geometry                                          */
+    P3D_WGRAD_ROUTE_F32_SMALL     = 9,   /* conv_wgrad_kernel<float, 32, true, true>: both sides <= 64 channels                              */
+    P3D_WGRAD_ROUTE_F32_X6        = 10,  /* conv_wgrad_kernel<float, 16, true, false, true>: P3D_F32_BF16X6 on whole 128 x 128 tiles         */
+    P3D_WGRAD_ROUTE_F32_FAST      = 11,  /* conv_wgrad_kernel<float, 16, true>: aligned whole channel groups                                 */
+    P3D_WGRAD_ROUTE_F32_GENERAL   = 12   /* conv_wgrad_kernel<float, 16, false>: any fp32 geometry                                           */
+};
+enum { P3D_WGRAD_SMALL_ALIGNED = 1, P3D_WGRAD_BIG_ALIGNED = 2 };
+int p3d_conv2d_bwd_weight_route(int dtype, int32_t n_img, int32_t small_h, int32_t small_w, int32_t c_small, int32_t big_h, int32_t big_w, int32_t c_big,
+                                int32_t kernel_size, int32_t stride, int32_t pad, uint32_t flags, int64_t workspace_bytes, int32_t* plan_out);
+
 /* p3d_conv2d_nhwc with optional split-K scratch (see p3d_conv2d_forward): workspace of p3d_conv2d_nhwc_workspace(...) bytes, or null */
 int p3d_conv2d_nhwc_ws(const void* x, const void* w, void* y, int dtype, const float* bias, const float* noise, const float* noise_strength,
                        const void* zeros128, int32_t n_img, int32_t h, int32_t wdt, int32_t ci, int32_t co, int64_t w_img_stride,

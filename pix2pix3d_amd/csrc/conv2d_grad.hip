@@ -96,6 +96,44 @@ __device__ __forceinline__ void pix_advance(PixPos& p, int d, int HS, int WS)
         if (p.i >= HS) { const int q2 = p.i / HS; p.i -= q2 * HS; p.n += q2; }
     }
 }
+__device__ __forceinline__ PixPos pix_from_index(int64_t m, int HS, int WS)       // (n, i, j) of pixel m of the small image
+{
+    const int64_t per = (int64_t)HS * WS;
+    PixPos p;
+    p.n = (int)(m / per);
+    const int rem = (int)(m - (int64_t)p.n * per);
+    p.i = rem / WS; p.j = rem - p.i * WS;
+    return p;
+}
+
+// What both weight-gradient kernels share besides their loaders, MFMA loops and the partial-tile store: the work item of a work-group, zeroed accumulators.
+// work item: (group = (split, tile), tap); the taps of a group sit on one XCD (work-group L runs on XCD L % 8)
+struct WgradItem { int taps, tap, split, cs0, cb0, dy, dx, c_begin, c_end; bool live; };
+__device__ __forceinline__ WgradItem wgrad_item(const WgradArgs& a, int L)
+{
+    WgradItem it;
+    it.taps = a.k * a.k; it.live = true;
+    const int groups = a.ksplit * a.tiles_s * a.tiles_b;
+    int g;
+    if (a.xcd_pad)              { g = (L & 7) + 8 * ((L >> 3) / it.taps); it.tap = (L >> 3) % it.taps; it.live = g < groups; }    // (grid padded to 8 groups a round)
+    else if ((groups & 7) == 0) { g = (L & 7) + 8 * ((L >> 3) / it.taps); it.tap = (L >> 3) % it.taps; }
+    else                        { g = L / it.taps; it.tap = L - g * it.taps; }
+    const int tile = g % (a.tiles_s * a.tiles_b); it.split = g / (a.tiles_s * a.tiles_b);
+    it.cs0 = (tile / a.tiles_b) * 128; it.cb0 = (tile % a.tiles_b) * 128;
+    const int ky = it.tap / a.k, kx = it.tap - ky * a.k; it.dy = ky - a.pad; it.dx = kx - a.pad;
+    it.c_begin = it.split * a.chunks_per_split; it.c_end = it.c_begin + a.chunks_per_split;
+    if (it.c_end > a.chunks) it.c_end = a.chunks;
+    return it;
+}
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][2])
+{
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
 
 // FAST: both images hold whole, 16-byte aligned channel groups and fewer than 2^31 bytes each (32-bit offsets on a uniform base, no element-wise tail code in
 // the loop); fp16 also wants rows of a multiple of four pixels (a lane's four pixels then share one row: one position, one row test).  The general loop carried
@@ -123,20 +161,9 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_kernel(WgradArgs a)
     const int wm = a.psplit == 1 ? wave >> 1 : (a.psplit == 2 && a.narrow_b ? wave & 1 : 0);
     const int wn = a.psplit == 1 ? wave & 1 : (a.psplit == 2 && !a.narrow_b ? wave & 1 : 0);
     const int part = a.psplit == 1 ? 0 : (a.psplit == 2 ? wave >> 1 : wave), pmask = a.psplit - 1;
-    const int taps = a.k * a.k;
-    // work item: (group = (split, tile), tap); the taps of a group sit on one XCD (work-group L runs on XCD L % 8)
-    const int groups = a.ksplit * a.tiles_s * a.tiles_b;
-    int L = blockIdx.x, g, tap;
-    if (a.xcd_pad)              { g = (L & 7) + 8 * ((L >> 3) / taps); tap = (L >> 3) % taps; if (g >= groups) return; }    // (grid padded to 8 groups a round)
-    else if ((groups & 7) == 0) { g = (L & 7) + 8 * ((L >> 3) / taps); tap = (L >> 3) % taps; }
-    else                        { g = L / taps; tap = L - g * taps; }
-    const int tile = g % (a.tiles_s * a.tiles_b), split = g / (a.tiles_s * a.tiles_b);
-    const int cs0 = (tile / a.tiles_b) * 128, cb0 = (tile % a.tiles_b) * 128;
-    const int ky = tap / a.k, kx = tap - ky * a.k;
-    const int dy = ky - a.pad, dx = kx - a.pad;
-    const int c_begin = split * a.chunks_per_split;
-    int c_end = c_begin + a.chunks_per_split;
-    if (c_end > a.chunks) c_end = a.chunks;
+    const WgradItem it = wgrad_item(a, blockIdx.x);
+    if (!it.live) return;
+    const int cs0 = it.cs0, cb0 = it.cb0, dy = it.dy, dx = it.dx, c_begin = it.c_begin, c_end = it.c_end;
     const int64_t Mtot = (int64_t)a.N * a.HS * a.WS;
     const T* const S = (const T*)a.s;
     const T* const B = (const T*)a.b;
@@ -144,12 +171,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_kernel(WgradArgs a)
     const bool vec_b = (a.Cb % EPC) == 0 && ((uintptr_t)a.b & 15u) == 0;
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
     const int frow = lane & 31, fk = lane >> 5;
 
     // ---- loader role of this thread -------------------------------------------------------------------------------------
@@ -172,13 +194,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_kernel(WgradArgs a)
     const int64_t m_end64 = (int64_t)c_end * KPB < Mtot ? (int64_t)c_end * KPB : Mtot;     // this work-group's pixels end here
     PixPos pos[NLD];                                                           // (n, i, j) of each load's pixel in the current chunk
 #pragma unroll
-    for (int q = 0; q < NLD; ++q) {
-        const int64_t m = (int64_t)c_begin * KPB + lp[q];
-        const int64_t per = (int64_t)a.HS * a.WS;
-        pos[q].n = (int)(m / per);
-        const int rem = (int)(m - (int64_t)pos[q].n * per);
-        pos[q].i = rem / a.WS; pos[q].j = rem - pos[q].i * a.WS;
-    }
+    for (int q = 0; q < NLD; ++q) pos[q] = pix_from_index((int64_t)c_begin * KPB + lp[q], a.HS, a.WS);
     f32x4 rs[NLD], rb[NLD];                                                    // staged operands of the NEXT chunk
 
     auto load16 = [&](const T* base, int64_t elem_off, int c_first, int C, bool vec) -> f32x4 {
@@ -336,7 +352,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_kernel(WgradArgs a)
     }
 
     // partial tile -> workspace [split][tap][CsP][CbP]: accumulator element r of tile (i, j) is row (r&3) + 8(r>>2) + 4 fk, column frow
-    float* out = a.ws + ((int64_t)(split * a.psplit + part) * taps + tap) * a.CsP * a.CbP;
+    float* out = a.ws + ((int64_t)(it.split * a.psplit + part) * it.taps + it.tap) * a.CsP * a.CbP;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -374,29 +390,14 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_tr_f16_kernel(WgradArgs a)
     const int wm = SMALL64 ? 0 : (a.psplit == 1 ? wave >> 1 : (a.narrow_b ? wave & 1 : 0));
     const int wn = SMALL64 ? 0 : (a.psplit == 1 ? wave & 1 : (!a.narrow_b ? wave & 1 : 0));
     const int part = SMALL64 ? wave : (a.psplit == 1 ? 0 : wave >> 1), pmask = a.psplit - 1;
-    const int taps = a.k * a.k;
-    const int groups = a.ksplit * a.tiles_s * a.tiles_b;
-    int L = blockIdx.x, g, tap;
-    if (a.xcd_pad)              { g = (L & 7) + 8 * ((L >> 3) / taps); tap = (L >> 3) % taps; if (g >= groups) return; }
-    else if ((groups & 7) == 0) { g = (L & 7) + 8 * ((L >> 3) / taps); tap = (L >> 3) % taps; }
-    else                        { g = L / taps; tap = L - g * taps; }
-    const int tile = g % (a.tiles_s * a.tiles_b), split = g / (a.tiles_s * a.tiles_b);
-    const int cs0 = (tile / a.tiles_b) * 128, cb0 = (tile % a.tiles_b) * 128;
-    const int ky = tap / a.k, kx = tap - ky * a.k;
-    const int dy = ky - a.pad, dx = kx - a.pad;
-    const int c_begin = split * a.chunks_per_split;
-    int c_end = c_begin + a.chunks_per_split;
-    if (c_end > a.chunks) c_end = a.chunks;
+    const WgradItem it = wgrad_item(a, blockIdx.x);
+    if (!it.live) return;
+    const int cs0 = it.cs0, cb0 = it.cb0, dy = it.dy, dx = it.dx, c_begin = it.c_begin, c_end = it.c_end;
     const int64_t Mtot = (int64_t)a.N * a.HS * a.WS;
     const int m_end = (int)((int64_t)c_end * KPB < Mtot ? (int64_t)c_end * KPB : Mtot);
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     // loader: TPR threads cover one pixel's channels (contiguous bytes of global memory), PASS pixels per pass, four passes per iteration
     const int lc = (tid % TPR) * 8;
@@ -407,13 +408,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_tr_f16_kernel(WgradArgs a)
     const int wrow = (lc * 2 + rot(tid / TPR)) & (ROW - 1);                     // byte position of this thread's 16 bytes inside its LDS rows
     PixPos pos[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int64_t m = (int64_t)c_begin * KPB + lp[q];
-        const int64_t per = (int64_t)a.HS * a.WS;
-        pos[q].n = (int)(m / per);
-        const int rem = (int)(m - (int64_t)pos[q].n * per);
-        pos[q].i = rem / a.WS; pos[q].j = rem - pos[q].i * a.WS;
-    }
+    for (int q = 0; q < 4; ++q) pos[q] = pix_from_index((int64_t)c_begin * KPB + lp[q], a.HS, a.WS);
     const bool s_ok = cs0 + lc < a.Cs, b_ok = cb0 + lc < a.Cb;
     const char* const Sb = (const char*)a.s;
     const char* const Bb = (const char*)a.b;
@@ -497,7 +492,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_tr_f16_kernel(WgradArgs a)
         buf ^= 1;
     }
 
-    float* out = a.ws + ((int64_t)(split * a.psplit + part) * taps + tap) * a.CsP * a.CbP;
+    float* out = a.ws + ((int64_t)(it.split * a.psplit + part) * it.taps + it.tap) * a.CsP * a.CbP;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -752,66 +747,117 @@ __global__ void __launch_bounds__(256) skinny_expand_kernel(const T* __restrict_
     }
 }
 
-static int wgrad_pixel_split(int cs, int cb)
-{
-    static const bool no_half = getenv("P3D_WGRAD_NO_HALF") != nullptr;         // (A/B switch of the measurement scripts)
-    if (cs <= 64 && cb <= 64) return 4;
-    return (cs <= 64 || cb <= 64) && !no_half ? 2 : 1;
-}
+// ---- host path of the weight gradient: WgradRequest -> plan_wgrad -> launch_wgrad_plan ------------------------------------------------------
+// A/B switches of the measurement scripts, read once per process
+struct WgradSwitches {
+    static bool on(const char* name) { return getenv(name) != nullptr; }
+    bool no_half = on("P3D_WGRAD_NO_HALF"), plan_old = on("P3D_WGRAD_PLAN_OLD"), no_skinny = on("P3D_WGRAD_NO_SKINNY"), no_fast = on("P3D_WGRAD_NO_FAST");
+    bool no_small = on("P3D_WGRAD_NO_SMALL"), no_tr = on("P3D_WGRAD_NO_TR"), no_tr_small = on("P3D_WGRAD_NO_TR_SMALL");
+    int wg_per_cu = on("P3D_WGRAD_WG_PER_CU") ? atoi(getenv("P3D_WGRAD_WG_PER_CU")) : 0;      // resident work-groups per CU the split plan aims at (0: its own figure)
+};
+static const WgradSwitches& wgrad_switches() { static const WgradSwitches sw; return sw; }
 
-static bool wgrad_plan_old()
-{
-    static const bool v = getenv("P3D_WGRAD_PLAN_OLD") != nullptr;              // (A/B switch of the measurement scripts)
-    return v;
-}
+struct WgradRequest {
+    // the sum: all plan_wgrad reads besides the facts below
+    int dtype = P3D_F32;                       // as passed (P3D_F32_BF16X6: fp32 tensors; the arithmetic of the whole-tile kernel only, anything else runs the exact kernels)
+    int32_t n_img = 0, small_h = 0, small_w = 0, c_small = 0, big_h = 0, big_w = 0, c_big = 0, kernel_size = 3, stride = 1, pad = 0;
+    bool out_f32 = false; float scale = 1.f;   // gw as fp32 whatever the activation dtype, times `scale` (p3d_conv2d_bwd_weight_scaled)
+    // the operands: read by launch_wgrad_plan only
+    const void* small_img = nullptr; const void* big_img = nullptr; void* gw = nullptr; void* workspace = nullptr; int64_t workspace_bytes = 0; p3d_stream_t stream = nullptr;
+    // what the plan may know about the operands
+    bool small_aligned = true, big_aligned = true; int64_t ws_bytes = 0;      // the images on a 16-byte boundary; bytes of workspace that came with the call
+    void note_operands() { small_aligned = (((uintptr_t)small_img) & 15u) == 0; big_aligned = (((uintptr_t)big_img) & 15u) == 0; ws_bytes = workspace_bytes; }      // a real call
+    void assume_plain_operands() { small_aligned = big_aligned = true; ws_bytes = INT64_MAX; }      // sizing and route entry points: aligned, all the workspace wanted
+};
 
+// What a request runs: plan_wgrad decides, launch_wgrad_plan only obeys.
+struct WgradPlan {
+    int route = 0, grid[2] = {0, 1};           // enum p3d_wgrad_route
+    int ksplit = 0, chunks = 0, chunks_per_split = 0, tiles_s = 0, tiles_b = 0, psplit = 0, narrow_b = 0, xcd_pad = 0;      // as stored into WgradArgs (the MFMA kernels' split plan)
+    int CsP = 0, CbP = 0;                      // partial-tile layout [.][taps][CsP][CbP] of the route: the MFMA kernels' padded tiles, or the skinny kernel's own
+    int few_is_rows = 0, F = 0, W = 0, rows = 0;      // skinny routes: which side is the `few` one, its channels F, the other side's W, pixels per block
+    int reduce_nsplit = 0, reduce_taps = 0, reduce_blocks = 0;      // the second launch: partial tiles to sum
+    int64_t workspace_bytes = 0;               // what p3d_conv2d_bwd_weight_workspace answers: the MFMA plan's partial tiles, whichever route runs
+};
+
+// Pure host: no launch, no device call.  The argument checks that need no pointer, then the split of the pixel axis, the skinny route if it fits, the route table.
 // Split of the pixel axis.  The kernel is MFMA-bound and its work-groups cost the same, so the launch ends when the fullest CU does: every work-group should be
 // resident at once, and the same number on every CU.  Work-group L runs on XCD L % 8 (32 CUs, r resident work-groups each) and a group's taps share an XCD, so
 // the unit is groups per XCD: floor(32 r / taps) of them, 8 times that in the launch, floor(that / tiles) splits.  Round 4's plan aimed at 3 work-groups per
 // CU and rounded UP: 22 splits of a 256 x 256 x 9 problem = 99 work-groups on an XCD's 96 places, 88 TFLOP/s; 28 splits at r = 4 (126 on 128) run 105
 // (profiles/round4_t_wgrad_variants.txt: every variant that overfills an XCD is the slow one of its row).
-static int wgrad_plan(int dtype, int64_t pixels, int cs, int cb, int k, int* ksplit, int* chunks, int* cps)
+static int plan_wgrad(const WgradRequest& r, WgradPlan* p)
 {
-    const int KP = dtype == P3D_F16 ? 64 : 16;
-    const int taps = k * k;
-    const int tiles = ceil_div(cs, 128) * ceil_div(cb, 128);
-    const int64_t nchunks = (pixels + KP - 1) / KP;
-    static const int env_per_cu = getenv("P3D_WGRAD_WG_PER_CU") ? atoi(getenv("P3D_WGRAD_WG_PER_CU")) : 0;
-    int64_t per, split;
-    if (wgrad_plan_old()) {
-        const int per_cu = env_per_cu > 0 ? env_per_cu : 3;
-        int64_t want = ((int64_t)per_cu * kNumCU + tiles * taps - 1) / (tiles * taps);
-        if (want < 1) want = 1;
-        if (want > nchunks) want = nchunks;
-        if (want > 1024) want = 1024;
-        per = (nchunks + want - 1) / want;
-        split = (nchunks + per - 1) / per;
-        if (tiles * split >= 8) {                                               // a multiple of 8 groups keeps a group's taps on one XCD
-            const int64_t up = ((tiles * split + 7) / 8) * 8;
-            if (up % tiles == 0 && up / tiles <= nchunks) { split = up / tiles; per = (nchunks + split - 1) / split; }
-        }
-    } else {
-        // resident work-groups per CU: fp16 holds 72 KB of LDS (2); fp32 32 KB and 120 VGPRs (4)
-        const int per_cu = env_per_cu > 0 ? env_per_cu : (dtype == P3D_F16 ? 2 : 4);
-        int gpx = (kNumCU / 8) * per_cu / taps;                                 // groups per XCD
-        if (gpx < 1) gpx = 1;
-        int64_t want = 8 * gpx / tiles;
-        if (want < 1) want = 1;
-        if (want > nchunks) want = nchunks;
-        if (want > 1024) want = 1024;
-        per = (nchunks + want - 1) / want;
-        if (cs <= 64 && cb <= 64 && per > 1) per = (per + 1) & ~(int64_t)1;       // the 64-channel kernels take two chunks an iteration: whole iterations per split, each
-        split = (nchunks + per - 1) / per;                                      // starting on a multiple of its 2 x KP pixels (what lets a row-aligned image share one position)
+    P3D_REQUIRE(r.dtype == P3D_F16 || r.dtype == P3D_F32 || r.dtype == P3D_F32_BF16X6, "conv2d_bwd_weight: dtype must be fp16, fp32 or fp32-as-bf16x6");
+    const bool x6 = r.dtype == P3D_F32_BF16X6, f16 = r.dtype == P3D_F16; const int cs = r.c_small, cb = r.c_big;
+    P3D_REQUIRE(r.n_img >= 1 && r.small_h >= 1 && r.small_w >= 1 && r.big_h >= 1 && r.big_w >= 1 && cs >= 1 && cb >= 1, "conv2d_bwd_weight: bad sizes");
+    P3D_REQUIRE((r.kernel_size == 1 || r.kernel_size == 3) && (r.stride == 1 || r.stride == 2) && r.pad >= 0 && r.pad <= 1, "conv2d_bwd_weight: k in {1,3}, stride in {1,2}, pad in {0,1}");
+    const WgradSwitches& sw = wgrad_switches();
+    const int KP = f16 ? 64 : 16, taps = r.kernel_size * r.kernel_size;
+    const int64_t pixels = (int64_t)r.n_img * r.small_h * r.small_w;
+    p->tiles_s = ceil_div(cs, 128); p->tiles_b = ceil_div(cb, 128); p->CsP = p->tiles_s * 128; p->CbP = p->tiles_b * 128;
+    p->psplit = cs <= 64 && cb <= 64 ? 4 : ((cs <= 64 || cb <= 64) && !sw.no_half ? 2 : 1);      // partial tiles per split: 4 when both sides hold <= 64 channels, 2 when one does
+    const int tiles = p->tiles_s * p->tiles_b; const int64_t nchunks = (pixels + KP - 1) / KP;
+    // resident work-groups per CU: fp16 holds 72 KB of LDS (2); fp32 32 KB and 120 VGPRs (4).  P3D_WGRAD_PLAN_OLD: round 4's plan
+    const int per_cu = sw.wg_per_cu > 0 ? sw.wg_per_cu : (sw.plan_old ? 3 : (f16 ? 2 : 4));
+    const int gpx = (kNumCU / 8) * per_cu / taps < 1 ? 1 : (kNumCU / 8) * per_cu / taps;      // groups per XCD
+    int64_t want = sw.plan_old ? ((int64_t)per_cu * kNumCU + tiles * taps - 1) / (tiles * taps) : 8 * gpx / tiles;
+    want = want < 1 ? 1 : (want > nchunks ? nchunks : want); if (want > 1024) want = 1024;
+    int64_t per = (nchunks + want - 1) / want;
+    if (!sw.plan_old && cs <= 64 && cb <= 64 && per > 1) per = (per + 1) & ~(int64_t)1;      // the 64-channel kernels take two chunks an iteration: whole iterations per split, each
+    int64_t split = (nchunks + per - 1) / per;                                  // starting on a multiple of its 2 x KP pixels (what lets a row-aligned image share one position)
+    if (sw.plan_old && tiles * split >= 8) {                                    // a multiple of 8 groups keeps a group's taps on one XCD
+        const int64_t up = ((tiles * split + 7) / 8) * 8;
+        if (up % tiles == 0 && up / tiles <= nchunks) { split = up / tiles; per = (nchunks + split - 1) / split; }
     }
-    *ksplit = (int)split; *chunks = (int)nchunks; *cps = (int)per;
-    return taps;
+    p->ksplit = (int)split; p->chunks = (int)nchunks; p->chunks_per_split = (int)per; p->narrow_b = cb <= 64 ? 1 : 0;
+    p->workspace_bytes = (int64_t)p->ksplit * p->psplit * taps * p->CsP * p->CbP * 4;
+    P3D_REQUIRE(r.ws_bytes >= p->workspace_bytes, "conv2d_bwd_weight: workspace too small");
+    p->reduce_taps = taps;                                                      // (the reduce launch: one thread per four cb of one (tap, cs))
+    const auto reduce_blocks = [&] { const int64_t total = (int64_t)taps * cs * (p->CbP / 4); return (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192); };
+
+    // skinny 1x1 (one side with a handful of channels, the other a whole number of 16-byte vectors): the memory-pass kernel, where its own scratch fits the bytes handed in
+    const int epc = f16 ? 8 : 4, esz = 16 / epc;
+    const bool few_small = cs <= 32 && cb % epc == 0, few_big = cb <= 32 && cs % epc == 0;
+    if (!sw.no_skinny && r.kernel_size == 1 && r.stride == 1 && r.pad == 0 && r.small_h == r.big_h && r.small_w == r.big_w && (few_small || few_big)) {
+        const bool few_is_rows = few_small && !(few_big && cb < cs);            // which side is the `few` one (the smaller if both qualify)
+        const int W = few_is_rows ? cb : cs, CbP = (cb + 3) & ~3;
+        const int wv = W / epc, cpb = wv < 32 ? wv : 32, rl = 256 / cpb;
+        int64_t rows = (pixels + 1023) / 1024;
+        if (rows < (int64_t)rl * 16) rows = (int64_t)rl * 16;
+        const int64_t nsplit = (pixels + rows - 1) / rows;
+        if ((cpb & (cpb - 1)) == 0 && nsplit * cs * CbP * 4 <= r.ws_bytes && (few_is_rows ? r.big_aligned : r.small_aligned) && rows < (1ll << 31)) {
+            p->route = f16 ? P3D_WGRAD_ROUTE_SKINNY_F16 : P3D_WGRAD_ROUTE_SKINNY_F32;
+            p->few_is_rows = few_is_rows ? 1 : 0; p->F = few_is_rows ? cs : cb; p->W = W; p->rows = (int)rows;
+            p->CsP = cs; p->CbP = CbP; p->grid[0] = (int)nsplit; p->grid[1] = (wv + cpb - 1) / cpb;
+            p->reduce_nsplit = (int)nsplit; p->reduce_blocks = reduce_blocks();
+            return P3D_OK;
+        }
+    }
+    p->xcd_pad = sw.plan_old ? 0 : 1;
+    const int ngroups = p->ksplit * tiles; p->grid[0] = (p->xcd_pad ? (ngroups + 7) / 8 * 8 : ngroups) * taps;
+    p->reduce_nsplit = p->ksplit * p->psplit; p->reduce_blocks = reduce_blocks();
+    // FAST / SMALL / the transposing-read kernels: see conv_wgrad_kernel and conv_wgrad_tr_f16_kernel.  32-bit byte offsets: both images below 2^31 bytes
+    const bool aligned = r.small_aligned && r.big_aligned && pixels * cs * esz < (1ll << 31) && (int64_t)r.n_img * r.big_h * r.big_w * cb * esz < (1ll << 31);
+    const bool fast = !sw.no_fast && cs % epc == 0 && cb % epc == 0 && aligned && (!f16 || r.small_w % 4 == 0);
+    const bool small64 = fast && !sw.no_small && p->psplit == 4;
+    const bool fast_tr = !sw.no_fast && !sw.no_tr && f16 && cs % 8 == 0 && cb % 8 == 0 && aligned;      // (handles its pixels one by one: no rows-of-four requirement)
+    // (one position per thread needs every iteration to start on a multiple of its 128 pixels: whole double chunks per split — what the split above hands out)
+    const bool row128 = r.small_w % 128 == 0 && (p->chunks_per_split % 2 == 0 || p->ksplit == 1);
+    // first match wins; the two fp16 rows below the transposing-read ones are reached only with P3D_WGRAD_NO_TR / _NO_TR_SMALL (fast implies fast_tr)
+    if (f16) p->route = fast_tr && p->psplit == 4 && !sw.no_small && !sw.no_tr_small ? (row128 ? P3D_WGRAD_ROUTE_TR_SMALL_ROWK : P3D_WGRAD_ROUTE_TR_SMALL)
+                      : small64                                                      ? P3D_WGRAD_ROUTE_F16_SMALL
+                      : fast_tr && p->psplit != 4                                    ? (r.small_w % 64 == 0 ? P3D_WGRAD_ROUTE_TR_ROWK : P3D_WGRAD_ROUTE_TR)
+                      : fast                                                         ? P3D_WGRAD_ROUTE_F16_FAST : P3D_WGRAD_ROUTE_F16_GENERAL;
+    else     p->route = small64                        ? P3D_WGRAD_ROUTE_F32_SMALL
+                      : fast && x6 && p->psplit == 1   ? P3D_WGRAD_ROUTE_F32_X6
+                      : fast                           ? P3D_WGRAD_ROUTE_F32_FAST : P3D_WGRAD_ROUTE_F32_GENERAL;
+    return P3D_OK;
 }
 
 } // namespace p3d
 
 using namespace p3d;
-
-enum { MODE_SAME = 0, MODE_STRIDE2 = 1 };
 
 static int relayout(const void* w, void* dst, int dtype, int A, int B, int taps, int swap, int flip, hipStream_t s)
 {
@@ -921,121 +967,94 @@ extern "C" int p3d_conv2d_bwd_data(const void* gy, const void* weight, void* gx,
     return conv_forward_impl(gy, weight, gx, w_scratch, zeros128, dtype, n_img, gy_h, gy_w, co, ci, kernel_size, stride, !transposed, x_h, x_w, workspace, workspace_bytes, stream);
 }
 
-extern "C" int64_t p3d_conv2d_bwd_weight_workspace(int dtype, int32_t n_img, int32_t small_h, int32_t small_w, int32_t c_small, int32_t c_big, int32_t kernel_size)
+static int launch_wgrad_reduce(const WgradRequest& r, const WgradPlan& p, const char* what)
 {
-    int ksplit, chunks, cps;
-    const int taps = wgrad_plan(dtype, (int64_t)n_img * small_h * small_w, c_small, c_big, kernel_size, &ksplit, &chunks, &cps);
-    const int per_wave = wgrad_pixel_split(c_small, c_big);                       // WgradArgs::psplit partial tiles per split
-    return (int64_t)ksplit * per_wave * taps * (ceil_div(c_small, 128) * 128) * (ceil_div(c_big, 128) * 128) * 4;
+    const dim3 grid(p.reduce_blocks); const float* ws = (const float*)r.workspace; hipStream_t s = (hipStream_t)r.stream;
+    if (r.dtype == P3D_F16 && !r.out_f32) hipLaunchKernelGGL(wgrad_reduce_kernel<__half>, grid, dim3(256), 0, s, ws, (__half*)r.gw, r.c_small, r.c_big, p.reduce_taps, p.reduce_nsplit, p.CsP, p.CbP, r.scale);
+    else                                  hipLaunchKernelGGL(wgrad_reduce_kernel<float>, grid, dim3(256), 0, s, ws, (float*)r.gw, r.c_small, r.c_big, p.reduce_taps, p.reduce_nsplit, p.CsP, p.CbP, r.scale);
+    count_launch(FAM_CONV);
+    return check_launch(what);
 }
 
-static int bwd_weight_impl(const void* small_img, const void* big_img, void* gw, void* workspace, int64_t workspace_bytes, int dtype,
-                           int32_t n_img, int32_t small_h, int32_t small_w, int32_t c_small, int32_t big_h, int32_t big_w, int32_t c_big,
-                           int32_t kernel_size, int32_t stride, int32_t pad, bool out_f32, float scale, p3d_stream_t stream)
+// the kernels of the eleven MFMA routes, in the order of enum p3d_wgrad_route from P3D_WGRAD_ROUTE_TR_SMALL_ROWK on
+static void (*const kWgradKernels[])(WgradArgs) = {
+    conv_wgrad_tr_f16_kernel<true, true>, conv_wgrad_tr_f16_kernel<false, true>, conv_wgrad_tr_f16_kernel<true, false>, conv_wgrad_tr_f16_kernel<false, false>,
+    conv_wgrad_kernel<__half, 128, true, true>, conv_wgrad_kernel<__half, 64, true>, conv_wgrad_kernel<__half, 64, false>,
+    conv_wgrad_kernel<float, 32, true, true>, conv_wgrad_kernel<float, 16, true, false, true>, conv_wgrad_kernel<float, 16, true>, conv_wgrad_kernel<float, 16, false>};
+static_assert(sizeof(kWgradKernels) / sizeof(kWgradKernels[0]) == P3D_WGRAD_ROUTE_F32_GENERAL - P3D_WGRAD_ROUTE_TR_SMALL_ROWK + 1, "one kernel per MFMA route");
+
+static int launch_wgrad_plan(const WgradRequest& r, const WgradPlan& p)
+{
+    P3D_REQUIRE((((uintptr_t)r.workspace) & 15u) == 0, "conv2d_bwd_weight: workspace must be 16-byte aligned");
+    const bool skinny = p.route == P3D_WGRAD_ROUTE_SKINNY_F16 || p.route == P3D_WGRAD_ROUTE_SKINNY_F32;
+    hipStream_t s = (hipStream_t)r.stream;
+    if (skinny) {
+        const void* few = p.few_is_rows ? r.small_img : r.big_img, * many = p.few_is_rows ? r.big_img : r.small_img;
+        const int64_t M = (int64_t)r.n_img * r.small_h * r.small_w; const dim3 grid(p.grid[0], p.grid[1]);
+        if (p.route == P3D_WGRAD_ROUTE_SKINNY_F16) hipLaunchKernelGGL(skinny_wgrad_kernel<__half>, grid, dim3(256), 0, s, (const __half*)few, (const __half*)many, (float*)r.workspace, M, p.F, p.W, p.rows, p.few_is_rows, p.CsP, p.CbP);
+        else                                       hipLaunchKernelGGL(skinny_wgrad_kernel<float>, grid, dim3(256), 0, s, (const float*)few, (const float*)many, (float*)r.workspace, M, p.F, p.W, p.rows, p.few_is_rows, p.CsP, p.CbP);
+    } else {
+        WgradArgs a{};
+        a.s = r.small_img; a.b = r.big_img; a.ws = (float*)r.workspace; a.k = r.kernel_size; a.stride = r.stride; a.pad = r.pad;
+        a.N = r.n_img; a.HS = r.small_h; a.WS = r.small_w; a.Cs = r.c_small; a.HB = r.big_h; a.WB = r.big_w; a.Cb = r.c_big;
+        a.ksplit = p.ksplit; a.chunks = p.chunks; a.chunks_per_split = p.chunks_per_split; a.xcd_pad = p.xcd_pad; a.psplit = p.psplit; a.narrow_b = p.narrow_b;
+        a.tiles_s = p.tiles_s; a.tiles_b = p.tiles_b; a.CsP = p.CsP; a.CbP = p.CbP;
+        hipLaunchKernelGGL(kWgradKernels[p.route - P3D_WGRAD_ROUTE_TR_SMALL_ROWK], dim3(p.grid[0]), dim3(256), 0, s, a);
+    }
+    count_launch(FAM_CONV);
+    const int rc = check_launch(skinny ? "skinny_wgrad" : "conv_wgrad");
+    return rc != P3D_OK ? rc : launch_wgrad_reduce(r, p, skinny ? "skinny_wgrad reduce" : "conv_wgrad reduce");
+}
+
+static int run_wgrad(const void* small_img, const void* big_img, void* gw, void* workspace, int64_t workspace_bytes, int dtype, int32_t n_img, int32_t small_h, int32_t small_w, int32_t c_small,
+                     int32_t big_h, int32_t big_w, int32_t c_big, int32_t kernel_size, int32_t stride, int32_t pad, bool out_f32, float scale, p3d_stream_t stream)
 {
     P3D_REQUIRE(small_img && big_img && gw && workspace, "conv2d_bwd_weight: null pointer");
-    P3D_REQUIRE(dtype == P3D_F16 || dtype == P3D_F32 || dtype == P3D_F32_BF16X6, "conv2d_bwd_weight: dtype must be fp16, fp32 or fp32-as-bf16x6");
-    const bool x6 = dtype == P3D_F32_BF16X6;                                     // fp32 tensors; the arithmetic of the whole-tile kernel only (anything else: the exact kernels)
-    if (x6) dtype = P3D_F32;
-    P3D_REQUIRE(n_img >= 1 && small_h >= 1 && small_w >= 1 && big_h >= 1 && big_w >= 1 && c_small >= 1 && c_big >= 1, "conv2d_bwd_weight: bad sizes");
-    P3D_REQUIRE((kernel_size == 1 || kernel_size == 3) && (stride == 1 || stride == 2) && pad >= 0 && pad <= 1, "conv2d_bwd_weight: k in {1,3}, stride in {1,2}, pad in {0,1}");
-    P3D_REQUIRE(workspace_bytes >= p3d_conv2d_bwd_weight_workspace(dtype, n_img, small_h, small_w, c_small, c_big, kernel_size), "conv2d_bwd_weight: workspace too small");
-    P3D_REQUIRE((((uintptr_t)workspace) & 15u) == 0, "conv2d_bwd_weight: workspace must be 16-byte aligned");
-    WgradArgs a{};
-    a.s = small_img; a.b = big_img; a.ws = (float*)workspace;
-    a.N = n_img; a.HS = small_h; a.WS = small_w; a.Cs = c_small; a.HB = big_h; a.WB = big_w; a.Cb = c_big;
-    a.k = kernel_size; a.stride = stride; a.pad = pad;
-    const int taps = wgrad_plan(dtype, (int64_t)n_img * small_h * small_w, c_small, c_big, kernel_size, &a.ksplit, &a.chunks, &a.chunks_per_split);
-    a.tiles_s = ceil_div(c_small, 128); a.tiles_b = ceil_div(c_big, 128);
-    a.CsP = a.tiles_s * 128; a.CbP = a.tiles_b * 128;
-    a.psplit = wgrad_pixel_split(c_small, c_big);
-    a.narrow_b = c_big <= 64 ? 1 : 0;
-    hipStream_t s = (hipStream_t)stream;
-    {   // skinny 1x1 (one side with a handful of channels, the other a whole number of 16-byte vectors): the memory-pass kernel
-        const int epc = dtype == P3D_F16 ? 8 : 4;
-        const bool few_small = c_small <= 32 && c_big % epc == 0, few_big = c_big <= 32 && c_small % epc == 0;
-        static const bool no_skinny = getenv("P3D_WGRAD_NO_SKINNY") != nullptr;
-        if (!no_skinny && kernel_size == 1 && stride == 1 && pad == 0 && small_h == big_h && small_w == big_w && (few_small || few_big)) {
-            const bool few_is_rows = few_small && !(few_big && c_big < c_small);            // which side is the `few` one (the smaller if both qualify)
-            const void* few = few_is_rows ? small_img : big_img;
-            const void* many = few_is_rows ? big_img : small_img;
-            const int F = few_is_rows ? c_small : c_big, W = few_is_rows ? c_big : c_small;
-            const int CsP = c_small, CbP = (c_big + 3) & ~3;
-            const int64_t M = (int64_t)n_img * small_h * small_w;
-            const int wv = W / epc, cpb = wv < 32 ? wv : 32, rl = 256 / cpb;
-            int64_t rows = (M + 1023) / 1024;
-            if (rows < (int64_t)rl * 16) rows = (int64_t)rl * 16;
-            const int64_t nsplit = (M + rows - 1) / rows;
-            const int64_t need = nsplit * CsP * CbP * 4;
-            if ((cpb & (cpb - 1)) == 0 && need <= workspace_bytes && (((uintptr_t)many) & 15u) == 0 && rows < (1ll << 31)) {
-                dim3 grid((unsigned)nsplit, (unsigned)((wv + cpb - 1) / cpb));
-                if (dtype == P3D_F16) hipLaunchKernelGGL(skinny_wgrad_kernel<__half>, grid, dim3(256), 0, s, (const __half*)few, (const __half*)many, a.ws, M, F, W, (int)rows, (int)few_is_rows, CsP, CbP);
-                else                  hipLaunchKernelGGL(skinny_wgrad_kernel<float>, grid, dim3(256), 0, s, (const float*)few, (const float*)many, a.ws, M, F, W, (int)rows, (int)few_is_rows, CsP, CbP);
-                count_launch(FAM_CONV);
-                int rc2 = check_launch("skinny_wgrad");
-                if (rc2 != P3D_OK) return rc2;
-                const int64_t total2 = (int64_t)c_small * (CbP / 4);
-                const int rb2 = (int)((total2 + 255) / 256 < 8192 ? (total2 + 255) / 256 : 8192);
-                if (dtype == P3D_F16 && !out_f32) hipLaunchKernelGGL(wgrad_reduce_kernel<__half>, dim3(rb2), dim3(256), 0, s, a.ws, (__half*)gw, c_small, c_big, 1, (int)nsplit, CsP, CbP, scale);
-                else                              hipLaunchKernelGGL(wgrad_reduce_kernel<float>, dim3(rb2), dim3(256), 0, s, a.ws, (float*)gw, c_small, c_big, 1, (int)nsplit, CsP, CbP, scale);
-                count_launch(FAM_CONV);
-                return check_launch("skinny_wgrad reduce");
-            }
-        }
-    }
-    a.xcd_pad = wgrad_plan_old() ? 0 : 1;
-    const int ngroups = a.ksplit * a.tiles_s * a.tiles_b;
-    const int blocks = (a.xcd_pad ? (ngroups + 7) / 8 * 8 : ngroups) * taps;
-    const int esz = dtype == P3D_F16 ? 2 : 4, epc16 = 16 / esz;
-    static const bool no_fast = getenv("P3D_WGRAD_NO_FAST") != nullptr;          // (A/B switches of the measurement scripts)
-    static const bool no_small = getenv("P3D_WGRAD_NO_SMALL") != nullptr;
-    const bool fast = !no_fast && c_small % epc16 == 0 && c_big % epc16 == 0 && ((((uintptr_t)small_img) | ((uintptr_t)big_img)) & 15u) == 0
-                      && (int64_t)n_img * small_h * small_w * c_small * esz < (1ll << 31) && (int64_t)n_img * big_h * big_w * c_big * esz < (1ll << 31)
-                      && (dtype != P3D_F16 || small_w % 4 == 0);
-    const bool small64 = fast && !no_small && a.psplit == 4;
-    static const bool no_tr = getenv("P3D_WGRAD_NO_TR") != nullptr;
-    // (the transposing-read kernel handles its pixels one by one: no rows-of-four requirement)
-    const bool fast_tr = !no_fast && !no_tr && dtype == P3D_F16 && c_small % 8 == 0 && c_big % 8 == 0 && ((((uintptr_t)small_img) | ((uintptr_t)big_img)) & 15u) == 0
-                         && (int64_t)n_img * small_h * small_w * c_small * 2 < (1ll << 31) && (int64_t)n_img * big_h * big_w * c_big * 2 < (1ll << 31);
-    static const bool no_tr_small = getenv("P3D_WGRAD_NO_TR_SMALL") != nullptr;
-    if (dtype == P3D_F16) {
-        if (fast_tr && a.psplit == 4 && !no_small && !no_tr_small) {
-            // (one position per thread needs every iteration to start on a multiple of its 128 pixels: whole double chunks per split — what wgrad_plan hands out)
-            if (small_w % 128 == 0 && (a.chunks_per_split % 2 == 0 || a.ksplit == 1)) hipLaunchKernelGGL((conv_wgrad_tr_f16_kernel<true, true>), dim3(blocks), dim3(256), 0, s, a);
-            else                    hipLaunchKernelGGL((conv_wgrad_tr_f16_kernel<false, true>), dim3(blocks), dim3(256), 0, s, a);
-        }
-        else if (small64) hipLaunchKernelGGL((conv_wgrad_kernel<__half, 128, true, true>), dim3(blocks), dim3(256), 0, s, a);
-        else if (fast_tr && a.psplit != 4 && small_w % 64 == 0) hipLaunchKernelGGL((conv_wgrad_tr_f16_kernel<true, false>), dim3(blocks), dim3(256), 0, s, a);
-        else if (fast_tr && a.psplit != 4) hipLaunchKernelGGL((conv_wgrad_tr_f16_kernel<false, false>), dim3(blocks), dim3(256), 0, s, a);
-        else if (fast) hipLaunchKernelGGL((conv_wgrad_kernel<__half, 64, true>), dim3(blocks), dim3(256), 0, s, a);
-        else           hipLaunchKernelGGL((conv_wgrad_kernel<__half, 64, false>), dim3(blocks), dim3(256), 0, s, a);
-    } else {
-        if (small64)   hipLaunchKernelGGL((conv_wgrad_kernel<float, 32, true, true>), dim3(blocks), dim3(256), 0, s, a);
-        else if (fast && x6 && a.psplit == 1) hipLaunchKernelGGL((conv_wgrad_kernel<float, 16, true, false, true>), dim3(blocks), dim3(256), 0, s, a);
-        else if (fast) hipLaunchKernelGGL((conv_wgrad_kernel<float, 16, true>), dim3(blocks), dim3(256), 0, s, a);
-        else           hipLaunchKernelGGL((conv_wgrad_kernel<float, 16, false>), dim3(blocks), dim3(256), 0, s, a);
-    }
-    count_launch(FAM_CONV);
-    int rc = check_launch("conv_wgrad");
+    WgradRequest r;
+    r.dtype = dtype; r.n_img = n_img; r.small_h = small_h; r.small_w = small_w; r.c_small = c_small; r.big_h = big_h; r.big_w = big_w; r.c_big = c_big;
+    r.kernel_size = kernel_size; r.stride = stride; r.pad = pad; r.out_f32 = out_f32; r.scale = scale;
+    r.small_img = small_img; r.big_img = big_img; r.gw = gw; r.workspace = workspace; r.workspace_bytes = workspace_bytes; r.stream = stream;
+    r.note_operands();
+    WgradPlan plan; const int rc = plan_wgrad(r, &plan);
+    return rc != P3D_OK ? rc : launch_wgrad_plan(r, plan);
+}
+
+extern "C" int64_t p3d_conv2d_bwd_weight_workspace(int dtype, int32_t n_img, int32_t small_h, int32_t small_w, int32_t c_small, int32_t c_big, int32_t kernel_size)
+{
+    WgradRequest r;                                                             // (the split plan reads neither the big image's size nor stride / pad)
+    r.dtype = dtype; r.n_img = n_img; r.small_h = r.big_h = small_h; r.small_w = r.big_w = small_w; r.c_small = c_small; r.c_big = c_big; r.kernel_size = kernel_size;
+    r.assume_plain_operands(); WgradPlan plan;
+    return plan_wgrad(r, &plan) == P3D_OK ? plan.workspace_bytes : 0;
+}
+
+extern "C" int p3d_conv2d_bwd_weight_route(int dtype, int32_t n_img, int32_t small_h, int32_t small_w, int32_t c_small, int32_t big_h, int32_t big_w, int32_t c_big,
+                                           int32_t kernel_size, int32_t stride, int32_t pad, uint32_t flags, int64_t workspace_bytes, int32_t* plan_out)
+{
+    WgradRequest r;
+    r.dtype = dtype; r.n_img = n_img; r.small_h = small_h; r.small_w = small_w; r.c_small = c_small; r.big_h = big_h; r.big_w = big_w; r.c_big = c_big;
+    r.kernel_size = kernel_size; r.stride = stride; r.pad = pad;
+    r.assume_plain_operands();
+    r.small_aligned = (flags & P3D_WGRAD_SMALL_ALIGNED) != 0; r.big_aligned = (flags & P3D_WGRAD_BIG_ALIGNED) != 0;
+    if (workspace_bytes >= 0) r.ws_bytes = workspace_bytes;
+    if (plan_out) for (int i = 0; i < 8; ++i) plan_out[i] = 0;
+    WgradPlan p;
+    const int rc = plan_wgrad(r, &p);
     if (rc != P3D_OK) return rc;
-    const int64_t total = (int64_t)taps * c_small * (a.CbP / 4);
-    const int rblocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    if (dtype == P3D_F16 && !out_f32) hipLaunchKernelGGL(wgrad_reduce_kernel<__half>, dim3(rblocks), dim3(256), 0, s, a.ws, (__half*)gw, c_small, c_big, taps, a.ksplit * a.psplit, a.CsP, a.CbP, scale);
-    else                              hipLaunchKernelGGL(wgrad_reduce_kernel<float>, dim3(rblocks), dim3(256), 0, s, a.ws, (float*)gw, c_small, c_big, taps, a.ksplit * a.psplit, a.CsP, a.CbP, scale);
-    count_launch(FAM_CONV);
-    return check_launch("conv_wgrad reduce");
+    const int out[8] = {p.grid[0] * p.grid[1], p.ksplit, p.chunks, p.chunks_per_split, p.psplit, p.narrow_b, p.xcd_pad, p.reduce_nsplit};
+    if (plan_out) for (int i = 0; i < 8; ++i) plan_out[i] = out[i];
+    return p.route;
 }
 
 extern "C" int p3d_conv2d_bwd_weight(const void* small_img, const void* big_img, void* gw, void* workspace, int64_t workspace_bytes, int dtype,
                                      int32_t n_img, int32_t small_h, int32_t small_w, int32_t c_small, int32_t big_h, int32_t big_w, int32_t c_big,
                                      int32_t kernel_size, int32_t stride, int32_t pad, p3d_stream_t stream)
 {
-    return bwd_weight_impl(small_img, big_img, gw, workspace, workspace_bytes, dtype, n_img, small_h, small_w, c_small, big_h, big_w, c_big, kernel_size, stride, pad, false, 1.f, stream);
+    return run_wgrad(small_img, big_img, gw, workspace, workspace_bytes, dtype, n_img, small_h, small_w, c_small, big_h, big_w, c_big, kernel_size, stride, pad, false, 1.f, stream);
 }
 
 extern "C" int p3d_conv2d_bwd_weight_scaled(const void* small_img, const void* big_img, float* gw_f32, void* workspace, int64_t workspace_bytes, int dtype,
                                             int32_t n_img, int32_t small_h, int32_t small_w, int32_t c_small, int32_t big_h, int32_t big_w, int32_t c_big,
                                             int32_t kernel_size, int32_t stride, int32_t pad, float scale, p3d_stream_t stream)
 {
-    return bwd_weight_impl(small_img, big_img, gw_f32, workspace, workspace_bytes, dtype, n_img, small_h, small_w, c_small, big_h, big_w, c_big, kernel_size, stride, pad, true, scale, stream);
+    return run_wgrad(small_img, big_img, gw_f32, workspace, workspace_bytes, dtype, n_img, small_h, small_w, c_small, big_h, big_w, c_big, kernel_size, stride, pad, true, scale, stream);
 }

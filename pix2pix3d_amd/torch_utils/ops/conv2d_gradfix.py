@@ -128,6 +128,7 @@ _lib.register('p3d_conv2d_forward_workspace', _i64, [ctypes.c_int] + [_i32] * 8)
 _lib.register('p3d_conv2d_bwd_weight_workspace', _i64, [ctypes.c_int] + [_i32] * 6)
 _lib.register('p3d_conv2d_bwd_weight', ctypes.c_int, [_vp] * 4 + [_i64, ctypes.c_int] + [_i32] * 10 + [_vp])
 _lib.register('p3d_conv2d_bwd_weight_scaled', ctypes.c_int, [_vp] * 4 + [_i64, ctypes.c_int] + [_i32] * 10 + [ctypes.c_float, _vp])
+_lib.register('p3d_conv2d_bwd_weight_route', ctypes.c_int, [ctypes.c_int] + [_i32] * 10 + [ctypes.c_uint32, _i64, ctypes.POINTER(_i32)])
 
 _zero_pages = {}
 

@@ -1,5 +1,5 @@
 """Weight-gradient kernel alone on the geometries that carry the training iteration's weight-gradient time (profiles/round4_o_train_conv_geometries.txt),
-event-timed over 20 calls each, one row per geometry; the environment (P3D_WGRAD_F32_KP16, P3D_WGRAD_WG_PER_CU, ...) selects the variant.
+event-timed over 20 calls each, one row per geometry; the environment (WGRAD_X6=1: fp32 as bf16x6; P3D_WGRAD_WG_PER_CU, P3D_WGRAD_NO_TR, ...: INTEGRATION.md) selects the variant.
     python tests/gpu_time_wgrad.py [label]  -> appends to gpurun_out/wgrad_variants.txt"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
