@@ -24,7 +24,7 @@
 //   * importance sampling is wave-cooperative per ray (lane = bin / fine sample): sequential fp32
 //     pdf/cdf (contraction off) so the searchsorted indices are reproducible bit for bit, then a
 //     64-lane bitonic sort of the fine depths.
-#include "render_device.h"
+#include "render_host.h"
 
 namespace p3d {
 
@@ -339,40 +339,23 @@ static int render_forward_impl(const float* planes_cl, const float* planes_sem_c
                                            : kDecoderFloats + kWavesPerBlock * (kWaveTile + kFeatTile + kTapTile)) * sizeof(float);      // + the cooperative gather's tiles
     const int blocks = (int)((total + wpb * 32 - 1) / (wpb * 32));
     hipLaunchKernelGGL(render_init_minmax_kernel, dim3(1), dim3(1), 0, s, minmax_ws);
-    if (dual) {
-        static std::atomic<uint64_t> onced_devs{0}; const hipError_t onced = reserve_lds_once((const void*)render_forward_kernel<2, false, true>, (int)lds_bytes, onced_devs);
-        if (onced != hipSuccess) return fail(P3D_ERR_LAUNCH, "render_forward_dual: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(onced));
-        hipLaunchKernelGGL((render_forward_kernel<2, false, true>), dim3(blocks), dim3(wpb * 64), lds_bytes, s, a);
-    } else if (d->mlp_bf16x3 == 2) {                        // layer 1 as bf16x6 (stream: p3d_pack_decoder_l1x6)
-        const size_t lds6 = lds_bytes + (size_t)(kDecoderFloatsL1X6 - kDecoderFloats) * sizeof(float);
-        if (d->n_nets == 1) {
-            static std::atomic<uint64_t> oncex1_devs{0}; const hipError_t e1 = reserve_lds_once((const void*)render_forward_kernel<1, false, false, false, true>, (int)lds6, oncex1_devs);
-            if (e1 != hipSuccess) return fail(P3D_ERR_LAUNCH, "render_forward: cannot reserve %zu B of LDS: %s", lds6, hipGetErrorString(e1));
-            hipLaunchKernelGGL((render_forward_kernel<1, false, false, false, true>), dim3(blocks), dim3(wpb * 64), lds6, s, a);
-        } else {
-            static std::atomic<uint64_t> oncex2_devs{0}; const hipError_t e2 = reserve_lds_once((const void*)render_forward_kernel<2, false, false, false, true>, (int)lds6, oncex2_devs);
-            if (e2 != hipSuccess) return fail(P3D_ERR_LAUNCH, "render_forward: cannot reserve %zu B of LDS: %s", lds6, hipGetErrorString(e2));
-            hipLaunchKernelGGL((render_forward_kernel<2, false, false, false, true>), dim3(blocks), dim3(wpb * 64), lds6, s, a);
-        }
-    } else if (d->mlp_bf16x3) {
-        if (d->n_nets == 1) {
-            static std::atomic<uint64_t> onceb1_devs{0}; const hipError_t e1 = reserve_lds_once((const void*)render_forward_kernel<1, false, false, true>, (int)lds_bytes, onceb1_devs);
-            if (e1 != hipSuccess) return fail(P3D_ERR_LAUNCH, "render_forward: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e1));
-            hipLaunchKernelGGL((render_forward_kernel<1, false, false, true>), dim3(blocks), dim3(wpb * 64), lds_bytes, s, a);
-        } else {
-            static std::atomic<uint64_t> onceb2_devs{0}; const hipError_t e2 = reserve_lds_once((const void*)render_forward_kernel<2, false, false, true>, (int)lds_bytes, onceb2_devs);
-            if (e2 != hipSuccess) return fail(P3D_ERR_LAUNCH, "render_forward: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e2));
-            hipLaunchKernelGGL((render_forward_kernel<2, false, false, true>), dim3(blocks), dim3(wpb * 64), lds_bytes, s, a);
-        }
-    } else if (d->n_nets == 1) {
-        static std::atomic<uint64_t> once1_devs{0}; const hipError_t once1 = reserve_lds_once((const void*)render_forward_kernel<1, false>, (int)lds_bytes, once1_devs);
-        if (once1 != hipSuccess) return fail(P3D_ERR_LAUNCH, "render_forward: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(once1));
-        hipLaunchKernelGGL((render_forward_kernel<1, false>), dim3(blocks), dim3(wpb * 64), lds_bytes, s, a);
-    } else {
-        static std::atomic<uint64_t> once2_devs{0}; const hipError_t once2 = reserve_lds_once((const void*)render_forward_kernel<2, false>, (int)lds_bytes, once2_devs);
-        if (once2 != hipSuccess) return fail(P3D_ERR_LAUNCH, "render_forward: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(once2));
-        hipLaunchKernelGGL((render_forward_kernel<2, false>), dim3(blocks), dim3(wpb * 64), lds_bytes, s, a);
+    if (dual)
+        rc = launch_lds_opt_in<render_forward_kernel<2, false, true>>("render_forward_dual", dim3(blocks), dim3(wpb * 64), lds_bytes, s, a);
+    else {
+        // one-plane-set kernels: [decoder form = p3d_render_desc.mlp_bf16x3][one net | two nets, raw label logits | two nets, squashed labels]
+        typedef int (*launch_fn)(const char*, dim3, dim3, size_t, hipStream_t, const RenderArgs&);
+#define P3D_FWD(NNETS, BF3, L1X6, SEMSIG) &launch_lds_opt_in<render_forward_kernel<NNETS, false, false, BF3, L1X6, SEMSIG>, RenderArgs>
+        static const launch_fn kForward[3][3] = {
+            {P3D_FWD(1, false, false, false), P3D_FWD(2, false, false, false), P3D_FWD(2, false, false, true)},      // exact fp32
+            {P3D_FWD(1, true,  false, false), P3D_FWD(2, true,  false, false), P3D_FWD(2, true,  false, true)},      // bf16x3
+            {P3D_FWD(1, false, true,  false), P3D_FWD(2, false, true,  false), P3D_FWD(2, false, true,  true)},      // layer 1 as bf16x6 (stream: p3d_pack_decoder_l1x6)
+        };
+#undef P3D_FWD
+        const int form = d->mlp_bf16x3 == 2 ? 2 : (d->mlp_bf16x3 ? 1 : 0);
+        const size_t lds = lds_bytes + (form == 2 ? (size_t)(kDecoderFloatsL1X6 - kDecoderFloats) * sizeof(float) : 0);
+        rc = kForward[form][d->n_nets == 1 ? 0 : (d->semantic_sigmoid ? 2 : 1)]("render_forward", dim3(blocks), dim3(wpb * 64), lds, s, a);
     }
+    if (rc != P3D_OK) return rc;
     rc = check_launch("render_forward");
     if (rc != P3D_OK) return rc;
     const int cb = (int)((total + 255) / 256);

@@ -88,6 +88,40 @@ __device__ __forceinline__ float softplus20_log2(float xs) {
 __device__ __forceinline__ float sigmoid_clamped(float x) {  // sigmoid(x) * (1 + 2*0.001) - 0.001
     return fmaf(__builtin_amdgcn_rcpf(1.f + fast_exp(-x)), 1.002f, -0.001f);
 }
+// sigmoid(x) from xn = -x log2(e): exp2, add, rcp.  The forward kernel's LDS copy of a squashed net's colour rows and biases carries the
+// -log2(e); sigmoid_clamped's affine part is applied once per ray, to the composite (see the epilogue of render_forward_kernel).
+__device__ __forceinline__ float sigmoid_neg_log2(float xn) { return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(xn)); }
+
+// Softplus of the lane's 32 hidden units of one net, in place.  The threshold select of softplus20 / softplus20_log2 (v_cmp + v_cndmask
+// per value) only matters for a pre-activation above the threshold, which the shipped decoders hardly ever produce: the lane's maximum
+// (a v_max3 chain, 16 instructions) decides ONE wave-uniform branch.  No lane above the threshold: exp2, add, log2 per value — the very instructions the
+// select form runs for such a value, so the same bits.  Any lane above it (that includes everything that would overflow the exp2):
+// the select form for the whole wave.  Either way a value's result is a function of that value alone, never of its wave-mates.
+template <bool LOG2>
+__device__ __forceinline__ void softplus_tiles(f32x16& h0, f32x16& h1)
+{
+    constexpr float kThreshold = LOG2 ? 28.853900817779268f : 20.f;
+    float m = __builtin_fmaxf(__builtin_fmaxf(h0[0], h0[1]), h0[2]);
+#pragma unroll
+    for (int r = 3; r < 15; r += 2) m = __builtin_fmaxf(__builtin_fmaxf(m, h0[r]), h0[r + 1]);
+    m = __builtin_fmaxf(__builtin_fmaxf(m, h0[15]), h1[0]);
+#pragma unroll
+    for (int r = 1; r < 15; r += 2) m = __builtin_fmaxf(__builtin_fmaxf(m, h1[r]), h1[r + 1]);
+    m = __builtin_fmaxf(m, h1[15]);
+    if (__builtin_amdgcn_ballot_w64(m > kThreshold) == 0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            h0[r] = LOG2 ? __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(h0[r])) : fast_log(1.f + fast_exp(h0[r]));
+            h1[r] = LOG2 ? __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(h1[r])) : fast_log(1.f + fast_exp(h1[r]));
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            h0[r] = LOG2 ? softplus20_log2(h0[r]) : softplus20(h0[r]);
+            h1[r] = LOG2 ? softplus20_log2(h1[r]) : softplus20(h1[r]);
+        }
+    }
+}
 
 // Depth of coarse sample i on ray g (renderer.py:169-192), fp32 with the same operation order.
 __device__ __forceinline__ float coarse_depth(const RenderArgs& a, int g, int i, float u)
@@ -361,11 +395,7 @@ __device__ __forceinline__ void mlp_layer1(const float* lds, int n, int lane, in
             }
         }
     }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        h0[r] = LOG2 ? softplus20_log2(h0[r]) : softplus20(h0[r]);
-        h1[r] = LOG2 ? softplus20_log2(h1[r]) : softplus20(h1[r]);
-    }
+    softplus_tiles<LOG2>(h0, h1);
 }
 
 // Layer 2 colour rows (decoder outputs 1..32) of net `n`: lane (j,h) gets channel (r&3)+8(r>>2)+4h in out[r].
@@ -463,8 +493,7 @@ __device__ __forceinline__ void mlp_layer1_bf3(const float* lds, int n, int lane
         h0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, fl[s], h0, 0, 0, 0);
         h1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, fl[s], h1, 0, 0, 0);
     }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { h0[r] = softplus20_log2(h0[r]); h1[r] = softplus20_log2(h1[r]); }
+    softplus_tiles<true>(h0, h1);
 }
 // colour rows of net n from its hidden units
 __device__ __forceinline__ void mlp_layer2_bf3(const float* lds, int n, int lane, int h, const f32x16& h0, const f32x16& h1, f32x16& out)
@@ -517,11 +546,7 @@ __device__ __forceinline__ void mlp_layer1_x6(const float* lds, int n, int lane,
             h1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(P3D_X6_A(term, a1h, a1m, a1l), P3D_X6_B(term, fh[s], fm[s], fl[s]), h1, 0, 0, 0);
         }
     }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        h0[r] = LOG2 ? softplus20_log2(h0[r]) : softplus20(h0[r]);
-        h1[r] = LOG2 ? softplus20_log2(h1[r]) : softplus20(h1[r]);
-    }
+    softplus_tiles<LOG2>(h0, h1);
 }
 __device__ __forceinline__ void split3_feat(const float (&feat)[16], bf8 (&fh)[2], bf8 (&fm)[2], bf8 (&fl)[2])
 {
@@ -619,14 +644,17 @@ __device__ __forceinline__ void bitonic_sort64(float (&v)[NR], int lane)
 // DUAL (NNETS == 2, inference only): two plane sets.  The label net (density + labels) reads the SEMANTIC planes' features, the colour
 // net reads cat(texture features, semantic features) through a 64-input first layer (renderer.py:324-333); everything else —
 // sampling, merge, compositing over cat(colour, label) — is the same sweep.
+// SEMSIG (one-plane-set inference kernels): the label net's outputs are squashed (the decoder's `sigmoid` option) — a template parameter there,
+// so that the decode loop holds no branch on it; the TAPE and DUAL kernels read a.sem_sigmoid.
 constexpr int kWavesPerBlockDual = 4;            // the DUAL kernel keeps two feature vectors live: one wave per SIMD (512 registers) instead of spilling
-template <int NNETS, bool TAPE, bool DUAL = false, bool BF3 = false, bool L1X6 = false>
+template <int NNETS, bool TAPE, bool DUAL = false, bool BF3 = false, bool L1X6 = false, bool SEMSIG = false>
 __global__ void __launch_bounds__((DUAL ? kWavesPerBlockDual : kWavesPerBlock) * 64, DUAL ? 1 : 2)
 render_forward_kernel(RenderArgs a)
 {
     static_assert(!DUAL || (NNETS == 2 && !TAPE), "the two-plane-set variant is the two-net inference kernel");
     static_assert(!BF3 || (!TAPE && !DUAL), "the bf16x3 decoder is the one-plane-set inference kernel");
     static_assert(!L1X6 || (!BF3 && !DUAL && !TAPE), "layer 1 as bf16x6 is a form of the exact one-plane-set forward kernel");
+    static_assert(!SEMSIG || (NNETS == 2 && !TAPE && !DUAL), "SEMSIG is a parameter of the two-net one-plane-set inference kernels");
     constexpr int kDecFloats = DUAL ? kDecoderFloatsDual : (L1X6 ? kDecoderFloatsL1X6 : kDecoderFloats);
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -635,7 +663,14 @@ render_forward_kernel(RenderArgs a)
     // Inference works in the log2 domain (softplus20_log2): its LDS copy of the decoder has layer 1 (weights, biases) scaled by log2(e) and
     // everything that consumes the hidden units (layer-2 colour rows, the density row) by ln 2.  The packed stream in global memory is
     // the same for every consumer; the tape sweep (TAPE) and the backward kernel keep natural units, their gradients use the hidden values.
+    // The one-plane-set inference kernels (FOLD) take the clamped sigmoid's scaling out of the decode loop as well:
+    //   * a squashed net's colour rows and colour biases carry -log2(e) on top of the ln 2, i.e. the rows become -W2: layer 2 then yields
+    //     -o log2(e) and sigmoid(o) is sigmoid_neg_log2 of it;
+    //   * sigmoid_clamped's affine part 1.002 s - 0.001 commutes with the (linear) composite: the loop accumulates the raw sigmoid and the
+    //     epilogue applies 1.002 acc - 0.001 w_sum, w_sum being the sum of the interval weights.
     constexpr bool LOG2 = !TAPE;
+    constexpr bool FOLD = !TAPE && !DUAL;
+    const auto squashed = [](int n) { return n == 0 || NNETS == 1 || SEMSIG; };      // FOLD: net n's colours are squashed (raw logits for the label net: triplane_cond.py:960-964)
     {   // decoder stream -> LDS (16 B per lane)
         const f32x4* src = (const f32x4*)a.decoder;
         f32x4* dst = (f32x4*)lds;
@@ -644,9 +679,16 @@ render_forward_kernel(RenderArgs a)
             f32x4 v = src[i];
             if (LOG2) {
                 const int f = i * 4;
-                const bool first  = f >= OFF_W1X ? true : (f < OFF_B1 ? (f & (kNetStride - 1)) < kNetStride / 2 : f < OFF_B2);      // layer-1 weights / biases
-                const bool second = f < OFF_B1 ? !first : (f >= OFF_W2S && f < OFF_B2S);                    // layer-2 colour rows / density row
-                const float sc = first ? 1.4426950408889634f : (second ? 0.6931471805599453f : 1.f);
+                constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
+                float sc = 1.f;
+                if (f >= OFF_W1X) sc = kLog2e;                                                             // (DUAL) layer-1 weights of inputs 32..63
+                else if (f < OFF_B1) {                                                                     // a net's weights: layer 1, then the layer-2 colour rows
+                    const bool squash = FOLD && squashed(f / kNetStride);
+                    sc = (f & (kNetStride - 1)) < kNetStride / 2 ? kLog2e : (squash ? -1.f : kLn2);
+                }
+                else if (f < OFF_B2) sc = kLog2e;                                                          // layer-1 biases
+                else if (f < OFF_W2S) sc = (FOLD && squashed((f - OFF_B2) / 32)) ? -kLog2e : 1.f;           // colour biases
+                else if (f < OFF_B2S) sc = kLn2;                                                           // density row (its bias stays)
                 v = v * sc;
             }
             if (BF3 && i * 4 < 2 * kNetStride) {                  // weights: the stream is [net][block][lane][8] floats (p3d_pack_decoder_bf16x3) -> [hi | lo] bf16
@@ -794,6 +836,7 @@ render_forward_kernel(RenderArgs a)
     float4* const tape_i = TAPE ? (float4*)a.tape_i + (size_t)g * (Sc + Sf - 1) : nullptr;
     float4* const tape_s = TAPE ? (float4*)a.tape_s + (size_t)g * (Sc + Sf) : nullptr;
     float T = 1.f, z_prev = 0.f, s_prev = 0.f, w_sum = 0.f, wz_sum = 0.f, z_first = 0.f;
+    float hw_prev = 0.f;                         // FOLD: half the weight of the interval that ENDED at the previous sample
     int ic = 0, jf = 0;
     float zc = coarse_depth(a, g, 0, uc[0]);
     float zf = (Sf > 0) ? tile[j] : INFINITY;
@@ -811,6 +854,8 @@ render_forward_kernel(RenderArgs a)
         // The density net goes first: its sigma closes interval k-1 (weight w), after which every net's
         // colours are folded into the accumulators as soon as its layer 2 retires — only `prev` (the
         // other end of the midpoint rule) stays live across samples.
+        // FOLD: sum_i hw_i (c_{i-1} + c_i) = sum_k c_k (hw_k + hw_{k+1}) — once interval k-1 is closed, sample k-1 (`prev`) has both its
+        // weights and is folded with ONE fma per channel; the last sample follows the loop.
         float sigma = 0.f, hw = 0.f;
         float t_alpha = 0.f, t_T = 0.f, t_sm = 0.f, t_A = 0.f;               // TAPE: record of interval k-1
         bf8 fh[2], fl[2];                                                    // BF3: the sample's features, split once for both nets
@@ -841,6 +886,14 @@ render_forward_kernel(RenderArgs a)
             }
             if constexpr (BF3) mlp_layer2_bf3(lds, n, lane, h, h0, h1, o);
             else               mlp_layer2(lds, n, lane, h, h0, h1, o);
+            if constexpr (FOLD) {
+                const float wk = hw_prev + hw;                                 // both are 0 at the first sample, and so is prev
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    acc[n][r] = fmaf(wk, prev[n][r], acc[n][r]);
+                    prev[n][r] = squashed(n) ? sigmoid_neg_log2(o[r]) : o[r];
+                }
+            } else {
             const bool squash = (n == 0) || (NNETS == 1) || a.sem_sigmoid;     // raw logits for the label net (triplane_cond.py:960-964)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -848,6 +901,7 @@ render_forward_kernel(RenderArgs a)
                 if (TAPE) t_A = fmaf(acc[n][r], prev[n][r] + c, t_A);          // dL/dw of interval k-1, colour part: sum_ch dC (c[k-1] + c[k]) / 2
                 else      acc[n][r] = fmaf(hw, prev[n][r] + c, acc[n][r]);     // hw == 0 for the first sample
                 prev[n][r] = c;
+            }
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -858,7 +912,7 @@ render_forward_kernel(RenderArgs a)
                 if (k > 0) tape_i[k - 1] = make_float4(t_alpha, t_T, 0.5f * t_A, t_sm);
             }
         }
-        z_prev = z; s_prev = sigma;
+        z_prev = z; s_prev = sigma; hw_prev = hw;
     }
     if (TAPE) {
         // ---- backward of the compositing (ray_marcher.py:25-57), one ray per lane, walking the intervals back to front:
@@ -895,6 +949,15 @@ render_forward_kernel(RenderArgs a)
 
     // ------------------------------ epilogue --------------------------------------------------------
     const float bg = a.white_back ? (1.f - w_sum) : 0.f;
+    if constexpr (FOLD) {
+#pragma unroll
+        for (int n = 0; n < NNETS; ++n)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float c = fmaf(hw_prev, prev[n][r], acc[n][r]);                  // the last sample closes only the last interval
+                acc[n][r] = squashed(n) ? fmaf(1.002f, c, -0.001f * w_sum) : c;         // sigmoid_clamped's affine part, once per ray
+            }
+    }
     if (live) {
         float* dst = a.feat + (size_t)g * (NNETS * 32);
 #pragma unroll
