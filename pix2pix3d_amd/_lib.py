@@ -7,6 +7,7 @@ then shared between torch and the kernels.
 """
 import ctypes
 import os
+import re
 import threading
 
 import torch  # noqa: F401  (must precede CDLL: see module docstring)
@@ -14,38 +15,96 @@ import torch  # noqa: F401  (must precede CDLL: see module docstring)
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('P3D_LIB_PATH') or os.path.join(_PKG_DIR, 'libp3d_hip.so')      # (P3D_LIB_PATH: A/B runs of two builds on one box)
 
-P3D_OK = 0
-P3D_ERR_UNSUPPORTED = -1
-DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.float64: 2}
 FAMILY = {'bias_act': 0, 'upfirdn2d': 1, 'filtered_lrelu': 2, 'render': 3, 'conv': 4, 'aux': 5}
 
-_c_void_p, _c_int, _c_i32, _c_i64, _c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-_vp, _i32, _f32, _f64 = _c_void_p, _c_i32, _c_float, ctypes.c_double      # short names for the op modules' register() calls
+_c_void_p = ctypes.c_void_p
 _i32x4, _i64x4 = ctypes.c_int32 * 4, ctypes.c_int64 * 4
 _i32x2, _i64x2 = ctypes.c_int32 * 2, ctypes.c_int64 * 2
 
-_SIGNATURES = {
-    'p3d_last_error': (ctypes.c_char_p, []),
-    'p3d_abi_version': (_c_int, []),
-    'p3d_launch_count': (ctypes.c_uint64, []),
-    'p3d_launch_count_of': (ctypes.c_uint64, [_c_int]),
-    'p3d_bias_act': (_c_int, [_c_void_p] * 6 + [_c_int, _c_int, _c_int, _c_float, _c_float, _c_float,
-                              _c_i64, _c_i32, _c_i64, _c_void_p]),
-    'p3d_upfirdn2d': (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int,
-                               ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64),
-                               ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64),
-                               ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64),
-                               _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_float, _c_void_p]),
-    'p3d_upfirdn2d_acc': (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int,
-                                   ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64),
-                                   ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64),
-                                   ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64),
-                                   _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_float, _c_void_p]),
-    'p3d_frame_finish': (_c_int, [_c_void_p, _c_i32, _c_void_p]),      # (host array of p3d_frame_job: pix2pix3d_amd/views.py)
-    'p3d_paint_strokes': (_c_int, [_c_void_p, _c_i64, _c_void_p, _c_i64, _c_i32, _c_i32, _c_void_p, _c_i32, _c_void_p]),      # (pix2pix3d_amd/edit.py)
-    'p3d_label_features': (_c_int, [_c_void_p, _c_i64, _c_i64, _c_void_p, _c_i32, _c_void_p, _c_i32, ctypes.POINTER(_c_i64),
-                                    _c_i32, _c_i32, _c_i32, _c_i32, _c_void_p]),
-}
+_C_TYPES = {'int': ctypes.c_int32, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'uint8_t': ctypes.c_uint8, 'uint32_t': ctypes.c_uint32,
+            'uint64_t': ctypes.c_uint64, 'float': ctypes.c_float, 'double': ctypes.c_double}
+_DECLARATOR = re.compile(r'(.*?)(\w+)\s*(?:\[\s*(\d*)\s*\])?', re.S)      # [type] name [[n]]
+
+
+class Header:
+    """What one of this project's C99 headers declares, as ctypes needs it: ``functions`` name -> (restype, argtypes), ``structs`` name ->
+    ctypes.Structure class, ``constants`` name -> int (every integer ``#define P3D_*`` and every enumerator).  Every pointer and array
+    parameter is a c_void_p (None, c_void_p, ctypes arrays, byref() and pointer() all convert to it); anything it cannot read is an error."""
+
+    def __init__(self, text, base=None):
+        self.types = dict(base.types if base else _C_TYPES)      # C name -> ctypes type; typedefs and structs join it (base: an #included header)
+        self.functions, self.structs, self.constants = {}, {}, {}
+        text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+        for name, value in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(P3D_\w+)[ \t]+\(?(-?\w+)\)?[ \t]*$', text, flags=re.M):
+            self.constants[name] = int(value, 0)
+        text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{', '', text, flags=re.M)
+        text = re.sub(r'\benum\s*\w*\s*\{([^}]*)\}', self._enum, text)
+        text = re.sub(r'\btypedef\s+struct\s*\w*\s*\{([^}]*)\}\s*(\w+)', self._struct, text)
+        for statement in filter(None, map(str.strip, text.replace('}', ';').split(';'))):      # (the '}' left over closes extern "C")
+            typedef = re.fullmatch(r'typedef\s+void\s*\*\s*(\w+)', statement)
+            proto = re.fullmatch(r'(.*?)(\w+)\s*\((.*)\)', statement, flags=re.S)
+            if typedef:
+                self.types[typedef.group(1)] = ctypes.c_void_p
+            elif proto:
+                ret, name, params = proto.groups()
+                argtypes = [] if params.strip() in ('', 'void') else [self._declare(name, p)[1] for p in params.split(',')]
+                self.functions[name] = (self._ctype(name, ret, returned=True), argtypes)
+            else:
+                raise ValueError(f'header: cannot parse {" ".join(statement.split())!r}')
+
+    def _enum(self, m):
+        value = -1
+        for item in filter(None, map(str.strip, m.group(1).split(','))):
+            name, _, given = map(str.strip, item.partition('='))
+            self.constants[name] = value = int(given, 0) if given else value + 1
+        return ''
+
+    def _struct(self, m):
+        name, fields = m.group(2), []
+        for members in filter(None, map(str.strip, m.group(1).split(';'))):
+            ctype = ''
+            for member in members.split(','):                       # int32_t ci, co;
+                field, t, ctype = self._declare(name, member, ctype, member=True)
+                fields.append((field, t))
+        self.structs[name] = self.types[name] = type(name, (ctypes.Structure,), {'_fields_': fields})
+        return ''
+
+    def _declare(self, symbol, text, ctype='', member=False):
+        """(name, ctypes type, C type) of a parameter or struct member; ``ctype``: the type a member list began with."""
+        m = _DECLARATOR.fullmatch(text.strip())
+        own = m.group(1).strip() if m else ''
+        if not (own or ctype) or (not own and ctype.endswith('*')):
+            raise ValueError(f'header: {symbol}: cannot parse {text.strip()!r}')
+        t = self._ctype(symbol, own or ctype)
+        if m.group(3) is not None:
+            t = t * int(m.group(3)) if member else ctypes.c_void_p      # an array parameter is a pointer
+        return m.group(2), t, own or ctype
+
+    def _ctype(self, symbol, ctype, returned=False):
+        words = ' '.join(w for w in ctype.replace('*', ' * ').split() if w != 'const')
+        if words.endswith('*'):
+            return ctypes.c_char_p if returned and words == 'char *' else ctypes.c_void_p
+        if words not in self.types:
+            raise ValueError(f'header: {symbol}: unknown type {" ".join(ctype.split())!r}')
+        return self.types[words]
+
+    def bind(self, handle):
+        """Set restype / argtypes of every declared function on a loaded library (AttributeError if one is not exported: a stale build)."""
+        for name, signature in self.functions.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = signature
+
+
+def read_header(path, base=None):
+    with open(path) as f:
+        return Header(f.read(), base)
+
+
+# include/p3d_hip.h is the only description of the ABI: every signature, struct and constant on the Python side is read from it, here.
+HEADER = read_header(os.path.join(os.path.dirname(_PKG_DIR), 'include', 'p3d_hip.h'))
+globals().update(HEADER.constants)      # _lib.P3D_OK, _lib.P3D_F32_BF16X3, _lib.P3D_FRAME_MAX_JOBS, ...: under their C names
+globals().update(HEADER.structs)        # _lib.p3d_render_desc, _lib.p3d_demod_job, _lib.p3d_fc_job, _lib.p3d_frame_job
+DTYPE_CODE = {torch.float32: HEADER.constants['P3D_F32'], torch.float16: HEADER.constants['P3D_F16'], torch.float64: HEADER.constants['P3D_F64']}
 
 _lib = None
 _load_error = None
@@ -58,9 +117,7 @@ def _load():
         return
     try:
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in _SIGNATURES.items():
-            fn = getattr(handle, name)          # AttributeError if the .so is stale
-            fn.restype, fn.argtypes = restype, argtypes
+        HEADER.bind(handle)
         _lib = handle
     except (OSError, AttributeError) as e:      # missing file, unresolved HIP runtime, stale build
         _load_error = e
@@ -115,16 +172,8 @@ def lib():
     return _guarded
 
 
-def register(name, restype, argtypes):
-    """Declare the signature of one more exported symbol (used by the op modules)."""
-    _SIGNATURES[name] = (restype, argtypes)
-    if _lib is not None:
-        fn = getattr(_lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-
-
 def check(code, what):
-    if code != P3D_OK:
+    if code != HEADER.constants['P3D_OK']:
         msg = lib().p3d_last_error().decode('utf-8', 'replace')
         raise RuntimeError(f'{what}: libp3d_hip error {code}: {msg}')
 

@@ -23,7 +23,6 @@ cells of 4.  Chart-based unwrapping, mip maps and inpainting of unseen texels ar
 Device tensors run csrc/mesh_atlas.hip, CPU tensors the formulation below, written operation by operation: it is the definition
 (include/p3d_hip.h, "mesh atlas"), and the kernels' bytes equal it.
 """
-import ctypes
 import math
 import os
 from typing import NamedTuple
@@ -31,15 +30,9 @@ from typing import NamedTuple
 import torch
 
 from . import _lib, mesh, texture
-from ._lib import _f32, _i32, _vp
 
 GREY = mesh.GREY
 MIN_SIZE, MAX_SIZE, MIN_CELL = 16, 8192, 4
-
-_lib.register('p3d_mesh_atlas_texels', ctypes.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp])             # csrc/mesh_atlas.hip
-_lib.register('p3d_mesh_atlas_assemble', ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp])
-_lib.register('p3d_mesh_shade_textured', ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _f32,
-                                                        _i32, _i32, _i32, _vp, _vp])
 
 
 # ---- layout -----------------------------------------------------------------------------------------------------------------

@@ -12,7 +12,9 @@ import torch
 
 from . import _lib
 
-PROBES_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'libp3d_probes.so')
+_PKG_DIR = os.path.dirname(os.path.abspath(__file__))
+PROBES_LIB_PATH = os.path.join(_PKG_DIR, 'libp3d_probes.so')
+HEADER = _lib.read_header(os.path.join(_PKG_DIR, 'csrc', 'probes', 'p3d_probes.h'), base=_lib.HEADER)      # (it includes the product header for p3d_stream_t)
 _handle = None
 
 
@@ -25,11 +27,8 @@ def probes():
             h = ctypes.CDLL(PROBES_LIB_PATH)
         except OSError as e:
             raise RuntimeError(f'pix2pix3d_amd: {PROBES_LIB_PATH} could not be loaded ({e}); build it with `python -m pix2pix3d_amd.build`')
-        h.p3d_last_error.restype = ctypes.c_char_p
-        h.p3d_probe_cvt_mfma_hazard.restype = ctypes.c_int
-        h.p3d_probe_cvt_mfma_hazard.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
-        h.p3d_probe_mfma_rate.restype = ctypes.c_int
-        h.p3d_probe_mfma_rate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_void_p]
+        h.p3d_last_error.restype, h.p3d_last_error.argtypes = _lib.HEADER.functions['p3d_last_error']      # (its own copy of the library services)
+        HEADER.bind(h)
         _handle = h
     return _handle
 

@@ -36,7 +36,7 @@ import torch
 
 from . import _lib, mesh, views
 
-MAX_SIZE, MAX_STROKES, MIN_COORD, MAX_COORD = 4096, 65535, -4096, 8191         # P3D_PAINT_* (include/p3d_hip.h)
+MAX_SIZE, MAX_STROKES, MIN_COORD, MAX_COORD = _lib.P3D_PAINT_MAX_SIZE, _lib.P3D_PAINT_MAX_STROKES, _lib.P3D_PAINT_MIN_COORD, _lib.P3D_PAINT_MAX_COORD
 SLIDER_RANGE = dict(yaw=math.pi / 2, pitch=math.pi, roll=math.pi / 4)         # radians per 100 slider units (qt_demo_seg2cat.py:374-379)
 DEMO_RADIUS = 2.7                                                              # (:381)
 FORWARD_FOCAL = 4.2647                                                         # (:439)

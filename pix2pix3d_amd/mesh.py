@@ -18,7 +18,6 @@
   tensors; the CPU formulation is the definition and the bytes are the same).
 * ``extract_mesh``: shape.extract_geometry, the optional clean-up and filters, the labels and the turntable in one call.
 """
-import ctypes
 import functools
 import math
 from typing import NamedTuple
@@ -27,30 +26,13 @@ import numpy as np
 import torch
 
 from . import _lib, configs, shape
-from ._lib import _c_i64 as _i64, _f32, _f64, _i32, _vp
 
-CAMERA_FLOATS = 24             # P3D_MESH_CAMERA_FLOATS
-GREY = 200                     # P3D_MESH_GREY: the albedo of a mesh without colours
+CAMERA_FLOATS = _lib.P3D_MESH_CAMERA_FLOATS
+GREY = _lib.P3D_MESH_GREY      # the albedo of a mesh without colours
 MAX_SIZE = 2048                # largest image edge the kernels take
 _GUARD = 4096 * 256            # guard band, sub-pixel units
 _KEY_BG = torch.iinfo(torch.int64).max
 _SCRIPT_PI = 3.14              # the script's turntable writes pi as 3.14 (extract_mesh.py:245-251)
-
-_lib.register('p3d_mesh_project', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp])
-_lib.register('p3d_mesh_raster_tiles', ctypes.c_int32, [_i32, _i32])
-_lib.register('p3d_mesh_raster_count', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp])
-_lib.register('p3d_mesh_raster_bin', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp])
-_lib.register('p3d_mesh_raster', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp])
-_lib.register('p3d_mesh_shade', ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _i32,
-                                           _vp, _vp])                       # (the above: csrc/mesh_raster.hip; below: csrc/mesh_ops.hip)
-_lib.register('p3d_mesh_components', ctypes.c_int, [_vp, _i32, _i32, _vp, _vp])
-_lib.register('p3d_mesh_cluster_keys', ctypes.c_int, [_vp, _i32, _f32, _f32, _f32, _f64, _i32, _i32, _i32, _vp, _vp])
-_lib.register('p3d_mesh_cluster_means', ctypes.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp])
-_lib.register('p3d_mesh_cluster_faces', ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp])
-_lib.register('p3d_mesh_smooth_step', ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _i64, _vp, _f64, _vp, _vp])         # (csrc/mesh_filter.hip)
-_lib.register('p3d_mesh_label_vote', ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp])
-_lib.register('p3d_mesh_shade_smooth', ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _i32,
-                                                  _i32, _vp, _vp])
 
 
 class Orthographic(NamedTuple):

@@ -14,8 +14,6 @@ The script's three steps and what stands in for each here:
 The per-vertex colour step (:198-215) needs nothing new: ``G.sample_mixed(vertices[None], None, ws, noise_mode='const')['rgb']``
 already runs on the point kernel.
 """
-import ctypes
-
 import torch
 
 from . import _lib, mc_table
@@ -87,11 +85,6 @@ def sigma_grid(G, ws, resolution=512, bound=None, **synthesis_kwargs):
 
 
 # ---- marching cubes -----------------------------------------------------------------------------------------
-_vp, _i32, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-_lib.register('p3d_marching_cubes_blocks', ctypes.c_int64, [_i32, _i32, _i32])
-_lib.register('p3d_marching_cubes_classify', ctypes.c_int, [_vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp])
-_lib.register('p3d_marching_cubes_emit', ctypes.c_int, [_vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64,
-                                                        _vp, _vp, _vp, _vp])
 _cpu_tables = None
 
 

@@ -23,14 +23,12 @@ Device tensors run csrc/surface.hip, CPU tensors the formulation below, written 
 bit for bit, the shade kernel's bytes equal ``_shade_cpu``'s; the occlusion kernel's counts equal ``occlusion_rays``' over the point kernel, the lit
 shade's bytes ``_shade_lit_cpu``'s.
 """
-import ctypes
 import math
 from typing import NamedTuple
 
 import torch
 
 from . import _lib, mesh, shape, texture, views
-from ._lib import _f32, _i32, _vp
 from .training.volumetric_rendering import renderer as _rmod
 
 GREY = mesh.GREY
@@ -38,9 +36,6 @@ MIN_STEPS, MAX_STEPS, MAX_REFINE = 2, 4096, 24          # p3d_surface_cast's lim
 MAX_DIRECTIONS = 255                                     # p3d_surface_occlusion's limit (its counts are bytes); its steps are 1 .. MAX_STEPS
 _MODES = {'lambert': 0, 'normal': 1}
 _RAY_BYTES = 1024                                        # what one ray of a chunk is budgeted at: its points, the features and hidden units behind them
-
-_lib.register('p3d_surface_shade', ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _i32, _i32, _i32, _vp, _vp])      # csrc/surface.hip
-_lib.register('p3d_surface_shade_lit', ctypes.c_int, [_vp] * 9 + [_i32, _i32, _i32, _f32, _i32, _i32, _i32, _vp, _vp])
 
 
 class SurfaceHit(NamedTuple):

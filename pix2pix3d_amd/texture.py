@@ -18,21 +18,14 @@ every vertex takes the weighted mean of the frames it is visible in.
 
 Per-vertex colours only; a UV atlas and a texture image baked by these same two steps are ``pix2pix3d_amd.atlas``.
 """
-import ctypes
 import math
 
 import numpy as np
 import torch
 
 from . import _lib, mesh, views
-from ._lib import _f64, _i32, _vp
 
 GREY = mesh.GREY
-
-_lib.register('p3d_mesh_vertex_normals', ctypes.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp])                 # csrc/mesh_bake.hip
-_lib.register('p3d_mesh_bake_accumulate', ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _i32,
-                                                         _vp, _vp, _vp])
-_lib.register('p3d_mesh_bake_finish', ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp])
 
 
 def _sqrt(x):

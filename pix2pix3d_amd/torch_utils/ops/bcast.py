@@ -5,17 +5,9 @@
 No new reference API — these are the kernels behind ``x * styles``, ``fma.fma`` and the bias-gradient sums where the operands are dense
 device tensors; anything else stays on the tensor-op formulation.  Arithmetic is fp32 with ONE rounding to the tensor dtype, which is
 what the reference's fp16 multiplies / addcmul produce."""
-import ctypes
-
 import torch
 
 from ... import _lib
-
-_vp, _i32 = ctypes.c_void_p, ctypes.c_int32
-_lib.register('p3d_bcast_fma', ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _i32, _i32, _i32, _i32, _i32, _vp])
-_lib.register('p3d_channel_dot_workspace', ctypes.c_int64, [_i32, _i32, _i32, _i32])
-_lib.register('p3d_channel_dot', ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _i32, _i32, _i32, _i32, _vp])
-_lib.register('p3d_pixel_sum', ctypes.c_int, [_vp, _vp, ctypes.c_int, _i32, _i32, _i32, _i32, _vp])
 
 enabled = True
 calls = {'fma': 0, 'dot': 0, 'sum': 0}          # launches through the native route (tests / census)

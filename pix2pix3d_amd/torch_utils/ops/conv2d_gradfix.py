@@ -13,7 +13,6 @@ Anything else (groups, dilation, other strides; CPU tensors) takes torch's own o
 """
 import contextlib
 import threading
-import ctypes
 import os
 
 import torch
@@ -121,15 +120,6 @@ def _note_aten(what, cfg, x, other):
     if len(aten_log) < 16:
         aten_log.append((what, cfg.transpose, cfg.wshape, cfg.stride, cfg.padding, cfg.output_padding, cfg.groups, str(x.dtype), str(getattr(other, 'dtype', None)), tuple(x.shape), str(x.device)))
 
-_vp, _i32, _i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-_lib.register('p3d_conv2d_forward', ctypes.c_int, [_vp] * 5 + [ctypes.c_int] + [_i32] * 10 + [_vp, _i64, _vp])
-_lib.register('p3d_conv2d_bwd_data', ctypes.c_int, [_vp] * 5 + [ctypes.c_int] + [_i32] * 10 + [_vp, _i64, _vp])
-_lib.register('p3d_conv2d_forward_workspace', _i64, [ctypes.c_int] + [_i32] * 8)
-_lib.register('p3d_conv2d_bwd_weight_workspace', _i64, [ctypes.c_int] + [_i32] * 6)
-_lib.register('p3d_conv2d_bwd_weight', ctypes.c_int, [_vp] * 4 + [_i64, ctypes.c_int] + [_i32] * 10 + [_vp])
-_lib.register('p3d_conv2d_bwd_weight_scaled', ctypes.c_int, [_vp] * 4 + [_i64, ctypes.c_int] + [_i32] * 10 + [ctypes.c_float, _vp])
-_lib.register('p3d_conv2d_bwd_weight_route', ctypes.c_int, [ctypes.c_int] + [_i32] * 10 + [ctypes.c_uint32, _i64, ctypes.POINTER(_i32)])
-
 _zero_pages = {}
 
 
@@ -194,11 +184,11 @@ def _native_conv(x, w, cfg, k, stride):
         x, ci = xp, cip
     y = torch.empty([n, co, oh, ow], dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     scratch = None if skinny else torch.empty([co * ci * k * k], dtype=x.dtype, device=x.device)
-    code_dtype = 3 if (cfg.split and x.dtype == torch.float32 and not skinny and k == 3 and ci % 32 == 0) else _lib.DTYPE_CODE[x.dtype]     # 3 = P3D_F32_BF16X3
-    if code_dtype == 0 and not skinny and ci % 32 == 0:
+    code_dtype = _lib.P3D_F32_BF16X3 if (cfg.split and x.dtype == torch.float32 and not skinny and k == 3 and ci % 32 == 0) else _lib.DTYPE_CODE[x.dtype]
+    if code_dtype == _lib.P3D_F32 and not skinny and ci % 32 == 0:
         from . import modconv
         if modconv.f32_x6:
-            code_dtype = 4                                     # P3D_F32_BF16X6: fp32-accurate products on the bf16 matrix pipe (opt-in, modconv.f32_x6)
+            code_dtype = _lib.P3D_F32_BF16X6                   # fp32-accurate products on the bf16 matrix pipe (opt-in, modconv.f32_x6)
     nbytes = 0 if skinny else int(_lib.lib().p3d_conv2d_forward_workspace(code_dtype, n, h, wd, ci, co, k, stride, int(tr)))
     work = torch.empty([nbytes // 4], dtype=torch.float32, device=x.device) if nbytes > 0 else None      # split-K partial tiles (low-resolution layers)
     code = _lib.lib().p3d_conv2d_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(y), _lib.ptr(scratch), _lib.ptr(_zeros_page(x.device)), code_dtype,
@@ -208,7 +198,7 @@ def _native_conv(x, w, cfg, k, stride):
     native_calls['forward'] += 1
     log = _lib.kernel_events.get('conv_flops')               # bench.py's arithmetic floor: (arithmetic class, multiply-add FLOPs) of every native convolution
     if log is not None:
-        log.append(('bf16x3' if code_dtype == 3 else ('bf16x6' if code_dtype == 4 else str(x.dtype)), 2.0 * n * ci * co * k * k * (h * wd if (tr and stride == 2) else oh * ow)))
+        log.append(('bf16x3' if code_dtype == _lib.P3D_F32_BF16X3 else ('bf16x6' if code_dtype == _lib.P3D_F32_BF16X6 else str(x.dtype)), 2.0 * n * ci * co * k * k * (h * wd if (tr and stride == 2) else oh * ow)))
     return y
 
 
@@ -246,7 +236,7 @@ def _native_weight_grad(grad_output, x, cfg, k, stride, scale=None):
         # takes the exact kernels for every other geometry, whatever the code says; mirrored here for the FLOP log's arithmetic class
         x6 = modconv.f32_x6 and modconv.wgrad_x6 and cs > 64 and cb > 64 and cs % 4 == 0 and cb % 4 == 0
         if x6:
-            code_dtype = 4
+            code_dtype = _lib.P3D_F32_BF16X6
     nbytes = int(_lib.lib().p3d_conv2d_bwd_weight_workspace(code_dtype, n, hs, ws_, cs, cb, k))
     work = torch.empty([nbytes // 4], dtype=torch.float32, device=x.device)
     if scale is None:

@@ -17,15 +17,12 @@ front of the convolution that conv2d_resample.py:108-118 makes it.
 Not taken (the caller falls back to the unfused formulation): CPU tensors, up-sampling layers, channel counts that are not whole K
 rows of the matrix-core kernels (the 6 / 18-channel fromrgb layers), activations other than linear / lrelu.
 """
-import ctypes
 import os
 
 import torch
 
 from ... import _lib
 from . import bias_act, conv2d_gradfix, modconv, upfirdn2d
-
-_lib.register('p3d_demod_coefs_backward', ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_int32] * 4 + [ctypes.c_void_p])
 
 enabled = os.environ.get('P3D_CONV_LAYER', '1') != '0'      # off: Conv2dLayer keeps the unfused formulation in training passes (tests / A-B measurements)
 calls = {'forward': 0, 'backward': 0}

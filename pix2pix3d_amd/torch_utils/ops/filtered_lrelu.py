@@ -12,8 +12,6 @@ autograd.  Geometries whose tiles do not fit LDS come back with the plugin's "no
 route the reference takes in that case: ``upfirdn2d`` -> ``p3d_filtered_lrelu_act`` (in place, same sign tensor) -> ``upfirdn2d``.
 CPU tensors use the plain four-step composition (:123-148).
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -21,11 +19,6 @@ from ... import _lib
 from . import bias_act
 from . import upfirdn2d
 from .upfirdn2d import _get_filter_size, _parse_padding
-
-_vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-_p32, _p64 = ctypes.POINTER(_i32), ctypes.POINTER(_i64)
-_lib.register('p3d_filtered_lrelu', ctypes.c_int, [_vp] * 6 + [ctypes.c_int, _p32, _p64, _p32, _p64, _i64] + [_i32] * 13 + [_f32] * 3 + [_i32, _i32, _vp])
-_lib.register('p3d_filtered_lrelu_act', ctypes.c_int, [_vp, _vp, ctypes.c_int, _p32, _p64] + [_i32] * 4 + [_f32] * 3 + [_i32, _vp])
 
 
 def _ref_composition(x, fu, fd, b, up, down, padding, gain, slope, clamp, flip_filter, impl):

@@ -47,31 +47,6 @@ def plan_joined(stream):
     return plan_wait_elision and plan_for(stream.device).joined(stream)
 
 
-_vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-_lib.register('p3d_modulate_weights', ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp])
-_lib.register('p3d_conv2d_nhwc', ctypes.c_int, [_vp] * 3 + [ctypes.c_int] + [_vp] * 4 + [_i32] * 5 + [_i64, _i32, _i32, _i32, _f32, _f32, _vp])
-_lib.register('p3d_conv2d_nhwc_ws', ctypes.c_int, [_vp] * 3 + [ctypes.c_int] + [_vp] * 4 + [_i32] * 5 + [_i64, _i32, _i32, _i32, _f32, _f32, _vp, _i64, _vp])
-_lib.register('p3d_conv2d_nhwc_workspace', _i64, [ctypes.c_int] + [_i32] * 5 + [_i64, _i32, _i32])
-_lib.register('p3d_conv2d_nhwc_route', ctypes.c_int, [ctypes.c_int] + [_i32] * 5 + [_i64] + [_i32] * 4 + [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64)])
-_lib.register('p3d_conv3x3_torgb_f16', ctypes.c_int, [_vp] * 8 + [_i32, _f32] + [_i32] * 5 + [ctypes.c_int64, _i32, _f32, _f32, _vp])
-_lib.register('p3d_conv3x3_torgb_split', ctypes.c_int, [_vp] * 11 + [_i32, _f32] + [_i32] * 5 + [ctypes.c_int64, _i32, _f32, _f32, _vp])
-_lib.register('p3d_conv2d_nhwc_scaled', ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp] + [_i32] * 5 + [ctypes.c_int64] + [_i32] * 3 + [_f32, _f32, _vp, ctypes.c_int64, _vp])
-_lib.register('p3d_demod_coefs', ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp])
-_lib.register('p3d_conv2d_nhwc_scaled_in', ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int] + [_vp] * 6 + [_i32] * 5 + [ctypes.c_int64, _i32, _i32, _i32, _f32, _f32, _vp, ctypes.c_int64, _vp])
-_lib.register('p3d_up2_fir_bf16x3', ctypes.c_int, [_vp] * 8 + [_i32] * 5 + [ctypes.c_int64, _f32, _i32, _f32, _f32, _vp])
-_lib.register('p3d_up2_fir_f16', ctypes.c_int, [_vp] * 8 + [_i32] * 5 + [ctypes.c_int64, _f32, _i32, _f32, _f32, _vp])
-_lib.register('p3d_fir4_bias_act_nhwc', ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int] + [_i32] * 9 + [_f32, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _vp])
-_lib.register('p3d_fc_forward', ctypes.c_int, [_vp] * 4 + [_i32] * 3 + [_i64, _f32, _f32, _i32, _f32, _f32, _f32, _vp])
-_lib.register('p3d_im2col3x3', ctypes.c_int, [_vp, _vp] + [_i32] * 6 + [_i64] * 4 + [_vp])
-_lib.register('p3d_noise_bias_act', ctypes.c_int, [_vp] * 5 + [_i32] * 4 + [_f32, _f32, _f32, _vp])
-_lib.register('p3d_torgb_nhwc_f16', ctypes.c_int, [_vp] * 5 + [_i32] * 4 + [_f32, _i32, _vp])
-_lib.register('p3d_conv2d_nhwc_bf16x3_io_plan', ctypes.c_int, [_i32] * 5 + [ctypes.c_int64, _i32, _i32, _i32, _i32, ctypes.POINTER(ctypes.c_int64)])
-_lib.register('p3d_conv2d_nhwc_bf16x3_io', ctypes.c_int, [_vp] * 7 + [_i32] * 5 + [ctypes.c_int64, _i32, _i32, _i32, _f32, _f32, _i32, _i32, _vp, ctypes.c_int64, _vp])
-_lib.register('p3d_torgb_wide_split', ctypes.c_int, [_vp] * 6 + [_i32] * 5 + [_f32, _vp])
-_lib.register('p3d_fir4_bias_act_nhwc_split', ctypes.c_int, [_vp] * 3 + [_i32] * 9 + [_f32, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _vp])
-_lib.register('p3d_demod_coefs_multi', ctypes.c_int, [ctypes.c_void_p, _i32, _i32, _vp])
-_lib.register('p3d_fc_multi', ctypes.c_int, [ctypes.c_void_p, _i32, _i32, _vp])
-
 min_pixels = 1               # every layer takes this module (the vendor conv library is never entered: its choices for the small
                              # layers — naive kernels on a fresh box — cost milliseconds)
 gemm_max_pixels = int(os.environ.get('P3D_GEMM_MAX_PIXELS', 0))
@@ -132,8 +107,8 @@ def torgb_supported(x, weight, styles, fused_modconv):
 
 
 BF16X3 = 'bf16x3'            # dtype tag: fp32 tensors whose products run as three bf16 MFMAs of (hi, lo) splits (csrc/conv2d.hip)
-DTYPE_F32_BF16X3 = 3         # p3d_dtype code of that formulation (include/p3d_hip.h)
-DTYPE_F32_BF16X6 = 4         # P3D_F32_BF16X6: plain fp32 tensors and weights, every product as SIX bf16 MFMAs of three-piece splits made in registers (fp32-accurate)
+DTYPE_F32_BF16X3 = _lib.P3D_F32_BF16X3         # p3d_dtype code of that formulation
+DTYPE_F32_BF16X6 = _lib.P3D_F32_BF16X6         # plain fp32 tensors and weights, every product as SIX bf16 MFMAs of three-piece splits made in registers (fp32-accurate)
 f32_x6 = os.environ.get('P3D_F32_BF16X6', '1') == '1'      # the fp32 convolutions that would run on the f32-input MFMA run as bf16x6 instead — inference layers here (when bf16x3 is off),
                              # training-mode forward / data gradient in conv2d_gradfix; ignored wherever bf16x3 is selected.  On by default since the whole GPU suite passed
                              # under it with unchanged bounds and its error against fp64 is the exact kernels' (DESIGN 2.4c); '0' = every product on v_mfma_f32_32x32x2_f32
@@ -266,18 +241,14 @@ def demod_coefs(weight, styles):
     return d
 
 
-class _DemodJob(ctypes.Structure):
-    _fields_ = [('styles', ctypes.c_void_p), ('w2', ctypes.c_void_p), ('d', ctypes.c_void_p), ('ci', ctypes.c_int32), ('co', ctypes.c_int32)]
-
-
-DEMOD_MAX_JOBS = 24
+DEMOD_MAX_JOBS = _lib.P3D_DEMOD_MAX_JOBS
 
 
 def demod_coefs_many(pairs):
     """demod_coefs for several (weight, styles) pairs with the same row count in ONE launch (bit-identical to one call each)."""
     if len(pairs) == 1 or len(pairs) > DEMOD_MAX_JOBS or len({st.shape[0] for _, st in pairs}) != 1:
         return [demod_coefs(w, st) for w, st in pairs]
-    arr, keep, outs = (_DemodJob * len(pairs))(), [], []
+    arr, keep, outs = (_lib.p3d_demod_job * len(pairs))(), [], []
     n = pairs[0][1].shape[0]
     for k, (weight, styles) in enumerate(pairs):
         w2 = _cached_weight(weight, 'w2_tapsum', lambda weight=weight: weight.detach().float().square().sum(dim=[2, 3]).contiguous())
@@ -285,7 +256,7 @@ def demod_coefs_many(pairs):
         d = torch.empty([n, weight.shape[0]], dtype=torch.float32, device=weight.device)
         keep.append((w2, s32))
         outs.append(d)
-        arr[k] = _DemodJob(_lib.ptr(s32), _lib.ptr(w2), _lib.ptr(d), s32.shape[1], weight.shape[0])
+        arr[k] = _lib.p3d_demod_job(_lib.ptr(s32), _lib.ptr(w2), _lib.ptr(d), s32.shape[1], weight.shape[0])
     _lib.check(_lib.lib().p3d_demod_coefs_multi(ctypes.cast(arr, ctypes.c_void_p), len(pairs), n, _lib.stream_of(outs[0])), 'demod_coefs_multi')
     return outs
 
@@ -568,13 +539,7 @@ def fc(x, weight, bias, weight_gain, bias_gain, activation='linear', out_scale=1
     return y
 
 
-class _FcJob(ctypes.Structure):
-    _fields_ = [('x', ctypes.c_void_p), ('w', ctypes.c_void_p), ('b', ctypes.c_void_p), ('y', ctypes.c_void_p), ('x_row_stride', ctypes.c_int64),
-                ('in_features', ctypes.c_int32), ('out_features', ctypes.c_int32), ('weight_gain', ctypes.c_float), ('bias_gain', ctypes.c_float),
-                ('act', ctypes.c_int32), ('alpha', ctypes.c_float), ('act_gain', ctypes.c_float), ('out_scale', ctypes.c_float)]
-
-
-FC_MAX_JOBS = 40
+FC_MAX_JOBS = _lib.P3D_FC_MAX_JOBS
 
 
 def fc_multi(jobs):
@@ -583,7 +548,7 @@ def fc_multi(jobs):
     n = jobs[0][0].shape[0]
     assert all(x.shape[1] % 4 == 0 for x, _, _ in jobs)
     outs, keep = [], []
-    arr = (_FcJob * len(jobs))()
+    arr = (_lib.p3d_fc_job * len(jobs))()
     for k, (x, layer, out_scale) in enumerate(jobs):
         x32 = x.detach()
         if x32.stride(1) != 1 or x32.stride(0) % 4 != 0 or x32.data_ptr() % 16 != 0:
@@ -593,7 +558,7 @@ def fc_multi(jobs):
         y = torch.empty([n, w32.shape[0]], dtype=torch.float32, device=x.device)
         keep.append((x32, w32, b32))
         outs.append(y)
-        arr[k] = _FcJob(_lib.ptr(x32), _lib.ptr(w32), _lib.ptr(b32), _lib.ptr(y), x32.stride(0) if n > 1 else x.shape[1], x.shape[1], w32.shape[0],
+        arr[k] = _lib.p3d_fc_job(_lib.ptr(x32), _lib.ptr(w32), _lib.ptr(b32), _lib.ptr(y), x32.stride(0) if n > 1 else x.shape[1], x.shape[1], w32.shape[0],
                         float(layer.weight_gain), float(layer.bias_gain), {'linear': 1, 'lrelu': 3}[layer.activation], 0.2,
                         float(bias_act.activation_funcs[layer.activation].def_gain), float(out_scale))
     code = _lib.lib().p3d_fc_multi(ctypes.cast(arr, ctypes.c_void_p), len(jobs), n, _lib.stream_of(outs[0]))

@@ -1,12 +1,8 @@
 """Pixel-centre rays from OpenCV-convention cameras (reference: training/volumetric_rendering/ray_sampler.py:24-62)."""
-import ctypes
-
 import torch
 
 from ... import _lib
 
-_lib.register('p3d_ray_sample', ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int32] * 2 + [ctypes.c_void_p])
-_lib.register('p3d_ray_sample_labels', ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int32] * 2 + [ctypes.c_void_p])
 native = True        # device inference: one launch instead of ~20 tensor ops (csrc/small_ops.hip)
 
 

@@ -44,40 +44,7 @@ fused_training = True          # graphs that need gradients: fused forward + rec
 fused_backward = True          # ... with the backward on the device kernels of csrc/render_bwd.hip (False: replay the tensor-op renderer)
 mlp_bf16x3 = os.environ.get('P3D_MLP_BF16X3', '1') != '0'      # inference: the decoder MLPs as three bf16 MFMAs per fp32 product (csrc/render_device.h)
 mlp_l1x6 = os.environ.get('P3D_MLP_L1X6', '1') != '0'          # exact forward passes (training, bf16x3 off), with modconv.f32_x6: layer 1 of the decoder MLPs as bf16x6 (fp32-accurate)
-
-
-class _RenderDesc(ctypes.Structure):          # p3d_render_desc (include/p3d_hip.h)
-    _fields_ = [('n_img', ctypes.c_int32), ('rays_per_img', ctypes.c_int32), ('plane_h', ctypes.c_int32), ('plane_w', ctypes.c_int32),
-                ('n_nets', ctypes.c_int32), ('semantic_sigmoid', ctypes.c_int32), ('depth_resolution', ctypes.c_int32),
-                ('depth_resolution_importance', ctypes.c_int32), ('disparity_space_sampling', ctypes.c_int32), ('white_back', ctypes.c_int32),
-                ('ray_start', ctypes.c_float), ('ray_end', ctypes.c_float), ('box_warp', ctypes.c_float),
-                ('image_stride', ctypes.c_int64), ('plane_stride', ctypes.c_int64), ('pixel_stride', ctypes.c_int64), ('raster_order', ctypes.c_int32),
-                ('mlp_bf16x3', ctypes.c_int32)]
-
-
-_vp, _i32, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-_lib.register('p3d_render_decoder_floats', ctypes.c_int, [])
-_lib.register('p3d_planes_to_channels_last', ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp])
-_lib.register('p3d_pack_decoder', ctypes.c_int, [_vp] * 8 + [_i32, _f32, _vp, _vp])
-_lib.register('p3d_pack_decoder_bf16x3', ctypes.c_int, [_vp] * 8 + [_i32, _f32, _vp, _vp])
-_lib.register('p3d_pack_decoder_l1x6', ctypes.c_int, [_vp] * 8 + [_i32, _f32, _vp, _vp])
-_lib.register('p3d_render_bwd_decoder_floats', ctypes.c_int, [])
-_lib.register('p3d_render_grad_decoder_floats', ctypes.c_int, [])
-_lib.register('p3d_pack_decoder_bwd', ctypes.c_int, [_vp] * 4 + [ctypes.c_int32, ctypes.c_float, _vp, _vp])
-_lib.register('p3d_render_backward', ctypes.c_int, [_vp] * 9 + [ctypes.POINTER(_RenderDesc)] + [_vp] * 6 + [_vp])
-_lib.register('p3d_render_forward', ctypes.c_int, [_vp] * 8 + [ctypes.POINTER(_RenderDesc)] + [_vp] * 6 + [_vp])
-_lib.register('p3d_render_forward_debug', ctypes.c_int, [_vp] * 8 + [ctypes.POINTER(_RenderDesc)] + [_vp] * 7 + [_vp])
-_lib.register('p3d_sample_points', ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(_RenderDesc), _i32, _vp, _vp, _vp])
-_lib.register('p3d_sample_points_backward', ctypes.c_int, [_vp] * 4 + [ctypes.POINTER(_RenderDesc), _i32] + [_vp] * 4 + [_vp])
-_lib.register('p3d_importance_sample', ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp])
-_lib.register('p3d_importance_sample_index', ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp])
-_lib.register('p3d_render_decoder_floats_dual', ctypes.c_int, [])
-_lib.register('p3d_pack_decoder_dual', ctypes.c_int, [_vp] * 8 + [_f32, _vp, _vp])
-_lib.register('p3d_render_forward_dual', ctypes.c_int, [_vp] * 9 + [ctypes.POINTER(_RenderDesc)] + [_vp] * 4 + [_vp])
-_lib.register('p3d_sample_points_dual', ctypes.c_int, [_vp] * 4 + [ctypes.POINTER(_RenderDesc), _i32, _vp, _vp, _vp])
-_lib.register('p3d_sample_lattice', ctypes.c_int, [_vp, _vp, ctypes.POINTER(_RenderDesc), _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp])
-_lib.register('p3d_surface_cast', ctypes.c_int, [_vp, _vp, ctypes.POINTER(_RenderDesc), _vp, _vp, _f32, _f32, _i32, _i32, _f32, _f32, _f32, _i32] + [_vp] * 5)
-_lib.register('p3d_surface_occlusion', ctypes.c_int, [_vp, _vp, ctypes.POINTER(_RenderDesc), _vp, _vp, _vp, _vp, _i32, _f32, _i32, _f32, _f32, _i32, _vp, _vp, _vp])
+_RenderDesc = _lib.p3d_render_desc      # the struct class, derived from include/p3d_hip.h
 
 
 def generate_planes():
@@ -231,7 +198,7 @@ def _needs_grad(tensors, decoders):
 def render_desc(n_img, rays_per_img, plane_h, plane_w, strides, n_nets, semantic_sigmoid, mode, options, numeric_limits=False, raster=0):
     """p3d_render_desc from shapes, plane strides, decoder form, MLP mode and options.  ``numeric_limits``: the rays run from options['ray_start'] to
     ['ray_end'] (else per-ray limits travel as tensors, or — point queries — there are no rays); ``raster`` is a pure scheduling hint, plus
-    P3D_RENDER_SHARED_PLANES (2)."""
+    P3D_RENDER_SHARED_PLANES."""
     start, end = (options['ray_start'], options['ray_end']) if numeric_limits else (0.0, 0.0)
     return _RenderDesc(n_img, rays_per_img, plane_h, plane_w, n_nets, int(semantic_sigmoid), int(options.get('depth_resolution', 0)),
                        int(options.get('depth_resolution_importance', 0)), int(bool(options.get('disparity_space_sampling', False))),
@@ -669,7 +636,7 @@ def fused_surface_cast(planes, decoder, ray_o, ray_d, opt, near, far, steps, ref
     hit = torch.empty([n, m], dtype=torch.uint8, device=dev)
     depth = torch.empty([n, m], dtype=torch.float32, device=dev)
     position, grad = torch.empty([n, m, 3], dtype=torch.float32, device=dev), torch.empty([n, m, 3], dtype=torch.float32, device=dev)
-    desc = ctx.desc(opt, rays_per_img=m, raster=2 if shared else 0, n_img=n)             # P3D_RENDER_SHARED_PLANES (2): the N ray sets all read the one plane set
+    desc = ctx.desc(opt, rays_per_img=m, raster=_lib.P3D_RENDER_SHARED_PLANES if shared else 0, n_img=n)             # the N ray sets all read the one plane set
     dt = (float(far) - float(near)) / (int(steps) - 1) if int(steps) > 1 else 0.0
     code = _lib.lib().p3d_surface_cast(_lib.ptr(ctx.planes_cl), _lib.ptr(ctx.packed), ctypes.byref(desc), _lib.ptr(o), _lib.ptr(d), float(near), dt,
                                        int(steps), int(refine), float(threshold), float(eps), float(half_box), int(raster_width),
@@ -700,7 +667,7 @@ def fused_surface_occlusion(planes, decoder, origin, facing, active, directions,
         raise RuntimeError(f'fused_surface_occlusion: raster_width {raster_width} must be 0, or a multiple of 8 whose square is the number of points ({m})')
     ctx = _FusedContext(planes, _decoder_nets(decoder))
     open_, total = torch.empty([n, m], dtype=torch.uint8, device=dev), torch.empty([n, m], dtype=torch.uint8, device=dev)
-    desc = ctx.desc(opt, rays_per_img=m, raster=2 if shared else 0, n_img=n)             # P3D_RENDER_SHARED_PLANES (2), as the cast
+    desc = ctx.desc(opt, rays_per_img=m, raster=_lib.P3D_RENDER_SHARED_PLANES if shared else 0, n_img=n)             # as the cast
     code = _lib.lib().p3d_surface_occlusion(_lib.ptr(ctx.planes_cl), _lib.ptr(ctx.packed), ctypes.byref(desc), _lib.ptr(o), _lib.ptr(f), _lib.ptr(act),
                                             _lib.ptr(dirs), k, float(reach) / steps, steps, float(threshold), float(half_box), raster_width,
                                             _lib.ptr(open_), _lib.ptr(total), _lib.stream_of(open_))
@@ -837,8 +804,8 @@ def fused_render(planes, decoder, ray_origins, ray_directions, opt, u_coarse, u_
     dbg_f = torch.empty([n * m, sf], device=dev, dtype=torch.float32) if debug else None
     dbg_w = torch.empty([n * m, sc - 1], device=dev, dtype=torch.float32) if debug else None
     dbg_b = torch.empty([n * m, sf], device=dev, dtype=torch.int32) if debug == 'bins' else None
-    # raster 1 is a pure scheduling hint; + P3D_RENDER_SHARED_PLANES (2): the N ray sets all read the one plane set, each keeping its own R x R raster
-    d = ctx.desc(opt, rays_per_img=m, numeric_limits=t0 is None, raster=3 if shared else 1, n_img=n)
+    # raster 1 is a pure scheduling hint; + P3D_RENDER_SHARED_PLANES: the N ray sets all read the one plane set, each keeping its own R x R raster
+    d = ctx.desc(opt, rays_per_img=m, numeric_limits=t0 is None, raster=1 | _lib.P3D_RENDER_SHARED_PLANES if shared else 1, n_img=n)
     with _lib.kernel_timer('render_forward', feat):
         if dbg_b is not None:
             code = _lib.lib().p3d_render_forward_debug(_lib.ptr(ctx.planes_cl), _lib.ptr(ctx.packed), _lib.ptr(ro), _lib.ptr(rd), _lib.ptr(uc), _lib.ptr(uf),

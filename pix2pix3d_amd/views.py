@@ -29,18 +29,9 @@ import torch
 from . import _lib, mesh
 from .training.volumetric_rendering import renderer as rmod
 
-SCALE, LABEL = 0, 1                    # P3D_FRAME_SCALE / P3D_FRAME_LABEL
-MAX_JOBS = 4                           # P3D_FRAME_MAX_JOBS
-
-
-class _FrameJobC(ctypes.Structure):    # p3d_frame_job (include/p3d_hip.h)
-    _fields_ = [('src', ctypes.c_void_p), ('src_stride', ctypes.c_int64 * 4),
-                ('dst', ctypes.c_void_p), ('dst_row_pitch', ctypes.c_int64), ('dst_frame_pitch', ctypes.c_int64),
-                ('dst_index', ctypes.c_void_p), ('index_row_pitch', ctypes.c_int64), ('index_frame_pitch', ctypes.c_int64),
-                ('palette_dev', ctypes.c_void_p),
-                ('mode', ctypes.c_int32), ('n', ctypes.c_int32), ('c', ctypes.c_int32), ('h', ctypes.c_int32), ('w', ctypes.c_int32),
-                ('x0', ctypes.c_int32), ('y0', ctypes.c_int32), ('dst_bpp', ctypes.c_int32),
-                ('lo', ctypes.c_float), ('scale', ctypes.c_float), ('palette', ctypes.c_uint8 * 192)]
+SCALE, LABEL = _lib.P3D_FRAME_SCALE, _lib.P3D_FRAME_LABEL
+MAX_JOBS = _lib.P3D_FRAME_MAX_JOBS
+_FrameJobC = _lib.p3d_frame_job         # the struct class, derived from include/p3d_hip.h
 
 
 class FrameJob(NamedTuple):

@@ -1,8 +1,12 @@
 """The C-ABI shared library: loads without a GPU and exports every symbol include/*.h declares."""
 import ctypes
 import glob
+import json
 import os
 import re
+import shutil
+import subprocess
+import sys
 
 import pytest
 
@@ -28,18 +32,139 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert isinstance(_lib.launch_count(), int)
 
 
-def test_python_binding_covers_every_declared_symbol():
+_KIND = {ctypes.c_void_p: 'ptr', ctypes.c_char_p: 'cstr', ctypes.c_int32: 'i32', ctypes.c_int64: 'i64', ctypes.c_uint32: 'u32', ctypes.c_uint64: 'u64',
+         ctypes.c_float: 'f32', ctypes.c_double: 'f64'}
+_PROBES_HEADER = os.path.join(ROOT, 'pix2pix3d_amd', 'csrc', 'probes', 'p3d_probes.h')
+_STRUCT_SIZES = {'p3d_frame_job': 328, 'p3d_demod_job': 32, 'p3d_fc_job': 72, 'p3d_render_desc': 88}      # of the hand-written mirrors this binding replaced
+
+
+def _probes_header():
     from pix2pix3d_amd import _lib
-    _lib.lib()
-    import importlib
-    for m in ('torch_utils.ops.bias_act', 'torch_utils.ops.upfirdn2d', 'torch_utils.ops.modconv', 'torch_utils.ops.filtered_lrelu', 'torch_utils.ops.conv2d_gradfix', 'torch_utils.ops.bcast', 'torch_utils.ops.conv_layer',
-              'training.volumetric_rendering.renderer', 'training.volumetric_rendering.ray_sampler', 'diagnostics'):
-        try:
-            importlib.import_module('pix2pix3d_amd.' + m)          # op modules register their entry points on import
-        except ImportError:
-            pass
-    missing = [n for n in _declared_symbols() if n not in _lib._SIGNATURES]
-    assert not missing, f'no ctypes signature for {missing}'
+    return _lib.read_header(_PROBES_HEADER, base=_lib.HEADER)
+
+
+def test_derived_signatures_equal_the_hand_written_table_they_replaced():
+    """tests/golden/abi_signatures_parent.json: the 95 hand-written signatures of the last commit that had them plus the probe library's two, as
+    name -> [restype kind, argument kinds...] (every pointer type a 'ptr', c_int an 'i32').  The header-derived table equalled it with no difference,
+    so no entry is corrected."""
+    from pix2pix3d_amd import _lib
+    with open(os.path.join(ROOT, 'tests', 'golden', 'abi_signatures_parent.json')) as f:
+        want = json.load(f)
+    functions = {**_lib.HEADER.functions, **_probes_header().functions}
+    got = {name: [_KIND[restype]] + [_KIND[a] for a in argtypes] for name, (restype, argtypes) in functions.items()}
+    assert len(want) == 97 and sorted(got) == sorted(want)
+    assert not {name: (got[name], want[name]) for name in want if got[name] != want[name]}
+
+
+def test_every_declared_prototype_is_parsed_and_bound_by_importing_lib_alone():
+    from pix2pix3d_amd import _lib
+    declared = _declared_symbols()
+    assert sorted(_lib.HEADER.functions) == declared and len(declared) >= 95
+    child = ('import json, sys; from pix2pix3d_amd import _lib; raw = _lib.lib()._handle; '
+             'print(json.dumps([n for n in sys.argv[1:] if getattr(raw, n).argtypes is None]))')
+    r = subprocess.run([sys.executable, '-c', child] + declared, capture_output=True, text=True, cwd=ROOT)
+    assert r.returncode == 0, r.stderr
+    assert json.loads(r.stdout.strip().splitlines()[-1]) == []
+
+
+def test_every_entry_point_the_package_calls_is_declared():
+    """The source scan of the test this replaces (test_render_routes.py, "every module registers the entry points it calls"): with the signatures
+    set from the header when the library is loaded (the test above), a call needs its name declared and nothing else — not an import of some module."""
+    import pathlib
+    from pix2pix3d_amd import _lib
+    root = pathlib.Path(ROOT) / 'pix2pix3d_amd'
+    probes = _probes_header().functions
+    assert probes and not set(probes) & set(_lib.HEADER.functions)
+    checked = 0
+    for path in sorted(root.rglob('*.py')):
+        called = set(re.findall(r'\blib(?:\(\))?\.(p3d_\w+)', path.read_text()))
+        declared = set(_lib.HEADER.functions) | (set(probes) if path.name == 'diagnostics.py' else set())
+        checked += bool(called)
+        assert called <= declared, (str(path.relative_to(root)), sorted(called - declared))
+    assert checked >= 8
+
+
+_LAYOUT_C = '''#include "p3d_hip.h"
+#include <stddef.h>
+#include <stdio.h>
+int main(void) {
+%s    return 0;
+}
+'''
+
+
+def _compile_and_run(tmp_path, gcc, source):
+    src, exe = tmp_path / 'abi_probe.c', tmp_path / 'abi_probe'
+    src.write_text(source)
+    r = subprocess.run([gcc, '-std=c99', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return [line.split() for line in r.stdout.splitlines()]
+
+
+def test_struct_layouts_equal_the_c_compilers(tmp_path):
+    from pix2pix3d_amd import _lib
+    structs = _lib.HEADER.structs
+    assert {name: ctypes.sizeof(c) for name, c in structs.items()} == _STRUCT_SIZES
+    assert all(getattr(_lib, name) is c for name, c in structs.items())
+    assert isinstance(_lib.p3d_frame_job().src_stride, ctypes.c_int64 * 4) and isinstance(_lib.p3d_frame_job().palette, ctypes.c_uint8 * 192)
+    gcc = shutil.which('gcc')
+    if gcc is None:
+        pytest.skip('no gcc')
+    body = ''
+    for name, c in structs.items():
+        body += f'    printf("{name} %zu\\n", sizeof({name}));\n'
+        for field, _ in c._fields_:
+            body += f'    printf("{name}.{field} %zu %zu\\n", offsetof({name}, {field}), sizeof((({name}*)0)->{field}));\n'
+    got = {k: [int(x) for x in v] for k, *v in _compile_and_run(tmp_path, gcc, _LAYOUT_C % body)}
+    want = {name: [ctypes.sizeof(c)] for name, c in structs.items()}
+    want.update({f'{name}.{field}': [getattr(c, field).offset, getattr(c, field).size] for name, c in structs.items() for field, _ in c._fields_})
+    assert got == want and len(want) == 4 + 18 + 5 + 13 + 20
+
+
+# the literals the package carried before it read them from the header, by the header's names
+_CONSTANTS_BEFORE = {'P3D_OK': 0, 'P3D_ERR_UNSUPPORTED': -1, 'P3D_F32': 0, 'P3D_F16': 1, 'P3D_F64': 2, 'P3D_F32_BF16X3': 3, 'P3D_F32_BF16X6': 4,
+                     'P3D_RENDER_SHARED_PLANES': 2, 'P3D_MESH_CAMERA_FLOATS': 24, 'P3D_MESH_GREY': 200, 'P3D_DEMOD_MAX_JOBS': 24, 'P3D_FC_MAX_JOBS': 40,
+                     'P3D_FRAME_MAX_JOBS': 4, 'P3D_FRAME_SCALE': 0, 'P3D_FRAME_LABEL': 1, 'P3D_PAINT_MAX_SIZE': 4096, 'P3D_PAINT_MAX_STROKES': 65535,
+                     'P3D_PAINT_MIN_COORD': -4096, 'P3D_PAINT_MAX_COORD': 8191}
+
+
+def test_constants_equal_the_c_compilers_and_the_public_names_follow_them(tmp_path):
+    import torch
+    from pix2pix3d_amd import _lib, edit, mesh, views
+    from pix2pix3d_amd.torch_utils.ops import modconv
+    constants = _lib.HEADER.constants
+    src = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'p3d_hip.h')).read(), flags=re.S)
+    defines = set(re.findall(r'#\s*define\s+(P3D_\w+)[ \t]+\S', src))
+    enumerators = {n for body in re.findall(r'\benum\b[^{;]*\{([^}]*)\}', src) for n in re.findall(r'\b(P3D_\w+)\b', body)}
+    assert len(defines) >= 14 and len(enumerators) >= 35 and set(constants) == defines | enumerators
+    assert all(getattr(_lib, name) == value for name, value in constants.items())
+    assert {name: constants[name] for name in _CONSTANTS_BEFORE} == _CONSTANTS_BEFORE
+    assert _lib.DTYPE_CODE == {torch.float32: 0, torch.float16: 1, torch.float64: 2}
+    assert (mesh.CAMERA_FLOATS, mesh.GREY, views.MAX_JOBS, views.SCALE, views.LABEL) == (24, 200, 4, 0, 1)
+    assert (edit.MAX_SIZE, edit.MAX_STROKES, edit.MIN_COORD, edit.MAX_COORD) == (4096, 65535, -4096, 8191)
+    assert (modconv.FC_MAX_JOBS, modconv.DEMOD_MAX_JOBS, modconv.DTYPE_F32_BF16X3, modconv.DTYPE_F32_BF16X6) == (40, 24, 3, 4)
+    gcc = shutil.which('gcc')
+    if gcc is None:
+        pytest.skip('no gcc')
+    body = ''.join(f'    printf("{name} %lld\\n", (long long)({name}));\n' for name in sorted(constants))
+    assert {k: int(v) for k, v in _compile_and_run(tmp_path, gcc, _LAYOUT_C % body)} == constants
+
+
+def test_a_prototype_the_parser_cannot_type_is_an_error_that_names_it():
+    from pix2pix3d_amd import _lib
+    ok = _lib.Header('typedef void* p3d_stream_t;\nint p3d_fine(const float* x, int32_t n[2], double f, p3d_stream_t stream);')
+    assert ok.functions == {'p3d_fine': (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p])}
+    for text, symbol, what in (('int p3d_fine(void);\nint p3d_odd(const float* x, unsigned n);', 'p3d_odd', 'unsigned'),
+                               ('size_t p3d_sized(int n);', 'p3d_sized', 'size_t'),
+                               ('int p3d_streamed(p3d_stream_t stream);', 'p3d_streamed', 'p3d_stream_t'),
+                               ('typedef struct p3d_s { int32_t a; long b; } p3d_s;', 'p3d_s', 'long')):
+        with pytest.raises(ValueError) as e:
+            _lib.Header(text)
+        assert symbol in str(e.value) and what in str(e.value), str(e.value)
+    with pytest.raises(ValueError):
+        _lib.Header('int p3d_fine(void);\nstatic inline int p3d_inline(int a) { return a; }')
 
 
 def test_argument_errors_are_reported_not_thrown():

@@ -325,26 +325,3 @@ def test_replay_draws_hands_a_logical_draw_back_in_the_order_it_is_asked_for():
     with rmod._replay_draws(u_c, u_f):
         a, b = rmod._draw_uniforms(n, m, sc, sf, 'cpu', tensor_limits=True)
     assert torch.equal(a, u_c) and torch.equal(b, u_f)
-
-
-# ---- registrations ----------------------------------------------------------------------------------------------------------------
-def test_every_module_registers_the_entry_points_it_calls():
-    """By parsing, not importing: an import chain (mesh -> shape -> renderer) can lend a module argtypes it never declared."""
-    import ast
-    import pathlib
-    import pix2pix3d_amd
-    root = pathlib.Path(pix2pix3d_amd.__file__).parent
-    tree = ast.parse((root / '_lib.py').read_text())
-    own = next(n.value for n in tree.body if isinstance(n, ast.Assign) and getattr(n.targets[0], 'id', None) == '_SIGNATURES')
-    base = {k.value for k in own.keys}
-    assert 'p3d_last_error' in base and not any('mesh' in k or 'render' in k for k in base)
-    checked = 0
-    for path in sorted(root.rglob('*.py')):
-        if path.name in ('_lib.py', 'diagnostics.py'):         # (diagnostics.py calls p3d_probe_* of its own probe library)
-            continue
-        src = path.read_text()
-        called = set(re.findall(r'\blib(?:\(\))?\.(p3d_\w+)', src))
-        registered = set(re.findall(r"_lib\.register\(\s*'(p3d_\w+)'", src))
-        checked += bool(called)
-        assert called <= registered | base, (str(path.relative_to(root)), sorted(called - registered - base))
-    assert checked >= 8
