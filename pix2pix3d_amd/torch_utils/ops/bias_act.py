@@ -27,10 +27,14 @@ activation_funcs = {
 _null = None  # "absent tensor" marker of the plugin protocol (an empty tensor in the reference, bias_act.py:38)
 
 
-def _dense_like(x):
-    """Kernel precondition (bias_act.cpp:51-55): dense, non-overlapping; keep channels_last if it is that."""
+def _dense_like(x, like=None):
+    """Kernel precondition (bias_act.cpp:51-55): dense, non-overlapping; keep channels_last if it is that.  A strided gradient is made dense in the layout of
+    ``like`` — the tensor the forward pass saved, which the kernel reads next to it: the saved tensor is then not copied to fit, and the result does not change
+    its layout (and with it the summation order of the bias gradient) with the form of the incoming gradient."""
     if x.is_contiguous() or (x.ndim == 4 and x.is_contiguous(memory_format=torch.channels_last)):
         return x
+    if like is not None and like.shape == x.shape and like.dtype == x.dtype:
+        return torch.empty_like(like).copy_(x)
     return x.contiguous()
 
 
@@ -159,7 +163,7 @@ class _BiasAct(torch.autograd.Function):
 class _BiasActGrad(torch.autograd.Function):
     @staticmethod
     def forward(ctx, dy, x, b, y, spec):
-        dy = _dense_like(dy)
+        dy = _dense_like(dy, y if y is not None else x)
         dx = _run(spec, 1, dy, b, x, y, None)
         ctx.save_for_backward(dy if spec.second else _null, x, b, y)
         ctx.spec = spec
@@ -170,7 +174,7 @@ class _BiasActGrad(torch.autograd.Function):
         dy, x, b, y = ctx.saved_tensors
         spec = ctx.spec
         d_dy = d_x = d_b = None
-        d_dx = _dense_like(d_dx)
+        d_dx = _dense_like(d_dx, dy if dy is not None else (y if y is not None else x))
         if ctx.needs_input_grad[0]:
             d_dy = _BiasActGrad.apply(d_dx, x, b, y, spec)
         if spec.second and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):

@@ -18,6 +18,7 @@ import os
 import torch
 
 from ... import _lib
+from . import modconv
 
 enabled = False                     # set True by training_loop.py:281
 weight_gradients_disabled = False   # toggled by no_weight_gradients()
@@ -145,7 +146,8 @@ def _native_geometry(x, w, cfg):
 
 
 def _channels_last(t):
-    return t if t.is_contiguous(memory_format=torch.channels_last) else t.contiguous(memory_format=torch.channels_last)
+    """``t`` as the kernels read it: dense channels-last from a 16-byte boundary, copied only when it is not (modconv.kernel_operand)."""
+    return modconv.kernel_operand_nhwc(t)
 
 
 def _native_conv(x, w, cfg, k, stride):
@@ -158,21 +160,22 @@ def _native_conv(x, w, cfg, k, stride):
         oh, ow = (h, wd) if stride == 1 else ((h - 3) // 2 + 1, (wd - 3) // 2 + 1)
     else:
         oh, ow = (h, wd) if stride == 1 else (2 * h + 1 + cfg.output_padding[0], 2 * wd + 1 + cfg.output_padding[1])
+    if n == 0:                                          # an empty batch: nothing to launch
+        return torch.empty([0, co, oh, ow], dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     if k == 1 and h == 1 and wd == 1 and x.dtype == torch.float32 and n <= 16 and n * ((ci + 3) // 4 * 4) <= 16384:
         # a 1x1 convolution of 1x1 images IS a fully connected layer on a few rows — what FullyConnectedLayer routes here in training passes (style affines,
         # mapping MLPs: ~210 forward / data-gradient calls per six-phase iteration, 28 us each as weight re-layout + GEMM-tile kernel + epilogue): one launch of
         # the fc kernel instead; the transposed op (the data gradient) reads the weight matrix transposed
-        from . import modconv
         wm = w.reshape(w.shape[0], w.shape[1])
         if tr:
             wm = wm.t()
-        y = modconv.fc(x.reshape(n, ci), wm.contiguous(), None, 1.0, 1.0)
+        y = modconv.fc(x.reshape(n, ci), modconv.kernel_operand(wm), None, 1.0, 1.0)      # (a temporary: realigned here, never cached)
         native_calls['forward'] += 1
         return y.reshape(n, co, 1, 1)
     mult = 64 if x.dtype == torch.float16 else 32
     skinny = k == 1 and (ci % mult != 0 or co < 32)
     x = _channels_last(x)
-    w = w.contiguous()
+    w = modconv.kernel_operand(w)
     if not skinny and ci % mult != 0 and not (tr and stride == 2 and x.dtype == torch.float16 and ci % 32 == 0 and co % 128 == 0 and h >= 32 and wd >= 32):
         cip = (ci + mult - 1) // mult * mult            # whole K rows for the matrix-core kernel: zero channels change nothing
         xp = torch.empty([n, cip, h, wd], dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
@@ -186,7 +189,6 @@ def _native_conv(x, w, cfg, k, stride):
     scratch = None if skinny else torch.empty([co * ci * k * k], dtype=x.dtype, device=x.device)
     code_dtype = _lib.P3D_F32_BF16X3 if (cfg.split and x.dtype == torch.float32 and not skinny and k == 3 and ci % 32 == 0) else _lib.DTYPE_CODE[x.dtype]
     if code_dtype == _lib.P3D_F32 and not skinny and ci % 32 == 0:
-        from . import modconv
         if modconv.f32_x6:
             code_dtype = _lib.P3D_F32_BF16X6                   # fp32-accurate products on the bf16 matrix pipe (opt-in, modconv.f32_x6)
     nbytes = 0 if skinny else int(_lib.lib().p3d_conv2d_forward_workspace(code_dtype, n, h, wd, ci, co, k, stride, int(tr)))
@@ -223,15 +225,16 @@ def _native_weight_grad(grad_output, x, cfg, k, stride, scale=None):
     """p3d_conv2d_bwd_weight: the SMALL image of (x, grad_output) is correlated against the big one, pixels are the contraction.
     ``scale``: the gradient of the fp32 PARAMETER behind a (weight * scale).to(dtype) operand — fp32, scaled (p3d_conv2d_bwd_weight_scaled)."""
     small, big = (x, grad_output) if cfg.transpose else (grad_output, x)
-    small, big = _channels_last(small), _channels_last(big)
     n, cs, hs, ws_ = small.shape
     _, cb, hb, wb = big.shape
     assert (cs, cb) == tuple(cfg.wshape[:2]) and big.shape[0] == n
+    if n == 0:                                          # an empty batch: a sum over nothing
+        return torch.zeros(cfg.wshape, dtype=x.dtype if scale is None else torch.float32, device=x.device)
+    small, big = _channels_last(small), _channels_last(big)
     gw = torch.empty(cfg.wshape, dtype=x.dtype if scale is None else torch.float32, device=x.device)
     code_dtype = _lib.DTYPE_CODE[x.dtype]
     x6 = False
     if x.dtype == torch.float32:
-        from . import modconv
         # P3D_F32_BF16X6 in the weight gradient: the whole-tile kernel's arithmetic only (both sides > 64 channels, whole aligned channel groups) — the library
         # takes the exact kernels for every other geometry, whatever the code says; mirrored here for the FLOP log's arithmetic class
         x6 = modconv.f32_x6 and modconv.wgrad_x6 and cs > 64 and cb > 64 and cs % 4 == 0 and cb % 4 == 0

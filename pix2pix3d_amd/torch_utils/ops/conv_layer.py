@@ -31,8 +31,8 @@ calls = {'forward': 0, 'backward': 0}
 def supported(x, weight, bias, up, down, activation):
     if not (enabled and conv2d_gradfix.enabled and conv2d_gradfix.native and modconv.enabled and torch.is_grad_enabled()):
         return False
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.ndim == 4 and x.dtype in (torch.float16, torch.float32) and weight.dtype == torch.float32):
-        return False
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.ndim == 4 and x.numel() > 0 and x.dtype in (torch.float16, torch.float32) and weight.dtype == torch.float32):
+        return False                                       # (an empty batch launches nothing: the unfused formulation answers it)
     if up != 1 or down not in (1, 2) or activation not in ('linear', 'lrelu') or weight.shape[2] != weight.shape[3] or weight.shape[2] not in (1, 3):
         return False
     if not (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
@@ -171,7 +171,8 @@ class _Fc(torch.autograd.Function):
 def demod_supported(weight, styles):
     if not (enabled and conv2d_gradfix.enabled and conv2d_gradfix.native and modconv.enabled and torch.is_grad_enabled()):
         return False
-    if not (isinstance(weight, torch.nn.Parameter) and weight.is_cuda and weight.dtype == torch.float32 and weight.ndim == 4 and weight.is_contiguous()):
+    if not (isinstance(weight, torch.nn.Parameter) and weight.is_cuda and weight.dtype == torch.float32 and weight.ndim == 4 and weight.is_contiguous()
+            and weight.data_ptr() % 16 == 0):
         return False                                       # (a derived tensor — the fp16 pre-scaled weights — has no version to key the tap sums on)
     if not (styles.is_cuda and styles.dtype == torch.float32 and styles.ndim == 2 and (weight.requires_grad or styles.requires_grad)):
         return False
@@ -209,7 +210,7 @@ class _Demod(torch.autograd.Function):
         co, ci, kh, kw = weight.shape
         n = styles.shape[0]
         w2 = modconv._cached_weight(weight, 'w2_tapsum', lambda: weight.detach().float().square().sum(dim=[2, 3]).contiguous())
-        s32, gd32 = styles.detach().contiguous(), gd.detach().float().contiguous()
+        s32, gd32 = modconv.kernel_operand(styles.detach()), modconv.kernel_operand(gd.detach().float())
         gw = torch.empty_like(weight, memory_format=torch.contiguous_format) if ctx.needs_input_grad[0] else None
         gs = torch.empty_like(s32) if ctx.needs_input_grad[1] else None
         code = _lib.lib().p3d_demod_coefs_backward(_lib.ptr(gd32), _lib.ptr(d), _lib.ptr(s32), _lib.ptr(w2), _lib.ptr(weight.detach()), _lib.ptr(gs), _lib.ptr(gw),

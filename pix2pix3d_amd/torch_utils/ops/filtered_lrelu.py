@@ -96,6 +96,8 @@ class _Plugin:
             assert s.dtype == torch.uint8 and s.is_contiguous() and s.ndim == 4 and tuple(s.shape[:2]) == (n, c)
             sw_active = s.shape[3] << 2
         mode = 1 if write_signs else (2 if read else 0)
+        if y.numel() == 0:                                        # an empty batch: nothing to launch (the library refuses empty tensors)
+            return y, (so if so is not None else torch.empty([0], device=x.device)), 0
         xs, xst = _sizes4(x)
         ys, yst = _sizes4(y)
         bb = None if b is None else b.to(x.dtype)

@@ -70,6 +70,37 @@ def _is_nhwc(x, dtypes=(torch.float16, torch.float32)):
     return x.is_cuda and x.dtype in dtypes and x.ndim == 4 and x.is_contiguous(memory_format=torch.channels_last)
 
 
+def kernel_operand(t, fmt=torch.contiguous_format):
+    """``t`` as the kernels need it — dense in ``fmt`` from a 16-byte boundary: they are handed a pointer and sizes, never strides, and load 16 bytes at a
+    time —: itself when it already is (every tensor a fresh allocation holds), else ONE copy in fresh, aligned memory.  ``t.contiguous(memory_format=fmt)`` alone returns a dense view at an odd storage offset — a batch slice, a view into a flat
+    parameter buffer — unchanged, and the library refuses such a pointer (P3D_REQUIRE(... & 15) == 0)."""
+    if t is None or (t.data_ptr() % 16 == 0 and t.is_contiguous(memory_format=fmt)):
+        return t
+    return _fresh(t, fmt)
+
+
+def _fresh(t, fmt=torch.contiguous_format):
+    return torch.empty_like(t, memory_format=fmt).copy_(t)
+
+
+def kernel_operand_nhwc(t):
+    return kernel_operand(t, torch.channels_last)
+
+
+def _aligned(*ts):
+    return all(t is None or t.data_ptr() % 16 == 0 for t in ts)
+
+
+def noise_fits(noise, h, w):
+    """The kernels' epilogues read ONE noise image of the output's size, by pointer: anything else must not reach them."""
+    return noise is None or (noise.ndim == 2 and tuple(noise.shape) == (h, w))
+
+
+def _check_noise(noise, h, w, what):
+    if not noise_fits(noise, h, w):
+        raise ValueError(f'{what}: the noise image must be [{h}, {w}] (the size of the layer output), got {list(noise.shape)}')
+
+
 def _is_nhwc_f16(x):
     return _is_nhwc(x, (torch.float16,))
 
@@ -80,7 +111,18 @@ def _no_grad_needed(*tensors):
 
 def _dense_dev(x):
     x = _raw(x)
-    return x.is_cuda and x.dtype in (torch.float16, torch.float32) and x.ndim == 4 and (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last))
+    return (x.is_cuda and x.dtype in (torch.float16, torch.float32) and x.ndim == 4 and x.shape[0] > 0      # (an empty batch launches nothing: torch's operators answer it)
+            and (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last)))
+
+
+def dense_input(x):
+    """Inference: a device activation tensor that is dense in neither layout (a channel slice, a crop, an ``expand``ed batch) made channels-last, so that the
+    layer's ``*_supported`` predicate sees what the kernels can read: one copy costs less than giving up the kernels, and keeps the result's dtype and layout
+    those of the dense call (the generic route answers an fp16 ToRGB in fp16, the native one in fp32)."""
+    if (enabled and isinstance(x, torch.Tensor) and x.is_cuda and x.ndim == 4 and x.shape[0] > 0 and not torch.is_grad_enabled()
+            and not (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last))):
+        return x.contiguous(memory_format=torch.channels_last)
+    return x
 
 
 gemm_max_pixels_up = int(os.environ.get('P3D_GEMM_MAX_PIXELS_UP', 0))     # same switch for the x2 layers (see gemm_max_pixels)
@@ -233,7 +275,7 @@ def shared_split_weights(weight):
 def demod_coefs(weight, styles):
     """rsqrt(sum over (i, taps) of (w * s)^2 + 1e-8) as [N, Co] fp32, from the per-(o, i) tap sums of w^2 (cached per weight version)."""
     w2 = _cached_weight(weight, 'w2_tapsum', lambda: weight.detach().float().square().sum(dim=[2, 3]).contiguous())
-    s32 = styles.detach().float().contiguous()
+    s32 = _f32c(styles)
     n, ci = s32.shape
     d = torch.empty([n, weight.shape[0]], dtype=torch.float32, device=weight.device)
     code = _lib.lib().p3d_demod_coefs(_lib.ptr(s32), _lib.ptr(w2), _lib.ptr(d), n, ci, weight.shape[0], _lib.stream_of(d))
@@ -252,7 +294,7 @@ def demod_coefs_many(pairs):
     n = pairs[0][1].shape[0]
     for k, (weight, styles) in enumerate(pairs):
         w2 = _cached_weight(weight, 'w2_tapsum', lambda weight=weight: weight.detach().float().square().sum(dim=[2, 3]).contiguous())
-        s32 = styles.detach().float().contiguous()
+        s32 = _f32c(styles)
         d = torch.empty([n, weight.shape[0]], dtype=torch.float32, device=weight.device)
         keep.append((w2, s32))
         outs.append(d)
@@ -266,7 +308,7 @@ def scale_input(x, styles):
     from . import bcast
     geo = bcast.layout(x)
     assert geo is not None
-    return bcast._scale_fma(x, geo, styles.detach().float().contiguous(), None)
+    return bcast._scale_fma(x, geo, _f32c(styles), None)
 
 
 def modulate_weights(weight, styles, demodulate=True, pre_scale=1.0, dtype=torch.float16, oihw=False):
@@ -275,9 +317,9 @@ def modulate_weights(weight, styles, demodulate=True, pre_scale=1.0, dtype=torch
     o, i, kh, kw = weight.shape
     n = styles.shape[0]
     w32 = weight.detach()
-    if w32.dtype != torch.float32 or not w32.is_contiguous():      # (channels-last parameters of the fp16 blocks: one copy per weight version, not per call)
-        w32 = _cached_weight(weight, 'f32_contiguous', lambda: weight.detach().float().contiguous())
-    s32 = styles.detach().float().contiguous()
+    if w32.dtype != torch.float32 or not w32.is_contiguous() or not _aligned(w32):      # (channels-last parameters of the fp16 blocks, views into a flat parameter buffer: one copy per weight version, not per call)
+        w32 = _cached_weight(weight, 'f32_contiguous', lambda: kernel_operand(weight.detach().float()))
+    s32 = _f32c(styles)
     split = dtype == BF16X3
     out = torch.empty([n, o, i, kh * kw] if oihw else [n, o, kh * kw, i], dtype=torch.float32 if split else dtype, device=weight.device)
     code = _lib.lib().p3d_modulate_weights(_lib.ptr(w32), _lib.ptr(s32), _lib.ptr(out), DTYPE_F32_BF16X3 if split else _lib.DTYPE_CODE[dtype], n, o, i, kh * kw,
@@ -307,12 +349,12 @@ fuse_input_scale = os.environ.get('P3D_FUSE_INPUT_SCALE', '1') != '0'      # sha
 
 
 def _f32c(t):
-    return None if t is None else t.detach().float().contiguous()
+    return None if t is None else kernel_operand(t.detach().float())
 
 
 def _epilogue(bias, noise, noise_strength):
     """(bias, noise image, noise strength [1]) as the contiguous fp32 tensors — or None — the kernels' epilogues read."""
-    return _f32c(bias), _f32c(noise), None if noise is None else noise_strength.detach().float().reshape(1).contiguous()
+    return _f32c(bias), _f32c(noise), None if noise is None else kernel_operand(noise_strength.detach().float().reshape(1))
 
 
 def _conv_geometry(x, wmod, transposed, down):
@@ -343,9 +385,12 @@ def conv2d(x, wmod, transposed=False, bias=None, noise=None, noise_strength=None
         assert split and out_scale is None
         return _conv2d_split_io(x, wmod, transposed, bias, noise, noise_strength, act, gain, clamp, down, out_split)
     assert _is_nhwc(x) and wmod.dtype == x.dtype and wmod.is_contiguous()
-    x, wmod = _pad_channels(x, wmod, transposed)
+    x, wmod = _pad_channels(kernel_operand_nhwc(x), kernel_operand(wmod), transposed)
     n, ci, h, w, co, k, oh, ow, stride, mode = _conv_geometry(x, wmod, transposed, down)
+    _check_noise(noise, oh, ow, 'conv2d')
     y = torch.empty([n, co, oh, ow], dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    if n == 0:
+        return y
     b32, nz, ns = _epilogue(bias, noise, noise_strength)
     code_dtype = DTYPE_F32_BF16X3 if split else _lib.DTYPE_CODE[x.dtype]          # split: wmod came from modulate_weights(dtype=BF16X3)
     x6 = f32_x6 and not split and x.dtype == torch.float32 and ci % 32 == 0
@@ -394,6 +439,10 @@ def _conv2d_split_io(x, wmod, transposed, bias, noise, noise_strength, act, gain
     xt = _raw(x)
     assert _is_nhwc(xt, (torch.float32,)) and wmod.dtype == torch.float32 and wmod.is_contiguous() and xt.shape[1] % 32 == 0 and wmod.shape[3] == xt.shape[1]
     n, ci, h, w, co, k, oh, ow, stride, mode = _conv_geometry(xt, wmod, transposed, down)
+    _check_noise(noise, oh, ow, 'conv2d')
+    if not x_split:
+        xt = kernel_operand_nhwc(xt)
+    wmod = kernel_operand(wmod)
     y = torch.empty([n, co, oh, ow], dtype=torch.float32, device=xt.device, memory_format=torch.channels_last)
     b32, nz, ns = _epilogue(bias, noise, noise_strength)
     y_split, nbytes = _split_io_plan(n, h, w, ci, co, stride, k, mode, int(x_split), int(bool(out_split) and co % 32 == 0 and k == 3 and mode == 0))
@@ -498,7 +547,7 @@ def plain_layer(x, weight, bias, weight_gain, resample_filter, down, padding, ac
     wmod = _cached_weight(weight, ('mfma', wdt, float(weight_gain)),
                           lambda: modulate_weights(weight, torch.ones([1, ci], dtype=torch.float32, device=weight.device), demodulate=False,
                                                    pre_scale=float(weight_gain), dtype=wdt))
-    x = x.contiguous(memory_format=torch.channels_last)
+    x = kernel_operand_nhwc(x)
     act_idx = {'linear': 0, 'lrelu': 1}[act]
     clampv = -1.0 if clamp is None else float(clamp)
     assert down != 1 or padding == k // 2
@@ -527,9 +576,11 @@ def fc(x, weight, bias, weight_gain, bias_gain, activation='linear', out_scale=1
         w32 = _cached_weight(weight, ('fc_pad', pad), lambda: torch.nn.functional.pad(weight.detach().float(), [0, pad]).contiguous())
         in_f += pad
     else:
-        w32 = weight.detach().contiguous()
-    if x32.stride(1) != 1 or x32.stride(0) % 4 != 0 or x32.data_ptr() % 16 != 0:
-        x32 = x32.contiguous()
+        w32 = weight.detach()
+        if not (w32.is_contiguous() and _aligned(w32)):      # (a parameter that is a view into a flat buffer: one copy per weight version; a temporary: one per call)
+            w32 = _cached_weight(weight, 'fc_aligned', lambda: kernel_operand(weight.detach())) if isinstance(weight, torch.nn.Parameter) else kernel_operand(w32)
+    if x32.stride(1) != 1 or (n > 1 and x32.stride(0) % 4 != 0) or not _aligned(x32):      # (rows at a stride of whole float4s — ws[:, k] — are read in place)
+        x32 = _fresh(x32)
     b32 = _f32c(bias)
     y = torch.empty([n, out_f], dtype=torch.float32, device=x.device)
     act_gain = bias_act.activation_funcs[activation].def_gain
@@ -551,10 +602,12 @@ def fc_multi(jobs):
     arr = (_lib.p3d_fc_job * len(jobs))()
     for k, (x, layer, out_scale) in enumerate(jobs):
         x32 = x.detach()
-        if x32.stride(1) != 1 or x32.stride(0) % 4 != 0 or x32.data_ptr() % 16 != 0:
-            x32 = x32.contiguous()
-        w32 = layer.weight.detach().contiguous()
-        b32 = None if layer.bias is None else layer.bias.detach().float().contiguous()
+        if x32.stride(1) != 1 or x32.stride(0) % 4 != 0 or not _aligned(x32):
+            x32 = _fresh(x32)
+        w32 = layer.weight.detach()
+        if not (w32.is_contiguous() and _aligned(w32)):
+            w32 = _cached_weight(layer.weight, 'fc_aligned', lambda w=layer.weight: kernel_operand(w.detach()))
+        b32 = _f32c(layer.bias)
         y = torch.empty([n, w32.shape[0]], dtype=torch.float32, device=x.device)
         keep.append((x32, w32, b32))
         outs.append(y)
@@ -579,6 +632,8 @@ def im2col3x3(x, pad=1, stride=1):
 def noise_bias_act(y, bias, noise, noise_strength, act, act_gain, clamp):
     """In place on a contiguous fp32 [N, C, H, W]: + noise * strength, + bias, activation, gain, clamp (networks_stylegan2.py:326-332)."""
     n, c, h, w = y.shape
+    _check_noise(noise, h, w, 'noise_bias_act')
+    assert y.is_contiguous() and _aligned(y)
     b32, nz, ns = _epilogue(bias, noise, noise_strength)
     code = _lib.lib().p3d_noise_bias_act(_lib.ptr(y), _lib.ptr(y), _lib.ptr(nz), _lib.ptr(ns), _lib.ptr(b32), n, c, h * w, {'linear': 1, 'lrelu': 3}[act], 0.2,
                                          float(act_gain), -1.0 if clamp is None else float(clamp), _lib.stream_of(y))
@@ -653,6 +708,7 @@ def synthesis_layer(x, weight, styles, bias, up, resample_filter, noise_const=No
     ``pre`` = (modulated weights, route tag) from ``premodulate`` — used when the tag matches the route taken here.
     x may be a SplitActs (bf16x3 inference); ``out_split`` asks for the result as one (granted where the producing kernel can)."""
     route = layer_route(x.shape[0], weight.shape[1], x.shape[2] * x.shape[3], up, x.dtype)
+    _check_noise(noise_const, up * x.shape[2], up * x.shape[3], 'synthesis_layer')      # before anything launches
     split, wtag = route.split, route.tag[2]
     if isinstance(x, SplitActs) and not route.reads_split:
         x = x.dense()
@@ -728,6 +784,8 @@ def up2_fir(x, wmod, taps, bias, noise, noise_strength, act, act_gain, clamp):
     n, ci, h, w = x.shape
     co = wmod.shape[1]
     assert wmod.shape[0] in (1, n) and wmod.shape[3] == ci
+    _check_noise(noise, 2 * h, 2 * w, 'up2_fir')
+    x, wmod = kernel_operand_nhwc(x), kernel_operand(wmod)
     y = torch.empty([n, co, 2 * h, 2 * w], dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     stride = 0 if wmod.shape[0] == 1 else co * 9 * ci
     b32, nz, ns = _epilogue(bias, noise, noise_strength)
@@ -743,6 +801,8 @@ def up2_fir(x, wmod, taps, bias, noise, noise_strength, act, act_gain, clamp):
 def fir4_bias_act(y, f, bias, noise, noise_strength, act, act_gain, clamp, out_split=False):
     """4x4 FIR (pad 1, gain 4) + noise + bias + activation on an NHWC tensor [N,C,2H+1,2W+1] -> [N,C,2H,2W] (``out_split``, fp32: a SplitActs)."""
     n, c, ih, iw = y.shape
+    _check_noise(noise, ih - 1, iw - 1, 'fir4_bias_act')
+    y = kernel_operand_nhwc(y)
     out = torch.empty([n, c, ih - 1, iw - 1], dtype=y.dtype, device=y.device, memory_format=torch.channels_last)
     f32 = _f32c(f)
     b32, nz, ns = _epilogue(bias, noise, noise_strength)
@@ -774,7 +834,7 @@ def torgb_fusable(x, conv_weight, rgb_weight, img, up, noise_const, act):
     n, ci, h, w = x.shape
     co = conv_weight.shape[0]
     return (torgb_fuses(n, ci, co, rgb_weight.shape[0], h, w, x.dtype, up, noise_const is not None, act) and tuple(conv_weight.shape[2:]) == (3, 3)
-            and tuple(rgb_weight.shape[1:]) == (co, 1, 1) and img.dtype == torch.float32 and img.is_contiguous() and tuple(img.shape) == (n, rgb_weight.shape[0], h, w)
+            and tuple(rgb_weight.shape[1:]) == (co, 1, 1) and img.dtype == torch.float32 and img.is_contiguous() and _aligned(img) and tuple(img.shape) == (n, rgb_weight.shape[0], h, w)
             and not img.requires_grad and _no_grad_needed(x, conv_weight, rgb_weight))
 
 
@@ -787,8 +847,9 @@ def conv3x3_torgb(x, wmod, bias, act, gain, clamp, rgb_wmod, rgb_bias, rgb_clamp
     y = torch.empty([n, co, h, w], dtype=x.dtype, device=x.device, memory_format=torch.channels_last) if store_y else None
     stride = 0 if wmod.shape[0] == 1 else co * 9 * ci
     b32, rb32 = _f32c(bias), _f32c(rgb_bias)
-    rw = rgb_wmod.reshape(n, -1, co)
-    assert rw.dtype == torch.float32 and rw.is_contiguous() and wmod.dtype == torch.float16 and wmod.is_contiguous()
+    x, wmod = kernel_operand_nhwc(x), kernel_operand(wmod)
+    rw = kernel_operand(rgb_wmod.reshape(n, -1, co))
+    assert rw.dtype == torch.float32 and wmod.dtype == torch.float16
     with _lib.kernel_timer('conv_f16', x):
         code = _lib.lib().p3d_conv3x3_torgb_f16(_lib.ptr(x), _lib.ptr(wmod), _lib.ptr(y), _lib.ptr(b32), _lib.ptr(_zeros_page(x.device)), _lib.ptr(rw), _lib.ptr(rb32),
                                                 _lib.ptr(img), rw.shape[1], -1.0 if rgb_clamp is None else float(rgb_clamp), n, h, w, ci, co, stride,
@@ -820,7 +881,7 @@ def torgb_wide_skip_supported(x, weight, prev, f):
     if ci not in (128, 256) or co not in (32, 64, 96) or w % 32 != 0:
         return False
     return prev is None or (f is not None and tuple(f.shape) == (4, 4) and prev.dtype == torch.float32 and tuple(prev.shape) == (n, co, h // 2, w // 2) and h % 2 == 0
-            and prev.is_cuda and prev.is_contiguous(memory_format=torch.channels_last) and not prev.requires_grad)
+            and prev.is_cuda and prev.is_contiguous(memory_format=torch.channels_last) and _aligned(prev) and not prev.requires_grad)
 
 
 def torgb_wide_skip(x, weight, styles, bias, clamp, prev, f, pre=None):
@@ -828,6 +889,7 @@ def torgb_wide_skip(x, weight, styles, bias, clamp, prev, f, pre=None):
     n, ci, h, w = x.shape
     co = weight.shape[0]
     wmod = pre[0] if pre is not None and pre[1] == _rgb_tag(BF16X3) else modulate_weights(weight, styles, demodulate=False, dtype=BF16X3)
+    wmod = kernel_operand(wmod)
     y = torch.empty([n, co, h, w], dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     b32 = _f32c(bias)
     fh = None if prev is None else _filter_host(f)
@@ -844,7 +906,7 @@ fuse_conv_wide_torgb = os.environ.get('P3D_FUSE_CONV_WIDE_TORGB', '1') != '0'   
 conv_wide_torgb_calls = 0
 
 
-def conv3x3_torgb_wide_supported(x, conv_weight, rgb_weight, prev, f, up, act):
+def conv3x3_torgb_wide_supported(x, conv_weight, rgb_weight, prev, f, up, act, noise=None):
     """p3d_conv3x3_torgb_split takes it: a SplitActs into a 3x3 'same' layer of 128 output channels whose result nobody but the block's wide ToRGB reads (the caller
     vouches for that), 32 / 64 / 96 image channels, enough 16 x 16 patches to fill the chip, and (if given) a channels-last fp32 predecessor image at half the resolution."""
     if not (fuse_conv_wide_torgb and fuse_wide_torgb and enabled and split_bf16 and split_activations and isinstance(x, SplitActs) and up == 1 and act in ('linear', 'lrelu')
@@ -854,6 +916,10 @@ def conv3x3_torgb_wide_supported(x, conv_weight, rgb_weight, prev, f, up, act):
     co, rco = conv_weight.shape[0], rgb_weight.shape[0]
     if (co != 128 or tuple(conv_weight.shape[1:]) != (ci, 3, 3) or tuple(rgb_weight.shape[1:]) != (co, 1, 1) or rco not in (32, 64, 96) or ci % 32 != 0 or h < 32 or w < 32
             or (h | w) & 1 or n * ((h + 15) // 16) * ((w + 15) // 16) < 192 or not layer_route(n, ci, h * w, 1, torch.float32).reads_split):
+        return False
+    # what p3d_conv3x3_torgb_split reads by pointer as it stands: a noise image of another size, or a skip image at an odd address, sends the block to the two-launch
+    # form (synthesis_layer refuses the noise from Python; upsample2d reads any strides).  Biases and weights are realigned by conv3x3_torgb_wide itself (_f32c, kernel_operand)
+    if not noise_fits(noise, h, w) or not _aligned(prev):
         return False
     return prev is None or (f is not None and tuple(f.shape) == (4, 4) and prev.dtype == torch.float32 and tuple(prev.shape) == (n, rco, h // 2, w // 2)
             and prev.is_cuda and prev.is_contiguous(memory_format=torch.channels_last) and not prev.requires_grad)
@@ -866,6 +932,9 @@ def conv3x3_torgb_wide(x, wmod, bias, noise, noise_strength, act, gain, clamp, r
     co, rco = wmod.shape[1], rgb_wmod.shape[1]
     assert wmod.dtype == torch.float32 and wmod.is_contiguous() and tuple(wmod.shape[1:]) == (co, 9, ci) and wmod.shape[0] in (1, n)
     assert rgb_wmod.dtype == torch.float32 and rgb_wmod.is_contiguous() and tuple(rgb_wmod.shape) == (n, rco, 1, co)
+    _check_noise(noise, h, w, 'conv3x3_torgb_wide')
+    assert prev is None or _aligned(prev)
+    wmod, rgb_wmod = kernel_operand(wmod), kernel_operand(rgb_wmod)
     img = torch.empty([n, rco, h, w], dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     stride = 0 if wmod.shape[0] == 1 else co * 9 * ci
     (b32, nz, ns), rb32 = _epilogue(bias, noise, noise_strength), _f32c(rgb_bias)
@@ -906,11 +975,12 @@ def torgb(x, weight, styles, bias, clamp=None, out=None, pre=None):
         wmod = pre[0] if pre is not None and pre[1] == route.tag else modulate_weights(weight, styles, demodulate=False, dtype=route.tag[1])
         y = conv2d(x, wmod, bias=bias, clamp=-1.0 if clamp is None else float(clamp), split=route.split)
         return y if out is None else out.add_(y)
-    w32, s32, b32 = weight.detach().float().reshape(co, ci).contiguous(), _f32c(styles), _f32c(bias)
-    acc = out is not None
+    w32, s32, b32 = kernel_operand(weight.detach().float().reshape(co, ci)), _f32c(styles), _f32c(bias)
+    x = kernel_operand_nhwc(x)
+    acc = out is not None and _aligned(out)                # (an image at an odd address is added to in a pass of its own)
     y = out if acc else torch.empty([n, co, h, w], dtype=torch.float32, device=x.device)
     assert y.is_contiguous() and y.dtype == torch.float32
     code = _lib.lib().p3d_torgb_nhwc_f16(_lib.ptr(x), _lib.ptr(w32), _lib.ptr(s32), _lib.ptr(b32), _lib.ptr(y), n, h * w, ci, co,
                                          -1.0 if clamp is None else float(clamp), int(acc), _lib.stream_of(x))
     _lib.check(code, 'torgb_nhwc_f16')
-    return y
+    return y if out is None or acc else out.add_(y)

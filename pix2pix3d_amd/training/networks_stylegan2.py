@@ -166,6 +166,7 @@ class Conv2dLayer(torch.nn.Module):
 
     def forward(self, x, gain=1):
         clamp = self.conv_clamp * gain if self.conv_clamp is not None else None
+        x = modconv.dense_input(x)
         if modconv.plain_layer_supported(x, self.weight, self.up, self.down, self.activation):
             return modconv.plain_layer(x, self.weight, self.bias, self.weight_gain, self.resample_filter, self.down, self.padding,
                                        self.activation, self.act_gain * gain, clamp)
@@ -278,7 +279,8 @@ class SynthesisLayer(torch.nn.Module):
             assert rgb is None
             torgb, w_rgb, prev, f = rgb_wide
             if fused_modconv is True and noise_mode != 'random' and x.is_cuda and \
-                    modconv.conv3x3_torgb_wide_supported(x, self.weight, torgb.weight, prev, f, self.up, self.activation):
+                    modconv.conv3x3_torgb_wide_supported(x, self.weight, torgb.weight, prev, f, self.up, self.activation,
+                                                         noise=self.noise_const if self.use_noise and noise_mode == 'const' else None):
                 planned = modconv.take_plan(self) if modconv._plan else None
                 styles, pre = (planned.styles, planned.pre) if planned is not None else (self.affine(w), None)
                 wmod = pre[0] if pre is not None and pre[1] == modconv.layer_route(x.shape[0], self.in_channels, in_res * in_res, 1, torch.float32).tag else modconv.modulate_weights(self.weight, styles, demodulate=True, dtype=modconv.BF16X3)
@@ -357,6 +359,7 @@ class ToRGBLayer(torch.nn.Module):
         SynthesisBlock without a separate launch.  The return value is then that image; callers check identity."""
         planned = modconv.take_plan(self) if modconv._plan else None
         styles = planned.styles if planned is not None else self.affine(w, out_scale=self.weight_gain)
+        x = modconv.dense_input(x)
         if modconv.torgb_supported(x, self.weight, styles, fused_modconv):
             out = accumulate_into if accumulate_into is not None and modconv.torgb_accumulates(x, self.weight, accumulate_into) else None
             return modconv.torgb(x, self.weight, styles, self.bias, clamp=self.conv_clamp, out=out, pre=planned.pre if planned is not None else None)      # fp32 NCHW, bias + clamp fused

@@ -18,6 +18,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from ... import _lib
+from ...torch_utils.ops import modconv
 from . import math_utils
 from .ray_marcher import MipRayMarcher2
 
@@ -127,7 +128,9 @@ def _dual_decoder_nets(decoder_texture, decoder_semantic):
 
 
 def _f32c(t):
-    return t.detach().to(torch.float32).contiguous()
+    """fp32, dense and 16-byte aligned, copied only when it is not (rays cut out of one [N, M, 6] tensor, ``expand``ed uniforms, decoder parameters that are
+    views into a flat buffer: ``contiguous()`` alone hands a dense view at an odd offset on as it is)."""
+    return modconv.kernel_operand(t.detach().to(torch.float32))
 
 
 def shared_planes(n_planes, n_rays, who, allowed=True):
@@ -794,7 +797,6 @@ def fused_render(planes, decoder, ray_origins, ray_directions, opt, u_coarse, u_
     shared = shared_planes(planes.shape[0], n, 'fused_render')
     sc, sf = int(opt['depth_resolution']), int(opt['depth_resolution_importance'])
     dev = planes.device
-    from pix2pix3d_amd.torch_utils.ops import modconv
     mode = 1 if (mlp_bf16x3 and not exact_fp32) else (2 if (mlp_l1x6 and modconv.f32_x6) else 0)      # (the training forward stays fp32-accurate: its backward recomputes in fp32)
     ctx = _FusedContext(planes, info, bf16x3=mode)
     t0, t1 = _flat_limits(t_start), _flat_limits(t_end)
