@@ -1,4 +1,4 @@
-"""Build libp3d_hip.so (the C-ABI kernel library) in-tree with hipcc for gfx950.
+"""Build libp3d_hip.so (the C-ABI kernel library), libp3d_probes.so and libp3d_regions.so in-tree with hipcc for gfx950.
 
 No torch headers, no pybind: every ``csrc/*.hip`` translation unit is compiled to an object
 (in parallel, cached by mtime) and linked into ``pix2pix3d_amd/libp3d_hip.so`` so the binary
@@ -16,6 +16,8 @@ OBJ_DIR = os.path.join(CSRC, '_obj')
 LIB_PATH = os.path.join(PKG_DIR, 'libp3d_hip.so')
 PROBES_DIR = os.path.join(CSRC, 'probes')
 PROBES_LIB_PATH = os.path.join(PKG_DIR, 'libp3d_probes.so')      # hardware probes: a library of its own, never part of the product ABI
+REGIONS_DIR = os.path.join(CSRC, 'regions')
+REGIONS_LIB_PATH = os.path.join(PKG_DIR, 'libp3d_regions.so')    # region tools of the edit session: a library of its own too (csrc/regions/p3d_regions.h)
 ARCH = 'gfx950'
 CXXFLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-Wall', '-Wno-unused-function',
             '-fno-gpu-rdc', '-DNDEBUG']
@@ -43,10 +45,15 @@ def probe_sources():
     return sorted(os.path.join(PROBES_DIR, f) for f in os.listdir(PROBES_DIR) if f.endswith('.hip'))
 
 
+def region_sources():
+    return sorted(os.path.join(REGIONS_DIR, f) for f in os.listdir(REGIONS_DIR) if f.endswith('.hip'))
+
+
 def headers():
     inc = os.path.join(os.path.dirname(PKG_DIR), 'include')
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')]
     hs += [os.path.join(PROBES_DIR, f) for f in os.listdir(PROBES_DIR) if f.endswith('.h')]
+    hs += [os.path.join(REGIONS_DIR, f) for f in os.listdir(REGIONS_DIR) if f.endswith('.h')]
     hs += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith('.h')]
     return sorted(hs)
 
@@ -84,25 +91,36 @@ def build_library(force=False, verbose=False):
         if r.returncode != 0:
             raise RuntimeError(f'link failed:\n{r.stdout}')
     build_probes(verbose=verbose)
+    build_regions(verbose=verbose)
     return LIB_PATH
 
 
-def build_probes(verbose=False):
-    """libp3d_probes.so (csrc/probes/*.hip, -DP3D_BUILD_PROBES): the hardware probes the tests and the kernel studies use, with their own
-    copy of the library services (p3d_common.hip) so that nothing of them is exported through libp3d_hip.so."""
+def _build_side_library(path, srcs, verbose, extra=()):
+    """A library beside libp3d_hip.so: its own sources plus a copy of the library services (_obj/p3d_common.o, built by build_library)."""
     os.makedirs(OBJ_DIR, exist_ok=True)
-    srcs = probe_sources()
     with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, min(8, len(srcs)))) as ex:
-        results = list(ex.map(lambda s: _compile(s, verbose, ('-DP3D_BUILD_PROBES',)), srcs))
+        results = list(ex.map(lambda s: _compile(s, verbose, extra), srcs))
     objs = [o for o, _ in results] + [os.path.join(OBJ_DIR, 'p3d_common.o')]
-    if any(changed for _, changed in results) or not _newer(PROBES_LIB_PATH, objs):
-        cmd = [_hipcc(), '-shared', '-fPIC', f'--offload-arch={ARCH}', '-o', PROBES_LIB_PATH] + objs
+    if any(changed for _, changed in results) or not _newer(path, objs):
+        cmd = [_hipcc(), '-shared', '-fPIC', f'--offload-arch={ARCH}', '-o', path] + objs
         if verbose:
             print(' '.join(cmd), flush=True)
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if r.returncode != 0:
             raise RuntimeError(f'link failed:\n{r.stdout}')
-    return PROBES_LIB_PATH
+    return path
+
+
+def build_probes(verbose=False):
+    """libp3d_probes.so (csrc/probes/*.hip, -DP3D_BUILD_PROBES): the hardware probes the tests and the kernel studies use, with their own
+    copy of the library services (p3d_common.hip) so that nothing of them is exported through libp3d_hip.so."""
+    return _build_side_library(PROBES_LIB_PATH, probe_sources(), verbose, ('-DP3D_BUILD_PROBES',))
+
+
+def build_regions(verbose=False):
+    """libp3d_regions.so (csrc/regions/*.hip): the region tools of pix2pix3d_amd/regions.py, with the same flags and their own copy of the
+    library services; the product ABI of libp3d_hip.so gains no symbol."""
+    return _build_side_library(REGIONS_LIB_PATH, region_sources(), verbose)
 
 
 if __name__ == '__main__':

@@ -1,52 +1,18 @@
 // Mesh clean-up for gfx950: connected components and vertex-clustering decimation (include/p3d_hip.h; pix2pix3d_amd/mesh.py).
 //
 // p3d_mesh_components: union-find in the ECL-CC shape (Jaiganesh & Burtscher, HPDC 2018): init, hook, flatten, three launches whatever
-// the mesh.  parent[] lives in the output array.  Every write keeps parent[x] <= x and parent[x] inside x's own component:
-//   * a hook is atomicCAS(&parent[hi], hi, lo) with lo < hi the two roots a face's edge joins: only a ROOT is ever hooked, and under a
-//     smaller id, so the root of a finished tree is the smallest vertex id of its component whatever the order of arrival;
-//   * path halving while finding stores an ancestor of x into parent[x] for a NON-root x; two such stores may race, both are ancestors.
-// A failed CAS means parent[hi] != hi: some other thread hooked hi, the component count went down, and this thread goes on from the
-// value the CAS returned (an ancestor).  Nothing waits for a value another thread has yet to write: no locks, no spinning on a flag, so
-// lanes of one wave that run in lockstep cannot starve each other.  Reads of parent[] go through relaxed agent-scope atomics (the
-// XCDs' L2s are not coherent for plain accesses inside one kernel); a stale read returns an older ancestor, which the loop tolerates.
+// the mesh.  parent[] lives in the output array.  The protocol (what a hook, a find and a failed CAS may do, and why no lane waits on
+// another) is stated with the functions, in csrc/union_find.h.
 //
 // p3d_mesh_cluster_keys / _means / _faces: the three kernels of mesh.simplify.  Plain gathers and stores, one thread per vertex,
 // cluster or face; the sums of _means run in a fixed order in fp64, so the output is a pure function of the inputs.
 #include "p3d_common.h"
+#include "union_find.h"
 #include <math.h>
 
 namespace p3d {
 
 constexpr int kMeshOpsBlock = 256;
-
-__device__ __forceinline__ int32_t uf_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void uf_store(int32_t* p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// The root of v's tree, halving the path on the way: every visited vertex is pointed at its grandparent.  Terminates because
-// parent[x] <= x, with equality only at a root.
-__device__ __forceinline__ int32_t uf_find(int32_t* parent, int32_t v)
-{
-    int32_t cur = uf_load(parent + v);
-    if (cur == v) return v;
-    int32_t prev = v, next;
-    while (cur > (next = uf_load(parent + cur))) {
-        uf_store(parent + prev, next);
-        prev = cur;
-        cur = next;
-    }
-    return cur;
-}
-
-__device__ __forceinline__ void uf_union(int32_t* parent, int32_t a, int32_t b)
-{
-    int32_t ra = uf_find(parent, a), rb = uf_find(parent, b);
-    while (ra != rb) {
-        const int32_t hi = ra > rb ? ra : rb, lo = ra > rb ? rb : ra;
-        const int32_t seen = atomicCAS(parent + hi, hi, lo);
-        if (seen == hi) return;                                      // hooked
-        ra = seen; rb = lo;                                          // hi was hooked by somebody else: go on from its new parent (< hi)
-    }
-}
 
 __global__ void __launch_bounds__(kMeshOpsBlock) cc_init_kernel(int32_t* __restrict__ parent, int32_t nv)
 {

@@ -15,6 +15,7 @@ with a Python loop over 512^2 pixels (:343-399, 429-463).  ``EditSession`` keeps
     s.render()                                            # the same dict as device tensors
     s.take_view_as_mask()                                 # cross-view edit: the rendered label map becomes the canvas
     s.paint([(250, 300, 260, 340, 20, 4)]); s.undo(); s.save('out/')
+    s.scale(4, 1.3); s.remove(5); s.move(('component', 260, 300), 0, -4)   # region tools (regions.py): each call is one undo step too
 
 Stroke coverage (identical bytes on the device kernel and in the torch formulation CPU tensors take).  cv2's polygon fill is not specified, so the rule is
 integer: with d = b - a, p = pixel - a, L = d.d, s = p.d, thickness t, all int64, a pixel is covered iff
@@ -193,7 +194,8 @@ class EditSession:
     """One editing session on the device ``G`` lives on; every method runs under ``torch.no_grad()``.
 
     Four stages, each recomputed only when its input changed: mask -> geometry ws -> planes -> frame (and, beside the frame, ``geometry()``'s surface frame).  ``paint`` / ``undo`` / ``clear`` / ``load`` /
-    ``take_view_as_mask`` dirty the mask; ``set_seed`` / ``clear_texture`` the ws; a camera change only the frame: ``render()`` after it is
+    ``take_view_as_mask`` and the region tools (``fill`` / ``grow`` / ``shrink`` / ``remove`` / ``move`` / ``scale`` / ``rotate`` / ``transform``) dirty the mask;
+    ``set_seed`` / ``clear_texture`` the ws; a camera change only the frame: ``render()`` after it is
     ``G.synthesis(ws, c, use_cached_backbone=True)`` on the kept planes and ``views.finish_frames`` — neither the Encoder nor the backbone runs.
 
     cfg            a key of ``views.VIDEO_CFG``: the ray resolution (``neural_rendering_resolution`` overrides it).
@@ -238,7 +240,8 @@ class EditSession:
             raise ValueError(f"EditSession: jitter must be 'frozen', 'random' or a pair of draws, got {jitter!r}")
         self._forward_c = G.mapping_label(forward_label(G).to(self.device))
         self._base = self._pose = self._intrinsics = self._cam2world = None
-        self._log = []                                                         # one checked int32 [k, 6] table per paint() call
+        self._log = []                                                         # typed entries, one per undo step: ('paint', int32 [k, 6] table) or a region op
+        self._kept = {}                                                        # n -> the mask after the first n entries (at most KEPT_MASKS of them)
         self._mask = self._geometry = self._ws = self._held = self._planes = self._frame = self._floats = None
         self._appearance = {}                                                  # seed -> [1, w_dim]
         self.seed = int(seed)
@@ -261,7 +264,7 @@ class EditSession:
         self._pose = pose.to(self.device).reshape(1, 25)
         self._intrinsics = self._pose[:, 16:25].reshape(3, 3)
         self._cam2world = self._pose[:, :16].reshape(4, 4)
-        self._log = []
+        self._log, self._kept = [], {}
         self._dirty_mask()
         self._frame = None
 
@@ -281,35 +284,172 @@ class EditSession:
         table = stroke_table(strokes)
         if len(table) and int(table[:, 5].max()) >= self.n_labels:
             raise ValueError(f'paint: label {int(table[:, 5].max())} in a mask of {self.n_labels} labels')
-        if sum(len(t) for t in self._log) + len(table) > MAX_STROKES:
+        if sum(len(e[1]) for e in self._log if e[0] == 'paint') + len(table) > MAX_STROKES:
             raise ValueError(f'paint: more than {MAX_STROKES} strokes in the log; take_view_as_mask() or clear() starts a new one')
         if len(table):
-            self._log.append(table)
-            self._dirty_mask()
+            self._append(('paint', table))
 
     def undo(self):
         if self._log:
             self._log.pop()
+            self._kept = {n: m for n, m in self._kept.items() if n <= len(self._log)}
             self._dirty_mask()
 
     def clear(self):
         if self._log:
-            self._log = []
+            self._log, self._kept = [], {}
             self._dirty_mask()
+
+    def _append(self, entry):
+        self._log.append(entry)
+        self._dirty_mask()
+
+    # -- region tools (regions.py): every call validates on the host, appends ONE entry and dirties the mask as paint() does -------------------------
+    def _own_label(self, label, what):
+        if isinstance(label, bool) or not isinstance(label, (int, np.integer)) or not 0 <= int(label) < self.n_labels:
+            raise ValueError(f'{what}: label {label!r} in a mask of {self.n_labels} labels')
+        return int(label)
+
+    def _pixel(self, x, y, what):
+        self._need_load()
+        h, w = self._base.shape
+        if not all(isinstance(v, (int, np.integer)) for v in (x, y)) or not (0 <= x < w and 0 <= y < h):
+            raise ValueError(f'{what}: pixel ({x!r}, {y!r}) is outside the {h} x {w} mask')
+        return int(x), int(y)
+
+    def _region_spec(self, region, what):
+        """A label, or ('component', x, y[, connectivity]): resolved against the mask when the entry is applied."""
+        if isinstance(region, (tuple, list)):
+            if len(region) not in (3, 4) or region[0] != 'component' or (len(region) == 4 and region[3] not in (4, 8)):
+                raise ValueError(f"{what}: a region is a label or ('component', x, y[, 4 or 8]), got {region!r}")
+            return ('component',) + self._pixel(region[1], region[2], what) + (int(region[3]) if len(region) == 4 else 4,)
+        return self._own_label(region, what)
+
+    def _resolve(self, mask, spec):
+        from . import regions
+        return regions.select(mask, *spec[1:]) if isinstance(spec, tuple) else mask == spec
+
+    def _centre(self, spec, centre):
+        """``centre`` (x, y), or the centre of the region's bounding box in the current mask — read once, here (one host synchronisation)."""
+        if centre is not None:
+            cx, cy = (float(v) for v in centre)
+            return cx, cy
+        from . import regions
+        box = regions.bbox(self._resolve(self.mask, spec))
+        return (0.0, 0.0) if box is None else ((box[0] + box[2]) / 2, (box[1] + box[3]) / 2)
+
+    def fill(self, x, y, label, connectivity=4):
+        """Bucket fill: ``label`` over the component of pixel (x, y)."""
+        if connectivity not in (4, 8):
+            raise ValueError(f'fill: connectivity must be 4 or 8, got {connectivity!r}')
+        self._append(('fill',) + self._pixel(x, y, 'fill') + (self._own_label(label, 'fill'), connectivity))
+
+    def grow(self, label, radius, over=None):
+        """Dilate ``label`` by the disc of ``radius`` pixels; ``over``: the labels it may grow over (default: all)."""
+        label, over = self._own_label(label, 'grow'), None if over is None else tuple(sorted({self._own_label(l, 'grow') for l in over}))
+        self._append(('grow', label, self._radius(radius, 'grow'), over))
+
+    def shrink(self, label, radius):
+        """Erode ``label`` by the disc of ``radius`` pixels; the vacated pixels take the nearest other label."""
+        self._append(('shrink', self._own_label(label, 'shrink'), self._radius(radius, 'shrink')))
+
+    def remove(self, label):
+        """The label disappears under its nearest surroundings (``shrink`` without a bound)."""
+        self._append(('shrink', self._own_label(label, 'remove'), -1))
+
+    def _radius(self, radius, what):
+        self._need_load()
+        if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= MAX_SIZE:
+            raise ValueError(f'{what}: radius must be an integer 0 .. {MAX_SIZE}, got {radius!r}')
+        return int(radius)
+
+    def move(self, region, dx, dy):
+        """Shift the region by (dx, dy) pixels (y grows downwards); what it vacates is filled from the nearest surroundings."""
+        self.transform(region, [[1, 0, dx], [0, 1, dy]])
+
+    def scale(self, region, factor, centre=None):
+        """Scale the region by ``factor`` (a number, or (fx, fy)) about ``centre`` (x, y; default: the centre of its bounding box in the current mask)."""
+        spec = self._region_spec(region, 'scale')
+        fx, fy = (float(v) for v in factor) if isinstance(factor, (tuple, list)) else (float(factor), float(factor))
+        cx, cy = self._centre(spec, centre)
+        self.transform(spec, [[fx, 0, cx - fx * cx], [0, fy, cy - fy * cy]])
+
+    def rotate(self, region, degrees, centre=None):
+        """Rotate the region by ``degrees`` about ``centre`` (as ``scale``'s): (x, y) -> (x cos - y sin, x sin + y cos) in pixel axes, y downwards."""
+        spec = self._region_spec(region, 'rotate')
+        c, s = math.cos(math.radians(degrees)), math.sin(math.radians(degrees))
+        cx, cy = self._centre(spec, centre)
+        self.transform(spec, [[c, -s, cx - c * cx + s * cy], [s, c, cy - s * cx - c * cy]])
+
+    def transform(self, region, matrix, fill='nearest'):
+        """Move the region by the forward 2 x 3 ``matrix``; ``fill`` as ``regions.transform``.  The entry stores the six integers of ``regions.affine_coef``,
+        neither the floats nor a centre: a replay never depends on float arithmetic."""
+        from . import regions
+        self._need_load()
+        spec = self._region_spec(region, 'transform')
+        if isinstance(fill, str):
+            if fill != 'nearest':
+                raise ValueError(f"transform: fill must be 'nearest' or a label, got {fill!r}")
+        else:
+            fill = self._own_label(fill, 'transform')
+        self._append(('warp', spec, regions.affine_coef(matrix), fill))
+
+    def _apply(self, mask, entry):
+        from . import regions
+        kind = entry[0]
+        if kind == 'fill':
+            return regions.flood_fill(mask, *entry[1:])
+        if kind == 'grow':
+            return regions.grow(mask, *entry[1:])
+        if kind == 'shrink':
+            return regions.shrink(mask, *entry[1:])
+        return regions.transform(mask, self._resolve(mask, entry[1]), entry[2], fill=entry[3])
+
+    @property
+    def log(self):
+        """The entries, oldest first: ('paint', table), ('fill', x, y, label, connectivity), ('grow', label, radius, over), ('shrink', label, radius — -1: remove),
+        ('warp', region, six integers, fill)."""
+        return tuple(self._log)
 
     @property
     def strokes(self):
-        """The log as one int32 [K, 6] CPU table, in the order the mask is painted in."""
-        table = torch.cat(self._log) if self._log else torch.zeros([0, 6], dtype=torch.int32)
+        """Every stroke of the log as one int32 [K, 6] CPU table, in the order a run of paint() calls is painted in."""
+        tables = [e[1] for e in self._log if e[0] == 'paint']
+        table = torch.cat(tables) if tables else torch.zeros([0, 6], dtype=torch.int32)
         return replay_order(table, self.replay)
+
+    KEPT_MASKS = 32
+
+    def _mask_after(self, n):
+        """The mask after the first ``n`` entries.  A maximal run of paint entries is ONE ``p3d_paint_strokes`` launch over the mask in front of the run (``replay``
+        orders the strokes inside it); any other entry runs on the mask in front of it.  Masks are kept, so appending an entry runs that entry alone (a paint entry: its run,
+        one launch) and ``undo()`` back to a mask that was read runs nothing; past ``KEPT_MASKS`` the oldest are dropped and replay from the nearest kept one."""
+        todo = []                                                              # (first entry, end) segments still to apply, newest first
+        while n > 0 and n not in self._kept:
+            first = n - 1
+            while self._log[n - 1][0] == 'paint' and first > 0 and self._log[first - 1][0] == 'paint':
+                first -= 1
+            todo.append((first, n))
+            n = first
+        mask = self._kept[n] if n else self._base
+        for first, end in reversed(todo):
+            if self._log[first][0] == 'paint':
+                mask = paint_strokes(mask, replay_order(torch.cat([e[1] for e in self._log[first:end]]), self.replay))
+            else:
+                mask = self._apply(mask, self._log[first])
+            self._kept[end] = mask
+            while len(self._kept) > self.KEPT_MASKS:
+                del self._kept[min(self._kept)]
+        return mask
 
     @property
     @torch.no_grad()
     def mask(self):
-        """uint8 [H, W] on the device: the base with the log painted into it (one launch when the log changed; the base itself while the log is empty)."""
+        """uint8 [H, W] on the device: the base with the log applied (the launches of the entries that are new since the last kept mask; the base itself
+        while the log is empty)."""
         self._need_load()
         if self._mask is None:
-            self._mask = paint_strokes(self._base, self.strokes) if self._log else self._base
+            self._mask = self._mask_after(len(self._log))
         return self._mask
 
     # -- cameras ----------------------------------------------------------------------------------------------------------------
@@ -421,7 +561,7 @@ class EditSession:
         res = int(self.G.backbone.mapping.in_resolution)
         if tuple(base.shape) != (res, res):
             raise ValueError(f'take_view_as_mask: the rendered label map is {tuple(base.shape)}, the mapping network takes {res} x {res}')
-        self._base, self._log = base.clone(), []
+        self._base, self._log, self._kept = base.clone(), [], {}
         self._dirty_mask()
 
     def save(self, directory):
