@@ -199,6 +199,7 @@ def _raw(x):
 
 LayerRoute = collections.namedtuple('LayerRoute', 'kind split tag reads_split hands_split')
 RgbRoute = collections.namedtuple('RgbRoute', 'kind split tag pre_tag')
+BlockRoute = collections.namedtuple('BlockRoute', 'conv0 conv1 split rgb rgb_route img_first')
 
 
 def layer_route(n, ci, in_pixels, up, dtype, small=None):
@@ -239,6 +240,54 @@ def torgb_route(ci, co, pixels, dtype, nhwc=True, fused=False):
         return RgbRoute('gemm', False, None, pre_tag)
     ok = nhwc and ci % (64 if dtype == torch.float16 else 32) == 0
     return RgbRoute('mfma' if ok else None, split, _rgb_tag(BF16X3 if split else dtype), pre_tag)
+
+
+def _form_fits(form, n, ci, co, rco, h, w):
+    """THE switches and size tests of the fused ToRGB forms: what their kernels need of a 3x3 layer ci -> co at h x w ('wide_skip': of the ToRGB's ci inputs), rco image channels."""
+    fills = h >= 32 and w >= 32 and n * ((h + 15) // 16) * ((w + 15) // 16) >= 192      # (fewer 16 x 16 patches do not fill the chip: the dispatcher would take the split-K kernel)
+    if form == 'fused':                                    # co = 128: one channel block per work-group; 256 (fuse_torgb_256): each work-group walks both blocks of its patch
+        return bool(fuse_torgb and enabled and fills and co in ((128, 256) if fuse_torgb_256 else (128,)) and ci % 64 == 0 and rco <= 8)
+    if form == 'conv_wide_skip':
+        return bool(fuse_conv_wide_torgb and fuse_wide_torgb and enabled and split_bf16 and split_activations and fills and co == 128 and rco in (32, 64, 96) and ci % 32 == 0
+                    and not (h | w) & 1 and layer_route(n, ci, h * w, 1, torch.float32).reads_split)
+    return bool(fuse_wide_torgb and enabled and ci in (128, 256) and rco in (32, 64, 96) and w % 32 == 0)      # 'wide_skip': rows that are whole 32-pixel tiles
+
+
+def torgb_fuses(n, ci, co, rgb_co, h, w, dtype, up, noise, act):
+    """The sizes-and-switches part of torgb_fusable."""
+    return up == 1 and not noise and act in ('linear', 'lrelu') and dtype == torch.float16 and _form_fits('fused', n, ci, co, rgb_co, h, w)
+
+
+def block_route(n, ci, co, rco, res, in_div, dtype, nhwc, architecture, is_last, fused_modconv, noise_mode, use_noise, act, has_img, split_ok=False, x_dead=False):
+    """THE form a SynthesisBlock (ci -> co channels, rco image channels, at res x res from res // in_div) takes in device inference, from numbers and switches alone
+    (DESIGN 2.4e): SynthesisBlock.forward and prefetch_styles ask here, with the dtype / layout / modulation mode of _block_mode.  use_noise, act: conv1's;
+    has_img: a skip image comes in; split_ok: the returned x may be a SplitActs; x_dead: nobody reads it.  conv0 (None: there is none), conv1: their LayerRoute
+    (conv0's is informational: synthesis_layer and premodulate_many ask layer_route with the same numbers themselves; the forward reads conv1.tag alone);
+    split: both hand their result over as SplitActs (conv0's feeds conv1; conv1's this block's wide ToRGB and the next block's conv0); rgb: the ToRGB forms the
+    numbers allow, in the order they fall to one another when a form's operand check fails — () without a ToRGB, else ending in 'layer', which takes anything;
+    rgb_route: the RgbRoute by which rgb[0]'s consumer takes the plan's product (the permissions do not change it); img_first: the narrow skip image is
+    upsampled before conv1, which is handed it."""
+    px = res * res
+    conv0 = None if ci == 0 else layer_route(n, ci, px // (in_div * in_div), in_div, dtype)      # (in_div = 1: SynthesisBlockNoUp, whose conv0 keeps the resolution)
+    conv1 = layer_route(n, co, px, 1, dtype)
+    chain = ci != 0 and architecture != 'resnet'           # conv0 -> conv1 -> ToRGB with nothing in between
+    split = bool(chain and split_ok and dtype == torch.float32 and nhwc and fused_modconv is True and co % 32 == 0 and noise_mode != 'random' and rco > 8 and conv1.reads_split)
+    if not (is_last or architecture == 'skip'):
+        return BlockRoute(conv0, conv1, split, (), None, False)
+    forms = ['conv_wide_skip'] if split and x_dead and in_div == 2 and act in ('linear', 'lrelu') and _form_fits('conv_wide_skip', n, co, co, rco, res, res) else []
+    if has_img and in_div == 2 and rco > 8 and rco % 4 == 0 and nhwc:      # the wide image (96 tri-plane channels)
+        forms += ['wide_skip', 'wide_add'] if split and res % 2 == 0 and _form_fits('wide_skip', n, co, co, rco, res, res) else ['wide_add']
+    img_first = chain and has_img and rco <= 8
+    fused = img_first and fused_modconv is True and noise_mode != 'random' and torgb_fuses(n, co, co, rco, res, res, dtype, 1, use_noise and noise_mode == 'const', act)
+    forms += ['fused_dead' if x_dead else 'fused'] if fused else []
+    return BlockRoute(conv0, conv1, split, (*forms, 'layer'), torgb_route(co, rco, px, dtype, fused=fused), img_first)
+
+
+def planned_weights(pre, tag, weight=None, styles=None, demodulate=True):
+    """A plan's product ``pre`` = (tensor, tag) where it is what the consumer wants (``tag``); else None or, given the weights, modulated here in the tag's dtype."""
+    if pre is not None and pre[1] == tag:
+        return pre[0]
+    return None if weight is None else modulate_weights(weight, styles, demodulate=demodulate, dtype=tag[-1])
 
 
 def accepts_split_input(n, ci, in_pixels, up):
@@ -713,7 +762,7 @@ def synthesis_layer(x, weight, styles, bias, up, resample_filter, noise_const=No
     if isinstance(x, SplitActs) and not route.reads_split:
         x = x.dense()
     out_split = bool(out_split) and route.hands_split and act in ('linear', 'lrelu')
-    wpre = pre[0] if pre is not None and pre[1] == route.tag else None
+    wpre = planned_weights(pre, route.tag)
     def tensor_ops(y, fir, noise=True):                    # what no kernel's epilogue took: (4x4 low-pass with gain 4,) noise, bias + activation as passes of their own
         if fir:
             y = upfirdn2d.upfirdn2d(y, resample_filter, padding=[1, 1, 1, 1], gain=4)
@@ -740,7 +789,7 @@ def synthesis_layer(x, weight, styles, bias, up, resample_filter, noise_const=No
         kw = dict(split=split)
         wmod = wpre if wpre is not None else modulate_weights(weight, styles, demodulate=True, dtype=wtag)
         if rgb is not None:                                # a FusedRgb: checked by torgb_fusable
-            rgb_wmod = rgb.pre[0] if rgb.pre is not None and rgb.pre[1] == _rgb_tag(torch.float32) else modulate_weights(rgb.weight, rgb.styles, demodulate=False, dtype=torch.float32)
+            rgb_wmod = planned_weights(rgb.pre, _rgb_tag(torch.float32), rgb.weight, rgb.styles, False)
             return conv3x3_torgb(x, wmod, bias, act_idx, act_gain, clampv, rgb_wmod, rgb.bias, rgb.clamp, rgb.img, store_y=not rgb.x_dead)
     if up == 1 and act_idx is not None:
         return conv2d(x, wmod, bias=bias, noise=noise_const, noise_strength=noise_strength, act=act_idx, gain=act_gain, clamp=clampv, out_split=out_split and route.kind == 'mfma', **kw)
@@ -819,21 +868,11 @@ fuse_torgb_256 = os.environ.get('P3D_FUSE_TORGB_256', '1') != '0'      # ... and
 fuse_torgb = os.environ.get('P3D_FUSE_TORGB', '1') != '0'      # SynthesisBlock.conv1 + ToRGB + skip-image sum in one launch where the kernel allows (Co = 128, fp16)
 
 
-def torgb_fuses(n, ci, co, rgb_co, h, w, dtype, up, noise, act):
-    """The sizes-and-switches part of torgb_fusable (prefetch_styles asks it ahead of the layer: torgb_route's ``fused``).  co = 128: one channel block per
-    work-group; 256 (fuse_torgb_256): each work-group walks both blocks of its patch."""
-    return bool(fuse_torgb and enabled and up == 1 and not noise and act in ('linear', 'lrelu') and dtype == torch.float16
-                and n * ((h + 15) // 16) * ((w + 15) // 16) >= 192          # (fewer 16 x 16 patches do not fill the chip: the dispatcher would take the split-K kernel)
-                and co in ((128, 256) if fuse_torgb_256 else (128,)) and ci % 64 == 0 and h >= 32 and w >= 32 and rgb_co <= 8)
-
-
 def torgb_fusable(x, conv_weight, rgb_weight, img, up, noise_const, act):
     """Can the block's last 3x3 layer also produce its ToRGB contribution (csrc/conv2d.hip: p3d_conv3x3_torgb_f16)?  x is that layer's INPUT."""
-    if img is None or not _is_nhwc_f16(x):
-        return False
     n, ci, h, w = x.shape
     co = conv_weight.shape[0]
-    return (torgb_fuses(n, ci, co, rgb_weight.shape[0], h, w, x.dtype, up, noise_const is not None, act) and tuple(conv_weight.shape[2:]) == (3, 3)
+    return (img is not None and _is_nhwc_f16(x) and torgb_fuses(n, ci, co, rgb_weight.shape[0], h, w, x.dtype, up, noise_const is not None, act) and tuple(conv_weight.shape[2:]) == (3, 3)
             and tuple(rgb_weight.shape[1:]) == (co, 1, 1) and img.dtype == torch.float32 and img.is_contiguous() and _aligned(img) and tuple(img.shape) == (n, rgb_weight.shape[0], h, w)
             and not img.requires_grad and _no_grad_needed(x, conv_weight, rgb_weight))
 
@@ -872,24 +911,24 @@ def _filter_host(f):
 
 
 def torgb_wide_skip_supported(x, weight, prev, f):
-    """p3d_torgb_wide_split takes it: SplitActs of 128 / 256 channels, 32 / 64 / 96 outputs, rows that are whole 32-pixel tiles, and (if given) a
-    channels-last fp32 predecessor image at half the resolution."""
-    if not (fuse_wide_torgb and enabled and isinstance(x, SplitActs) and tuple(weight.shape[2:]) == (1, 1) and not torch.is_grad_enabled()):
-        return False
+    """p3d_torgb_wide_split takes it: SplitActs of the 'wide_skip' form's sizes (_form_fits) and a predecessor image as _prev_fits describes it, at even h."""
     n, ci, h, w = x.shape
     co = weight.shape[0]
-    if ci not in (128, 256) or co not in (32, 64, 96) or w % 32 != 0:
-        return False
-    return prev is None or (f is not None and tuple(f.shape) == (4, 4) and prev.dtype == torch.float32 and tuple(prev.shape) == (n, co, h // 2, w // 2) and h % 2 == 0
-            and prev.is_cuda and prev.is_contiguous(memory_format=torch.channels_last) and _aligned(prev) and not prev.requires_grad)
+    return (isinstance(x, SplitActs) and tuple(weight.shape[2:]) == (1, 1) and not torch.is_grad_enabled() and _form_fits('wide_skip', n, ci, ci, co, h, w)
+            and not (prev is not None and h % 2) and _prev_fits(prev, f, n, co, h, w))
+
+
+def _prev_fits(prev, f, n, co, h, w):
+    """The predecessor image as the wide kernels read it by pointer: none, or channels-last fp32 at half the resolution from a 16-byte boundary, with its 4x4 filter."""
+    return prev is None or (f is not None and tuple(f.shape) == (4, 4) and prev.dtype == torch.float32 and tuple(prev.shape) == (n, co, h // 2, w // 2)
+                            and prev.is_cuda and prev.is_contiguous(memory_format=torch.channels_last) and _aligned(prev) and not prev.requires_grad)
 
 
 def torgb_wide_skip(x, weight, styles, bias, clamp, prev, f, pre=None):
     """ToRGB of a SplitActs (wide image: the backbone's tri-planes) + the block's skip-image sum ``upsample2d(prev, f) + y`` in one launch -> fp32 NHWC."""
     n, ci, h, w = x.shape
     co = weight.shape[0]
-    wmod = pre[0] if pre is not None and pre[1] == _rgb_tag(BF16X3) else modulate_weights(weight, styles, demodulate=False, dtype=BF16X3)
-    wmod = kernel_operand(wmod)
+    wmod = kernel_operand(planned_weights(pre, _rgb_tag(BF16X3), weight, styles, False))
     y = torch.empty([n, co, h, w], dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     b32 = _f32c(bias)
     fh = None if prev is None else _filter_host(f)
@@ -907,22 +946,14 @@ conv_wide_torgb_calls = 0
 
 
 def conv3x3_torgb_wide_supported(x, conv_weight, rgb_weight, prev, f, up, act, noise=None):
-    """p3d_conv3x3_torgb_split takes it: a SplitActs into a 3x3 'same' layer of 128 output channels whose result nobody but the block's wide ToRGB reads (the caller
-    vouches for that), 32 / 64 / 96 image channels, enough 16 x 16 patches to fill the chip, and (if given) a channels-last fp32 predecessor image at half the resolution."""
-    if not (fuse_conv_wide_torgb and fuse_wide_torgb and enabled and split_bf16 and split_activations and isinstance(x, SplitActs) and up == 1 and act in ('linear', 'lrelu')
-            and not torch.is_grad_enabled()):
-        return False
+    """p3d_conv3x3_torgb_split takes it: a SplitActs into a 3x3 'same' layer of the 'conv_wide_skip' form's sizes (_form_fits) whose result nobody but the block's
+    wide ToRGB reads (the caller vouches for that), and what the kernel reads by pointer as it stands: a noise image of another size, or a skip image at an odd
+    address, sends the block to the two-launch form (synthesis_layer refuses the noise from Python; upsample2d reads any strides).  Biases and weights are
+    realigned by conv3x3_torgb_wide itself (_f32c, kernel_operand)."""
     n, ci, h, w = x.shape
     co, rco = conv_weight.shape[0], rgb_weight.shape[0]
-    if (co != 128 or tuple(conv_weight.shape[1:]) != (ci, 3, 3) or tuple(rgb_weight.shape[1:]) != (co, 1, 1) or rco not in (32, 64, 96) or ci % 32 != 0 or h < 32 or w < 32
-            or (h | w) & 1 or n * ((h + 15) // 16) * ((w + 15) // 16) < 192 or not layer_route(n, ci, h * w, 1, torch.float32).reads_split):
-        return False
-    # what p3d_conv3x3_torgb_split reads by pointer as it stands: a noise image of another size, or a skip image at an odd address, sends the block to the two-launch
-    # form (synthesis_layer refuses the noise from Python; upsample2d reads any strides).  Biases and weights are realigned by conv3x3_torgb_wide itself (_f32c, kernel_operand)
-    if not noise_fits(noise, h, w) or not _aligned(prev):
-        return False
-    return prev is None or (f is not None and tuple(f.shape) == (4, 4) and prev.dtype == torch.float32 and tuple(prev.shape) == (n, rco, h // 2, w // 2)
-            and prev.is_cuda and prev.is_contiguous(memory_format=torch.channels_last) and not prev.requires_grad)
+    return (isinstance(x, SplitActs) and not torch.is_grad_enabled() and up == 1 and act in ('linear', 'lrelu') and _form_fits('conv_wide_skip', n, ci, co, rco, h, w)
+            and tuple(conv_weight.shape[1:]) == (ci, 3, 3) and tuple(rgb_weight.shape[1:]) == (co, 1, 1) and noise_fits(noise, h, w) and _prev_fits(prev, f, n, rco, h, w))
 
 
 def conv3x3_torgb_wide(x, wmod, bias, noise, noise_strength, act, gain, clamp, rgb_wmod, rgb_bias, rgb_clamp, prev, f):
@@ -972,7 +1003,7 @@ def torgb(x, weight, styles, bias, clamp=None, out=None, pre=None):
         y = bias_act.bias_act(y, None if bias is None else bias.to(y.dtype), clamp=clamp)
         return y if out is None else out.add_(y)
     if route.kind != 'streaming':                          # the wide fp32 ToRGB (96 tri-plane channels) as bf16x3 too: as exact-fp32 MFMA it ran at a third of that pipe's peak, 0.29 ms per step
-        wmod = pre[0] if pre is not None and pre[1] == route.tag else modulate_weights(weight, styles, demodulate=False, dtype=route.tag[1])
+        wmod = planned_weights(pre, route.tag, weight, styles, False)
         y = conv2d(x, wmod, bias=bias, clamp=-1.0 if clamp is None else float(clamp), split=route.split)
         return y if out is None else out.add_(y)
     w32, s32, b32 = kernel_operand(weight.detach().float().reshape(co, ci)), _f32c(styles), _f32c(bias)

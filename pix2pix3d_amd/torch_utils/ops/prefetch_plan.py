@@ -35,6 +35,25 @@ class PrefetchPlan:
         self.entries[id(layer)] = Entry(styles, pre, mark[0], mark[1], self)
         return id(layer)
 
+    def enter(self, records, products, rgb_products, ahead):
+        """Enter a network's layers behind the events they wait for -> their keys.  records: (layer, styles) in forward order; products: per record (product, did
+        making it launch anything?), consumed as the marks are set — a generator's launches land right in front of their layer's mark; rgb_products(): called once,
+        right behind the first mark — {record index: (product, launched?)} of the ToRGB group.
+        One mark per layer that LAUNCHED something; a layer that did not (a shared-weight layer after the first) shares the mark of the last one that did (take
+        skips a position its stream already waits behind).  Right behind the FIRST layer's mark: every ToRGB layer's weight modulation (3-6 us each, eleven per
+        step, otherwise in line in front of their layers) and one mark for all that launched one — the network's first layer does not stand behind them, its
+        first ToRGB (tens of microseconds later) waits for that one mark, and from there on a wait is for everything issued."""
+        mark, rgb_pre, keys = None, {}, []
+        for k, ((layer, styles), (pre, fresh)) in enumerate(zip(records, products)):
+            if fresh or mark is None:
+                first = mark is None
+                mark = self.issue(own=first and not ahead)
+                if first:
+                    rgb_pre = rgb_products()
+                    rgb_mark = self.issue(own=not ahead) if any(launched for _, launched in rgb_pre.values()) else mark
+            keys.append(self.add(layer, styles, rgb_pre[k][0], rgb_mark) if k in rgb_pre else self.add(layer, styles, pre, mark))
+        return keys
+
     @classmethod
     def take(cls, layer, elision=True, wait_latest=True):
         """Pop this layer's Entry and make the current stream wait for it — unless (``elision``) the stream already waits behind its position: in the captured

@@ -4,6 +4,7 @@ Mirror of training/networks_stylegan2.py (line references below are to that file
 names, constructor arguments, parameter/buffer names (so ``copy_params_and_buffers`` and released
 checkpoints map 1:1) and forward semantics; the arithmetic runs on this package's operators.
 """
+import collections
 import os
 
 import weakref
@@ -244,6 +245,13 @@ class MappingNetwork(torch.nn.Module):
         return f'z_dim={self.z_dim:d}, c_dim={self.c_dim:d}, w_dim={self.w_dim:d}, num_ws={self.num_ws:d}'
 
 
+def _styles(layer, w, out_scale=1):
+    """(styles, the plan's product or None) of a modulated layer: its entry of the prefetch plan — made ahead on the side stream; taking it makes the current
+    stream wait for it — else the layer's affine of ``w``, computed here.  The one place that takes from the plan."""
+    planned = modconv.take_plan(layer) if modconv._plan else None
+    return (planned.styles, planned.pre) if planned is not None else (layer.affine(w, out_scale=out_scale), None)
+
+
 @persistence.persistent_class
 class SynthesisLayer(torch.nn.Module):
     """affine(w) -> modulated 3x3 conv (optionally x2 up) -> noise -> bias + lrelu (:277-337)."""
@@ -265,43 +273,32 @@ class SynthesisLayer(torch.nn.Module):
         self.bias = torch.nn.Parameter(torch.zeros([out_channels]))
 
     def forward(self, x, w, noise_mode='random', fused_modconv=True, gain=1, rgb=None, out_split=False, rgb_wide=None):
-        """``rgb`` (device inference, from SynthesisBlock): (torgb layer, its latent, skip image) — when the native kernel can, this layer
-        also adds the block's ToRGB output into the skip image from its own launch and returns (x, True); otherwise (x, False).
-        ``out_split`` (device inference, bf16x3): the caller's consumers read modconv.SplitActs; x may be one.
-        ``rgb_wide`` (device inference, bf16x3, from the LAST block of a network whose x nobody reads): (torgb layer, its latent, the skip image of the
-        block below or None, the resampling filter) — returns (None, img) when this layer's launch also produced the block's wide image
-        (modconv.conv3x3_torgb_wide: the activations are never stored), else (x, None) with x as ``out_split`` asks."""
+        """The private keywords are SynthesisBlock's, in device inference, as modconv.block_route decided.  ``rgb``: (torgb layer, its latent, the carried skip
+        image, x_dead, fuses) — with ``fuses``, where the operands allow it too (modconv.torgb_fusable), this layer's launch also adds the block's ToRGB output
+        into the skip image (x_dead: and does not store its own activations, x is None); returns (x, did it?).  ``out_split`` (bf16x3): the caller's consumers read
+        modconv.SplitActs; x may be one.  ``rgb_wide`` (bf16x3; the block has checked the operands): (torgb layer, its latent, the skip image of the block below or None,
+        the resampling filter, BlockRoute.conv1.tag, .rgb_route.tag) — this layer's launch produces the block's wide image and never stores x; returns (None, img)."""
         if noise_mode not in ('random', 'const', 'none'):
             raise AssertionError(f'unknown noise_mode {noise_mode!r}')
         in_res = self.resolution // self.up
         misc.assert_shape(x, [None, self.in_channels, in_res, in_res])
+        const_noise = self.use_noise and noise_mode == 'const'
+        noise_const, noise_strength = (self.noise_const, self.noise_strength) if const_noise else (None, None)
+        clamp = self.conv_clamp * gain if self.conv_clamp is not None else None
         if rgb_wide is not None:
-            assert rgb is None
-            torgb, w_rgb, prev, f = rgb_wide
-            if fused_modconv is True and noise_mode != 'random' and x.is_cuda and \
-                    modconv.conv3x3_torgb_wide_supported(x, self.weight, torgb.weight, prev, f, self.up, self.activation,
-                                                         noise=self.noise_const if self.use_noise and noise_mode == 'const' else None):
-                planned = modconv.take_plan(self) if modconv._plan else None
-                styles, pre = (planned.styles, planned.pre) if planned is not None else (self.affine(w), None)
-                wmod = pre[0] if pre is not None and pre[1] == modconv.layer_route(x.shape[0], self.in_channels, in_res * in_res, 1, torch.float32).tag else modconv.modulate_weights(self.weight, styles, demodulate=True, dtype=modconv.BF16X3)
-                planned_rgb = modconv.take_plan(torgb) if modconv._plan else None
-                s_rgb, pre_rgb = (planned_rgb.styles, planned_rgb.pre) if planned_rgb is not None else (torgb.affine(w_rgb, out_scale=torgb.weight_gain), None)
-                rgb_wmod = pre_rgb[0] if pre_rgb is not None and pre_rgb[1] == modconv.torgb_route(torgb.in_channels, torgb.out_channels, in_res * in_res, torch.float32).tag else \
-                    modconv.modulate_weights(torgb.weight, s_rgb, demodulate=False, dtype=modconv.BF16X3)
-                const_noise = self.use_noise and noise_mode == 'const'
-                img = modconv.conv3x3_torgb_wide(x, wmod, self.bias, self.noise_const if const_noise else None, self.noise_strength if const_noise else None,
-                                                 {'linear': 0, 'lrelu': 1}[self.activation], self.act_gain * gain,
-                                                 -1.0 if self.conv_clamp is None else float(self.conv_clamp * gain), rgb_wmod, torgb.bias, torgb.conv_clamp, prev, f)
-                return None, img
-            return self.forward(x, w, noise_mode=noise_mode, fused_modconv=fused_modconv, gain=gain, out_split=out_split), None
+            torgb, w_rgb, prev, f, tag, rgb_tag = rgb_wide
+            styles, pre = _styles(self, w)
+            wmod = modconv.planned_weights(pre, tag, self.weight, styles, True)
+            s_rgb, pre_rgb = _styles(torgb, w_rgb, torgb.weight_gain)
+            rgb_wmod = modconv.planned_weights(pre_rgb, rgb_tag, torgb.weight, s_rgb, False)
+            return None, modconv.conv3x3_torgb_wide(x, wmod, self.bias, noise_const, noise_strength, {'linear': 0, 'lrelu': 1}[self.activation], self.act_gain * gain,
+                                                    -1.0 if clamp is None else float(clamp), rgb_wmod, torgb.bias, torgb.conv_clamp, prev, f)
         if isinstance(x, modconv.SplitActs) and (rgb is not None or not modconv.layer_supported(x, self.weight, None, noise_mode, fused_modconv, self.up)):
             x = x.dense()
-        planned = modconv.take_plan(self) if modconv._plan else None
-        styles, pre = (planned.styles, planned.pre) if planned is not None else (self.affine(w), None)
+        styles, pre = _styles(self, w)
         noise = None
         if self.use_noise and noise_mode == 'random':
             noise = torch.randn([x.shape[0], 1, self.resolution, self.resolution], device=x.device) * self.noise_strength
-        clamp = self.conv_clamp * gain if self.conv_clamp is not None else None
         if native_channels_last and fused_modconv is True and x.is_cuda and not torch.is_grad_enabled() and not modconv.is_small(x, self.up) \
                 and not x.is_contiguous(memory_format=torch.channels_last):
             x = x.contiguous(memory_format=torch.channels_last)      # e.g. the output of a small generic-route layer feeding a native one
@@ -315,21 +312,16 @@ class SynthesisLayer(torch.nn.Module):
             return bias_act.bias_act(y, self.bias.to(y.dtype), act=self.activation, gain=self.act_gain * gain, clamp=clamp)
         if modconv.layer_supported(x, self.weight, styles, noise_mode, fused_modconv, self.up):
             # fp16 channels-last inference: weight modulation, MFMA conv, noise, bias, activation in native kernels
-            const_noise = self.use_noise and noise_mode == 'const'
             fused_rgb = None
             if rgb is not None:
-                torgb, w_rgb, img = rgb[:3]
-                if modconv.torgb_fusable(x, self.weight, torgb.weight, img, self.up, self.noise_const if const_noise else None, self.activation):
-                    planned_rgb = modconv.take_plan(torgb) if modconv._plan else None
-                    s_rgb = planned_rgb.styles if planned_rgb is not None else torgb.affine(w_rgb, out_scale=torgb.weight_gain)
-                    fused_rgb = modconv.FusedRgb(torgb.weight, s_rgb, torgb.bias, torgb.conv_clamp, img, x_dead=len(rgb) > 3 and bool(rgb[3]),
-                                                 pre=planned_rgb.pre if planned_rgb is not None else None)
-            y = modconv.synthesis_layer(x, self.weight, styles, self.bias, self.up, self.resample_filter,
-                                        noise_const=self.noise_const if const_noise else None,
-                                        noise_strength=self.noise_strength if const_noise else None,
+                torgb, w_rgb, img, x_dead, fuses = rgb
+                if fuses and modconv.torgb_fusable(x, self.weight, torgb.weight, img, self.up, noise_const, self.activation):
+                    s_rgb, pre_rgb = _styles(torgb, w_rgb, torgb.weight_gain)
+                    fused_rgb = modconv.FusedRgb(torgb.weight, s_rgb, torgb.bias, torgb.conv_clamp, img, x_dead=bool(x_dead), pre=pre_rgb)
+            y = modconv.synthesis_layer(x, self.weight, styles, self.bias, self.up, self.resample_filter, noise_const=noise_const, noise_strength=noise_strength,
                                         act=self.activation, act_gain=self.act_gain * gain, clamp=clamp, pre=pre, rgb=fused_rgb, out_split=out_split)
             return y if rgb is None else (y, fused_rgb is not None)
-        if self.use_noise and noise_mode == 'const':
+        if const_noise:
             noise = self.noise_const * self.noise_strength
         x = modulated_conv2d(x=x, weight=self.weight, styles=styles, noise=noise, up=self.up, padding=self.padding,
                              resample_filter=self.resample_filter, flip_weight=(self.up == 1), fused_modconv=fused_modconv)
@@ -357,12 +349,11 @@ class ToRGBLayer(torch.nn.Module):
     def forward(self, x, w, fused_modconv=True, accumulate_into=None):
         """``accumulate_into`` (device inference): an fp32 image the native kernel may add its result to in place — the skip-image sum of
         SynthesisBlock without a separate launch.  The return value is then that image; callers check identity."""
-        planned = modconv.take_plan(self) if modconv._plan else None
-        styles = planned.styles if planned is not None else self.affine(w, out_scale=self.weight_gain)
+        styles, pre = _styles(self, w, self.weight_gain)
         x = modconv.dense_input(x)
         if modconv.torgb_supported(x, self.weight, styles, fused_modconv):
             out = accumulate_into if accumulate_into is not None and modconv.torgb_accumulates(x, self.weight, accumulate_into) else None
-            return modconv.torgb(x, self.weight, styles, self.bias, clamp=self.conv_clamp, out=out, pre=planned.pre if planned is not None else None)      # fp32 NCHW, bias + clamp fused
+            return modconv.torgb(x, self.weight, styles, self.bias, clamp=self.conv_clamp, out=out, pre=pre)      # fp32 NCHW, bias + clamp fused
         if isinstance(x, modconv.SplitActs):
             x = x.dense()
         x = modulated_conv2d(x=x, weight=self.weight, styles=styles, demodulate=False, fused_modconv=fused_modconv)
@@ -447,12 +438,18 @@ class SynthesisBlock(torch.nn.Module):
     def forward(self, x, img, ws, force_fp32=False, fused_modconv=None, update_emas=False, _split_ok=False, _x_dead=False, **layer_kwargs):
         """``_split_ok`` (private, set by SynthesisNetwork.forward only): the returned ``x`` may be a modconv.SplitActs that only the next block of the
         same network reads.  Every other caller — a feature extractor stepping through the blocks, a forward hook — gets the reference's contract: a
-        tensor."""
+        tensor.  ``_x_dead`` (private: the last block of SynthesisNetwork.forward and of the super-resolution heads): the caller drops x, so a form
+        whose launch also makes the ToRGB contribution returns None for it."""
         del update_emas
         misc.assert_shape(ws, [None, self.num_conv + self.num_torgb, self.w_dim])
         dtype, fmt, fused_modconv = _block_mode(self, ws, force_fp32, fused_modconv)
         per_layer = list(ws.unbind(dim=1))                       # one w per conv layer, then one for ToRGB
         conv_kwargs = dict(layer_kwargs, fused_modconv=fused_modconv)
+        w_rgb, noise_mode = per_layer[-1], layer_kwargs.get('noise_mode', 'random')      # (w_rgb: where the block has a ToRGB)
+        # device inference: the form is decided once, from numbers; every other pass takes the reference's: plain layers, then the ToRGB layer
+        route = (self._route(ws.shape[0], dtype, fmt, fused_modconv, noise_mode, img is not None, _split_ok, _x_dead) if ws.is_cuda and not torch.is_grad_enabled()
+                 else modconv.BlockRoute(None, None, False, ('layer',) * self.num_torgb, None, False))
+        forms = route.rgb
 
         x = self._entry_features(x, ws.shape[0], dtype, fmt)
         if self.in_channels == 0:
@@ -462,67 +459,54 @@ class SynthesisBlock(torch.nn.Module):
             x = self.conv0(x, per_layer[0], **conv_kwargs)
             x = self.conv1(x, per_layer[1], gain=np.sqrt(0.5), **conv_kwargs)
             x = shortcut.add_(x)
-        rgb_done = False
-        wants_rgb = self.is_last or self.architecture == 'skip'
-        if self.in_channels != 0 and self.architecture != 'resnet':
-            # bf16x3 device inference: x stays in the matrix cores' (hi, lo) layout between the layers whose kernels read it (modconv.SplitActs):
-            # conv0's result feeds conv1; conv1's feeds this block's ToRGB and the next block's conv0 (a consumer that cannot read it calls dense())
-            keep_split = (_split_ok and dtype == torch.float32 and fmt == torch.channels_last and fused_modconv is True and ws.is_cuda and not torch.is_grad_enabled()
-                          and self.conv1.out_channels % 32 == 0 and layer_kwargs.get('noise_mode', 'random') != 'random' and self.img_channels > 8
-                          and modconv.accepts_split_input(ws.shape[0], self.conv1.out_channels, self.resolution ** 2, 1))
-            x = self.conv0(x, per_layer[0], out_split=keep_split, **conv_kwargs)
-            if keep_split and _x_dead and wants_rgb and self._in_div == 2 and (img is None or img.is_contiguous(memory_format=torch.channels_last)):
-                # the network's LAST block (SynthesisNetwork.forward: nobody reads its x): conv1, the wide ToRGB and the skip-image sum in one launch where
-                # the kernel takes the sizes — the layer's activations are then never written (csrc/conv2d.hip: conv3x3_r2_bf16x3_kernel<TR>)
-                if img is not None:
-                    misc.assert_shape(img, [None, self.img_channels, self.resolution // 2, self.resolution // 2])
-                x, fused_img = self.conv1(x, per_layer[1], out_split=True, rgb_wide=(self.torgb, per_layer[self.num_conv], img, self.resample_filter), **conv_kwargs)
-                if fused_img is not None:
-                    return None, fused_img
-                img_carried = False
-            elif keep_split:
-                x = self.conv1(x, per_layer[1], out_split=True, **conv_kwargs)
-                img_carried = False
-            elif wants_rgb and img is not None and self.img_channels <= 8 and x.is_cuda and not torch.is_grad_enabled():
-                img = self._carry_image(img)                     # (independent of the convolutions: done first so that conv1 can add into it)
-                # _x_dead (private, set by the super-resolution heads for their last block): the caller drops the returned x, so when conv1 also produces
-                # the ToRGB contribution its activations are never stored and x comes back as None
-                x, rgb_done = self.conv1(x, per_layer[1], rgb=(self.torgb, per_layer[self.num_conv], img, _x_dead), **conv_kwargs)
-                img_carried = True
-            else:
-                x = self.conv1(x, per_layer[1], **conv_kwargs)
-                img_carried = False
         else:
-            img_carried = False
+            x = self.conv0(x, per_layer[0], out_split=route.split, **conv_kwargs)
+            if forms[:1] == ('conv_wide_skip',):
+                if self._operands_fit('conv_wide_skip', x, img, noise_mode):
+                    return self.conv1(x, per_layer[1], rgb_wide=(self.torgb, w_rgb, img, self.resample_filter, route.conv1.tag, route.rgb_route.tag), **conv_kwargs)
+                forms = forms[1:]
+            if route.img_first:
+                img = self._carry_image(img)                     # (independent of the convolutions: done first so that conv1 can add into it)
+                x, rgb_done = self.conv1(x, per_layer[1], rgb=(self.torgb, w_rgb, img, _x_dead, forms[0] != 'layer'), **conv_kwargs)
+                if rgb_done:
+                    return x, img
+            else:
+                x = self.conv1(x, per_layer[1], out_split=route.split, **conv_kwargs)
 
-        if (wants_rgb and not rgb_done and img is not None and not img_carried and self._in_div == 2 and self.img_channels > 8 and self.img_channels % 4 == 0
-                and img.is_cuda and not torch.is_grad_enabled() and fmt == torch.channels_last and img.is_contiguous(memory_format=torch.channels_last)):
-            # wide skip image (the 96 tri-plane channels), device inference: ToRGB first, then its upsampled predecessor is added INTO it by the
-            # upsampling launch — one pass over the image instead of three (upsample, ToRGB, add)
+        form = next((f for f in forms if self._operands_fit(f, x, img, noise_mode)), None)
+        if form == 'wide_skip':                                  # split activations in: ToRGB and the skip-image sum in ONE pass over the image (csrc/torgb_split.hip)
+            s_rgb, pre = _styles(self.torgb, w_rgb, self.torgb.weight_gain)
+            img = modconv.torgb_wide_skip(x, self.torgb.weight, s_rgb, self.torgb.bias, self.torgb.conv_clamp, img, self.resample_filter, pre=pre)
+        elif form == 'wide_add':     # ToRGB first, then its upsampled predecessor is added INTO it by the upsampling launch — one pass over the image instead of three
             misc.assert_shape(img, [None, self.img_channels, self.resolution // 2, self.resolution // 2])
-            if fused_modconv is True and modconv.torgb_wide_skip_supported(x, self.torgb.weight, img, self.resample_filter):
-                # split activations in: ToRGB and the skip-image sum in ONE pass over the image (csrc/torgb_split.hip)
-                planned = modconv.take_plan(self.torgb) if modconv._plan else None
-                s_rgb = planned.styles if planned is not None else self.torgb.affine(per_layer[self.num_conv], out_scale=self.torgb.weight_gain)
-                img = modconv.torgb_wide_skip(x, self.torgb.weight, s_rgb, self.torgb.bias, self.torgb.conv_clamp, img, self.resample_filter,
-                                              pre=planned.pre if planned is not None else None)
-                return x, img
-            y = self.torgb(x, per_layer[self.num_conv], fused_modconv=fused_modconv)
+            y = self.torgb(x, w_rgb, fused_modconv=fused_modconv)
             if y.dtype == torch.float32 and y.is_contiguous(memory_format=torch.channels_last):
                 img = upfirdn2d.upsample2d_add_(y, img, self.resample_filter)
             else:
                 img = self._accumulate_image(self._carry_image(img), y, fmt)
-            assert x.dtype == dtype and img.dtype == torch.float32
-            return x, img
-        if img is not None and not img_carried:
-            img = self._carry_image(img)
-        if wants_rgb and not rgb_done:
-            y = self.torgb(x, per_layer[self.num_conv], fused_modconv=fused_modconv, accumulate_into=img)
-            img = img if y is img else self._accumulate_image(img, y, fmt)
-
-        assert (x is None and _x_dead and rgb_done) or x.dtype == dtype
+        else:                                                    # 'layer', or no ToRGB at all: the reference's step (:453-463)
+            if img is not None and not route.img_first:
+                img = self._carry_image(img)
+            if self.num_torgb:
+                y = self.torgb(x, w_rgb, fused_modconv=fused_modconv, accumulate_into=img)      # (the native ToRGB adds into the carried image in its own launch where it can)
+                img = img if y is img else self._accumulate_image(img, y, fmt)
+        assert x.dtype == dtype
         assert img is None or img.dtype == torch.float32
         return x, img
+
+    def _route(self, batch, dtype, fmt, fused_modconv, noise_mode, has_img, split_ok, x_dead):
+        return modconv.block_route(batch, self.in_channels, self.conv1.out_channels, self.img_channels, self.resolution, self._in_div, dtype, fmt == torch.channels_last,
+                                   self.architecture, self.is_last, fused_modconv, noise_mode, self.conv1.use_noise, self.conv1.activation, has_img, split_ok, x_dead)
+
+    def _operands_fit(self, form, x, img, noise_mode):
+        """A form's operand check: what only the tensors at hand can say — layout, address, dtype and requires_grad of the images, a noise image of another size, whether
+        x really arrived split.  A form whose check fails leaves the block to the next one of BlockRoute.rgb.  ('fused' / 'fused_dead': conv1's own, modconv.torgb_fusable.)"""
+        if form == 'conv_wide_skip':                             # (x: conv1's input)
+            return modconv.conv3x3_torgb_wide_supported(x, self.conv1.weight, self.torgb.weight, img, self.resample_filter, self.conv1.up, self.conv1.activation,
+                                                        noise=self.conv1.noise_const if self.conv1.use_noise and noise_mode == 'const' else None)
+        if form == 'wide_skip':
+            return modconv.torgb_wide_skip_supported(x, self.torgb.weight, img, self.resample_filter)
+        return form == 'layer' or (form == 'wide_add' and img.is_cuda and img.is_contiguous(memory_format=torch.channels_last))
 
     def _carry_image(self, img):
         """The running skip image at this block's resolution (:453-456)."""
@@ -583,14 +567,19 @@ _const_batches = weakref.WeakKeyDictionary()      # SynthesisBlock (b4) -> (stam
 modconv.on_invalidate(_const_batches.clear)
 
 
-def prefetch_styles(blocks, block_ws, block_kwargs, ahead=False):
+# One modulated layer of a plan.  pixels: per image at its input; rgb: a ToRGB layer; fused: ... that its block's conv1 takes along (BlockRoute.rgb_route)
+PlanRecord = collections.namedtuple('PlanRecord', 'layer w out_scale pixels dtype rgb fused', defaults=(False, False))
+
+
+def prefetch_styles(blocks, block_ws, block_kwargs, ahead=False, has_img=False):
     """Device inference: every layer's style affine and weight modulation depend on ``ws`` alone, so they are issued up front on a
     second stream and run under the convolutions of the layers before them (they are memory-bound, the convolutions are not);
-    a layer waits for its entry's event (modconv.take_plan).  Anything the plan gets wrong (a layer that ends up on another route) is
+    a layer waits for its entry's event (modconv.take_plan).  A product whose layer ends up on another route (an operand check that fails) is
     simply recomputed.  Returns the plan's keys when a plan was made — the caller joins the side stream and drops them afterwards (finish_prefetch) — else None.
     ``ahead``: issued for a network that runs LATER in the step (the super-resolution heads, from inside the backbone's forward right after its own plan,
     ``PrefetchPlan.defer``): the side stream is already ordered behind whatever made ``ws`` and nothing of the earlier plan has been released yet, so
-    it neither waits for the calling stream again nor touches other networks' entries."""
+    it neither waits for the calling stream again nor touches other networks' entries.  ``has_img``: the first block is handed a skip image.  The plan
+    assumes that ``blocks`` run in this order, each handed the img the one before returned, as SynthesisNetwork.forward and the heads thread it."""
     ws0 = block_ws[0]
     fused = block_kwargs.get('fused_modconv')
     own = [id(l) for b in blocks for l in (getattr(b, 'conv0', None), b.conv1, getattr(b, 'torgb', None)) if l is not None]
@@ -599,50 +588,33 @@ def prefetch_styles(blocks, block_ws, block_kwargs, ahead=False):
     if not (modconv.prefetch_styles and modconv.enabled and native_channels_last and ws0.is_cuda and not torch.is_grad_enabled()
             and (fused is None or fused is True)):
         return None
-    force_fp32 = bool(block_kwargs.get('force_fp32', False))
     plan = modconv.plan_for(ws0.device)
     main, side = torch.cuda.current_stream(), plan.side
     if not ahead:
         side.wait_stream(main)
-    keys = []
     with torch.cuda.stream(side):
-        todo = []                                          # (layer, latent row, out_scale, input pixels or None for ToRGB, dtype)
+        todo = []                                          # decided by the _block_mode and the block_route the forward itself will ask (the two permissions aside)
         for block, cur in zip(blocks, block_ws):
+            img_in, has_img = has_img, has_img or hasattr(block, 'torgb')      # (the forward's img: None until a block with a ToRGB has run)
             if block.fused_modconv_default is not True and fused is None and block.training and not native_no_grad_fused(ws0):
                 continue
-            res = block.resolution
-            dtype = torch.float16 if block.use_fp16 and not force_fp32 else torch.float32
-            ws_iter = iter(cur.unbind(dim=1))
-            layers = [(block.conv1, res)] if block.in_channels == 0 else [(block.conv0, res // block._in_div), (block.conv1, res)]
-            for layer, in_res in layers:
-                todo.append((layer, next(ws_iter), 1, in_res * in_res, dtype))
-            if block.is_last or block.architecture == 'skip':
-                # (its modulated weights too — ('rgb', pixels, fused into conv1?) — where something would otherwise launch that modulation in line; premodulate_torgb)
-                rgb_fused = (block.in_channels != 0 and block.architecture == 'skip' and block.img_channels <= 8 and block_kwargs.get('noise_mode', 'random') != 'random'
-                         and modconv.torgb_fuses(ws0.shape[0], block.conv1.in_channels, block.conv1.out_channels, block.img_channels, res, res, dtype, block.conv1.up,
-                                                 block.conv1.use_noise and block_kwargs.get('noise_mode') == 'const', block.conv1.activation))
-                todo.append((block.torgb, next(ws_iter), block.torgb.weight_gain, ('rgb', res * res, rgb_fused) if modconv.premodulate_rgb else None, dtype))
+            dtype, fmt, fused_modconv = _block_mode(block, cur, bool(block_kwargs.get('force_fp32', False)), fused)
+            route = block._route(cur.shape[0], dtype, fmt, fused_modconv, block_kwargs.get('noise_mode', 'random'), img_in, False, False)
+            ws_iter, res = iter(cur.unbind(dim=1)), block.resolution
+            if block.in_channels != 0:
+                todo.append(PlanRecord(block.conv0, next(ws_iter), 1, (res // block._in_div) ** 2, dtype))
+            todo.append(PlanRecord(block.conv1, next(ws_iter), 1, res * res, dtype))
+            if route.rgb:
+                todo.append(PlanRecord(block.torgb, next(ws_iter), block.torgb.weight_gain, res * res, dtype, True, route.rgb_route.kind == 'fused'))
         # every style affine of the network in one launch (they are ~6 us of launch latency each on their own)
-        batched = (0 < len(todo) <= modconv.FC_MAX_JOBS and len({t[1].shape[0] for t in todo}) == 1 and all(t[1].shape[1] % 4 == 0 for t in todo)   # (fc_multi takes whole float4 rows; fc() pads)
-                   and all(modconv.fc_supported(w, l.affine.weight, l.affine.bias, l.affine.activation) for l, w, *_ in todo))
-        all_styles = (modconv.fc_multi([(w, l.affine, sc) for l, w, sc, _, _ in todo]) if batched
-                      else [l.affine(w) if sc == 1 else l.affine(w, out_scale=sc) for l, w, sc, _, _ in todo])
-        # (ToRGB entries carry ('rgb', pixels): premodulate_many itself launches nothing for them — their modulations are issued together, below)
-        items = [(layer.weight, styles, getattr(layer, 'up', 1), None if isinstance(in_pixels, tuple) else in_pixels, dtype) for (layer, _, _, in_pixels, dtype), styles in zip(todo, all_styles)]
-        pres = modconv.premodulate_many(items)
-        # one event per layer that LAUNCHED something; a layer that did not (a shared-weight layer after the first) shares the event of the last one that did
-        # (PrefetchPlan.take skips a position its stream already waits behind).  Right behind the FIRST layer's event: every ToRGB layer's weight modulation (3-6 us
-        # each, eleven per step, otherwise in line in front of their layers) and one event for all that launched one — the network's first layer does not stand
-        # behind them, its first ToRGB (tens of microseconds later) waits for that one event, and from there on a wait is for everything issued.
-        mark, rgb_pre = None, {}
-        for k, ((layer, _, _, in_pixels, dtype), styles, (pre, fresh)) in enumerate(zip(todo, all_styles, pres)):
-            if fresh or mark is None:
-                first = mark is None
-                mark = plan.issue(own=first and not ahead)
-                if first:
-                    rgb_pre = {j: modconv.premodulate_torgb(t[0].weight, all_styles[j], t[3][1], t[4], fused=t[3][2]) for j, t in enumerate(todo) if isinstance(t[3], tuple)}
-                    rgb_mark = plan.issue(own=not ahead) if any(p is not None for p in rgb_pre.values()) else mark
-            keys.append(plan.add(layer, styles, rgb_pre[k], rgb_mark) if k in rgb_pre else plan.add(layer, styles, pre, mark))
+        batched = (0 < len(todo) <= modconv.FC_MAX_JOBS and len({t.w.shape[0] for t in todo}) == 1 and all(t.w.shape[1] % 4 == 0 for t in todo)   # (fc_multi takes whole float4 rows; fc() pads)
+                   and all(modconv.fc_supported(t.w, t.layer.affine.weight, t.layer.affine.bias, t.layer.affine.activation) for t in todo))
+        all_styles = modconv.fc_multi([(t.w, t.layer.affine, t.out_scale) for t in todo]) if batched else [t.layer.affine(t.w, out_scale=t.out_scale) for t in todo]
+        # (premodulate_many itself launches nothing for the ToRGB layers — pixels None —: their modulations are issued together, behind the first mark)
+        pres = modconv.premodulate_many([(t.layer.weight, st, getattr(t.layer, 'up', 1), None if t.rgb else t.pixels, t.dtype) for t, st in zip(todo, all_styles)])
+        rgb_pres = lambda: {k: (pre, pre is not None) for k, pre in ((k, modconv.premodulate_torgb(t.layer.weight, all_styles[k], t.pixels, t.dtype, fused=t.fused))
+                                                                     for k, t in enumerate(todo) if t.rgb and modconv.premodulate_rgb)}
+        keys = plan.enter([(t.layer, st) for t, st in zip(todo, all_styles)], pres, rgb_pres, ahead)
     if not ahead:
         plan.run_deferred()            # (networks later in the step: their plans follow this one on the side stream, before any of its tensors is released)
     return keys
@@ -682,11 +654,11 @@ class SynthesisNetwork(torch.nn.Module):
                 block = getattr(self, f'b{res}')
                 block_ws.append(ws.narrow(1, idx, block.num_conv + block.num_torgb))     # ToRGB shares the next block's first w
                 idx += block.num_conv
-        planned = self._prefetch(block_ws, block_kwargs)
+        blocks = [getattr(self, f'b{res}') for res in self.block_resolutions]
+        planned = prefetch_styles(blocks, block_ws, block_kwargs)
         x = img = None
         try:
             _m = torch.nn.modules.module
-            blocks = [getattr(self, f'b{res}') for res in self.block_resolutions]
             for i, (block, cur) in enumerate(zip(blocks, block_ws)):
                 # x is private to this loop unless somebody can observe it: a forward hook on the producing block (its output), a forward PRE-hook on
                 # the consuming block (its input), or a global hook of either kind — then it stays a tensor.  Sampled per block, not per pass.
@@ -701,9 +673,6 @@ class SynthesisNetwork(torch.nn.Module):
             if planned is not None:
                 finish_prefetch(ws.device, planned)
         return img
-
-    def _prefetch(self, block_ws, block_kwargs):
-        return prefetch_styles([getattr(self, f'b{res}') for res in self.block_resolutions], block_ws, block_kwargs)
 
     def extra_repr(self):
         return (f'w_dim={self.w_dim:d}, num_ws={self.num_ws:d}, img_resolution={self.img_resolution:d}, '

@@ -43,7 +43,7 @@ class _SuperresolutionBase(torch.nn.Module):
         if not (ws.is_cuda and not torch.is_grad_enabled()):
             return
         row = ws[:, -1:, :].expand(-1, 3, -1)
-        keys = prefetch_styles([self.block0, self.block1], [row, row], block_kwargs, ahead=True)
+        keys = prefetch_styles([self.block0, self.block1], [row, row], block_kwargs, ahead=True, has_img=True)
         if keys is not None:
             modconv.plan_for(ws.device).hand_over(self, ws, keys)
 
@@ -56,7 +56,7 @@ class _SuperresolutionBase(torch.nn.Module):
         else:
             ws = ws[:, -1:, :].repeat(1, 3, 1)
         rgb, x = self._prep(rgb, x)
-        planned = ahead if ahead is not None else prefetch_styles([self.block0, self.block1], [ws, ws], block_kwargs)
+        planned = ahead if ahead is not None else prefetch_styles([self.block0, self.block1], [ws, ws], block_kwargs, has_img=True)
         try:
             x, rgb = self.block0(x, rgb, ws, **block_kwargs)
             # block1's x is returned to nobody (:297-354 of the reference return rgb only): unless somebody hooked the block to look at it, its last

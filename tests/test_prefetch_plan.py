@@ -31,17 +31,10 @@ class Device:
 
 
 def issue(plan, layers, rgb, ahead=False, fresh=None):
-    """What networks_stylegan2.prefetch_styles does with the plan: an event behind the first layer's work (the network's own), one behind the ToRGB group's weight
-    modulations, then one per layer that launched something (``fresh``: all but the ToRGB layers and the shared-weight layers after the first)."""
-    mark, keys = None, []
-    for k, layer in enumerate(layers):
-        if mark is None or (layer not in rgb and (fresh is None or fresh[k])):
-            first = mark is None
-            mark = plan.issue(own=first and not ahead)
-            if first:
-                rgb_mark = plan.issue(own=not ahead)
-        keys.append(plan.add(layer, ('styles', layer), None, rgb_mark if layer in rgb else mark))
-    return keys
+    """PrefetchPlan.enter — the loop prefetch_styles itself runs — over stand-in layers: a mark behind the first layer's work (the network's own), one behind
+    the ToRGB group's weight modulations, then one per layer that launched something (``fresh``: all but the ToRGB layers and the shared-weight layers after the first)."""
+    launched = [(None, layer not in rgb and (fresh is None or fresh[k])) for k, layer in enumerate(layers)]
+    return plan.enter([(layer, ('styles', layer)) for layer in layers], launched, lambda: {k: (None, True) for k, layer in enumerate(layers) if layer in rgb}, ahead)
 
 
 def network(n_blocks):
