@@ -327,20 +327,36 @@ def image_grid(frames, grid_size):
 
 
 @torch.no_grad()
-def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=120, fps=60, **render_kwargs):
+def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=120, fps=60, gif='pil', **render_kwargs):
     """generate_video.py after its inputs: the ``cfg`` cameras (``video_cameras``) at the script's ray resolution with ``noise_mode='const'``, rendered by
-    ``render_views`` (its keyword arguments pass through); ``path`` / ``path_label`` receive the two GIFs the script writes with imageio at 60 fps
-    (through ``mesh.save_gif``).  Returns ``render_views``' dict."""
+    ``render_views`` (its keyword arguments pass through); ``path`` / ``path_label`` receive the two GIFs the script writes with imageio at 60 fps.
+    ``gif='pil'``: through ``mesh.save_gif``, PIL quantising every frame on the host.  ``gif='device'``: the image through ``video.save_gif`` (one palette for
+    the clip, made and applied where the frames are) and the label video losslessly through ``video.save_gif_indexed`` — ``label_index`` with the frames'
+    palette, or the edge generators' grey frames with a grey ramp.  Returns ``render_views``' dict."""
+    if gif not in ('pil', 'device'):
+        raise ValueError(f"generate_video: gif must be 'pil' or 'device', got {gif!r}")
     cams = video_cameras(G, cfg, n_frames).to(ws.device)
     render_kwargs.setdefault('noise_mode', 'const')
     render_kwargs.setdefault('neural_rendering_resolution', VIDEO_CFG[cfg]['neural_rendering_resolution'])
     frames = render_views(G, ws, cams, **render_kwargs)
     if path is not None:
-        mesh.save_gif(path, frames['image'], fps=fps)
+        if gif == 'device':
+            from . import video
+            video.save_gif(path, frames['image'], fps=fps)
+        else:
+            mesh.save_gif(path, frames['image'], fps=fps)
     if path_label is not None:
         if 'label' not in frames:
             raise ValueError(f'generate_video: {type(G).__name__} has no label output for path_label')
-        mesh.save_gif(path_label, frames['label'], fps=fps)
+        if gif == 'device':
+            from . import video
+            if 'label_index' in frames:                                        # default_palette(c) is the first c rows of default_palette(256)
+                pal = render_kwargs.get('palette')
+                video.save_gif_indexed(path_label, frames['label_index'], mesh.default_palette(256) if pal is None else torch.as_tensor(pal), fps=fps)
+            else:
+                video.save_gif_indexed(path_label, frames['label'], torch.arange(256, dtype=torch.uint8)[:, None].expand(256, 3), fps=fps)
+        else:
+            mesh.save_gif(path_label, frames['label'], fps=fps)
     return frames
 
 
