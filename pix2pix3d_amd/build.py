@@ -1,4 +1,4 @@
-"""Build libp3d_hip.so (the C-ABI kernel library), libp3d_probes.so, libp3d_regions.so and libp3d_video.so in-tree with hipcc for gfx950.
+"""Build libp3d_hip.so (the C-ABI kernel library), libp3d_probes.so, libp3d_regions.so, libp3d_video.so and libp3d_sketch.so in-tree with hipcc for gfx950.
 
 No torch headers, no pybind: every ``csrc/*.hip`` translation unit is compiled to an object
 (in parallel, cached by mtime) and linked into ``pix2pix3d_amd/libp3d_hip.so`` so the binary
@@ -20,6 +20,8 @@ REGIONS_DIR = os.path.join(CSRC, 'regions')
 REGIONS_LIB_PATH = os.path.join(PKG_DIR, 'libp3d_regions.so')    # region tools of the edit session: a library of its own too (csrc/regions/p3d_regions.h)
 VIDEO_DIR = os.path.join(CSRC, 'video')
 VIDEO_LIB_PATH = os.path.join(PKG_DIR, 'libp3d_video.so')        # palette, dither and index frames of the GIF writer: likewise (csrc/video/p3d_video.h)
+SKETCH_DIR = os.path.join(CSRC, 'sketch')
+SKETCH_LIB_PATH = os.path.join(PKG_DIR, 'libp3d_sketch.so')      # edge-map canvas of the sketch session: likewise (csrc/sketch/p3d_sketch.h)
 ARCH = 'gfx950'
 CXXFLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-Wall', '-Wno-unused-function',
             '-fno-gpu-rdc', '-DNDEBUG']
@@ -55,12 +57,17 @@ def video_sources():
     return sorted(os.path.join(VIDEO_DIR, f) for f in os.listdir(VIDEO_DIR) if f.endswith('.hip'))
 
 
+def sketch_sources():
+    return sorted(os.path.join(SKETCH_DIR, f) for f in os.listdir(SKETCH_DIR) if f.endswith('.hip'))
+
+
 def headers():
     inc = os.path.join(os.path.dirname(PKG_DIR), 'include')
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')]
     hs += [os.path.join(PROBES_DIR, f) for f in os.listdir(PROBES_DIR) if f.endswith('.h')]
     hs += [os.path.join(REGIONS_DIR, f) for f in os.listdir(REGIONS_DIR) if f.endswith('.h')]
     hs += [os.path.join(VIDEO_DIR, f) for f in os.listdir(VIDEO_DIR) if f.endswith('.h')]
+    hs += [os.path.join(SKETCH_DIR, f) for f in os.listdir(SKETCH_DIR) if f.endswith('.h')]
     hs += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith('.h')]
     return sorted(hs)
 
@@ -100,6 +107,7 @@ def build_library(force=False, verbose=False):
     build_probes(verbose=verbose)
     build_regions(verbose=verbose)
     build_video(verbose=verbose)
+    build_sketch(verbose=verbose)
     return LIB_PATH
 
 
@@ -135,6 +143,12 @@ def build_video(verbose=False):
     """libp3d_video.so (csrc/video/*.hip): the palette kernels of pix2pix3d_amd/video.py, built as the region tools are; the product ABI of
     libp3d_hip.so gains no symbol."""
     return _build_side_library(VIDEO_LIB_PATH, video_sources(), verbose)
+
+
+def build_sketch(verbose=False):
+    """libp3d_sketch.so (csrc/sketch/*.hip): the canvas kernels of pix2pix3d_amd/sketch.py, built as the region tools are; the product ABI of
+    libp3d_hip.so gains no symbol."""
+    return _build_side_library(SKETCH_LIB_PATH, sketch_sources(), verbose)
 
 
 if __name__ == '__main__':

@@ -1,0 +1,70 @@
+/* libp3d_sketch.so — the edge-map canvas of a sketch session (pix2pix3d_amd/sketch.py): ink to the Encoder's conditioning
+ * image, edges from a picture, hysteresis, thinning.  A library of its own, like libp3d_regions.so: the product ABI (include/p3d_hip.h,
+ * libp3d_hip.so) exports none of this.  It carries its own copy of the library services (p3d_last_error, p3d_launch_count).
+ *
+ * Every image is uint8 [h][w], pixels contiguous, rows `*_row_pitch` bytes apart (>= w; >= 3 w for RGB); 1 <= h, w <= P3D_PAINT_MAX_SIZE.  Every
+ * result is written out of place and is a pure function of the inputs: the torch formulations of pix2pix3d_amd/sketch.py produce the same bytes.
+ * All pointers are device memory.  Argument errors return P3D_ERR_ARGUMENT before any launch.
+ *
+ * REFLECT: a tap at index i of an axis of n pixels reads the index after three steps in this order: if i < 0, i = -i; if i >= n,
+ * i = 2 n - 2 - i; i = min(max(i, 0), n - 1)  (reflect-101; the clamp keeps it defined for n = 1 and n = 2).  All arithmetic is in 32-bit
+ * integers.                                                                                                                                */
+#ifndef P3D_SKETCH_H
+#define P3D_SKETCH_H
+#include <stdint.h>
+#include "../../../include/p3d_hip.h"
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define P3D_SKETCH_MAX_MAGNITUDE 2040     /* |gx| + |gy| of the 3 x 3 Sobel pair on 8-bit values: 4 * 255 each */
+#define P3D_SKETCH_TILE_W 64              /* the work-group tile of p3d_sketch_edge_classes (tests straddle it) */
+#define P3D_SKETCH_TILE_H 16
+
+/* Ink canvas (255 = full ink, 0 = paper) -> the Encoder's conditioning image, float32 [resolution][resolution], rows `out_row_pitch` FLOATS
+ * apart (>= resolution).  For the output pixel (x, y):
+ *     sy = min(y * h / resolution, h - 1),  sx = min(x * w / resolution, w - 1)                     (integer division: a nearest resize)
+ *     m  = blur ? (sum of the nine REFLECT taps of ink about (sx, sy) + 4) / 9 : ink[sy][sx]        (the 3 x 3 box blur, at the sampled pixel only)
+ *     out[y][x] = table[m]                                                                          (table float32 [256])
+ * 1 <= resolution <= P3D_PAINT_MAX_SIZE.  One launch.                                                                                     */
+int p3d_sketch_condition(const uint8_t* ink, int64_t ink_row_pitch, int32_t h, int32_t w, int32_t blur, const float* table, float* out,
+                         int64_t out_row_pitch, int32_t resolution, p3d_stream_t stream);
+
+/* A frame -> edge classes uint8 [h][w]: 0 none, 1 weak, 2 strong.  `channels` 3: image is RGB uint8 [h][w][3] (row pitch >= 3 w);
+ * `channels` 1: grey uint8 [h][w].  0 <= low <= high <= P3D_SKETCH_MAX_MAGNITUDE.
+ *   1. luma    g = (77 r + 150 g + 29 b + 128) >> 8                                  (a grey frame is g itself)
+ *   2. smooth  (if `smooth`) v = sum over i, j in -2 .. 2 of k[i] k[j] g[REFLECT(y + i)][REFLECT(x + j)], k = [1 4 6 4 1] — the separable
+ *              filter, rounded once after both passes: s = (v + 128) >> 8; otherwise s = g
+ *   3. Sobel   on REFLECT taps of s:  gx = (s[y-1][x+1] + 2 s[y][x+1] + s[y+1][x+1]) - (s[y-1][x-1] + 2 s[y][x-1] + s[y+1][x-1]),
+ *              gy = (s[y+1][x-1] + 2 s[y+1][x] + s[y+1][x+1]) - (s[y-1][x-1] + 2 s[y-1][x] + s[y-1][x+1]);  mag = |gx| + |gy|
+ *   4. non-maximum suppression; mag OUTSIDE the image counts as 0.  ax = |gx|, ay = |gy| << 15, t22 = ax * 13573, t67 = t22 + (ax << 16)
+ *              (tan 22.5 degrees in 15-bit fixed point):
+ *                  ay < t22:   keep iff mag > mag[y][x-1] && mag >= mag[y][x+1]
+ *                  ay > t67:   keep iff mag > mag[y-1][x] && mag >= mag[y+1][x]
+ *                  otherwise,  s = ((gx ^ gy) < 0) ? -1 : 1:  keep iff mag > mag[y-1][x-s] && mag > mag[y+1][x+s]
+ *   5. class   kept && mag > high ? 2 : (kept && mag > low ? 1 : 0)
+ * ONE launch: a work-group owns P3D_SKETCH_TILE_W x P3D_SKETCH_TILE_H pixels and keeps the grey tile with its halo, the smoothed tile and the
+ * gradients of the tile and its one-pixel halo in LDS; global memory is read once per tile.                                                */
+int p3d_sketch_edge_classes(const uint8_t* image, int64_t image_row_pitch, int32_t channels, uint8_t* classes, int64_t classes_row_pitch,
+                            int32_t h, int32_t w, int32_t low, int32_t high, int32_t smooth, p3d_stream_t stream);
+
+/* Hysteresis.  classes: the class map; ids int32 [h][w], contiguous: p3d_label_components (libp3d_regions.so) of the byte map classes != 0
+ * under the 8-neighbourhood, so ids[p] is a linear index inside [0, h w).  flag: int32 [h * w] workspace.
+ *     ink[p] = classes[p] != 0 && the component of p holds a class-2 pixel ? 255 : 0.
+ * The workspace is cleared by a memset on the stream, then TWO launches: mark (every class-2 pixel stores 1 to flag[ids[p]]: plain vector
+ * stores of one value, whatever their order) and select (reads flag[ids[p]]).  An id outside [0, h w) is never followed.                 */
+int p3d_sketch_link(const uint8_t* classes, int64_t classes_row_pitch, const int32_t* ids, int32_t* flag, uint8_t* ink, int64_t ink_row_pitch,
+                    int32_t h, int32_t w, p3d_stream_t stream);
+
+/* One parallel Zhang-Suen sub-iteration.  A pixel is SET iff src >= threshold (1 <= threshold <= 255).  Its neighbour code has bit i set for the
+ * set neighbour i of N, NE, E, SE, S, SW, W, NW (outside the image: unset).  With B = the number of set neighbours and A = the number of unset -> set
+ * steps around the cycle N, NE, .., NW, N a code is DELETABLE in step 0 iff 2 <= B <= 6, A == 1, N E S == 0 and E S W == 0, and in step 1 iff
+ * 2 <= B <= 6, A == 1, N E W == 0 and N S W == 0 (csrc/sketch/thin_table.h, generated by pix2pix3d_amd/sketch.py).
+ *     dst = set && !deletable[step][code] ? 255 : 0.         step is 0 or 1; dst must not be src.  One launch.                              */
+int p3d_sketch_thin_step(const uint8_t* src, int64_t src_row_pitch, uint8_t* dst, int64_t dst_row_pitch, int32_t h, int32_t w, int32_t threshold,
+                         int32_t step, p3d_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

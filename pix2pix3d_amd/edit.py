@@ -24,8 +24,9 @@ integer: with d = b - a, p = pixel - a, L = d.d, s = p.d, thickness t, all int64
 table order that covers a pixel gives it its label.  Limits (ValueError before any launch): 1 <= t <= 255, 0 <= label <= 255, H, W <= 4096, endpoints in
 [-4096, 8191], at most 65 535 strokes; they keep 4 (p x d)^2 below 2^60.
 
-The fast label entry exists for ``MaskMappingNetwork_disentangle`` with ``one_hot=True`` and a 'resnet' Encoder.  ``one_hot=False`` masks, the edge networks
-and the entangled mapping networks have float conditioning images (no table): a session serves them through the ordinary ``G.mapping``, staleness tracking unchanged.
+The fast label entry exists for ``MaskMappingNetwork_disentangle`` with ``one_hot=True`` and a 'resnet' Encoder.  ``one_hot=False`` masks and the entangled
+mapping networks have float conditioning images (no table): a session serves them through the ordinary ``G.mapping``, staleness tracking unchanged.  The edge
+networks have a session of their own, ``sketch.SketchSession`` (an ink canvas instead of a label map); the stages below the canvas are ``_StageSession``, shared.
 """
 import contextlib
 import copy
@@ -189,8 +190,150 @@ def forward_label(G):
     return views.camera_labels(pose, torch.tensor([[f, 0, 0.5], [0, f, 0.5], [0, 0, 1]], dtype=torch.float32))
 
 
+# ---- the stages below the canvas ----------------------------------------------------------------------------------------------------
+class _StageSession:
+    """What ``EditSession`` and ``sketch.SketchSession`` share — everything below the canvas: the camera and the loaded pose, the seed and the held texture
+    rows, ws -> planes -> frame with staleness, the frozen jitter draws and ``geometry()``.  A subclass brings the canvas (``_base`` and what edits it, calling
+    ``_dirty_ws()``), ``_check_generator(G)``, ``_conditioned_ws()`` (the ws of the current canvas and seed, before the texture hold) and ``_finish(out)``
+    (one ``G.synthesis`` dict -> the frame dict)."""
+
+    def __init__(self, G, cfg, seed, truncation_psi, jitter, hold_texture, neural_rendering_resolution):
+        who = type(self).__name__
+        if cfg not in views.VIDEO_CFG:
+            raise ValueError(f'{who}: cfg must be one of {sorted(views.VIDEO_CFG)}, got {cfg!r}')
+        self._check_generator(G)
+        self.G, self.cfg, self.truncation_psi, self.hold_texture = G, cfg, truncation_psi, hold_texture
+        self.device = next(G.parameters()).device
+        self.nrr = int(views.VIDEO_CFG[cfg]['neural_rendering_resolution'] if neural_rendering_resolution is None else neural_rendering_resolution)
+        rk = G.rendering_kwargs
+        m, sc, sf = self.nrr * self.nrr, int(rk['depth_resolution']), int(rk['depth_resolution_importance'])
+        if isinstance(jitter, (tuple, list)):
+            self._draws = tuple(torch.as_tensor(u, dtype=torch.float32).to(self.device) for u in jitter)
+            if tuple(self._draws[0].shape) != (1, m, sc, 1) or tuple(self._draws[1].shape) != (m, sf):
+                raise ValueError(f'{who}: frozen draws must be [1, {m}, {sc}, 1] and [{m}, {sf}]')
+        elif jitter == 'frozen':
+            self._draws = (torch.rand([1, m, sc, 1], device=self.device), torch.rand([m, sf], device=self.device))
+        elif jitter == 'random':
+            self._draws = None
+        else:
+            raise ValueError(f"{who}: jitter must be 'frozen', 'random' or a pair of draws, got {jitter!r}")
+        self.palette = None
+        self._base = self._pose = self._intrinsics = self._cam2world = None
+        self._ws = self._held = self._planes = self._frame = self._floats = None
+        self.seed = int(seed)
+
+    def _load_pose(self, pose):
+        """``pose`` [25], the item's camera label: its intrinsics serve every later camera (:335) and it is the first camera."""
+        pose = torch.as_tensor(pose, dtype=torch.float32).reshape(-1)
+        if pose.numel() != 25:
+            raise ValueError(f'load: pose must hold 25 floats, got {pose.numel()}')
+        self._pose = pose.to(self.device).reshape(1, 25)
+        self._intrinsics = self._pose[:, 16:25].reshape(3, 3)
+        self._cam2world = self._pose[:, :16].reshape(4, 4)
+
+    def set_seed(self, seed):
+        if int(seed) != self.seed:
+            self.seed = int(seed)
+            self._dirty_ws()
+
+    def clear_texture(self):
+        """Release the held ``ws[:, 8:]``: the next ``encode()`` takes the appearance rows of the current seed and holds those."""
+        self._held = None
+        self._dirty_ws()
+
+    # -- cameras ----------------------------------------------------------------------------------------------------------------
+    def set_camera(self, yaw=0.0, pitch=0.0, roll=0.0, radius=DEMO_RADIUS):
+        """The demo's three sliders (units of 1/100 of pi/2, pi and pi/4)."""
+        self.set_pose(camera_from_euler(*slider_angles(yaw, pitch, roll), radius=radius))
+
+    def set_pose(self, cam2world):
+        cam2world = torch.as_tensor(cam2world, dtype=torch.float32).reshape(4, 4).to(self.device)
+        self._need_load()
+        if not torch.equal(cam2world, self._cam2world):
+            self._cam2world = cam2world
+            self._frame = None
+
+    @property
+    def camera(self):
+        """float32 [1, 25]: the current pose with the loaded item's intrinsics."""
+        self._need_load()
+        return views.camera_labels(self._cam2world, self._intrinsics)
+
+    # -- stages -----------------------------------------------------------------------------------------------------------------
+    _LOAD = 'load(...)'                                                        # the subclass's own signature, for the message below
+
+    def _need_load(self):
+        if self._base is None:
+            raise RuntimeError(f'{type(self).__name__}: {self._LOAD} first')
+
+    def _dirty_ws(self):
+        self._ws = self._planes = self._frame = None
+
+    def _z(self):
+        return torch.from_numpy(np.random.RandomState(self.seed).randn(1, self.G.z_dim).astype('float32')).to(self.device)      # (:430)
+
+    @torch.no_grad()
+    def encode(self):
+        """``ws`` [1, num_ws, w_dim]: geometry rows from the canvas, appearance rows from z(seed) under the forward-facing conditioning pose, truncated as
+        ``G.mapping`` does; with ``hold_texture`` rows 8.. are those of the first encode."""
+        if self._ws is not None:
+            return self._ws
+        ws = self._conditioned_ws()
+        if self.hold_texture:
+            if self._held is None:
+                self._held = ws[:, TEXTURE_FROM:].clone()
+            else:
+                ws = torch.cat([ws[:, :TEXTURE_FROM], self._held], dim=1)
+        self._ws = ws
+        return ws
+
+    @torch.no_grad()
+    def render(self, return_float=False):
+        """The frame dict of ``_finish`` as uint8 tensors on the device; with ``return_float`` also 'float', the ``G.synthesis`` dict the frame was finished
+        from.  Planes and frame are kept: after a camera change this is ``G.synthesis(ws, c, use_cached_backbone=True)`` on the kept planes and the finishing
+        launch — neither the Encoder nor the backbone runs."""
+        ws, G = self.encode(), self.G
+        if self._planes is None:
+            self._planes = G.backbone_planes(ws, noise_mode='const')
+        if self._frame is None:
+            found, G._last_planes = G._last_planes, self._planes
+            try:
+                draws = views._frozen_draws(self._draws[0], self._draws[1]) if self._draws is not None else contextlib.nullcontext()
+                with draws:
+                    out = G.synthesis(ws, self.camera, neural_rendering_resolution=self.nrr, use_cached_backbone=True, noise_mode='const')
+            finally:
+                G._last_planes = found
+            self._frame = {k: v[0] for k, v in self._finish(out).items()}
+            self._floats = out
+        return dict(self._frame, float=self._floats) if return_float else dict(self._frame)
+
+    def frame(self):
+        """``render()`` on the host, as numpy arrays."""
+        return {k: v.cpu().numpy() for k, v in self.render().items()}
+
+    _surface = None                                                            # geometry()'s product: (planes, cam2world, arguments, frame)
+
+    @torch.no_grad()
+    def geometry(self, resolution=None, color='grey', **cast_kwargs):
+        """uint8 [R, R, 3] on the device: the SHAPE the current edit produced, seen from the current camera — ``surface.render`` on the kept planes
+        (R = ``resolution``, default ``G.img_resolution``; ``color`` and ``cast_kwargs`` as there).  A fifth kept product: it is recomputed when the planes
+        or the camera were replaced (whatever dirties them dirties it) or the arguments differ; a camera move runs one cast launch and the shade launch,
+        neither the Encoder nor the backbone ('rgb' / 'label' colours query ``G.sample_mixed``, which does run the backbone)."""
+        from . import surface
+        ws, G = self.encode(), self.G
+        if self._planes is None:
+            self._planes = G.backbone_planes(ws, noise_mode='const')
+        res = int(G.img_resolution if resolution is None else resolution)
+        key = (res, color, sorted(cast_kwargs.items()))
+        kept = self._surface
+        if kept is None or kept[0] is not self._planes or kept[1] is not self._cam2world or kept[2] != key:
+            frame = surface.render(G, ws, self.camera, res, color=color, palette=self.palette, planes=self._planes, **cast_kwargs)[0]
+            self._surface = kept = (self._planes, self._cam2world, key, frame)
+        return kept[3]
+
+
 # ---- the session ----------------------------------------------------------------------------------------------------------------
-class EditSession:
+class EditSession(_StageSession):
     """One editing session on the device ``G`` lives on; every method runs under ``torch.no_grad()``.
 
     Four stages, each recomputed only when its input changed: mask -> geometry ws -> planes -> frame (and, beside the frame, ``geometry()``'s surface frame).  ``paint`` / ``undo`` / ``clear`` / ``load`` /
@@ -207,14 +350,9 @@ class EditSession:
 
     def __init__(self, G, cfg='seg2cat', seed=0, truncation_psi=1, jitter='frozen', hold_texture=True, replay='time', neural_rendering_resolution=None,
                  palette=None):
-        if cfg not in views.VIDEO_CFG:
-            raise ValueError(f'EditSession: cfg must be one of {sorted(views.VIDEO_CFG)}, got {cfg!r}')
-        if not hasattr(G, 'backbone_planes') or not hasattr(G, 'mapping_label') or not hasattr(G, 'semantic_channels') or G.semantic_channels < 2:
-            raise TypeError(f'EditSession: {type(G).__name__} is not a label-map generator on the one-backbone tri-plane core')
+        super().__init__(G, cfg, seed, truncation_psi, jitter, hold_texture, neural_rendering_resolution)
         replay_order(torch.zeros([0, 6], dtype=torch.int32), replay)
-        self.G, self.cfg, self.truncation_psi, self.hold_texture, self.replay = G, cfg, truncation_psi, hold_texture, replay
-        self.device = next(G.parameters()).device
-        self.nrr = int(views.VIDEO_CFG[cfg]['neural_rendering_resolution'] if neural_rendering_resolution is None else neural_rendering_resolution)
+        self.replay = replay
         self.n_labels = int(G.semantic_channels)
         self.palette = mesh.default_palette(self.n_labels) if palette is None else torch.as_tensor(palette)
         if self.device.type == 'cuda':
@@ -226,25 +364,17 @@ class EditSession:
         if self.fast_entry:
             enc = mapping.embed_mask
             self._table = label_table(getattr(enc, f'b{enc.block_resolutions[0]}').fromrgb, self.n_labels).to(self.device)
-        rk = G.rendering_kwargs
-        m, sc, sf = self.nrr * self.nrr, int(rk['depth_resolution']), int(rk['depth_resolution_importance'])
-        if isinstance(jitter, (tuple, list)):
-            self._draws = tuple(torch.as_tensor(u, dtype=torch.float32).to(self.device) for u in jitter)
-            if tuple(self._draws[0].shape) != (1, m, sc, 1) or tuple(self._draws[1].shape) != (m, sf):
-                raise ValueError(f'EditSession: frozen draws must be [1, {m}, {sc}, 1] and [{m}, {sf}]')
-        elif jitter == 'frozen':
-            self._draws = (torch.rand([1, m, sc, 1], device=self.device), torch.rand([m, sf], device=self.device))
-        elif jitter == 'random':
-            self._draws = None
-        else:
-            raise ValueError(f"EditSession: jitter must be 'frozen', 'random' or a pair of draws, got {jitter!r}")
         self._forward_c = G.mapping_label(forward_label(G).to(self.device))
-        self._base = self._pose = self._intrinsics = self._cam2world = None
         self._log = []                                                         # typed entries, one per undo step: ('paint', int32 [k, 6] table) or a region op
         self._kept = {}                                                        # n -> the mask after the first n entries (at most KEPT_MASKS of them)
-        self._mask = self._geometry = self._ws = self._held = self._planes = self._frame = self._floats = None
+        self._mask = self._geometry = None
         self._appearance = {}                                                  # seed -> [1, w_dim]
-        self.seed = int(seed)
+
+    _LOAD = 'load(mask, pose)'
+
+    def _check_generator(self, G):
+        if not hasattr(G, 'backbone_planes') or not hasattr(G, 'mapping_label') or not hasattr(G, 'semantic_channels') or G.semantic_channels < 2:
+            raise TypeError(f'EditSession: {type(G).__name__} is not a label-map generator on the one-backbone tri-plane core')
 
     # -- inputs ---------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -257,26 +387,11 @@ class EditSession:
             raise ValueError(f'load: mask must be uint8 [{res}, {res}], got {mask.dtype} {tuple(mask.shape)}')
         if int(mask.max()) >= self.n_labels:
             raise ValueError(f'load: label {int(mask.max())} in a mask of {self.n_labels} labels')
-        pose = torch.as_tensor(pose, dtype=torch.float32).reshape(-1)
-        if pose.numel() != 25:
-            raise ValueError(f'load: pose must hold 25 floats, got {pose.numel()}')
+        self._load_pose(pose)
         self._base = mask.to(self.device).contiguous()
-        self._pose = pose.to(self.device).reshape(1, 25)
-        self._intrinsics = self._pose[:, 16:25].reshape(3, 3)
-        self._cam2world = self._pose[:, :16].reshape(4, 4)
         self._log, self._kept = [], {}
         self._dirty_mask()
         self._frame = None
-
-    def set_seed(self, seed):
-        if int(seed) != self.seed:
-            self.seed = int(seed)
-            self._dirty_ws()
-
-    def clear_texture(self):
-        """Release the held ``ws[:, 8:]``: the next ``encode()`` takes the appearance rows of the current seed and holds those."""
-        self._held = None
-        self._dirty_ws()
 
     # -- painting ---------------------------------------------------------------------------------------------------------------
     def paint(self, strokes):
@@ -452,45 +567,14 @@ class EditSession:
             self._mask = self._mask_after(len(self._log))
         return self._mask
 
-    # -- cameras ----------------------------------------------------------------------------------------------------------------
-    def set_camera(self, yaw=0.0, pitch=0.0, roll=0.0, radius=DEMO_RADIUS):
-        """The demo's three sliders (units of 1/100 of pi/2, pi and pi/4)."""
-        self.set_pose(camera_from_euler(*slider_angles(yaw, pitch, roll), radius=radius))
-
-    def set_pose(self, cam2world):
-        cam2world = torch.as_tensor(cam2world, dtype=torch.float32).reshape(4, 4).to(self.device)
-        self._need_load()
-        if not torch.equal(cam2world, self._cam2world):
-            self._cam2world = cam2world
-            self._frame = None
-
-    @property
-    def camera(self):
-        """float32 [1, 25]: the current pose with the loaded item's intrinsics."""
-        self._need_load()
-        return views.camera_labels(self._cam2world, self._intrinsics)
-
-    # -- stages -----------------------------------------------------------------------------------------------------------------
-    def _need_load(self):
-        if self._base is None:
-            raise RuntimeError('EditSession: load(mask, pose) first')
-
+    # -- stages (the camera, encode(), render(), frame() and geometry() are the base class's) -------------------------------------------------------
     def _dirty_mask(self):
         self._mask = self._geometry = None
         self._dirty_ws()
 
-    def _dirty_ws(self):
-        self._ws = self._planes = self._frame = None
-
-    def _z(self):
-        return torch.from_numpy(np.random.RandomState(self.seed).randn(1, self.G.z_dim).astype('float32')).to(self.device)      # (:430)
-
-    @torch.no_grad()
-    def encode(self):
-        """``ws`` [1, num_ws, w_dim]: geometry rows from the mask, appearance rows from z(seed) under the forward-facing conditioning pose (cached per seed),
-        truncated as ``G.mapping`` does; with ``hold_texture`` rows 8.. are those of the first encode."""
-        if self._ws is not None:
-            return self._ws
+    def _conditioned_ws(self):
+        """Geometry rows from the mask (the label entry and the Encoder, kept until the mask changes), appearance rows from z(seed) under the forward-facing
+        conditioning pose (cached per seed), truncated as ``G.mapping`` does."""
         mask, mapping = self.mask, self.G.backbone.mapping
         if self.fast_entry:
             from .training.networks_stylegan2 import truncate_ws
@@ -503,56 +587,11 @@ class EditSession:
             ws = truncate_ws(mapping, ws, self.truncation_psi, None)
         else:
             ws = self.G.mapping(self._z(), forward_label(self.G).to(self.device), {'mask': mask[None, None], 'pose': self._pose}, truncation_psi=self.truncation_psi)
-        if self.hold_texture:
-            if self._held is None:
-                self._held = ws[:, TEXTURE_FROM:].clone()
-            else:
-                ws = torch.cat([ws[:, :TEXTURE_FROM], self._held], dim=1)
-        self._ws = ws
         return ws
 
-    @torch.no_grad()
-    def render(self, return_float=False):
-        """{'image' [H,W,3], 'label' [H,W,3], 'label_index' [H,W]} uint8 on the device — the demo's output image, its coloured label map and its
-        ``buffer_mask``; with ``return_float`` also 'float', the ``G.synthesis`` dict the frame was finished from."""
-        ws, G = self.encode(), self.G
-        if self._planes is None:
-            self._planes = G.backbone_planes(ws, noise_mode='const')
-        if self._frame is None:
-            found, G._last_planes = G._last_planes, self._planes
-            try:
-                draws = views._frozen_draws(self._draws[0], self._draws[1]) if self._draws is not None else contextlib.nullcontext()
-                with draws:
-                    out = G.synthesis(ws, self.camera, neural_rendering_resolution=self.nrr, use_cached_backbone=True, noise_mode='const')
-            finally:
-                G._last_planes = found
-            self._frame = {k: v[0] for k, v in views.finish_frames(out, palette=self.palette, label_mode='palette').items()}
-            self._floats = out
-        return dict(self._frame, float=self._floats) if return_float else dict(self._frame)
-
-    def frame(self):
-        """``render()`` on the host, as numpy arrays."""
-        return {k: v.cpu().numpy() for k, v in self.render().items()}
-
-    _surface = None                                                            # geometry()'s product: (planes, cam2world, arguments, frame)
-
-    @torch.no_grad()
-    def geometry(self, resolution=None, color='grey', **cast_kwargs):
-        """uint8 [R, R, 3] on the device: the SHAPE the current edit produced, seen from the current camera — ``surface.render`` on the kept planes
-        (R = ``resolution``, default ``G.img_resolution``; ``color`` and ``cast_kwargs`` as there).  A fifth kept product: it is recomputed when the planes
-        or the camera were replaced (whatever dirties them dirties it) or the arguments differ; a camera move runs one cast launch and the shade launch,
-        neither the Encoder nor the backbone ('rgb' / 'label' colours query ``G.sample_mixed``, which does run the backbone)."""
-        from . import surface
-        ws, G = self.encode(), self.G
-        if self._planes is None:
-            self._planes = G.backbone_planes(ws, noise_mode='const')
-        res = int(G.img_resolution if resolution is None else resolution)
-        key = (res, color, sorted(cast_kwargs.items()))
-        kept = self._surface
-        if kept is None or kept[0] is not self._planes or kept[1] is not self._cam2world or kept[2] != key:
-            frame = surface.render(G, ws, self.camera, res, color=color, palette=self.palette, planes=self._planes, **cast_kwargs)[0]
-            self._surface = kept = (self._planes, self._cam2world, key, frame)
-        return kept[3]
+    def _finish(self, out):
+        """{'image' [1,H,W,3], 'label' [1,H,W,3], 'label_index' [1,H,W]} uint8 — the demo's output image, its coloured label map and its ``buffer_mask``."""
+        return views.finish_frames(out, palette=self.palette, label_mode='palette')
 
     @torch.no_grad()
     def take_view_as_mask(self):
