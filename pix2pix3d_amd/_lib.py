@@ -12,6 +12,8 @@ import threading
 
 import torch  # noqa: F401  (must precede CDLL: see module docstring)
 
+from . import build
+
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('P3D_LIB_PATH') or os.path.join(_PKG_DIR, 'libp3d_hip.so')      # (P3D_LIB_PATH: A/B runs of two builds on one box)
 
@@ -176,6 +178,39 @@ def check(code, what):
     if code != HEADER.constants['P3D_OK']:
         msg = lib().p3d_last_error().decode('utf-8', 'replace')
         raise RuntimeError(f'{what}: libp3d_hip error {code}: {msg}')
+
+
+class SideLibrary:
+    """A kernel library beside libp3d_hip.so (a row of ``build.SIDE_LIBRARIES``): ``header`` is its own header, read on top of the product's (which it
+    includes for p3d_stream_t and the status codes); ``lib()`` is the loaded library (device-guarded) or RuntimeError — device tensors have no fallback."""
+
+    def __init__(self, name):
+        paths = build.side_paths(name)
+        self.name, self.path, self.header = name, paths.lib, read_header(paths.header, base=HEADER)
+        self._raw = self._guarded = None
+
+    def lib(self):
+        if self._guarded is None:
+            lib()                                                   # maps the HIP runtime torch uses first
+            try:
+                h = ctypes.CDLL(self.path)
+            except OSError as e:
+                raise RuntimeError(f'pix2pix3d_amd: {self.path} could not be loaded ({e}); build it with `python -m pix2pix3d_amd.build`')
+            for service in ('p3d_last_error', 'p3d_launch_count'):      # the library's own copy of the library services
+                fn = getattr(h, service)
+                fn.restype, fn.argtypes = HEADER.functions[service]
+            self.header.bind(h)
+            self._raw, self._guarded = h, _Guarded(h)
+        return self._guarded
+
+    def launch_count(self):
+        """Kernel launches of this library so far (its own counter: the product's ``launch_count`` does not see them)."""
+        self.lib()
+        return int(self._raw.p3d_launch_count())
+
+    def check(self, code, what):
+        if code != HEADER.constants['P3D_OK']:
+            raise RuntimeError(f'{what}: libp3d_{self.name} error {code}: {self.lib().p3d_last_error().decode("utf-8", "replace")}')
 
 
 def stream_of(t):

@@ -1,9 +1,12 @@
-"""Build libp3d_hip.so (the C-ABI kernel library), libp3d_probes.so, libp3d_regions.so, libp3d_video.so and libp3d_sketch.so in-tree with hipcc for gfx950.
+"""Build libp3d_hip.so (the C-ABI kernel library) and the side libraries of ``SIDE_LIBRARIES`` in-tree with hipcc for gfx950.
 
-No torch headers, no pybind: every ``csrc/*.hip`` translation unit is compiled to an object
-(in parallel, cached by mtime) and linked into ``pix2pix3d_amd/libp3d_hip.so`` so the binary
-travels with the source tree to the GPU box.  hipcc cross-compiles without a GPU present.
+No torch headers, no pybind: every ``csrc/*.hip`` translation unit is compiled to an object under ``csrc/_obj`` (in parallel, cached by mtime) and
+linked into ``pix2pix3d_amd/libp3d_hip.so`` so the binary travels with the source tree to the GPU box.  A side library ``<name>`` is
+``csrc/<name>/*.hip`` compiled into ``csrc/_obj/<name>/`` and linked with a copy of the library services (``_obj/p3d_common.o``) into
+``pix2pix3d_amd/libp3d_<name>.so``: a library of its own, so that the product ABI of libp3d_hip.so gains no symbol.  hipcc cross-compiles without a
+GPU present.
 """
+import collections
 import concurrent.futures
 import os
 import shutil
@@ -14,17 +17,21 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, 'csrc')
 OBJ_DIR = os.path.join(CSRC, '_obj')
 LIB_PATH = os.path.join(PKG_DIR, 'libp3d_hip.so')
-PROBES_DIR = os.path.join(CSRC, 'probes')
-PROBES_LIB_PATH = os.path.join(PKG_DIR, 'libp3d_probes.so')      # hardware probes: a library of its own, never part of the product ABI
-REGIONS_DIR = os.path.join(CSRC, 'regions')
-REGIONS_LIB_PATH = os.path.join(PKG_DIR, 'libp3d_regions.so')    # region tools of the edit session: a library of its own too (csrc/regions/p3d_regions.h)
-VIDEO_DIR = os.path.join(CSRC, 'video')
-VIDEO_LIB_PATH = os.path.join(PKG_DIR, 'libp3d_video.so')        # palette, dither and index frames of the GIF writer: likewise (csrc/video/p3d_video.h)
-SKETCH_DIR = os.path.join(CSRC, 'sketch')
-SKETCH_LIB_PATH = os.path.join(PKG_DIR, 'libp3d_sketch.so')      # edge-map canvas of the sketch session: likewise (csrc/sketch/p3d_sketch.h)
 ARCH = 'gfx950'
 CXXFLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-Wall', '-Wno-unused-function',
             '-fno-gpu-rdc', '-DNDEBUG']
+# The libraries beside libp3d_hip.so, name -> extra compile flags.  Everything else about one follows from its name (side_paths).
+SIDE_LIBRARIES = {'probes': ('-DP3D_BUILD_PROBES',),      # hardware probes the tests and the kernel studies use (diagnostics.py)
+                  'regions': (),                         # region tools of the edit session (regions.py)
+                  'video': (),                           # palette, dither and index frames of the GIF writer (video.py)
+                  'sketch': ()}                          # edge-map canvas of the sketch session (sketch.py)
+SidePaths = collections.namedtuple('SidePaths', 'src_dir header lib obj_dir')
+
+
+def side_paths(name):
+    """Where the side library ``name`` lives: the only statement of the convention (_lib.SideLibrary binds from the same paths)."""
+    src_dir = os.path.join(CSRC, name)
+    return SidePaths(src_dir, os.path.join(src_dir, f'p3d_{name}.h'), os.path.join(PKG_DIR, f'libp3d_{name}.so'), os.path.join(OBJ_DIR, name))
 
 
 def _hipcc():
@@ -41,114 +48,78 @@ def _newer(target, deps):
     return all(os.path.getmtime(d) <= t for d in deps)
 
 
+def _files(directory, suffix):
+    return sorted(os.path.join(directory, f) for f in os.listdir(directory) if f.endswith(suffix))
+
+
 def sources():
-    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hip'))
-
-
-def probe_sources():
-    return sorted(os.path.join(PROBES_DIR, f) for f in os.listdir(PROBES_DIR) if f.endswith('.hip'))
-
-
-def region_sources():
-    return sorted(os.path.join(REGIONS_DIR, f) for f in os.listdir(REGIONS_DIR) if f.endswith('.hip'))
-
-
-def video_sources():
-    return sorted(os.path.join(VIDEO_DIR, f) for f in os.listdir(VIDEO_DIR) if f.endswith('.hip'))
-
-
-def sketch_sources():
-    return sorted(os.path.join(SKETCH_DIR, f) for f in os.listdir(SKETCH_DIR) if f.endswith('.hip'))
+    return _files(CSRC, '.hip')
 
 
 def headers():
-    inc = os.path.join(os.path.dirname(PKG_DIR), 'include')
-    hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')]
-    hs += [os.path.join(PROBES_DIR, f) for f in os.listdir(PROBES_DIR) if f.endswith('.h')]
-    hs += [os.path.join(REGIONS_DIR, f) for f in os.listdir(REGIONS_DIR) if f.endswith('.h')]
-    hs += [os.path.join(VIDEO_DIR, f) for f in os.listdir(VIDEO_DIR) if f.endswith('.h')]
-    hs += [os.path.join(SKETCH_DIR, f) for f in os.listdir(SKETCH_DIR) if f.endswith('.h')]
-    hs += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith('.h')]
-    return sorted(hs)
+    dirs = [CSRC] + [side_paths(name).src_dir for name in SIDE_LIBRARIES] + [os.path.join(os.path.dirname(PKG_DIR), 'include')]
+    return sorted(h for d in dirs for h in _files(d, '.h'))
 
 
-def _compile(src, verbose, extra=()):
-    obj = os.path.join(OBJ_DIR, os.path.basename(src)[:-4] + '.o')
-    if _newer(obj, [src] + headers()):
-        return obj, False
-    cmd = [_hipcc()] + CXXFLAGS + list(extra) + ['-c', src, '-o', obj]
+def _object(src, obj_dir=OBJ_DIR):
+    return os.path.join(obj_dir, os.path.basename(src)[:-4] + '.o')
+
+
+def product_objects():
+    """The objects libp3d_hip.so is linked from, in link order: one per ``csrc/*.hip``, nothing of a side library."""
+    return [_object(src) for src in sources()]
+
+
+def _run(cmd, verbose, what):
     if verbose:
         print(' '.join(cmd), flush=True)
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
-        raise RuntimeError(f'hipcc failed for {src}:\n{r.stdout}')
-    if verbose and r.stdout.strip():
-        print(r.stdout)
+        raise RuntimeError(f'{what}:\n{r.stdout}')
+    return r.stdout
+
+
+def _compile(src, verbose, extra=(), obj_dir=OBJ_DIR):
+    obj = _object(src, obj_dir)
+    if _newer(obj, [src] + headers()):
+        return obj, False
+    os.makedirs(obj_dir, exist_ok=True)
+    out = _run([_hipcc()] + CXXFLAGS + list(extra) + ['-c', src, '-o', obj], verbose, f'hipcc failed for {src}')
+    if verbose and out.strip():
+        print(out)
     return obj, True
 
 
-def build_library(force=False, verbose=False):
-    """Compile + link; returns the path of the shared library."""
-    os.makedirs(OBJ_DIR, exist_ok=True)
-    if force:
-        for f in os.listdir(OBJ_DIR):
-            os.remove(os.path.join(OBJ_DIR, f))
-    srcs = sources()
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
-        results = list(ex.map(lambda s: _compile(s, verbose), srcs))
-    objs = [o for o, _ in results]
-    if any(changed for _, changed in results) or not _newer(LIB_PATH, objs):
-        cmd = [_hipcc(), '-shared', '-fPIC', f'--offload-arch={ARCH}', '-o', LIB_PATH] + objs
-        if verbose:
-            print(' '.join(cmd), flush=True)
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f'link failed:\n{r.stdout}')
-    build_probes(verbose=verbose)
-    build_regions(verbose=verbose)
-    build_video(verbose=verbose)
-    build_sketch(verbose=verbose)
-    return LIB_PATH
-
-
-def _build_side_library(path, srcs, verbose, extra=()):
-    """A library beside libp3d_hip.so: its own sources plus a copy of the library services (_obj/p3d_common.o, built by build_library)."""
-    os.makedirs(OBJ_DIR, exist_ok=True)
+def _compile_all(srcs, verbose, extra=(), obj_dir=OBJ_DIR):
     with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, min(8, len(srcs)))) as ex:
-        results = list(ex.map(lambda s: _compile(s, verbose, extra), srcs))
-    objs = [o for o, _ in results] + [os.path.join(OBJ_DIR, 'p3d_common.o')]
+        return list(ex.map(lambda s: _compile(s, verbose, extra, obj_dir), srcs))
+
+
+def _link(path, results, verbose):
+    """Link the (object, recompiled) pairs into ``path`` unless it is newer than all of them."""
+    objs = [o for o, _ in results]
     if any(changed for _, changed in results) or not _newer(path, objs):
-        cmd = [_hipcc(), '-shared', '-fPIC', f'--offload-arch={ARCH}', '-o', path] + objs
-        if verbose:
-            print(' '.join(cmd), flush=True)
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f'link failed:\n{r.stdout}')
+        _run([_hipcc(), '-shared', '-fPIC', f'--offload-arch={ARCH}', '-o', path] + objs, verbose, 'link failed')
     return path
 
 
-def build_probes(verbose=False):
-    """libp3d_probes.so (csrc/probes/*.hip, -DP3D_BUILD_PROBES): the hardware probes the tests and the kernel studies use, with their own
-    copy of the library services (p3d_common.hip) so that nothing of them is exported through libp3d_hip.so."""
-    return _build_side_library(PROBES_LIB_PATH, probe_sources(), verbose, ('-DP3D_BUILD_PROBES',))
+def build_library(force=False, verbose=False):
+    """Compile + link libp3d_hip.so and every side library; returns the path of libp3d_hip.so."""
+    if force:
+        shutil.rmtree(OBJ_DIR, ignore_errors=True)
+    _link(LIB_PATH, _compile_all(sources(), verbose), verbose)
+    for name in SIDE_LIBRARIES:
+        build_side(name, verbose=verbose)
+    return LIB_PATH
 
 
-def build_regions(verbose=False):
-    """libp3d_regions.so (csrc/regions/*.hip): the region tools of pix2pix3d_amd/regions.py, with the same flags and their own copy of the
-    library services; the product ABI of libp3d_hip.so gains no symbol."""
-    return _build_side_library(REGIONS_LIB_PATH, region_sources(), verbose)
-
-
-def build_video(verbose=False):
-    """libp3d_video.so (csrc/video/*.hip): the palette kernels of pix2pix3d_amd/video.py, built as the region tools are; the product ABI of
-    libp3d_hip.so gains no symbol."""
-    return _build_side_library(VIDEO_LIB_PATH, video_sources(), verbose)
-
-
-def build_sketch(verbose=False):
-    """libp3d_sketch.so (csrc/sketch/*.hip): the canvas kernels of pix2pix3d_amd/sketch.py, built as the region tools are; the product ABI of
-    libp3d_hip.so gains no symbol."""
-    return _build_side_library(SKETCH_LIB_PATH, sketch_sources(), verbose)
+def build_side(name, verbose=False):
+    """libp3d_<name>.so: the sources of ``csrc/<name>`` with the product's flags plus the row's, and their own copy of the library services
+    (``_obj/p3d_common.o``, compiled here if it is missing or stale: a side library builds on a clean tree by itself)."""
+    paths = side_paths(name)
+    common = _compile(os.path.join(CSRC, 'p3d_common.hip'), verbose)
+    results = _compile_all(_files(paths.src_dir, '.hip'), verbose, SIDE_LIBRARIES[name], paths.obj_dir)
+    return _link(paths.lib, results + [common], verbose)
 
 
 if __name__ == '__main__':

@@ -5,37 +5,13 @@ product ABI (include/p3d_hip.h, libp3d_hip.so) exports none of this and no op of
 ``v_cvt_pk_bf16_f32`` wrote a few wait states earlier (csrc/probes/hazard_probe.hip).
 ``mfma_rate``: what the matrix pipe sustains with nothing but ``v_mfma_f32_32x32x16_f16`` in the loop, in the fp16 3x3 kernel's register
 blocking, and the clock the chip holds meanwhile (csrc/probes/mfma_rate_probe.hip)."""
-import ctypes
-import os
-
 import torch
 
 from . import _lib
 
-_PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-PROBES_LIB_PATH = os.path.join(_PKG_DIR, 'libp3d_probes.so')
-HEADER = _lib.read_header(os.path.join(_PKG_DIR, 'csrc', 'probes', 'p3d_probes.h'), base=_lib.HEADER)      # (it includes the product header for p3d_stream_t)
-_handle = None
-
-
-def probes():
-    """The probe library, or RuntimeError (built by ``pix2pix3d_amd.build.build_probes`` / ``__graft_entry__.build``)."""
-    global _handle
-    if _handle is None:
-        _lib.lib()                                                  # maps the HIP runtime torch uses first
-        try:
-            h = ctypes.CDLL(PROBES_LIB_PATH)
-        except OSError as e:
-            raise RuntimeError(f'pix2pix3d_amd: {PROBES_LIB_PATH} could not be loaded ({e}); build it with `python -m pix2pix3d_amd.build`')
-        h.p3d_last_error.restype, h.p3d_last_error.argtypes = _lib.HEADER.functions['p3d_last_error']      # (its own copy of the library services)
-        HEADER.bind(h)
-        _handle = h
-    return _handle
-
-
-def _check(code, what):
-    if code != 0:
-        raise RuntimeError(f'{what}: {probes().p3d_last_error().decode()} (code {code})')
+_side = _lib.SideLibrary('probes')                   # libp3d_probes.so: loaded on the first call (the device guard is idle: no probe calls stream_of)
+PROBES_LIB_PATH, HEADER = _side.path, _side.header
+probes, _check = _side.lib, _side.check
 
 
 def cvt_mfma_hazard(wait_states, iters=4000, device='cuda', src_a=False, war=False):

@@ -14,47 +14,16 @@ side (``edit._check_mask``); everything is written out of place.  ``EditSession.
 ``transform`` log these as undo steps (edit.py)."""
 import ctypes
 import math
-import os
 
 import torch
 
 from . import _lib
 from .edit import _check_mask
 
-_PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-REGIONS_LIB_PATH = os.path.join(_PKG_DIR, 'libp3d_regions.so')
-HEADER = _lib.read_header(os.path.join(_PKG_DIR, 'csrc', 'regions', 'p3d_regions.h'), base=_lib.HEADER)      # (it includes the product header for p3d_stream_t)
 MAX_LINEAR, MAX_TRANSLATION = 1 << 22, 1 << 40       # bounds of the six warp integers: c * 4095 stays far inside an int64
-_SERVICES = ('p3d_last_error', 'p3d_launch_count')   # the library's own copy of the library services
-_raw = _guarded = None
-
-
-def regions_lib():
-    """The region library (device-guarded), or RuntimeError: device tensors have no fallback (built by ``pix2pix3d_amd.build.build_regions``)."""
-    global _raw, _guarded
-    if _guarded is None:
-        _lib.lib()                                                  # maps the HIP runtime torch uses first
-        try:
-            h = ctypes.CDLL(REGIONS_LIB_PATH)
-        except OSError as e:
-            raise RuntimeError(f'pix2pix3d_amd: {REGIONS_LIB_PATH} could not be loaded ({e}); build it with `python -m pix2pix3d_amd.build`')
-        for name in _SERVICES:
-            fn = getattr(h, name)
-            fn.restype, fn.argtypes = _lib.HEADER.functions[name]
-        HEADER.bind(h)
-        _raw, _guarded = h, _lib._Guarded(h)
-    return _guarded
-
-
-def launch_count():
-    """Kernel launches of libp3d_regions.so so far (its own counter: ``_lib.launch_count`` does not see them)."""
-    regions_lib()
-    return int(_raw.p3d_launch_count())
-
-
-def _check(code, what):
-    if code != _lib.P3D_OK:
-        raise RuntimeError(f'{what}: libp3d_regions error {code}: {regions_lib().p3d_last_error().decode("utf-8", "replace")}')
+_side = _lib.SideLibrary('regions')                  # libp3d_regions.so: loaded on the first call, device-guarded; launch_count() is its own counter
+REGIONS_LIB_PATH, HEADER = _side.path, _side.header
+regions_lib, launch_count, _check = _side.lib, _side.launch_count, _side.check
 
 
 def site_words(sites):

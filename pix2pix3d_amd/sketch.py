@@ -29,7 +29,6 @@ for n = 1 and 2).  Images are uint8 with contiguous pixels and any row pitch, 1 
     s.set_camera(yaw=40); s.render()                      # neither the Encoder nor the backbone runs
     s.take_view_as_canvas()                               # the rendered edge frame, traced, becomes the canvas
 """
-import ctypes
 import os
 
 import torch
@@ -37,41 +36,11 @@ import torch
 from . import _lib, edit, views
 from .edit import _check_mask
 
-_PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-SKETCH_LIB_PATH = os.path.join(_PKG_DIR, 'libp3d_sketch.so')
-HEADER = _lib.read_header(os.path.join(_PKG_DIR, 'csrc', 'sketch', 'p3d_sketch.h'), base=_lib.HEADER)      # (it includes the product header for p3d_stream_t)
+_side = _lib.SideLibrary('sketch')                   # libp3d_sketch.so: loaded on the first call, device-guarded; launch_count() is its own counter
+SKETCH_LIB_PATH, HEADER = _side.path, _side.header
+sketch_lib, launch_count, _check = _side.lib, _side.launch_count, _side.check
 MAX_MAGNITUDE, TILE_W, TILE_H = (HEADER.constants[k] for k in ('P3D_SKETCH_MAX_MAGNITUDE', 'P3D_SKETCH_TILE_W', 'P3D_SKETCH_TILE_H'))
-THIN_TABLE_PATH = os.path.join(_PKG_DIR, 'csrc', 'sketch', 'thin_table.h')
-_SERVICES = ('p3d_last_error', 'p3d_launch_count')   # the library's own copy of the library services
-_raw = _guarded = None
-
-
-def sketch_lib():
-    """The sketch library (device-guarded), or RuntimeError: device tensors have no fallback (built by ``pix2pix3d_amd.build.build_sketch``)."""
-    global _raw, _guarded
-    if _guarded is None:
-        _lib.lib()                                                  # maps the HIP runtime torch uses first
-        try:
-            h = ctypes.CDLL(SKETCH_LIB_PATH)
-        except OSError as e:
-            raise RuntimeError(f'pix2pix3d_amd: {SKETCH_LIB_PATH} could not be loaded ({e}); build it with `python -m pix2pix3d_amd.build`')
-        for name in _SERVICES:
-            fn = getattr(h, name)
-            fn.restype, fn.argtypes = _lib.HEADER.functions[name]
-        HEADER.bind(h)
-        _raw, _guarded = h, _lib._Guarded(h)
-    return _guarded
-
-
-def launch_count():
-    """Kernel launches of libp3d_sketch.so so far (its own counter: ``_lib.launch_count`` and ``regions.launch_count`` do not see them)."""
-    sketch_lib()
-    return int(_raw.p3d_launch_count())
-
-
-def _check(code, what):
-    if code != _lib.P3D_OK:
-        raise RuntimeError(f'{what}: libp3d_sketch error {code}: {sketch_lib().p3d_last_error().decode("utf-8", "replace")}')
+THIN_TABLE_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'sketch', 'thin_table.h')
 
 
 def _image_size(image, what):

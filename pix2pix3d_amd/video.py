@@ -15,49 +15,16 @@ three that touch every pixel, device kernels whose bytes equal it:
 is the two together.  Frames are uint8 [F, H, W, 3] with contiguous pixels (``stride(3) == 1``, ``stride(2) == 3``) and any row and frame pitch: a strided
 selection ``frames[::4]`` and a window of a larger canvas are read in place.  One palette serves the whole clip (``per_frame=False``) or one frame
 (``per_frame=True``)."""
-import ctypes
-import os
-
 import numpy as np
 import torch
 
 from . import _lib
 
-_PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-VIDEO_LIB_PATH = os.path.join(_PKG_DIR, 'libp3d_video.so')
-HEADER = _lib.read_header(os.path.join(_PKG_DIR, 'csrc', 'video', 'p3d_video.h'), base=_lib.HEADER)      # (it includes the product header for p3d_stream_t)
+_side = _lib.SideLibrary('video')                    # libp3d_video.so: loaded on the first call, device-guarded; launch_count() is its own counter
+VIDEO_LIB_PATH, HEADER = _side.path, _side.header
+video_lib, launch_count, _check = _side.lib, _side.launch_count, _side.check
 BINS, COLORS, MAX_AMPLITUDE = (HEADER.constants[k] for k in ('P3D_VIDEO_BINS', 'P3D_VIDEO_COLORS', 'P3D_VIDEO_MAX_AMPLITUDE'))
 MAX_PIXELS = 1 << 31                                 # F * H * W stays below it
-_SERVICES = ('p3d_last_error', 'p3d_launch_count')   # the library's own copy of the library services
-_raw = _guarded = None
-
-
-def video_lib():
-    """The video library (device-guarded), or RuntimeError: device tensors have no fallback (built by ``pix2pix3d_amd.build.build_video``)."""
-    global _raw, _guarded
-    if _guarded is None:
-        _lib.lib()                                                  # maps the HIP runtime torch uses first
-        try:
-            h = ctypes.CDLL(VIDEO_LIB_PATH)
-        except OSError as e:
-            raise RuntimeError(f'pix2pix3d_amd: {VIDEO_LIB_PATH} could not be loaded ({e}); build it with `python -m pix2pix3d_amd.build`')
-        for name in _SERVICES:
-            fn = getattr(h, name)
-            fn.restype, fn.argtypes = _lib.HEADER.functions[name]
-        HEADER.bind(h)
-        _raw, _guarded = h, _lib._Guarded(h)
-    return _guarded
-
-
-def launch_count():
-    """Kernel launches of libp3d_video.so so far (its own counter: ``_lib.launch_count`` does not see them)."""
-    video_lib()
-    return int(_raw.p3d_launch_count())
-
-
-def _check(code, what):
-    if code != _lib.P3D_OK:
-        raise RuntimeError(f'{what}: libp3d_video error {code}: {video_lib().p3d_last_error().decode("utf-8", "replace")}')
 
 
 def _check_frames(frames, what='frames'):

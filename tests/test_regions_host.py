@@ -305,17 +305,11 @@ def test_kept_masks_are_bounded_and_older_entries_replay(loaded):
 
 
 # ---- 6. the binding -------------------------------------------------------------------------------------------------------------
-def test_every_entry_point_regions_calls_is_declared_exported_and_its_own():
-    from pix2pix3d_amd import _lib, regions, diagnostics
+def test_regions_calls_its_three_entry_points_and_its_header_declares_functions_only():
+    """Declared, exported by its own library alone, bound: the regions row of tests/test_side_libraries.py."""
+    from pix2pix3d_amd import regions
     called = set(re.findall(r'\bregions_lib\(\)\.(p3d_\w+)', (ROOT / 'pix2pix3d_amd' / 'regions.py').read_text()))
-    declared = set(regions.HEADER.functions)
-    assert {'p3d_label_components', 'p3d_label_nearest', 'p3d_label_warp'} <= called and called - {'p3d_last_error'} <= declared, sorted(called - declared)
-    assert declared and not declared & set(_lib.HEADER.functions) and not declared & set(diagnostics.HEADER.functions)
-    handle = ctypes.CDLL(regions.REGIONS_LIB_PATH)
-    for name in sorted(declared | {'p3d_last_error', 'p3d_launch_count'}):
-        assert hasattr(handle, name), name
-    main = ctypes.CDLL(_lib.LIB_PATH)
-    assert not [name for name in declared if hasattr(main, name)]                # the product library gained no symbol
+    assert {'p3d_label_components', 'p3d_label_nearest', 'p3d_label_warp'} <= called
     assert not regions.HEADER.constants and not regions.HEADER.structs          # the header declares functions only
 
 

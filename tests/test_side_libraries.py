@@ -1,0 +1,109 @@
+"""The kernel libraries beside libp3d_hip.so (``build.SIDE_LIBRARIES``), one row each: what the Python module calls is declared in the library's own
+header, the headers are disjoint, every library exports its own entry points and the product library none of them, ``SideLibrary.lib()`` binds every
+signature, and the library's own launch counter is wired.  No GPU is needed — the argument checks run before any device call — but the built libraries are."""
+import ctypes
+import importlib
+import os
+import pathlib
+import re
+
+import pytest
+
+from pix2pix3d_amd import build
+
+ROOT = pathlib.Path(__file__).resolve().parent.parent
+SERVICES = {'p3d_last_error', 'p3d_launch_count'}      # every side library links its own copy; their signatures come from the product header
+BOUND_BY = {'probes': ('diagnostics', 'probes'), 'regions': ('regions', 'regions_lib'), 'video': ('video', 'video_lib'),
+            'sketch': ('sketch', 'sketch_lib')}        # library -> (module of pix2pix3d_amd, the accessor its calls go through)
+NAMES = sorted(build.SIDE_LIBRARIES)
+
+
+def _module(name):
+    return importlib.import_module('pix2pix3d_amd.' + BOUND_BY[name][0])
+
+
+def _exported(path, names):
+    handle = ctypes.CDLL(str(path))
+    return {n for n in names if hasattr(handle, n)}
+
+
+@pytest.mark.parametrize('name', NAMES)
+def test_calls_are_declared(name):
+    module, accessor = _module(name), BOUND_BY[name][1]
+    assert getattr(module, accessor) == module._side.lib and module.HEADER is module._side.header
+    called = set(re.findall(r'\b%s\(\)\.(p3d_\w+)' % accessor, pathlib.Path(module.__file__).read_text()))
+    declared = set(module.HEADER.functions)
+    assert called - SERVICES and called - SERVICES <= declared, (name, sorted(called - SERVICES - declared))
+
+
+@pytest.mark.parametrize('name', NAMES)
+def test_headers_are_disjoint(name):
+    from pix2pix3d_amd import _lib
+    declared = set(_module(name).HEADER.functions)
+    assert declared and not declared & set(_lib.HEADER.functions)
+    for other in NAMES:
+        if other != name:
+            assert not declared & set(_module(other).HEADER.functions), (name, other)
+
+
+@pytest.mark.parametrize('name', NAMES)
+def test_exports_are_right(name):
+    from pix2pix3d_amd import _lib
+    module = _module(name)
+    declared = set(module.HEADER.functions)
+    assert module._side.path == build.side_paths(name).lib
+    assert _exported(module._side.path, declared | SERVICES) == declared | SERVICES
+    assert _exported(_lib.LIB_PATH, declared) == set()                           # the product library gained no symbol
+
+
+@pytest.mark.parametrize('name', NAMES)
+def test_binding_is_complete(name):
+    side = _module(name)._side
+    side.lib()
+    assert [n for n in sorted(set(side.header.functions) | SERVICES) if getattr(side._raw, n).argtypes is None] == []
+
+
+@pytest.mark.parametrize('name', NAMES)
+def test_the_launch_counter_is_wired(name):
+    """The first declared entry point with null pointers (1 for every integer: one frame, one pixel): its null check comes before any device call."""
+    from pix2pix3d_amd import _lib
+    side = _module(name)._side
+    n0 = side.launch_count()
+    assert type(n0) is int
+    fn_name, (_, argtypes) = next(iter(side.header.functions.items()))
+    assert ctypes.c_void_p in argtypes
+    code = getattr(side.lib(), fn_name)(*[None if t is ctypes.c_void_p else t(1) for t in argtypes])
+    assert code == _lib.P3D_ERR_ARGUMENT == -2 and side.lib().p3d_last_error(), (fn_name, code)
+    with pytest.raises(RuntimeError) as e:
+        side.check(code, 'probe')
+    assert str(e.value) == f'probe: libp3d_{name} error -2: {side.lib().p3d_last_error().decode()}'
+    assert side.launch_count() == n0
+
+
+def test_the_table_is_complete():
+    """A directory of kernels without a row would silently be left out of the build."""
+    with_kernels = {d.name for d in pathlib.Path(build.CSRC).iterdir() if d.is_dir() and list(d.glob('*.hip'))}
+    assert with_kernels == set(build.SIDE_LIBRARIES) == set(BOUND_BY)
+    for name in NAMES:
+        paths = build.side_paths(name)
+        assert os.path.isfile(paths.header) and paths.header in build.headers() and os.path.dirname(paths.obj_dir) == build.OBJ_DIR
+
+
+def test_the_products_objects_are_the_products_only():
+    objects = build.product_objects()
+    assert [os.path.basename(o)[:-2] for o in objects] == [os.path.basename(s)[:-4] for s in build.sources()]
+    assert sorted(os.path.basename(s) for s in build.sources()) == sorted(p.name for p in pathlib.Path(build.CSRC).glob('*.hip'))
+    assert {os.path.dirname(o) for o in objects} == {build.OBJ_DIR}
+    assert build.OBJ_DIR not in {build.side_paths(name).obj_dir for name in NAMES}
+
+
+def test_the_load_error_is_unchanged(tmp_path):
+    from pix2pix3d_amd import _lib
+    side = _lib.SideLibrary('regions')
+    side.path = str(tmp_path / 'libp3d_absent.so')
+    with pytest.raises(OSError) as absent:
+        ctypes.CDLL(side.path)
+    with pytest.raises(RuntimeError) as e:
+        side.lib()
+    assert str(e.value) == f'pix2pix3d_amd: {side.path} could not be loaded ({absent.value}); build it with `python -m pix2pix3d_amd.build`'
+    assert side._raw is None and side._guarded is None

@@ -110,7 +110,7 @@ rep("""            const int n = (idx == 0) ? SN : idx - 1;
             if constexpr (BF3)  mlp_layer1_bf3(lds, n, lane, h, fh, fl, h0, h1);""")
 open(hdr, 'w').write(s)
 
-objs = [os.path.join(B.OBJ_DIR, f) for f in os.listdir(B.OBJ_DIR) if f.endswith('.o') and f not in ('render.o', 'hazard_probe.o', 'mfma_rate_probe.o')]
+objs = [o for o in B.product_objects() if os.path.basename(o) != 'render.o']
 for bits in [int(v) for v in sys.argv[1:]]:
     obj = f'/tmp/p3d_rv/render_{bits}.o'
     cmd = [B._hipcc()] + B.CXXFLAGS + [f'-DP3D_RENDER_DEBUG={bits}', '-c', os.path.join(work, 'pix2pix3d_amd', 'csrc', 'render.hip'), '-o', obj]
