@@ -36,6 +36,38 @@ int p3d_label_warp(const uint8_t* mask, int64_t mask_row_pitch, const uint8_t* r
                    int64_t under_row_pitch, uint8_t* dst, int64_t dst_row_pitch, const int64_t coef[6], int32_t h, int32_t w,
                    p3d_stream_t stream);
 
+/* ---- agreement metrics (csrc/regions/label_metrics.hip; pix2pix3d_amd/evaluate.py) ----------------------------
+ * The three counters below ACCUMULATE (+=, 64-bit integer atomics: the sums do not depend on the order) into int64 device memory, 8-byte
+ * aligned, that the caller zeroed: a loop over a dataset never touches the host.
+ *
+ * Confusion matrix.  truth, pred and the optional valid (null: every pixel is valid): uint8 [frames][h][w], rows `*_row_pitch` bytes apart
+ * and frames `*_frame_pitch` bytes apart (>= (h - 1) * row pitch + w; not looked at for one frame); 0 <= frames <= 65536,
+ * 1 <= n_labels <= 32.  counts int64 [n_labels * n_labels + 1]:
+ *     counts[t * n_labels + p] += pixels with truth == t, pred == p, both < n_labels, and valid != 0
+ *     counts[n_labels * n_labels] += pixels left out for any of those reasons.
+ * frames == 0 is a success that launches nothing.  One launch.                                                                          */
+int p3d_label_confusion(const uint8_t* truth, int64_t truth_row_pitch, int64_t truth_frame_pitch, const uint8_t* pred,
+                        int64_t pred_row_pitch, int64_t pred_frame_pitch, const uint8_t* valid, int64_t valid_row_pitch,
+                        int64_t valid_frame_pitch, int32_t frames, int32_t h, int32_t w, int32_t n_labels, int64_t* counts,
+                        p3d_stream_t stream);
+
+/* Boundary map.  out[p] = mask[p] if some in-image 4-neighbour of p has a different label, else 255.  (A pixel labelled 255 is therefore
+ * never a boundary pixel itself, but it counts as different to its neighbours.)  p3d_label_nearest of the result with the site set {c} is
+ * then "the nearest boundary pixel of class c", with the set 0 .. 254 the class-agnostic boundary.  The byte ranges of mask and out must not
+ * overlap.  One launch.                                                                                                                 */
+int p3d_label_boundary(const uint8_t* mask, int64_t mask_row_pitch, uint8_t* out, int64_t out_row_pitch, int32_t h, int32_t w,
+                       p3d_stream_t stream);
+
+/* Histogram of squared distances.  `sites` (HOST memory, read during the call): the 256-bit label set of p3d_label_nearest.  nearest int32
+ * [h][w], contiguous, as p3d_label_nearest wrote it for the OTHER map; 1 <= bins <= 4096; hist int64 [bins + 2].  For every pixel p = (px, py)
+ * whose `from` label is in the set, with q = nearest[p] = qy * w + qx and d2 = (px - qx)^2 + (py - qy)^2:
+ *     q >= 0 and d2 <  bins:  hist[d2] += 1
+ *     q >= 0 and d2 >= bins:  hist[bins] += 1
+ *     q <  0:                 hist[bins + 1] += 1.
+ * A q >= h * w is NOT checked on the device (it only yields a large d2): the pointer contract is the caller's.  One launch.               */
+int p3d_label_distance_histogram(const uint8_t* from, int64_t from_row_pitch, const uint32_t sites[8], const int32_t* nearest, int32_t bins,
+                                 int64_t* hist, int32_t h, int32_t w, p3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -603,6 +603,22 @@ class EditSession(_StageSession):
         self._base, self._log, self._kept = base.clone(), [], {}
         self._dirty_mask()
 
+    _agreement = None                                                          # agreement()'s product: (frame, mask, bins, counters, their host copy)
+
+    @torch.no_grad()
+    def agreement(self, tolerance=2, bins=65):
+        """How faithfully the current frame follows the current mask: ``evaluate.Agreement.result(tolerance)`` of ``self.mask`` against
+        ``self.render()['label_index']`` at the current camera (``n_labels`` is the generator's).  Kept with the frame: whatever replaces the frame (an edit,
+        a seed, a camera move) recomputes it — after a camera move without the Encoder or the backbone —, a repeated call launches nothing and copies nothing."""
+        from . import evaluate
+        self.render()
+        frame, mask, kept = self._frame, self.mask, self._agreement
+        if kept is None or kept[0] is not frame or kept[1] is not mask or kept[2] != int(bins):
+            total = evaluate.Agreement(self.n_labels, self.device, bins)
+            evaluate._add_label_frame(total, mask, frame['label_index'])
+            self._agreement = kept = (frame, mask, int(bins), total, total.host_counters())
+        return kept[3].metrics_of(kept[4], tolerance)
+
     def save(self, directory):
         """The demo's three PNGs (:465-472): mask.png (labels), mask_color.png (palette colours), output.png (the rendered image)."""
         from PIL import Image

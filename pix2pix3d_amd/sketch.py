@@ -472,6 +472,23 @@ class SketchSession(edit._StageSession):
         self._log, self._kept = [], None
         self._dirty_canvas()
 
+    _agreement = None                                                          # agreement()'s product: (frame, canvas, arguments, counters, their host copy)
+
+    @torch.no_grad()
+    def agreement(self, threshold=128, tolerance=2, trace_passes=2, bins=65):
+        """How faithfully the current frame follows the current canvas — the edge counterpart of ``EditSession.agreement``:
+        ``evaluate.Agreement.result(tolerance)`` after ``add_ink(self.canvas, trace(255 - frame['label'], passes=trace_passes), threshold)``, the map
+        ``take_view_as_canvas`` would take; its 'ink' entry holds the measures.  The canvas must have the frame's size (ValueError otherwise).  Kept with the
+        frame: a camera move recomputes it without the Encoder or the backbone, a repeated call launches nothing."""
+        from . import evaluate
+        self.render()
+        frame, canvas, key, kept = self._frame, self.canvas, (int(threshold), int(trace_passes), int(bins)), self._agreement
+        if kept is None or kept[0] is not frame or kept[1] is not canvas or kept[2] != key:
+            total = evaluate.Agreement(1, self.device, bins)
+            evaluate._add_ink_frame(total, canvas, frame['label'], threshold, trace_passes)
+            self._agreement = kept = (frame, canvas, key, total, total.host_counters())
+        return kept[3].metrics_of(kept[4], tolerance)
+
     def save(self, directory):
         """Three PNGs: canvas.png (the ink), condition.png (the conditioning image, [-1, 1] as grey) and output.png (the rendered image)."""
         from PIL import Image
