@@ -71,4 +71,8 @@ int p3d_label_distance_histogram(const uint8_t* from, int64_t from_row_pitch, co
 #ifdef __cplusplus
 }
 #endif
+
+/* The cross-view consistency kernels of the same library (csrc/regions/view_reproject.hip) are declared in a header of their own, which every
+ * includer of this one sees: pix2pix3d_amd/regions.py binds the six prototypes above, pix2pix3d_amd/reproject.py the three of that header.  */
+#include "p3d_view_reproject.h"
 #endif

@@ -331,6 +331,30 @@ class _StageSession:
             self._surface = kept = (self._planes, self._cam2world, key, frame)
         return kept[3]
 
+    @torch.no_grad()
+    def consistency(self, yaw=0.0, pitch=0.0, roll=0.0, tolerance=None, radius=0):
+        """How well the current frame agrees in 3D with a second view of the same planes: the current camera turned about the generator's camera pivot by
+        ``yaw`` / ``pitch`` / ``roll`` RADIANS (``reproject.turned_camera``) is rendered by one extra ``G.synthesis(..., use_cached_backbone=True)`` on the kept
+        planes — neither the Encoder nor the backbone runs —, both views become frames at the neural rendering resolution (``reproject.raw_frames``) and the
+        current one is warped into the second: ``reproject.consistency_counts(..., pairs=[(0, 1)])``.  Returns ``reproject.Consistency.result()`` with
+        'tolerance' (default ``reproject.default_tolerance(G)``) and 'views', the dict of what was compared ('labels', 'images', 'depth', 'cameras')."""
+        from . import reproject
+        G = self.G
+        first = self.render(return_float=True)['float']
+        cams = torch.cat([self.camera, reproject.turned_camera(self.camera, G.rendering_kwargs['avg_camera_pivot'], yaw, pitch, roll)])
+        found, G._last_planes = G._last_planes, self._planes
+        try:
+            with views._frozen_draws(self._draws[0], self._draws[1]) if self._draws is not None else contextlib.nullcontext():
+                second = G.synthesis(self.encode(), cams[1:], neural_rendering_resolution=self.nrr, use_cached_backbone=True, noise_mode='const')
+        finally:
+            G._last_planes = found
+        both = reproject.raw_frames({k: torch.cat([first[k], second[k]]) for k in ('image_raw', 'image_depth', 'semantic_raw') if k in first})
+        tolerance = reproject.default_tolerance(G) if tolerance is None else tolerance
+        total = reproject.consistency_counts(both['labels'], both['images'], both['depth'], cams, [(0, 1)], both['n_labels'], tolerance, radius)
+        out = total.result()
+        out.update(tolerance=int(tolerance), views=dict(both, cameras=cams))
+        return out
+
 
 # ---- the session ----------------------------------------------------------------------------------------------------------------
 class EditSession(_StageSession):

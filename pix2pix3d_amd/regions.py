@@ -12,7 +12,7 @@ and compositions of them in torch element-wise ops on the mask's device, none of
 ``select``, ``flood_fill``, ``grow``, ``shrink``, ``remove``, ``transform``.  Masks are uint8 [H, W] with contiguous pixels and any row pitch, 1 .. 4096 pixels a
 side (``edit._check_mask``); everything is written out of place.  ``EditSession.fill`` / ``grow`` / ``shrink`` / ``remove`` / ``move`` / ``scale`` / ``rotate`` /
 ``transform`` log these as undo steps (edit.py).  The library also carries the three counting kernels of the agreement metrics (evaluate.py calls them through
-``regions_lib()``)."""
+``regions_lib()``) and the three kernels of the cross-view warp (reproject.py, which binds their own header onto the same library)."""
 import ctypes
 import math
 
