@@ -23,7 +23,7 @@ _c_void_p = ctypes.c_void_p
 _i32x4, _i64x4 = ctypes.c_int32 * 4, ctypes.c_int64 * 4
 _i32x2, _i64x2 = ctypes.c_int32 * 2, ctypes.c_int64 * 2
 
-_C_TYPES = {'int': ctypes.c_int32, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'uint8_t': ctypes.c_uint8, 'uint32_t': ctypes.c_uint32,
+_C_TYPES = {'int': ctypes.c_int32, 'int16_t': ctypes.c_int16, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'uint8_t': ctypes.c_uint8, 'uint32_t': ctypes.c_uint32,
             'uint64_t': ctypes.c_uint64, 'float': ctypes.c_float, 'double': ctypes.c_double}
 _DECLARATOR = re.compile(r'(.*?)(\w+)\s*(?:\[\s*(\d*)\s*\])?', re.S)      # [type] name [[n]]
 

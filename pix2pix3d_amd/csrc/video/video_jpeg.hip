@@ -1,0 +1,304 @@
+// Baseline JPEG frames for the MJPEG writer (p3d_video.h; pix2pix3d_amd/video.py).  Integer rules throughout: every byte is
+// defined by the header, and the formulations of video.py produce the same bytes.
+//
+// p3d_video_jpeg_blocks  a wave owns one 8 x 8 block, a lane one sample: colour transform (and the 2 x 2 chroma mean at 4:2:0) on the way in, the row
+//                        pass and the column pass of the integer DCT through 2 x 64 ints of LDS, then lane z quantises the coefficient of zigzag
+//                        position z, so a block leaves as one 128-byte store.  Four blocks a work-group.
+// p3d_video_jpeg_scan    a work-group of ONE wave owns a restart interval (at most 48 blocks), a lane one block.  Every lane walks its block once to
+//                        count its bits, a wave prefix sum gives every block its first bit, and a second walk ORs the codes into the interval's
+//                        bit string in LDS (a lane gathers 32 bits in a register before it touches LDS; only the words two blocks share see two
+//                        lanes).  The wave then reads the string 64 bytes at a time: a ballot of the 0xFF bytes gives every byte its place after
+//                        stuffing.  The first launch only counts the bytes, the second writes them: nothing of an interval's worst case (9948
+//                        bytes before stuffing) ever sits in device memory, and no interval shares a bit or a byte with another.
+#include "../p3d_common.h"
+#include "p3d_video.h"
+
+namespace {
+
+using namespace p3d;
+
+constexpr int kRestart = P3D_VIDEO_JPEG_RESTART;
+constexpr int kMaxBlocks = kRestart * 6;                                     // of an interval, at 4:2:0
+constexpr int kBlockBits = 16 + 11 + 63 * (16 + 10);                          // what a block can take under ANY table of codes up to 16 bits (Annex K: P3D_VIDEO_JPEG_BLOCK_BITS)
+static_assert(kBlockBits >= P3D_VIDEO_JPEG_BLOCK_BITS, "the LDS bound covers the header's");
+constexpr int kWords = (kMaxBlocks * kBlockBits + 31) / 32 + 1;                // the bit string of an interval, and the word after it (zeroed, never ORed)
+static_assert(kMaxBlocks <= kWave, "a lane per block: an interval must fit one wave");
+
+__constant__ int kDct[8][8] = {{P3D_VIDEO_JPEG_DCT_ROW0}, {P3D_VIDEO_JPEG_DCT_ROW1}, {P3D_VIDEO_JPEG_DCT_ROW2}, {P3D_VIDEO_JPEG_DCT_ROW3},
+                               {P3D_VIDEO_JPEG_DCT_ROW4}, {P3D_VIDEO_JPEG_DCT_ROW5}, {P3D_VIDEO_JPEG_DCT_ROW6}, {P3D_VIDEO_JPEG_DCT_ROW7}};
+__constant__ unsigned char kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                          41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                          30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};      // zigzag position -> 8 v + u
+
+struct Layout {                                     // how a clip is cut into MCUs
+    int mcus_x, n_mcu, bpm;                         // MCUs of a row, of a frame; blocks of an MCU
+    int n_intervals;                                // restart intervals of a frame
+};
+
+struct BlockArgs {
+    const uint8_t* frames; int64_t frame_pitch, row_pitch;
+    int H, W, subsampling;
+    Layout l;
+    int64_t blocks;                                 // of the clip
+    const uint8_t* luma_q; const uint8_t* chroma_q;
+    int16_t* out;
+};
+
+// Component `comp` (0 Y, 1 Cb, 2 Cr) of the pixel (x, y) of the padded plane: the last row and column repeat.
+__device__ __forceinline__ int component(const BlockArgs& a, const uint8_t* frame, int x, int y, int comp)
+{
+    const uint8_t* const px = frame + (int64_t)min(y, a.H - 1) * a.row_pitch + 3 * (int64_t)min(x, a.W - 1);
+    const int r = px[0], g = px[1], b = px[2];
+    if (comp == 0) return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
+    const int v = comp == 1 ? -11059 * r - 21709 * g + 32768 * b : 32768 * r - 27439 * g - 5329 * b;
+    return min(max((v + 32768 + (128 << 16)) >> 16, 0), 255);
+}
+
+__global__ void __launch_bounds__(256) jpeg_blocks_kernel(const BlockArgs a)
+{
+    __shared__ int tile[4][2][64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & (kWave - 1);
+    const int64_t b = (int64_t)blockIdx.x * 4 + wave;
+    const bool valid = b < a.blocks;
+    const int64_t bc = valid ? b : a.blocks - 1;                               // waves past the clip redo its last block and store nothing
+    const int64_t per_frame = (int64_t)a.l.n_mcu * a.l.bpm;
+    const int64_t f = bc / per_frame;
+    const int rem = (int)(bc - f * per_frame);
+    const int mcu = rem / a.l.bpm, k = rem - mcu * a.l.bpm;
+    const int my = mcu / a.l.mcus_x, mx = mcu - my * a.l.mcus_x;
+    const uint8_t* const frame = a.frames + f * a.frame_pitch;
+    const int y = lane >> 3, x = lane & 7;
+    int s;
+    if (a.subsampling == 0) {
+        s = component(a, frame, mx * 8 + x, my * 8 + y, k);
+    } else if (k < 4) {
+        s = component(a, frame, mx * 16 + (k & 1) * 8 + x, my * 16 + (k >> 1) * 8 + y, 0);
+    } else {
+        const int px = 2 * (mx * 8 + x), py = 2 * (my * 8 + y), comp = k - 3;
+        s = (component(a, frame, px, py, comp) + component(a, frame, px + 1, py, comp) + component(a, frame, px, py + 1, comp) +
+             component(a, frame, px + 1, py + 1, comp) + 2) >> 2;
+    }
+    int (&in)[64] = tile[wave][0];
+    int (&mid)[64] = tile[wave][1];
+    in[lane] = s - 128;
+    __syncthreads();
+    int acc = 0;                                                              // lane (y, u = x): the row pass
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc += kDct[x][i] * in[y * 8 + i];
+    mid[lane] = (acc + 128) >> 8;
+    __syncthreads();
+    acc = 0;                                                                  // lane (v = y, u = x): the column pass
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc += kDct[y][i] * mid[i * 8 + x];
+    in[lane] = (acc + 16384) >> 15;                                           // (every read of `in` came before the barrier above)
+    __syncthreads();
+    const int c8 = in[kZigzag[lane]];                                         // lane z: the coefficient of zigzag position z
+    const uint8_t* const table = (a.subsampling == 0 ? k == 0 : k < 4) ? a.luma_q : a.chroma_q;
+    const int q = max((int)table[lane], 1);
+    const int mag = (abs(c8) + 4 * q) / (8 * q);
+    if (valid) a.out[b * 64 + lane] = (int16_t)(c8 < 0 ? -mag : mag);
+}
+
+struct ScanArgs {
+    const int16_t* coefficients;
+    Layout l;
+    const uint32_t* huffman;
+    int32_t* lengths; const int64_t* offsets;
+    uint8_t* data; int64_t data_bytes;
+};
+
+struct CountBits {
+    int bits = 0;
+    __device__ __forceinline__ void put(unsigned, int n) { bits += n; }
+};
+
+// Appends codes to the bit string in LDS, most significant bit first, from bit `first` on.  The string starts as zeros, so an OR writes it; the words at
+// the two ends of a block's bits belong to its neighbours too.
+struct WriteBits {
+    unsigned* words; unsigned word; unsigned cur; int fill;                    // `fill` bits of `cur`, from its top, are gathered for words[word]
+    __device__ __forceinline__ WriteBits(unsigned* w, int first) : words(w), word((unsigned)first >> 5), cur(0), fill(first & 31) {}
+    __device__ __forceinline__ void put(unsigned v, int n)                    // 1 <= n <= 27, v < 2^n
+    {
+        const unsigned long long t = ((unsigned long long)cur << 32) | ((unsigned long long)v << (64 - fill - n));
+        fill += n;
+        if (fill >= 32) {
+            atomicOr(&words[word], (unsigned)(t >> 32));
+            ++word; cur = (unsigned)t; fill -= 32;
+        } else {
+            cur = (unsigned)(t >> 32);
+        }
+    }
+    __device__ __forceinline__ void flush() { if (fill) atomicOr(&words[word], cur); }
+};
+
+__device__ __forceinline__ int clamp_ac(int v) { return min(max(v, -1023), 1023); }
+__device__ __forceinline__ int clamp_dc(int v) { return min(max(v, -1024), 1023); }
+
+// One symbol: its Huffman code, then the `size` extra bits of v.  A table entry is length << 16 | code; whatever the caller's table holds, a symbol
+// stays within 16 + 10 bits, so the interval stays within its LDS.
+template <class Sink> __device__ __forceinline__ void put_symbol(Sink& s, const unsigned* table, int symbol, int v, int size)
+{
+    const unsigned e = table[symbol];
+    const int len = min(max((int)(e >> 16), 1), 16);
+    const unsigned code = e & ((1u << len) - 1u);
+    const unsigned extra = (unsigned)(v < 0 ? v - 1 : v) & ((1u << size) - 1u);
+    s.put((code << size) | extra, len + size);
+}
+
+template <class Sink> __device__ __forceinline__ void code_block(Sink& s, const int16_t* block, int dc_pred, const unsigned* dc_table, const unsigned* ac_table)
+{
+    int run = 0;
+    for (int c = 0; c < 8; ++c) {
+        const uint4 raw = ((const uint4*)block)[c];
+        const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int v16 = (int)(int16_t)(w[j >> 1] >> (16 * (j & 1)));
+            if (c == 0 && j == 0) {
+                const int d = clamp_dc(v16) - dc_pred;
+                const int size = 32 - __clz(abs(d));                          // 0 for d = 0
+                put_symbol(s, dc_table, size, d, size);
+            } else {
+                const int v = clamp_ac(v16);
+                if (v == 0) {
+                    ++run;
+                } else {
+                    for (; run > 15; run -= 16) put_symbol(s, ac_table, 0xF0, 0, 0);
+                    const int size = 32 - __clz(abs(v));
+                    put_symbol(s, ac_table, (run << 4) | size, v, size);
+                    run = 0;
+                }
+            }
+        }
+    }
+    if (run) put_symbol(s, ac_table, 0x00, 0, 0);
+}
+
+template <bool kWrite> __global__ void __launch_bounds__(kWave) jpeg_scan_kernel(const ScanArgs a)
+{
+    __shared__ unsigned table[4 * 256];
+    __shared__ unsigned words[kWords];
+    const int lane = threadIdx.x;
+    const int64_t f = blockIdx.x / (unsigned)a.l.n_intervals;
+    const int interval = (int)(blockIdx.x - f * a.l.n_intervals);
+    for (int i = lane; i < 4 * 256; i += kWave) table[i] = a.huffman[i];
+    const int mcu0 = interval * kRestart, bpm = a.l.bpm;
+    const int n_blocks = min(kRestart, a.l.n_mcu - mcu0) * bpm;               // 3 .. 48
+    const int16_t* const blocks = a.coefficients + ((int64_t)f * a.l.n_mcu + mcu0) * bpm * 64;
+    const bool active = lane < n_blocks;
+    const int k = lane % bpm;
+    const bool chroma = bpm == 3 ? k > 0 : k >= 4;
+    const int prev = bpm == 3 ? lane - 3 : (k == 0 ? lane - 3 : (k < 4 ? lane - 1 : lane - 6));      // the block before of the same component
+    const int16_t* const block = blocks + (active ? lane : 0) * 64;
+    const int dc_pred = active && prev >= 0 ? clamp_dc(blocks[prev * 64]) : 0;
+    const unsigned* const dc_table = table + (chroma ? 256 : 0);
+    const unsigned* const ac_table = table + (chroma ? 768 : 512);
+    __syncthreads();
+
+    CountBits count;
+    if (active) code_block(count, block, dc_pred, dc_table, ac_table);
+    int end = count.bits;                                                     // inclusive prefix sum over the wave
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const int t = __shfl_up(end, d);
+        if (lane >= d) end += t;
+    }
+    const int total = __shfl(end, kWave - 1);                                  // <= kMaxBlocks * kBlockBits
+    const int n_words = (total + 31) >> 5;
+    for (int i = lane; i <= n_words; i += kWave) words[i] = 0;                 // (n_words < kWords)
+    __syncthreads();
+    if (active) {
+        WriteBits writer(words, end - count.bits);
+        code_block(writer, block, dc_pred, dc_table, ac_table);
+        writer.flush();
+    }
+    const int pad = (-total) & 7;                                             // 1-bits up to the byte
+    if (lane == 0 && pad) atomicOr(&words[total >> 5], ((1u << pad) - 1u) << (32 - (total & 31) - pad));
+    __syncthreads();
+
+    const int n_bytes = (total + 7) >> 3;
+    const bool last = interval == a.l.n_intervals - 1;
+    const int64_t at = kWrite ? a.offsets[blockIdx.x] : 0;
+    int stuffed = 0;                                                          // 0x00 bytes put in so far
+    for (int base = 0; base < n_bytes; base += kWave) {
+        const int j = base + lane;
+        const unsigned byte = j < n_bytes ? (words[j >> 2] >> (24 - 8 * (j & 3))) & 255u : 0u;
+        const unsigned long long ff = __ballot(byte == 255u);
+        if (kWrite && j < n_bytes) {
+            const int64_t pos = at + j + stuffed + __popcll(ff & ((1ull << lane) - 1ull));
+            if (pos < a.data_bytes) a.data[pos] = (uint8_t)byte;
+            if (byte == 255u && pos + 1 < a.data_bytes) a.data[pos + 1] = 0;
+        }
+        stuffed += __popcll(ff);
+    }
+    if (lane == 0) {
+        if (!kWrite) {
+            a.lengths[blockIdx.x] = n_bytes + stuffed + (last ? 0 : 2);
+        } else if (!last) {
+            const int64_t pos = at + n_bytes + stuffed;
+            if (pos + 1 < a.data_bytes) { a.data[pos] = 0xFF; a.data[pos + 1] = (uint8_t)(0xD0 + (interval & 7)); }
+        }
+    }
+}
+
+// The checks both entry points share.  `pixels` = n_frames * h * w.
+int layout(const char* what, int32_t n_frames, int32_t h, int32_t w, int32_t subsampling, Layout* l, int64_t* pixels)
+{
+    P3D_REQUIRE(n_frames >= 0 && h >= 0 && w >= 0, "%s: n_frames, h and w must be >= 0 (got %d, %d, %d)", what, n_frames, h, w);
+    P3D_REQUIRE(subsampling == 0 || subsampling == 1, "%s: subsampling is 0 (4:4:4) or 1 (4:2:0) (got %d)", what, subsampling);
+    const int64_t hw = (int64_t)h * w;
+    P3D_REQUIRE(hw < (1ll << 31) && hw * n_frames < (1ll << 31), "%s: %d x %d x %d pixels reach 2^31", what, n_frames, h, w);
+    *pixels = hw * n_frames;
+    const int mcu = 8 << subsampling;
+    const int64_t mcus_x = ((int64_t)w + mcu - 1) / mcu, mcus_y = ((int64_t)h + mcu - 1) / mcu;
+    l->mcus_x = (int)mcus_x; l->n_mcu = (int)(mcus_x * mcus_y); l->bpm = subsampling ? 6 : 3;
+    l->n_intervals = (l->n_mcu + kRestart - 1) / kRestart;
+    return P3D_OK;
+}
+
+} // namespace
+
+extern "C" int p3d_video_jpeg_blocks(const uint8_t* frames, int64_t frame_pitch, int64_t row_pitch, int32_t n_frames, int32_t h, int32_t w,
+                                     int32_t subsampling, const uint8_t* luma_q, const uint8_t* chroma_q, int16_t* coefficients, p3d_stream_t stream)
+{
+    using namespace p3d;
+    BlockArgs a;
+    int64_t pixels = 0;
+    const int rc = layout("video_jpeg_blocks", n_frames, h, w, subsampling, &a.l, &pixels);
+    if (rc != P3D_OK) return rc;
+    if (pixels == 0) return P3D_OK;
+    P3D_REQUIRE(frames && luma_q && chroma_q && coefficients, "video_jpeg_blocks: frames, the two tables and coefficients must be non-null");
+    P3D_REQUIRE(row_pitch >= 3 * (int64_t)w && frame_pitch >= 0, "video_jpeg_blocks: the row pitch is shorter than the row, or the frame pitch negative");
+    P3D_REQUIRE(((uintptr_t)coefficients & 1u) == 0, "video_jpeg_blocks: coefficients must be 2-byte aligned");
+    a.frames = frames; a.frame_pitch = frame_pitch; a.row_pitch = row_pitch; a.H = h; a.W = w; a.subsampling = subsampling;
+    a.blocks = (int64_t)n_frames * a.l.n_mcu * a.l.bpm;
+    a.luma_q = luma_q; a.chroma_q = chroma_q; a.out = coefficients;
+    const int64_t groups = (a.blocks + 3) / 4;
+    P3D_REQUIRE(groups < (1ll << 31), "video_jpeg_blocks: %lld blocks are too many for one launch", (long long)a.blocks);
+    hipLaunchKernelGGL(jpeg_blocks_kernel, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, a);
+    count_launch(FAM_AUX);
+    return check_launch("video_jpeg_blocks");
+}
+
+extern "C" int p3d_video_jpeg_scan(const int16_t* coefficients, int32_t n_frames, int32_t h, int32_t w, int32_t subsampling, const uint32_t* huffman,
+                                   int32_t* lengths, const int64_t* offsets, uint8_t* data, int64_t data_bytes, p3d_stream_t stream)
+{
+    using namespace p3d;
+    ScanArgs a;
+    int64_t pixels = 0;
+    const int rc = layout("video_jpeg_scan", n_frames, h, w, subsampling, &a.l, &pixels);
+    if (rc != P3D_OK) return rc;
+    P3D_REQUIRE(data_bytes >= 0, "video_jpeg_scan: data_bytes must be >= 0 (got %lld)", (long long)data_bytes);
+    if (pixels == 0) return P3D_OK;
+    P3D_REQUIRE(coefficients && ((uintptr_t)coefficients & 15u) == 0, "video_jpeg_scan: coefficients must be non-null and 16-byte aligned");
+    P3D_REQUIRE(huffman && ((uintptr_t)huffman & 3u) == 0, "video_jpeg_scan: huffman must be non-null and 4-byte aligned");
+    if (data) P3D_REQUIRE(offsets && ((uintptr_t)offsets & 7u) == 0, "video_jpeg_scan: with data, offsets must be non-null and 8-byte aligned");
+    else      P3D_REQUIRE(lengths && ((uintptr_t)lengths & 3u) == 0, "video_jpeg_scan: without data, lengths must be non-null and 4-byte aligned");
+    const int64_t groups = (int64_t)n_frames * a.l.n_intervals;
+    P3D_REQUIRE(groups < (1ll << 31), "video_jpeg_scan: %lld restart intervals are too many for one launch", (long long)groups);
+    a.coefficients = coefficients; a.huffman = huffman; a.lengths = lengths; a.offsets = offsets; a.data = data; a.data_bytes = data_bytes;
+    if (data) hipLaunchKernelGGL(jpeg_scan_kernel<true>, dim3((unsigned)groups), dim3(kWave), 0, (hipStream_t)stream, a);
+    else      hipLaunchKernelGGL(jpeg_scan_kernel<false>, dim3((unsigned)groups), dim3(kWave), 0, (hipStream_t)stream, a);
+    count_launch(FAM_AUX);
+    return check_launch("video_jpeg_scan");
+}

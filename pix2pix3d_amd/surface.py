@@ -594,13 +594,17 @@ def render(G, ws, cameras, resolution=512, color='grey', palette=None, backgroun
 
 
 @torch.no_grad()
-def geometry_video(G, ws, cfg='seg2cat', n_frames=120, views_per_step=4, resolution=512, color='grey', path=None, fps=60, gif='pil', **render_kwargs):
+def geometry_video(G, ws, cfg='seg2cat', n_frames=120, views_per_step=4, resolution=512, color='grey', path=None, fps=60, gif='pil', format='gif',
+                   **render_kwargs):
     """The geometry turntable of ``ws`` [1, num_ws, w_dim]: ``render`` over ``views.video_cameras(G, cfg, n_frames)``, ``views_per_step``
     cameras per cast launch, the backbone run once for all of them where the cast kernel serves.  uint8 [n_frames, R, R, 3] on ws's
     device; with ``path`` also written as a GIF: ``gif='pil'`` through ``mesh.save_gif``, ``gif='device'`` through ``video.save_gif`` (one palette for the
-    clip, made and applied on the frames' device)."""
+    clip, made and applied on the frames' device).  ``format='avi'``: a true-colour Motion-JPEG AVI through ``video.save_avi`` instead, encoded on the
+    frames' device (``gif`` plays no part)."""
     if gif not in ('pil', 'device'):
         raise ValueError(f"geometry_video: gif must be 'pil' or 'device', got {gif!r}")
+    if format not in ('gif', 'avi'):
+        raise ValueError(f"geometry_video: format must be 'gif' or 'avi', got {format!r}")
     step = int(views_per_step)
     if step < 1:
         raise ValueError(f'geometry_video: views_per_step must be >= 1, got {views_per_step}')
@@ -610,7 +614,10 @@ def geometry_video(G, ws, cfg='seg2cat', n_frames=120, views_per_step=4, resolut
         kw['planes'] = shape._planes(G, ws, noise_mode=kw.get('noise_mode', 'const'))
     frames = [render(G, ws, cameras[s:s + step], resolution, color=color, **kw) for s in range(0, cameras.shape[0], step)]
     out = torch.cat(frames) if frames else torch.empty([0, int(resolution), int(resolution), 3], dtype=torch.uint8, device=ws.device)
-    if path is not None and gif == 'device':
+    if path is not None and format == 'avi':
+        from . import video
+        video.save_avi(path, out, fps=fps)
+    elif path is not None and gif == 'device':
         from . import video
         video.save_gif(path, out, fps=fps)
     elif path is not None:

@@ -14,7 +14,12 @@ three that touch every pixel, device kernels whose bytes equal it:
 ``palettize`` runs them in order, ``save_gif_indexed`` writes index frames and their palette as a GIF without any further quantisation, and ``save_gif``
 is the two together.  Frames are uint8 [F, H, W, 3] with contiguous pixels (``stride(3) == 1``, ``stride(2) == 3``) and any row and frame pitch: a strided
 selection ``frames[::4]`` and a window of a larger canvas are read in place.  One palette serves the whole clip (``per_frame=False``) or one frame
-(``per_frame=True``)."""
+(``per_frame=True``).
+
+True colour needs no palette: ``encode_jpeg`` turns the same frames into baseline JPEG streams where they are (``jpeg_coefficients``: colour transform, chroma
+subsampling, an integer 8 x 8 DCT and the quantiser; ``jpeg_scan``: Huffman coding in restart intervals, byte stuffing), ``save_jpeg`` writes a still and
+``save_avi`` a Motion-JPEG AVI, which needs no codec library to write and which ffmpeg, VLC and OpenCV read; ``read_avi`` takes one apart again.  The same
+rule holds: p3d_video.h states every step in integers, the formulation here is the definition, the device bytes equal it."""
 import numpy as np
 import torch
 
@@ -306,3 +311,400 @@ def save_gif(path, frames, fps=60, colors=COLORS, dither=16, palette='global'):
     result = palettize(frames, colors, dither, palette)
     save_gif_indexed(path, result[0], result[1], fps=fps)
     return result
+
+
+# ---- baseline JPEG and Motion-JPEG -----------------------------------------------------------------------------------------------------------
+# True colour without a codec library: every frame a baseline JFIF of its own, the clip an AVI of them.  csrc/video/p3d_video.h states the rules; the
+# formulations here are those rules operation by operation, and the kernels' bytes equal them.
+JPEG_RESTART, JPEG_BLOCK_BITS = HEADER.constants['P3D_VIDEO_JPEG_RESTART'], HEADER.constants['P3D_VIDEO_JPEG_BLOCK_BITS']
+MAX_AVI_BYTES = 1 << 31                              # a RIFF file of one 'movi' list stays below it (OpenDML is out of scope)
+_SUBSAMPLING = {'4:4:4': 0, '4:2:0': 1}
+_BASE_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+              18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+_BASE_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+# Annex K.3: (BITS: the number of codes of every length 1 .. 16, HUFFVAL: the symbols in code order) of DC luma, DC chroma, AC luma, AC chroma.
+_AC_LUMA_VALUES = bytes.fromhex(
+    '01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a434445464748494a53545556'
+    '5758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6'
+    'd7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa')
+_AC_CHROMA_VALUES = bytes.fromhex(
+    '000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a434445464748494a5354'
+    '55565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3'
+    'd4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa')
+_ANNEX_K = (((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), tuple(range(12))),
+            ((0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), tuple(range(12))),
+            ((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d), tuple(_AC_LUMA_VALUES)),
+            ((0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77), tuple(_AC_CHROMA_VALUES)))
+
+
+def jpeg_zigzag():
+    """int64 [64]: the natural index 8 v + u of every zigzag position — the diagonals v + u in turn, odd ones downwards (v rising), even ones upwards."""
+    return torch.tensor(sorted(range(64), key=lambda n: (n // 8 + n % 8, n // 8 if (n // 8 + n % 8) % 2 else n % 8)), dtype=torch.int64)
+
+
+def jpeg_dct_table():
+    """int64 [8, 8]: T[u][x] = round(8192 a(u) cos((2 x + 1) u pi / 16)), a(0) = sqrt(1 / 8), a(u) = 1 / 2 otherwise — the literals of p3d_video.h."""
+    u, x = np.arange(8.0)[:, None], np.arange(8.0)[None, :]
+    a = np.where(u == 0, np.sqrt(0.125), 0.5)
+    return torch.from_numpy(np.round(8192 * a * np.cos((2 * x + 1) * u * np.pi / 16)).astype(np.int64))
+
+
+def jpeg_dct(samples):
+    """int64 [..., 8, 8] (v, u) of integer level-shifted samples [..., 8, 8] (y, x): 8 x the orthonormal DCT by the header's two integer passes,
+    r[y][u] = (sum_x T[u][x] s[y][x] + 128) >> 8, then c8[v][u] = (sum_y T[v][y] r[y][u] + 16384) >> 15, with arithmetic shifts."""
+    t = jpeg_dct_table()
+    r = (torch.matmul(samples.to(torch.int64), t.T) + 128) >> 8
+    return (torch.matmul(t, r) + 16384) >> 15
+
+
+def _check_quality(quality):
+    if isinstance(quality, bool) or int(quality) != quality or not 1 <= int(quality) <= 100:
+        raise ValueError(f'quality must be an integer 1 .. 100, got {quality!r}')
+    return int(quality)
+
+
+def jpeg_tables(quality):
+    """(luma, chroma): two uint8 [64] quantisation tables in ZIGZAG order on the host — the Annex K base tables under the IJG scaling, scale = 5000 / quality
+    (an integer division) below 50 and 200 - 2 quality from 50, entry = clamp((base scale + 50) / 100, 1, 255).  1 <= ``quality`` <= 100."""
+    q = _check_quality(quality)
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    zigzag = jpeg_zigzag()
+    return tuple(((torch.tensor(base, dtype=torch.int64) * scale + 50) // 100).clamp(1, 255).to(torch.uint8)[zigzag] for base in (_BASE_LUMA, _BASE_CHROMA))
+
+
+class JpegHuffman:
+    """The four Annex K tables, in the order DC luma, DC chroma, AC luma, AC chroma: ``bits`` (four tuples of 16: the number of codes of every length) and
+    ``values`` (four tuples: the symbols in code order) as a DHT segment states them, and ``lookup`` uint32 [4, 256] on the host: per table and symbol
+    length << 16 | code, 0 for a symbol without a code — what ``p3d_video_jpeg_scan`` reads."""
+
+    def __init__(self):
+        self.bits, self.values = tuple(b for b, _ in _ANNEX_K), tuple(v for _, v in _ANNEX_K)
+        lookup = np.zeros([4, 256], dtype=np.int64)
+        for t, (bits, values) in enumerate(_ANNEX_K):
+            code, k = 0, 0
+            for length, n in enumerate(bits, start=1):                          # the canonical assignment of Annex C
+                for _ in range(n):
+                    lookup[t, values[k]] = length << 16 | code
+                    code, k = code + 1, k + 1
+                code <<= 1
+        self.lookup = torch.from_numpy(lookup.astype(np.uint32).view(np.int32)).view(torch.int32)      # (torch has little use for uint32: the same 32 bits)
+
+
+_huffman = None
+_on_device = {}                                      # (what, device) -> the constant tables there: uploaded once
+
+
+def jpeg_huffman():
+    """The ``JpegHuffman`` of this module (made once)."""
+    global _huffman
+    if _huffman is None:
+        _huffman = JpegHuffman()
+    return _huffman
+
+
+def _device_tables(what, device, make):
+    key = (what, str(device))
+    if key not in _on_device:
+        _on_device[key] = tuple(t.to(device) for t in make())
+    return _on_device[key]
+
+
+def _check_subsampling(subsampling):
+    if subsampling in (0, 1) and not isinstance(subsampling, bool):
+        return int(subsampling)
+    if subsampling not in _SUBSAMPLING:
+        raise ValueError(f"subsampling must be '4:4:4' or '4:2:0' (0 or 1), got {subsampling!r}")
+    return _SUBSAMPLING[subsampling]
+
+
+def jpeg_layout(h, w, subsampling):
+    """(MCUs of a row, MCUs of a frame, blocks of an MCU, restart intervals of a frame) of an ``h`` x ``w`` picture."""
+    sub = _check_subsampling(subsampling)
+    mcu = 8 << sub
+    mcus_x, mcus_y = -(-int(w) // mcu), -(-int(h) // mcu)
+    return mcus_x, mcus_x * mcus_y, 6 if sub else 3, -(-(mcus_x * mcus_y) // JPEG_RESTART)
+
+
+def _jpeg_coefficients_torch(frames, luma_q, chroma_q, sub):
+    f, h, w = frames.shape[:3]
+    mcu = 8 << sub
+    hp, wp = -(-h // mcu) * mcu, -(-w // mcu) * mcu
+    rows, cols = torch.arange(hp).clamp(max=h - 1), torch.arange(wp).clamp(max=w - 1)      # the last row and column repeat
+    rgb = frames[:, rows][:, :, cols].to(torch.int64)
+    r, g, b = rgb.unbind(dim=3)
+    planes = [(19595 * r + 38470 * g + 7471 * b + 32768) >> 16,
+              ((-11059 * r - 21709 * g + 32768 * b + 32768 + (128 << 16)) >> 16).clamp(0, 255),
+              ((32768 * r - 27439 * g - 5329 * b + 32768 + (128 << 16)) >> 16).clamp(0, 255)]
+    if sub:
+        planes[1:] = [(p[:, 0::2, 0::2] + p[:, 0::2, 1::2] + p[:, 1::2, 0::2] + p[:, 1::2, 1::2] + 2) >> 2 for p in planes[1:]]
+    zigzag = jpeg_zigzag()
+
+    def blocks(plane, q):
+        """[F, rows of blocks, columns of blocks, 64]: the quantised coefficients of every 8 x 8 block in zigzag order."""
+        hb, wb = plane.shape[1] // 8, plane.shape[2] // 8
+        c8 = jpeg_dct(plane.reshape(f, hb, 8, wb, 8).permute(0, 1, 3, 2, 4) - 128).reshape(f, hb, wb, 64)[..., zigzag]
+        q = q.to(torch.int64).clamp(min=1)
+        return torch.sign(c8) * ((c8.abs() + 4 * q) // (8 * q))
+    y, cb, cr = blocks(planes[0], luma_q), blocks(planes[1], chroma_q), blocks(planes[2], chroma_q)
+    my, mx = hp // mcu, wp // mcu
+    if sub:                                                                       # Y00 Y01 Y10 Y11 of every MCU
+        y = y.reshape(f, my, 2, mx, 2, 64).permute(0, 1, 3, 2, 4, 5).reshape(f, my, mx, 4, 64)
+    else:
+        y = y[:, :, :, None]
+    return torch.cat([y, cb[:, :, :, None], cr[:, :, :, None]], dim=3).reshape(f, my * mx, -1, 64).to(torch.int16)
+
+
+def jpeg_coefficients(frames, tables, subsampling='4:2:0'):
+    """int16 [F, n_mcu, 3 or 6, 64]: the quantised DCT coefficients of the frames, MCUs in raster order, the blocks of an MCU Y Cb Cr (4:4:4, an MCU of
+    8 x 8 pixels) or Y00 Y01 Y10 Y11 Cb Cr (4:2:0, 16 x 16), every block in zigzag order.  ``tables``: (luma, chroma) uint8 [64] in zigzag order
+    (``jpeg_tables``).  The rules — the fixed-point JFIF colour transform, edge replication up to the MCU, the rounded 2 x 2 chroma mean, the two integer DCT
+    passes, the rounding quantiser — are p3d_video.h's.  Device tensors: ONE ``p3d_video_jpeg_blocks`` launch; CPU tensors: the torch formulation."""
+    f, h, w = _check_frames(frames)
+    sub = _check_subsampling(subsampling)
+    luma_q, chroma_q = (torch.as_tensor(t) for t in tables)
+    for t in (luma_q, chroma_q):
+        if t.dtype != torch.uint8 or tuple(t.shape) != (64,):
+            raise ValueError('jpeg_coefficients: tables must be two uint8 [64] tensors')
+    _, n_mcu, bpm, _ = jpeg_layout(h, w, sub)
+    if f * h * w == 0:
+        return torch.zeros([f, 0, bpm, 64], dtype=torch.int16, device=frames.device)      # no pixel, no MCU
+    if not frames.is_cuda:
+        return _jpeg_coefficients_torch(frames, luma_q.cpu(), chroma_q.cpu(), sub)
+    luma_q, chroma_q = luma_q.to(frames.device).contiguous(), chroma_q.to(frames.device).contiguous()
+    out = torch.empty([f, n_mcu, bpm, 64], dtype=torch.int16, device=frames.device)
+    with _lib.kernel_timer('video_jpeg_blocks', out):
+        code = video_lib().p3d_video_jpeg_blocks(*_clip(frames), sub, _lib.ptr(luma_q), _lib.ptr(chroma_q), _lib.ptr(out), _lib.stream_of(out))
+    _check(code, 'video_jpeg_blocks')
+    return out
+
+
+def _bit_length(v):
+    """The size category of every entry: the number of bits of its magnitude (0 for 0; the entries stay below 2^11)."""
+    a = np.abs(v)
+    return sum(((a >> b) > 0).astype(np.int64) for b in range(11))
+
+
+def _jpeg_scan_numpy(blocks, bpm):
+    """The scan bytes of ONE frame: ``blocks`` int64 [n_mcu * bpm, 64].  Every (block, coefficient) slot and every block's end becomes a token of up to 59 bits
+    (the ZRLs before a value, its code, its extra bits); the tokens' bit positions are a cumulative sum that restarts, byte-aligned, at every interval."""
+    table = jpeg_huffman().lookup.numpy().view(np.uint32).astype(np.int64)
+    code, length = table & 0xFFFF, table >> 16
+    nb = blocks.shape[0]
+    k = np.arange(nb) % bpm
+    interval = np.arange(nb) // bpm // JPEG_RESTART
+    n_intervals = int(interval[-1]) + 1
+    component = k if bpm == 3 else np.maximum(k - 3, 0)
+    chroma = (component > 0).astype(np.int64)
+    dc, ac = np.clip(blocks[:, 0], -1024, 1023), np.clip(blocks[:, 1:], -1023, 1023)
+    pred = np.zeros(nb, dtype=np.int64)
+    for c in range(3):                                                            # the previous block of the same component, if the interval holds it
+        idx = np.flatnonzero(component == c)
+        pred[idx[1:]] = np.where(interval[idx[1:]] == interval[idx[:-1]], dc[idx[:-1]], 0)
+    values, lengths = np.zeros([nb, 65], dtype=np.int64), np.zeros([nb, 65], dtype=np.int64)
+
+    def extra(v, size):
+        return np.where(v < 0, v - 1, v) & ((1 << size) - 1)
+    d = dc - pred
+    size = _bit_length(d)
+    values[:, 0], lengths[:, 0] = code[chroma, size] << size | extra(d, size), length[chroma, size] + size
+    position = np.arange(1, 64)[None, :]
+    nonzero = ac != 0
+    before = np.maximum.accumulate(np.where(nonzero, position, 0), axis=1)        # the last non-zero position up to here ...
+    before = np.concatenate([np.zeros([nb, 1], dtype=np.int64), before[:, :-1]], axis=1)      # ... and before here (0: the DC)
+    run = position - before - 1
+    size = _bit_length(ac)
+    tab = (2 + chroma)[:, None]
+    v, n = code[tab, (run & 15) << 4 | size] << size | extra(ac, size), length[tab, (run & 15) << 4 | size] + size
+    for j in range(3):                                                            # one ZRL per 16 zeros of the run, in front
+        more = (run >> 4) > j
+        v, n = np.where(more, code[tab, 0xF0] << n | v, v), np.where(more, n + length[tab, 0xF0], n)
+    values[:, 1:64], lengths[:, 1:64] = np.where(nonzero, v, 0), np.where(nonzero, n, 0)
+    values[:, 64], lengths[:, 64] = code[2 + chroma, 0], np.where(ac[:, 62] == 0, length[2 + chroma, 0], 0)      # EOB unless coefficient 63 is non-zero
+
+    values, lengths, token_interval = values.reshape(-1), lengths.reshape(-1), np.repeat(interval, 65)
+    first = np.cumsum(lengths) - lengths
+    interval_bits = np.bincount(token_interval, weights=lengths, minlength=n_intervals).astype(np.int64)
+    interval_bytes = (interval_bits + 7) // 8
+    base = np.cumsum(interval_bytes) - interval_bytes                              # of an interval, in the unstuffed bytes
+    first = first - (np.cumsum(interval_bits) - interval_bits)[token_interval] + 8 * base[token_interval]
+    bits = np.zeros(8 * int(interval_bytes.sum()), dtype=np.uint8)
+    for b in range(int(lengths.max())):
+        on = lengths > b
+        bits[first[on] + b] = (values[on] >> (lengths[on] - 1 - b)) & 1
+    for b in range(7):                                                            # 1-bits up to the byte
+        on = interval_bits + b < 8 * interval_bytes
+        bits[8 * base[on] + interval_bits[on] + b] = 1
+    raw = np.packbits(bits)
+    ff = (raw == 255).astype(np.int64)
+    stuffed_before = np.cumsum(ff) - ff
+    place = np.arange(raw.shape[0]) + stuffed_before + 2 * np.repeat(np.arange(n_intervals), interval_bytes)
+    out = np.zeros(raw.shape[0] + int(ff.sum()) + 2 * (n_intervals - 1), dtype=np.uint8)
+    out[place] = raw
+    marked = np.arange(n_intervals - 1)                                           # every interval but the last: RSTm after it
+    at = base[1:] + np.cumsum(ff)[base[1:] - 1] + 2 * marked
+    out[at], out[at + 1] = 255, 0xD0 + (marked & 7)
+    return out
+
+
+def jpeg_scan(coefficients, h, w, subsampling='4:2:0'):
+    """``(data uint8 [total], offsets int64 [F + 1])``: the entropy-coded scans of ``coefficients`` (``jpeg_coefficients``' layout, for pictures of ``h`` x ``w``),
+    frame i at ``data[offsets[i]:offsets[i + 1]]``; ``data`` on the coefficients' device, ``offsets`` on the host.  A frame is cut into restart intervals of
+    ``JPEG_RESTART`` MCUs: each starts byte-aligned with the DC predictors 0, is padded with 1-bits, byte-stuffed and — but for the last — followed by RSTm,
+    m = interval index mod 8, so that no interval shares a bit with another.  The Annex K tables (``jpeg_huffman``).  Device tensors: two
+    ``p3d_video_jpeg_scan`` launches — the byte length of every interval, then, after their prefix sum, the bytes — with the copy of the lengths to the
+    host between them, the ONLY synchronisation (it sizes ``data``).  CPU tensors: the numpy formulation, frame by frame."""
+    sub = _check_subsampling(subsampling)
+    _, n_mcu, bpm, n_intervals = jpeg_layout(h, w, sub)
+    if not torch.is_tensor(coefficients) or coefficients.dtype != torch.int16 or coefficients.ndim != 4:
+        raise ValueError('jpeg_scan: coefficients must be an int16 [F, n_mcu, blocks, 64] tensor')
+    f = coefficients.shape[0]
+    if int(h) < 0 or int(w) < 0 or f * int(h) * int(w) >= MAX_PIXELS:
+        raise ValueError(f'jpeg_scan: {f} x {h} x {w} pixels are negative or reach 2^31')
+    if f * int(h) * int(w) == 0:
+        return torch.zeros([0], dtype=torch.uint8, device=coefficients.device), torch.zeros([f + 1], dtype=torch.int64)
+    if tuple(coefficients.shape[1:]) != (n_mcu, bpm, 64):
+        raise ValueError(f'jpeg_scan: {h} x {w} at subsampling {subsampling!r} has [{n_mcu}, {bpm}, 64] coefficients a frame, got {list(coefficients.shape[1:])}')
+    if not coefficients.is_cuda:
+        scans = [_jpeg_scan_numpy(c.reshape(-1, 64).to(torch.int64).numpy(), bpm) for c in coefficients]
+        sizes = torch.tensor([0] + [s.shape[0] for s in scans], dtype=torch.int64)
+        return torch.from_numpy(np.concatenate(scans)), torch.cumsum(sizes, 0)
+    coefficients = coefficients.contiguous()
+    huffman, = _device_tables('huffman', coefficients.device, lambda: (jpeg_huffman().lookup,))
+    lengths = torch.empty([f, n_intervals], dtype=torch.int32, device=coefficients.device)
+    stream = lambda: _lib.stream_of(coefficients)
+    with _lib.kernel_timer('video_jpeg_scan_lengths', lengths):
+        code = video_lib().p3d_video_jpeg_scan(_lib.ptr(coefficients), f, int(h), int(w), sub, _lib.ptr(huffman), _lib.ptr(lengths), None, None, 0, stream())
+    _check(code, 'video_jpeg_scan')
+    ends = torch.cumsum(lengths.reshape(-1), 0, dtype=torch.int64)
+    starts = ends - lengths.reshape(-1)                                            # on the device: the second launch does not wait for the host
+    offsets = torch.cat([torch.zeros([1], dtype=torch.int64), torch.cumsum(lengths.cpu().sum(dim=1, dtype=torch.int64), 0)])
+    data = torch.empty([int(offsets[-1])], dtype=torch.uint8, device=coefficients.device)
+    with _lib.kernel_timer('video_jpeg_scan_bytes', data):
+        code = video_lib().p3d_video_jpeg_scan(_lib.ptr(coefficients), f, int(h), int(w), sub, _lib.ptr(huffman), None, _lib.ptr(starts), _lib.ptr(data),
+                                               data.shape[0], stream())
+    _check(code, 'video_jpeg_scan')
+    return data, offsets
+
+
+def _segment(marker, payload):
+    return bytes([0xFF, marker]) + (len(payload) + 2).to_bytes(2, 'big') + payload
+
+
+def jpeg_header(h, w, tables, subsampling='4:2:0'):
+    """Everything of a baseline JFIF before its scan: SOI, APP0 (JFIF 1.01, square pixels), two DQT, SOF0 (8 bits, three components, Y sampled 2 x 2 at 4:2:0),
+    the four Annex K DHT, DRI (``JPEG_RESTART`` MCUs) and SOS.  The scan and EOI (0xFF 0xD9) follow."""
+    sub = _check_subsampling(subsampling)
+    if not (1 <= int(h) <= 65535 and 1 <= int(w) <= 65535):
+        raise ValueError(f'a JPEG is 1 .. 65535 pixels a side, got {h} x {w}')
+    huffman = jpeg_huffman()
+    out = b'\xff\xd8' + _segment(0xE0, b'JFIF\0' + bytes([1, 1, 0, 0, 1, 0, 1, 0, 0]))
+    for i, table in enumerate(tables):
+        out += _segment(0xDB, bytes([i]) + bytes(torch.as_tensor(table).cpu().tolist()))
+    out += _segment(0xC0, bytes([8]) + int(h).to_bytes(2, 'big') + int(w).to_bytes(2, 'big') + bytes([3, 1, 0x22 if sub else 0x11, 0, 2, 0x11, 1, 3, 0x11, 1]))
+    for i, (bits, values) in enumerate(zip(huffman.bits, huffman.values)):       # Tc << 4 | Th: DC 0, DC 1, AC 0, AC 1
+        out += _segment(0xC4, bytes([(i >> 1) << 4 | (i & 1)]) + bytes(bits) + bytes(values))
+    out += _segment(0xDD, JPEG_RESTART.to_bytes(2, 'big'))
+    return out + _segment(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
+
+
+def encode_jpeg(frames, quality=90, subsampling='4:2:0'):
+    """A list of ``bytes``, one complete baseline JFIF per frame of uint8 [F, H, W, 3] (the module's frame contract; on the device or the host, or a numpy
+    array): ``jpeg_header``, the frame's scan, EOI.  ``quality`` 1 .. 100 picks the tables (``jpeg_tables``).  From device frames: the two kernels' three
+    launches, ONE synchronisation with the host (the interval lengths) and ONE device -> host copy (the scans, a few percent of the frames' bytes)."""
+    frames = torch.as_tensor(frames)
+    f, h, w = _check_frames(frames)
+    sub, tables = _check_subsampling(subsampling), jpeg_tables(quality)
+    if f == 0:
+        return []
+    header = jpeg_header(h, w, tables, sub)
+    on_device = _device_tables(('quantisation', _check_quality(quality)), frames.device, lambda: tables) if frames.is_cuda else tables
+    data, offsets = jpeg_scan(jpeg_coefficients(frames, on_device, sub), h, w, sub)
+    data, offsets = data.cpu().numpy().tobytes(), offsets.tolist()
+    return [header + data[offsets[i]:offsets[i + 1]] + b'\xff\xd9' for i in range(f)]
+
+
+def save_jpeg(path, frame, quality=90, subsampling='4:2:0'):
+    """One uint8 [H, W, 3] frame, on the device or the host, as a baseline JPEG file (``encode_jpeg``).  Returns its bytes."""
+    frame = torch.as_tensor(frame)
+    if frame.ndim != 3:
+        raise ValueError(f'save_jpeg: frame must be uint8 [H, W, 3], got {tuple(frame.shape)}')
+    stream, = encode_jpeg(frame[None], quality, subsampling)
+    with open(path, 'wb') as fh:
+        fh.write(stream)
+    return stream
+
+
+def _chunk(fourcc, payload):
+    return fourcc + len(payload).to_bytes(4, 'little') + payload + b'\0' * (len(payload) & 1)
+
+
+def save_avi(path, frames, fps=60, quality=90, subsampling='4:2:0'):
+    """The frames (``encode_jpeg``'s contract) as a Motion-JPEG AVI: a RIFF 'AVI ' file with the list 'hdrl' ('avih', and one 'strl' of 'strh' — 'vids' /
+    'MJPG', the rate ``fps`` as dwRate / dwScale — and 'strf', a 40-byte BITMAPINFOHEADER of 24 bits), the list 'movi' of one '00dc' chunk per frame,
+    padded to an even length, and 'idx1': per frame the key-frame flag, the chunk's offset from 'movi' and its length.  Every frame is a key frame.
+    ValueError for no frame and for a file that would reach 2^31 bytes (OpenDML is out of scope).  Returns the JPEG streams."""
+    import fractions
+    import struct
+    frames = torch.as_tensor(frames)
+    f, h, w = _check_frames(frames)
+    if f == 0:
+        raise ValueError('save_avi: an AVI needs at least one frame')
+    rate = fractions.Fraction(fps).limit_denominator(1 << 16)
+    if rate <= 0:
+        raise ValueError(f'save_avi: fps must be > 0, got {fps!r}')
+    streams = encode_jpeg(frames, quality, subsampling)
+    movi, index = b'movi', b''
+    chunks = [movi]
+    at = 4                                                                        # of the next chunk, from the 'movi' word
+    for s in streams:
+        index += b'00dc' + struct.pack('<III', 0x10, at, len(s))                  # AVIIF_KEYFRAME
+        chunks.append(_chunk(b'00dc', s))
+        at += len(chunks[-1])
+    largest = max(len(s) for s in streams)
+    avih = struct.pack('<14I', round(1e6 / rate), int(largest * rate) + 1, 0, 0x10, f, 0, 1, largest, w, h, 0, 0, 0, 0)       # AVIF_HASINDEX
+    strh = b'vidsMJPG' + struct.pack('<IHHIIIIIIIi4H', 0, 0, 0, 0, rate.denominator, rate.numerator, 0, f, largest, 0xFFFFFFFF, 0, 0, 0, w, h)
+    strf = struct.pack('<IiiHH4sIiiII', 40, w, h, 1, 24, b'MJPG', 3 * w * h, 0, 0, 0, 0)
+    hdrl = b'hdrl' + _chunk(b'avih', avih) + _chunk(b'LIST', b'strl' + _chunk(b'strh', strh) + _chunk(b'strf', strf))
+    body = b'AVI ' + _chunk(b'LIST', hdrl) + _chunk(b'LIST', b''.join(chunks)) + _chunk(b'idx1', index)
+    if len(body) + 8 >= MAX_AVI_BYTES:
+        raise ValueError(f'save_avi: the file would take {len(body) + 8} bytes; an AVI of one RIFF chunk stays below 2^31')
+    with open(path, 'wb') as fh:
+        fh.write(b'RIFF' + len(body).to_bytes(4, 'little') + body)
+    return streams
+
+
+def read_avi(path):
+    """``(the JPEG bytes of every frame, fps, (w, h))`` of a Motion-JPEG AVI, by following 'idx1' into 'movi' — for tests, and for users without a player.
+    ``fps`` is dwRate / dwScale of the stream header, an int where that is whole.  ValueError for anything that is not such a file."""
+    import struct
+    with open(path, 'rb') as fh:
+        data = fh.read()
+    if len(data) < 12 or data[:4] != b'RIFF' or data[8:12] != b'AVI ':
+        raise ValueError(f'read_avi: {path} is not a RIFF AVI file')
+
+    def chunks(begin, end):
+        """(fourcc, payload begin, payload end) of the chunks in data[begin:end]; of a LIST the fourcc is its type and the payload what follows it."""
+        while begin + 8 <= end:
+            fourcc, size = data[begin:begin + 4], int.from_bytes(data[begin + 4:begin + 8], 'little')
+            if begin + 8 + size > end:
+                raise ValueError(f'read_avi: the chunk {fourcc!r} at {begin} runs past its parent')
+            yield (data[begin + 8:begin + 12], begin + 12, begin + 8 + size) if fourcc == b'LIST' else (fourcc, begin + 8, begin + 8 + size)
+            begin += 8 + size + (size & 1)
+    top = {name: (a, b) for name, a, b in chunks(12, min(len(data), 8 + int.from_bytes(data[4:8], 'little')))}
+    if not all(name in top for name in (b'hdrl', b'movi', b'idx1')):
+        raise ValueError(f'read_avi: {path} lacks one of hdrl, movi, idx1')
+    strl = {name: (a, b) for name, a, b in chunks(*dict((n, (a, b)) for n, a, b in chunks(*top[b'hdrl']))[b'strl'])}
+    strh, strf = data[slice(*strl[b'strh'])], data[slice(*strl[b'strf'])]
+    if strh[:8] != b'vidsMJPG':
+        raise ValueError(f'read_avi: the stream is {strh[:8]!r}, not vids / MJPG')
+    scale, rate = struct.unpack('<II', strh[20:28])
+    w, h = struct.unpack('<ii', strf[4:12])
+    movi = top[b'movi'][0] - 4                                                     # the 'movi' word: what idx1 counts from
+    streams = []
+    for entry in range(top[b'idx1'][0], top[b'idx1'][1], 16):
+        fourcc, _, offset, size = struct.unpack('<4sIII', data[entry:entry + 16])
+        at = movi + offset
+        if fourcc != b'00dc' or data[at:at + 4] != b'00dc' or int.from_bytes(data[at + 4:at + 8], 'little') != size:
+            raise ValueError(f'read_avi: the index entry at {entry} does not point at a 00dc chunk of {size} bytes')
+        streams.append(data[at + 8:at + 8 + size])
+    return streams, (rate // scale if rate % scale == 0 else rate / scale), (w, h)

@@ -327,20 +327,26 @@ def image_grid(frames, grid_size):
 
 
 @torch.no_grad()
-def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=120, fps=60, gif='pil', **render_kwargs):
+def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=120, fps=60, gif='pil', format='gif', **render_kwargs):
     """generate_video.py after its inputs: the ``cfg`` cameras (``video_cameras``) at the script's ray resolution with ``noise_mode='const'``, rendered by
     ``render_views`` (its keyword arguments pass through); ``path`` / ``path_label`` receive the two GIFs the script writes with imageio at 60 fps.
     ``gif='pil'``: through ``mesh.save_gif``, PIL quantising every frame on the host.  ``gif='device'``: the image through ``video.save_gif`` (one palette for
     the clip, made and applied where the frames are) and the label video losslessly through ``video.save_gif_indexed`` — ``label_index`` with the frames'
-    palette, or the edge generators' grey frames with a grey ramp.  Returns ``render_views``' dict."""
+    palette, or the edge generators' grey frames with a grey ramp.  ``format='avi'``: both clips in true colour as Motion-JPEG AVIs through
+    ``video.save_avi``, encoded where the frames are (``gif`` plays no part).  Returns ``render_views``' dict."""
     if gif not in ('pil', 'device'):
         raise ValueError(f"generate_video: gif must be 'pil' or 'device', got {gif!r}")
+    if format not in ('gif', 'avi'):
+        raise ValueError(f"generate_video: format must be 'gif' or 'avi', got {format!r}")
     cams = video_cameras(G, cfg, n_frames).to(ws.device)
     render_kwargs.setdefault('noise_mode', 'const')
     render_kwargs.setdefault('neural_rendering_resolution', VIDEO_CFG[cfg]['neural_rendering_resolution'])
     frames = render_views(G, ws, cams, **render_kwargs)
     if path is not None:
-        if gif == 'device':
+        if format == 'avi':
+            from . import video
+            video.save_avi(path, frames['image'], fps=fps)
+        elif gif == 'device':
             from . import video
             video.save_gif(path, frames['image'], fps=fps)
         else:
@@ -348,7 +354,11 @@ def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=12
     if path_label is not None:
         if 'label' not in frames:
             raise ValueError(f'generate_video: {type(G).__name__} has no label output for path_label')
-        if gif == 'device':
+        if format == 'avi':
+            from . import video
+            label = frames['label']                                            # (the edge generators' frames are grey: [F, H, W])
+            video.save_avi(path_label, label if label.ndim == 4 else label[..., None].expand(-1, -1, -1, 3).contiguous(), fps=fps)
+        elif gif == 'device':
             from . import video
             if 'label_index' in frames:                                        # default_palette(c) is the first c rows of default_palette(256)
                 pal = render_kwargs.get('palette')
