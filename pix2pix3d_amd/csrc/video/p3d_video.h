@@ -1,5 +1,5 @@
 /* libp3d_video.so — palette, dither and index frames for the GIF writer (pix2pix3d_amd/video.py) and, at the end, baseline JPEG
- * frames for the Motion-JPEG writer (section 2.1u).  A library of its
+ * frames for the Motion-JPEG writer (section 2.1u) and the zlib streams of PNG and APNG files (section 2.1v).  A library of its
  * own, like libp3d_regions.so: the product ABI (include/p3d_hip.h, libp3d_hip.so) exports none of this.  It carries its own copy of the
  * library services (p3d_last_error, p3d_launch_count).  Nothing here has a counterpart in the reference, which writes videos with imageio.
  *
@@ -85,6 +85,66 @@ int p3d_video_jpeg_blocks(const uint8_t* frames, int64_t frame_pitch, int64_t ro
  * block; the bits are ORed into LDS words and leave the work-group as plain byte stores.                                                           */
 int p3d_video_jpeg_scan(const int16_t* coefficients, int32_t n_frames, int32_t h, int32_t w, int32_t subsampling, const uint32_t* huffman,
                         int32_t* lengths, const int64_t* offsets, uint8_t* data, int64_t data_bytes, p3d_stream_t stream);
+
+/* ---- lossless frames: the zlib streams of PNG and APNG files (video_png.hip) ------------------------------------------------
+ * Pixels are bpp = 1 .. 4 bytes; the kernels know only bpp, the colour type is the file header's business ('L' 1, 'LA' and 16-bit grey 2, 'RGB' 3,
+ * 'RGBA' 4, palette indices 1).  Frames uint8 [n_frames][h][w][bpp] with frame_pitch / row_pitch (>= w bpp) as above; n_frames h w bpp < 2^31 and
+ * n_frames h (1 + w bpp) < 2^31; a clip with n_frames h w = 0 launches nothing.  Three stages, ONE launch each; integer arithmetic and a pure function
+ * of the inputs throughout: the formulations of pix2pix3d_amd/video.py produce the same bytes.
+ *
+ * FILTER.  A row's filtered form is row_bytes = 1 + w bpp bytes: the filter type, then per byte x the residual (x - predictor) mod 256, with a the byte
+ * bpp to the left (0 for the first pixel), b the byte above (0 in a frame's first row: every frame is filtered on its own) and c the byte above a.
+ * Type 0 None: 0; 1 Sub: a; 2 Up: b; 3 Average: (a + b) >> 1; 4 Paeth: with p = a + b - c, pa = |p - a|, pb = |p - b|, pc = |p - c|: a if pa <= pb
+ * and pa <= pc, else b if pb <= pc, else c.  filter 0 .. 4 forces a type; filter 5 (adaptive) takes, per row, the type with the smallest sum over
+ * the row of |residual as int8| (r for r < 128, 256 - r otherwise), the lowest type on a tie.
+ *
+ * SEGMENTS.  segment_rows >= 1 consecutive filtered rows of a frame are a segment, the last of a frame possibly shorter: n_segments =
+ * ceil(h / segment_rows) a frame.  A segment is coded on its own: no match and no bit crosses from one into the next.
+ *
+ * TOKENS of a segment.  Its bytes are cut into maximal runs of equal bytes.  A run of length n gives one literal; then, over the remaining m = n - 1
+ * bytes, while m >= 3 a match of length min(m, 258) at distance 1; what remains, 1 or 2 bytes, as literals.  (By position: the byte k of a run,
+ * k = 0 its first, carries a literal for k = 0; a match of 258 where k mod 258 = 0; and at the run's last byte, with r = k mod 258, a match of r for
+ * r >= 3 and r literals for r = 1, 2.  No token needs more of the run than its own byte's k and whether the next byte differs.)  A match of length l
+ * is the length symbol and extra bits of RFC 1951: 285 for 258; otherwise with v = l - 3, 257 + v for v < 8, else e = floor(log2 v) - 2 extra bits
+ * of value v mod 2^e after the symbol 261 + 4 e + ((v >> e) & 3).  End of block (256) comes once per segment.
+ *
+ * CODES.  One literal/length code a FRAME, made on the host from the frame's symbol counts (256 counted once per segment): an optimal prefix code
+ * under a limit of 15 bits, canonical as RFC 1951 section 3.2.2 assigns it.  The distance code is constant: symbols 0 and 1 with one bit each, so
+ * a match costs one distance bit, a 0.  The dynamic block header — BTYPE = 10, HLIT, HDIST, HCLEN, the code-length code, the lengths — is made on
+ * the host once a frame, as a bit string WITHOUT its BFINAL bit.
+ *
+ * BYTES of a segment, bits packed from the least significant bit of every byte on, as deflate packs them: BFINAL, the frame's header bits, the tokens
+ * (a Huffman code from its most significant bit on, extra bits from their least), the code of 256.  Every segment but the frame's last has BFINAL = 0
+ * and is followed by an empty stored block: the bits 000, zero bits up to the byte, then 00 00 FF FF — the next segment starts on a byte.  The last
+ * has BFINAL = 1 and is padded with zero bits.  A frame's zlib stream is 78 01, its segments, and the big-endian Adler-32 of its filtered bytes.     */
+#define P3D_VIDEO_PNG_SYMBOLS 286       /* literal/length symbols 0 .. 285 */
+#define P3D_VIDEO_PNG_STATS 290         /* int32 a segment: [0 .. 285] symbol counts ([256] stays 0), [286] extra bits, [287] matches, [288] s1, [289] s2 */
+#define P3D_VIDEO_PNG_HEADER_WORDS 144  /* uint32 a frame for the header bit string: 73 bits and 288 lengths of at most 7 + 7 bits fit 4105 */
+#define P3D_VIDEO_PNG_ADAPTIVE 5        /* the filter argument that chooses per row */
+
+/* filtered uint8 [n_frames][h][1 + w bpp], contiguous; it must not overlap the frames.  A wave per row: the five candidate sums by wave reductions, then
+ * the type and the residuals as plain stores.                                                                                                          */
+int p3d_video_png_filter(const uint8_t* frames, int64_t frame_pitch, int64_t row_pitch, int32_t n_frames, int32_t h, int32_t w, int32_t bpp,
+                         int32_t filter, uint8_t* filtered, p3d_stream_t stream);
+
+/* stats int32 [n_frames][n_segments][P3D_VIDEO_PNG_STATS] of filtered rows of row_bytes (= 1 + w bpp) bytes: per segment the number of times every
+ * literal/length symbol is coded (without 256), the sum of the matches' extra bits, the number of matches, and the Adler pair
+ * s1 = sum b mod 65521, s2 = sum (L - i) b_i mod 65521 (i the 0-based index of byte b_i in the segment, L the segment's bytes).  n_frames h row_bytes
+ * < 2^31; n_frames h = 0 or row_bytes <= 1 launches nothing.  A wave per segment, 64 bytes a step: a ballot of b[i] != b[i - 1] gives the run starts,
+ * the length of the run left open is carried to the next step, the counts gather in LDS.                                                              */
+int p3d_video_png_count(const uint8_t* filtered, int32_t n_frames, int32_t h, int32_t row_bytes, int32_t segment_rows, int32_t* stats,
+                        p3d_stream_t stream);
+
+/* tables uint32 [n_frames][P3D_VIDEO_PNG_SYMBOLS]: per frame and symbol, length << 16 | the code with its bits reversed (length 0 .. 15, more counts as
+ * 15).  headers uint32 [n_frames][P3D_VIDEO_PNG_HEADER_WORDS]: the frame's header bit string, bit i at bit i & 31 of word i >> 5; header_bits int32
+ * [n_frames] its length (clamped to 0 .. 32 P3D_VIDEO_PNG_HEADER_WORDS).  adler uint32 [n_frames]: the frame's Adler-32.  offsets int64
+ * [n_frames][n_segments]: where in data every segment starts.  The segment's bytes, stored block included, go to data + offset; the first segment of a
+ * frame also writes 78 01 to the two bytes before its own, the last the four bytes of adler after its own.  Nothing is written before data or at or
+ * past data_bytes.  A wave per segment: the bits of 64 bytes are ORed into a window in LDS, whose whole words leave at once; a segment's output need
+ * not fit LDS.                                                                                                                                         */
+int p3d_video_png_emit(const uint8_t* filtered, int32_t n_frames, int32_t h, int32_t row_bytes, int32_t segment_rows, const uint32_t* tables,
+                       const uint32_t* headers, const int32_t* header_bits, const uint32_t* adler, const int64_t* offsets, uint8_t* data,
+                       int64_t data_bytes, p3d_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -600,11 +600,11 @@ def geometry_video(G, ws, cfg='seg2cat', n_frames=120, views_per_step=4, resolut
     cameras per cast launch, the backbone run once for all of them where the cast kernel serves.  uint8 [n_frames, R, R, 3] on ws's
     device; with ``path`` also written as a GIF: ``gif='pil'`` through ``mesh.save_gif``, ``gif='device'`` through ``video.save_gif`` (one palette for the
     clip, made and applied on the frames' device).  ``format='avi'``: a true-colour Motion-JPEG AVI through ``video.save_avi`` instead, encoded on the
-    frames' device (``gif`` plays no part)."""
+    frames' device (``gif`` plays no part); ``format='apng'``: a lossless animated PNG through ``video.save_apng``, likewise."""
     if gif not in ('pil', 'device'):
         raise ValueError(f"geometry_video: gif must be 'pil' or 'device', got {gif!r}")
-    if format not in ('gif', 'avi'):
-        raise ValueError(f"geometry_video: format must be 'gif' or 'avi', got {format!r}")
+    if format not in ('gif', 'avi', 'apng'):
+        raise ValueError(f"geometry_video: format must be 'gif', 'avi' or 'apng', got {format!r}")
     step = int(views_per_step)
     if step < 1:
         raise ValueError(f'geometry_video: views_per_step must be >= 1, got {views_per_step}')
@@ -617,6 +617,9 @@ def geometry_video(G, ws, cfg='seg2cat', n_frames=120, views_per_step=4, resolut
     if path is not None and format == 'avi':
         from . import video
         video.save_avi(path, out, fps=fps)
+    elif path is not None and format == 'apng':
+        from . import video
+        video.save_apng(path, out, fps=fps)
     elif path is not None and gif == 'device':
         from . import video
         video.save_gif(path, out, fps=fps)

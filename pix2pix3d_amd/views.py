@@ -333,11 +333,13 @@ def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=12
     ``gif='pil'``: through ``mesh.save_gif``, PIL quantising every frame on the host.  ``gif='device'``: the image through ``video.save_gif`` (one palette for
     the clip, made and applied where the frames are) and the label video losslessly through ``video.save_gif_indexed`` — ``label_index`` with the frames'
     palette, or the edge generators' grey frames with a grey ramp.  ``format='avi'``: both clips in true colour as Motion-JPEG AVIs through
-    ``video.save_avi``, encoded where the frames are (``gif`` plays no part).  Returns ``render_views``' dict."""
+    ``video.save_avi``, encoded where the frames are (``gif`` plays no part).  ``format='apng'``: both clips losslessly as animated PNGs through
+    ``video.save_apng``, encoded where the frames are — the image as RGB, the label video as palette indices (``label_index`` with the frames' palette) or,
+    for the edge generators, as 8-bit grey.  Returns ``render_views``' dict."""
     if gif not in ('pil', 'device'):
         raise ValueError(f"generate_video: gif must be 'pil' or 'device', got {gif!r}")
-    if format not in ('gif', 'avi'):
-        raise ValueError(f"generate_video: format must be 'gif' or 'avi', got {format!r}")
+    if format not in ('gif', 'avi', 'apng'):
+        raise ValueError(f"generate_video: format must be 'gif', 'avi' or 'apng', got {format!r}")
     cams = video_cameras(G, cfg, n_frames).to(ws.device)
     render_kwargs.setdefault('noise_mode', 'const')
     render_kwargs.setdefault('neural_rendering_resolution', VIDEO_CFG[cfg]['neural_rendering_resolution'])
@@ -346,6 +348,9 @@ def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=12
         if format == 'avi':
             from . import video
             video.save_avi(path, frames['image'], fps=fps)
+        elif format == 'apng':
+            from . import video
+            video.save_apng(path, frames['image'], fps=fps)
         elif gif == 'device':
             from . import video
             video.save_gif(path, frames['image'], fps=fps)
@@ -358,6 +363,13 @@ def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=12
             from . import video
             label = frames['label']                                            # (the edge generators' frames are grey: [F, H, W])
             video.save_avi(path_label, label if label.ndim == 4 else label[..., None].expand(-1, -1, -1, 3).contiguous(), fps=fps)
+        elif format == 'apng':
+            from . import video
+            if 'label_index' in frames:
+                pal = render_kwargs.get('palette')
+                video.save_apng(path_label, frames['label_index'], fps=fps, mode='P', palette=mesh.default_palette(256) if pal is None else torch.as_tensor(pal))
+            else:
+                video.save_apng(path_label, frames['label'], fps=fps)
         elif gif == 'device':
             from . import video
             if 'label_index' in frames:                                        # default_palette(c) is the first c rows of default_palette(256)
@@ -371,15 +383,25 @@ def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=12
 
 
 @torch.no_grad()
-def generate_sample(G, ws, camera, path_color=None, path_label=None, palette=None, **synthesis_kwargs):
+def generate_sample(G, ws, camera, path_color=None, path_label=None, palette=None, png='pil', **synthesis_kwargs):
     """generate_samples.py:108-120 after its inputs: one ``G.synthesis(ws, camera, noise_mode='const')`` finished by ``finish_frames``; the image and the
-    label map go to ``path_color`` / ``path_label`` through PIL.  ``camera`` is a [25] or [N, 25] label.  Returns ``finish_frames``' dict."""
+    label map go to ``path_color`` / ``path_label`` through PIL.  ``png='device'``: through ``video.save_png`` instead, encoded where the frames are — the
+    image as RGB, the label map as palette indices where ``label_index`` exists (the same pixels, a smaller file).  ``camera`` is a [25] or [N, 25] label.
+    Returns ``finish_frames``' dict."""
     from PIL import Image
+    if png not in ('pil', 'device'):
+        raise ValueError(f"generate_sample: png must be 'pil' or 'device', got {png!r}")
     camera = torch.as_tensor(camera, dtype=torch.float32).to(ws.device).reshape(-1, 25)
     synthesis_kwargs.setdefault('noise_mode', 'const')
     out = G.synthesis(ws, camera, **synthesis_kwargs)
     frames = finish_frames(out, palette=palette, label_mode='grey' if getattr(G, 'data_type', None) == 'edge' else 'auto')
     for p, key in ((path_color, 'image'), (path_label, 'label')):
-        if p is not None:
+        if p is not None and png == 'device':
+            from . import video
+            if key == 'label' and 'label_index' in frames:
+                video.save_png(p, frames['label_index'][0], mode='P', palette=mesh.default_palette(256) if palette is None else torch.as_tensor(palette))
+            else:
+                video.save_png(p, frames[key][0])
+        elif p is not None:
             Image.fromarray(frames[key][0].cpu().numpy()).save(p)
     return frames
