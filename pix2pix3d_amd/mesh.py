@@ -16,6 +16,7 @@
   (``trimesh.smoothing.filter_taubin``): neighbour lists and boundary flags from sorts, Taubin smoothing of positions or of any
   per-vertex attribute, majority voting of labels, and smooth shading through ``shade(..., normals=)`` (csrc/mesh_filter.hip on device
   tensors; the CPU formulation is the definition and the bytes are the same).
+* ``simplify_to``: ``simplify`` with the cell picked from a tolerance, measured by ``geometry.compare`` (geometry.py).
 * ``extract_mesh``: shape.extract_geometry, the optional clean-up and filters, the labels and the turntable in one call.
 """
 import functools
@@ -729,6 +730,49 @@ def simplify(vertices, faces, cell):
     return means, mapped[keep].long()
 
 
+SIMPLIFY_RUNGS = 32            # simplify_to's ladder of cells: tolerance / 4 * 2^(i / 4), i = 0 .. 31 (up to about 54 tolerances)
+
+
+def simplify_to(vertices, faces, tolerance, spacing=None):
+    """``simplify`` with its cell picked from a tolerance: (vertices', faces', cell, agreement).  The cell comes from the fixed ladder
+    tolerance / 4 * 2^(i / 4), i = 0 .. 31: rung 0 is tried, then a bisection over the rung index in five steps looks for the largest
+    rung whose result keeps the sampled symmetric Hausdorff distance to the input (``geometry.compare`` at ``spacing``, default the
+    input's diagonal over 512; one device-to-host copy per rung tried, six in all) at or below ``tolerance``.  The distance is NOT
+    monotone in the cell (a thin sheet collapses at one cell and not at the next), so the only promise is the post-condition: the
+    mesh that comes back met the tolerance as measured, ``agreement`` being that measurement (A = the input), and the next rung, if
+    the ladder has one, did not.  If rung 0 fails the input comes back unchanged with cell None (and that rung's agreement, or None where
+    the cell was too fine for ``simplify`` to take)."""
+    from . import geometry                                                 # (geometry imports this module)
+    tolerance = float(tolerance)
+    if not (tolerance > 0.0 and math.isfinite(tolerance)):
+        raise ValueError(f'simplify_to: tolerance must be positive and finite, got {tolerance}')
+    vertices = _mesh_vertices('simplify_to', vertices)
+    faces = _mesh_faces('simplify_to', faces, vertices.shape[0]).to(vertices.device)
+    spacing = geometry.diagonal(vertices) / 512 if spacing is None else float(spacing)
+
+    def rung(i):
+        cell = tolerance / 4 * 2.0 ** (i / 4)
+        try:
+            v, f = simplify(vertices, faces, cell)
+        except ValueError:                                                 # more cells than a key holds: a rung that cannot be taken fails
+            return False, (vertices, faces, None, None)
+        agreement = geometry.compare(vertices, faces, v, f, spacing, (tolerance,))
+        return bool(agreement.hausdorff <= tolerance), (v, f, cell, agreement)
+
+    ok, best = rung(0)
+    if not ok:
+        return vertices, faces, None, best[3]
+    passed, failed = 0, SIMPLIFY_RUNGS
+    for _ in range(5):                                                     # 32 rungs: five halvings leave failed = passed + 1
+        mid = (passed + failed) // 2
+        ok, result = rung(mid)
+        if ok:
+            passed, best = mid, result
+        else:
+            failed = mid
+    return best
+
+
 # ---- filtering: adjacency, Taubin smoothing, label voting -----------------------------------------------------------------------
 class Adjacency(NamedTuple):
     """The vertex adjacency of an indexed mesh (``adjacency``): the list of v is neighbours[offsets[v]:offsets[v + 1]]."""
@@ -967,13 +1011,19 @@ def vertex_labels(G, ws, vertices, palette=None, max_batch=10_000_000):
     return labels.to(vertices.device), pal.to(vertices.device)[labels.to(vertices.device)]
 
 
-def _clean_geometry(G, ws, resolution, threshold, keep, min_faces, cell, **synthesis_kwargs):
-    """extract_mesh's geometry: shape.extract_geometry and the optional clean-up (see ``extract_mesh``)."""
+def _clean_geometry(G, ws, resolution, threshold, keep, min_faces, cell, tolerance=None, **synthesis_kwargs):
+    """extract_mesh's geometry: shape.extract_geometry and the optional clean-up (see ``extract_mesh``).  ``tolerance`` (world units)
+    decimates through ``simplify_to`` instead of a given ``cell``; the two exclude each other."""
+    if cell is not None and tolerance is not None:
+        raise ValueError('cell= and tolerance= exclude each other: give the cell, or the tolerance that picks it')
     vertices, faces = shape.extract_geometry(G, ws, resolution, threshold, **synthesis_kwargs)
     if keep is not None or min_faces > 1:
         vertices, faces, _ = clean(vertices, faces, keep, min_faces)
-    if cell is not None:
+    if tolerance is not None and len(faces):
+        vertices, faces, cell, _ = simplify_to(vertices, faces, tolerance)
+    elif cell is not None:
         vertices, faces = simplify(vertices, faces, cell)
+    if cell is not None:
         if keep is not None:
             vertices, faces, _ = clean(vertices, faces, keep)
     return vertices, faces
@@ -1003,20 +1053,21 @@ def script_turntable(G, n_frames=120):
 
 @torch.no_grad()
 def extract_mesh(G, ws, resolution=512, threshold=50., n_frames=120, image_size=512, palette=None, keep=None, min_faces=1, cell=None,
-                 smooth=0, smooth_labels=0, smooth_shading=False, lam=0.5, mu=-0.53, **synthesis_kwargs):
+                 smooth=0, smooth_labels=0, smooth_shading=False, lam=0.5, mu=-0.53, tolerance=None, **synthesis_kwargs):
     """applications/extract_mesh.py after its inputs: shape.extract_geometry, per-vertex label colours unless G is an edge-map
     generator (data_type 'edge') or has no label channels, and the script's turntable — orthographic xmag = ymag = 0.3 at radius 1 (edge2car: 0.6 at 1.2) about
     G.rendering_kwargs['avg_camera_pivot'], image_size^2 pixels.  Returns (vertices, faces, vertex_colors or None, frames uint8
     [n_frames, image_size, image_size, 3]).  Clean-up, off by default, runs on the bare geometry before the labels and the
     turntable: ``clean(keep, min_faces)`` when ``keep`` is given or ``min_faces`` exceeds 1, then ``simplify(cell)`` when ``cell``
-    (world units) is given.  Clustering can pinch a thin neck into an edge, which no face carries, and so detach a crumb (and leaves
+    (world units) is given, or ``simplify_to(tolerance)`` when ``tolerance`` (world units: the sampled Hausdorff distance the
+    decimation may cost) is given instead; both together are a ValueError.  Clustering can pinch a thin neck into an edge, which no face carries, and so detach a crumb (and leaves
     the vertices of cells whose faces all collapsed): with both ``keep`` and ``cell`` the component count asked for is applied to the
     simplified mesh once more, so that keep=1 hands over one component.  Filtering, off by default too, follows the clean-up and
     leaves the faces alone: the labels are read at the unsmoothed vertices (the decoder's own level set), ``smooth_labels`` voting
     steps (``mesh.smooth_labels``) go over them before they become colours, ``smooth`` Taubin iterations with ``lam`` and ``mu``
     (``mesh.smooth``, boundary pinned) then move the vertices that are returned and rendered, and ``smooth_shading`` renders with
     ``texture.vertex_normals`` of that mesh instead of face normals."""
-    vertices, faces = _clean_geometry(G, ws, resolution, threshold, keep, min_faces, cell, **synthesis_kwargs)
+    vertices, faces = _clean_geometry(G, ws, resolution, threshold, keep, min_faces, cell, tolerance, **synthesis_kwargs)
     edge = getattr(G, 'data_type', None) == 'edge'                      # the script's edge2car branch; every other generator is seg-like
     labelled = not edge and int(getattr(G, 'semantic_channels', 0) or 0) > 1
     adj = adjacency(faces, len(vertices)) if (smooth or smooth_labels) and len(vertices) else None
