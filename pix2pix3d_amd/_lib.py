@@ -26,6 +26,14 @@ _i32x2, _i64x2 = ctypes.c_int32 * 2, ctypes.c_int64 * 2
 _C_TYPES = {'int': ctypes.c_int32, 'int16_t': ctypes.c_int16, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'uint8_t': ctypes.c_uint8, 'uint32_t': ctypes.c_uint32,
             'uint64_t': ctypes.c_uint64, 'float': ctypes.c_float, 'double': ctypes.c_double}
 _DECLARATOR = re.compile(r'(.*?)(\w+)\s*(?:\[\s*(\d*)\s*\])?', re.S)      # [type] name [[n]]
+_INTEGER = re.compile(r'(-?(?:0[xX][0-9a-fA-F]+|\d+))(?:[uU](?:ll?|LL?)?|(?:ll?|LL?)[uU]?)?')      # a C integer literal and its suffix (u, l, ll)
+
+
+def _integer(text):
+    m = _INTEGER.fullmatch(text)
+    if not m:
+        raise ValueError(f'header: {text!r} is not an integer literal')
+    return int(m.group(1), 0)
 
 
 class Header:
@@ -38,7 +46,7 @@ class Header:
         self.functions, self.structs, self.constants = {}, {}, {}
         text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
         for name, value in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(P3D_\w+)[ \t]+\(?(-?\w+)\)?[ \t]*$', text, flags=re.M):
-            self.constants[name] = int(value, 0)
+            self.constants[name] = _integer(value)
         text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{', '', text, flags=re.M)
         text = re.sub(r'\benum\s*\w*\s*\{([^}]*)\}', self._enum, text)
         text = re.sub(r'\btypedef\s+struct\s*\w*\s*\{([^}]*)\}\s*(\w+)', self._struct, text)
@@ -58,7 +66,7 @@ class Header:
         value = -1
         for item in filter(None, map(str.strip, m.group(1).split(','))):
             name, _, given = map(str.strip, item.partition('='))
-            self.constants[name] = value = int(given, 0) if given else value + 1
+            self.constants[name] = value = _integer(given) if given else value + 1
         return ''
 
     def _struct(self, m):
@@ -102,7 +110,8 @@ def read_header(path, base=None):
         return Header(f.read(), base)
 
 
-# include/p3d_hip.h is the only description of the ABI: every signature, struct and constant on the Python side is read from it, here.
+# include/p3d_hip.h is the only description of the ABI: every signature, struct and constant on the Python side is read from it, here,
+# and _load binds every function it declares (a library exports nothing that its header does not declare: tests/test_side_libraries.py).
 HEADER = read_header(os.path.join(os.path.dirname(_PKG_DIR), 'include', 'p3d_hip.h'))
 globals().update(HEADER.constants)      # _lib.P3D_OK, _lib.P3D_F32_BF16X3, _lib.P3D_FRAME_MAX_JOBS, ...: under their C names
 globals().update(HEADER.structs)        # _lib.p3d_render_desc, _lib.p3d_demod_job, _lib.p3d_fc_job, _lib.p3d_frame_job
@@ -182,7 +191,9 @@ def check(code, what):
 
 class SideLibrary:
     """A kernel library beside libp3d_hip.so (a row of ``build.SIDE_LIBRARIES``): ``header`` is its own header, read on top of the product's (which it
-    includes for p3d_stream_t and the status codes); ``lib()`` is the loaded library (device-guarded) or RuntimeError — device tensors have no fallback."""
+    includes for p3d_stream_t and the status codes), and the only description of the library's ABI — every module that calls the library reads its
+    constants from ``header`` and calls through ``lib()``, which binds all the header declares; ``lib()`` is the loaded library (device-guarded) or
+    RuntimeError — device tensors have no fallback."""
 
     def __init__(self, name):
         paths = build.side_paths(name)

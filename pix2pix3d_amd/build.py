@@ -22,8 +22,8 @@ CXXFLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-Wall', '-W
             '-fno-gpu-rdc', '-DNDEBUG']
 # The libraries beside libp3d_hip.so, name -> extra compile flags.  Everything else about one follows from its name (side_paths).
 SIDE_LIBRARIES = {'probes': ('-DP3D_BUILD_PROBES',),      # hardware probes the tests and the kernel studies use (diagnostics.py)
-                  'regions': (),                         # region tools of the edit session (regions.py)
-                  'video': (),                           # palette, dither and index frames of the GIF writer (video.py)
+                  'regions': (),                         # region tools of the edit session, agreement metrics, cross-view reprojection (regions.py, evaluate.py, reproject.py)
+                  'video': (),                           # frame encoders of the video writers: GIF, JPEG / MJPEG AVI, PNG / APNG (video.py)
                   'sketch': ()}                          # edge-map canvas of the sketch session (sketch.py)
 SidePaths = collections.namedtuple('SidePaths', 'src_dir header lib obj_dir')
 

@@ -1,5 +1,5 @@
 // Mesh-to-mesh distances for gfx950: surface samples, a bounding-volume hierarchy over the faces, the closest-triangle query
-// (csrc/p3d_mesh_distance.h states every rule; pix2pix3d_amd/geometry.py holds the definition the bytes are tested against).
+// (include/p3d_hip.h, "mesh distances", states every rule; pix2pix3d_amd/geometry.py holds the definition the bytes are tested against).
 //
 // sample_counts / sample_points: one thread per face / per point, plain gathers and stores.
 // bvh_keys: one thread per item.  bvh_leaves, bvh_level: one thread per leaf / per node of one level; a level reads only the level
@@ -7,7 +7,6 @@
 // closest: one query point per lane, a stack of node ids in LDS laid out [row][lane] (a lane's column lives in its own bank, so a
 // push or pop of the whole wave is conflict-free), boxes and corners read as float4.
 #include "p3d_common.h"
-#include "p3d_mesh_distance.h"
 #include <math.h>
 
 namespace p3d {

@@ -23,7 +23,7 @@ namespace {
 
 using namespace p3d;
 
-constexpr int kMaxLabels = 32, kMaxBins = 4096, kMaxFrames = 65536;
+constexpr int kMaxLabels = P3D_LABEL_MAX_LABELS, kMaxBins = P3D_LABEL_MAX_BINS, kMaxFrames = P3D_LABEL_MAX_FRAMES;
 
 // ---- confusion ---------------------------------------------------------------------------------------------------------------------
 constexpr int kConfWaves = 4, kItem = 16, kTileItems = kWave * kConfWaves;

@@ -278,8 +278,8 @@ extern "C" int p3d_label_warp(const uint8_t* mask, int64_t mask_row_pitch, const
     P3D_REQUIRE(dst != mask && dst != region && dst != under, "label_warp: the mask is written out of place");
     WarpArgs a;
     for (int k = 0; k < 6; ++k) {
-        const int64_t bound = (k == 2 || k == 5) ? (1ll << 40) : (1ll << 22);
-        P3D_REQUIRE(coef[k] >= -bound && coef[k] <= bound, "label_warp: coef[%d] = %lld leaves +-2^%d", k, (long long)coef[k], (k == 2 || k == 5) ? 40 : 22);
+        const int log2_bound = (k == 2 || k == 5) ? P3D_LABEL_MAX_TRANSLATION_LOG2 : P3D_LABEL_MAX_LINEAR_LOG2;
+        P3D_REQUIRE(coef[k] >= -(1ll << log2_bound) && coef[k] <= (1ll << log2_bound), "label_warp: coef[%d] = %lld leaves +-2^%d", k, (long long)coef[k], log2_bound);
         a.c[k] = coef[k];
     }
     a.mask = mask; a.mask_pitch = mask_row_pitch; a.region = region; a.region_pitch = region_row_pitch; a.under = under; a.under_pitch = under_row_pitch;

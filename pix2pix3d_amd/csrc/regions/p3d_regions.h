@@ -1,6 +1,8 @@
 /* libp3d_regions.so — region tools on the uint8 label map of an edit session (pix2pix3d_amd/regions.py).  A library of
  * its own, like libp3d_probes.so: the product ABI (include/p3d_hip.h, libp3d_hip.so) exports none of this.  It carries its own copy of the
  * library services (p3d_last_error, p3d_launch_count).  Nothing here has a counterpart in the reference, whose demo edits with the mouse only.
+ * The agreement metrics and the cross-view consistency kernels live in the same library and are declared further down: this header is the only
+ * description of the library's ABI, and pix2pix3d_amd/regions.py binds every prototype of it when the library is loaded.
  *
  * Every mask is uint8 [h][w], pixels contiguous, rows `*_row_pitch` bytes apart (>= w); 1 <= h, w <= P3D_PAINT_MAX_SIZE.  Every result is
  * written out of place and is a pure function of the inputs: the torch formulations of pix2pix3d_amd/regions.py produce the same bytes.
@@ -28,10 +30,12 @@ int p3d_label_nearest(const uint8_t* mask, int64_t mask_row_pitch, const uint32_
                       int32_t* nearest, int32_t h, int32_t w, p3d_stream_t stream);
 
 /* Inverse affine warp of a region.  `coef` (HOST memory, read during the call): six integers in 1 / 65536 pixel, the linear ones within
- * +-2^22 and the translations coef[2], coef[5] within +-2^40.  For the destination pixel (px, py):
+ * +-2^P3D_LABEL_MAX_LINEAR_LOG2 and the translations coef[2], coef[5] within +-2^P3D_LABEL_MAX_TRANSLATION_LOG2.  For the destination pixel (px, py):
  *     qx = (coef[0] px + coef[1] py + coef[2] + 32768) >> 16,   qy = (coef[3] px + coef[4] py + coef[5] + 32768) >> 16   (arithmetic shifts)
  *     dst[py][px] = q inside the image and region[qy][qx] != 0 ? mask[qy][qx] : under[py][px].
  * dst must not overlap the other three.  One launch.                                                                                     */
+#define P3D_LABEL_MAX_LINEAR_LOG2 22
+#define P3D_LABEL_MAX_TRANSLATION_LOG2 40
 int p3d_label_warp(const uint8_t* mask, int64_t mask_row_pitch, const uint8_t* region, int64_t region_row_pitch, const uint8_t* under,
                    int64_t under_row_pitch, uint8_t* dst, int64_t dst_row_pitch, const int64_t coef[6], int32_t h, int32_t w,
                    p3d_stream_t stream);
@@ -41,11 +45,14 @@ int p3d_label_warp(const uint8_t* mask, int64_t mask_row_pitch, const uint8_t* r
  * aligned, that the caller zeroed: a loop over a dataset never touches the host.
  *
  * Confusion matrix.  truth, pred and the optional valid (null: every pixel is valid): uint8 [frames][h][w], rows `*_row_pitch` bytes apart
- * and frames `*_frame_pitch` bytes apart (>= (h - 1) * row pitch + w; not looked at for one frame); 0 <= frames <= 65536,
- * 1 <= n_labels <= 32.  counts int64 [n_labels * n_labels + 1]:
+ * and frames `*_frame_pitch` bytes apart (>= (h - 1) * row pitch + w; not looked at for one frame); 0 <= frames <= P3D_LABEL_MAX_FRAMES,
+ * 1 <= n_labels <= P3D_LABEL_MAX_LABELS.  counts int64 [n_labels * n_labels + 1]:
  *     counts[t * n_labels + p] += pixels with truth == t, pred == p, both < n_labels, and valid != 0
  *     counts[n_labels * n_labels] += pixels left out for any of those reasons.
  * frames == 0 is a success that launches nothing.  One launch.                                                                          */
+#define P3D_LABEL_MAX_LABELS 32
+#define P3D_LABEL_MAX_BINS 4096
+#define P3D_LABEL_MAX_FRAMES 65536               /* of the cross-view functions below as well */
 int p3d_label_confusion(const uint8_t* truth, int64_t truth_row_pitch, int64_t truth_frame_pitch, const uint8_t* pred,
                         int64_t pred_row_pitch, int64_t pred_frame_pitch, const uint8_t* valid, int64_t valid_row_pitch,
                         int64_t valid_frame_pitch, int32_t frames, int32_t h, int32_t w, int32_t n_labels, int64_t* counts,
@@ -59,7 +66,7 @@ int p3d_label_boundary(const uint8_t* mask, int64_t mask_row_pitch, uint8_t* out
                        p3d_stream_t stream);
 
 /* Histogram of squared distances.  `sites` (HOST memory, read during the call): the 256-bit label set of p3d_label_nearest.  nearest int32
- * [h][w], contiguous, as p3d_label_nearest wrote it for the OTHER map; 1 <= bins <= 4096; hist int64 [bins + 2].  For every pixel p = (px, py)
+ * [h][w], contiguous, as p3d_label_nearest wrote it for the OTHER map; 1 <= bins <= P3D_LABEL_MAX_BINS; hist int64 [bins + 2].  For every pixel p = (px, py)
  * whose `from` label is in the set, with q = nearest[p] = qy * w + qx and d2 = (px - qx)^2 + (py - qy)^2:
  *     q >= 0 and d2 <  bins:  hist[d2] += 1
  *     q >= 0 and d2 >= bins:  hist[bins] += 1
@@ -68,11 +75,81 @@ int p3d_label_boundary(const uint8_t* mask, int64_t mask_row_pitch, uint8_t* out
 int p3d_label_distance_histogram(const uint8_t* from, int64_t from_row_pitch, const uint32_t sites[8], const int32_t* nearest, int32_t bins,
                                  int64_t* hist, int32_t h, int32_t w, p3d_stream_t stream);
 
+/* ---- cross-view consistency (csrc/regions/view_reproject.hip; pix2pix3d_amd/reproject.py) ---------------------------
+ * A forward warp between cameras: the pixels of one view, lifted to world points, are projected into another camera, the nearest point per
+ * target pixel is kept (p3d_view_splat), labels and colours are carried across and the depths compared (p3d_view_resolve), and the carried
+ * colours are compared with what the target view shows (p3d_view_difference_histogram).
+ *
+ * Sizes: a source view is h x w and a target view H x W pixels, each 1 .. P3D_PAINT_MAX_SIZE a side, and they may differ;
+ * 0 <= frames <= P3D_LABEL_MAX_FRAMES (the one frame bound of this library); frames == 0 is a success that launches nothing.  Counters ACCUMULATE
+ * as above.
+ *
+ * Cameras: float32 [frames][25], a camera label (views.camera_labels): the row-major 4 x 4 cam2world m (m03 = cameras[3], ...) followed by
+ * the row-major normalised 3 x 3 intrinsics k (k0 = cameras[16], ...).  cam2world is taken to be a rigid motion: world -> camera is the
+ * transposed rotation after the translation is taken off, no inverse is computed (the convention of mesh_project_kernel, csrc/mesh_raster.hip).
+ *
+ * Arithmetic: fp64 from the float32 operands, every operator rounded once (no contraction), in exactly this order.  The projection of a
+ * world point P under the camera (m, k) into a W x H image:
+ *     q  = P - (m03, m13, m23)
+ *     xc = m00 qx;  xc = xc + m10 qy;  xc = xc + m20 qz        yc: column 1 (m01, m11, m21)        zc: column 2 (m02, m12, m22)
+ *     a  = k0 xc;   a = a + k1 yc;     u = a / zc + k2         v = (k4 yc) / zc + k5
+ *     sx = floor(u W),  sy = floor(v H),  zkey = floor(zc 65536)
+ * The point is DROPPED when a component of P is not finite, or not zc > 0, or not zc 65536 < 2^31; a SPLAT point also when its valid byte is
+ * 0 or not -G <= sx < W + G or not -G <= sy < H + G, G = P3D_VIEW_GUARD (tested on the doubles, before any conversion to an integer).  The
+ * torch formulation of pix2pix3d_amd/reproject.py, fp64 element-wise ops in this order on CPU tensors, is the definition; the device bytes
+ * equal it.                                                                                                                              */
+#define P3D_VIEW_MAX_RADIUS 2
+#define P3D_VIEW_MAX_CHANNELS 4
+#define P3D_VIEW_GUARD 4
+#define P3D_VIEW_MAX_TOLERANCE 2147483647
+#define P3D_VIEW_EMPTY 0x7fffffffffffffffLL      /* INT64_MAX: a z-buffer cell nothing landed on */
+enum {                                           /* the status of a target pixel */
+    P3D_VIEW_HOLE = 0,
+    P3D_VIEW_CONSISTENT = 1,
+    P3D_VIEW_BEHIND = 2,                         /* the target sees a surface in front of the carried one: a disocclusion, not an error */
+    P3D_VIEW_IN_FRONT = 3,                       /* the source puts matter where the target sees through: an inconsistency */
+    P3D_VIEW_NO_TARGET = 4                       /* no target depth */
+};
+
+/* Splat.  points float32 [frames or 1][h * w][3], point i = y * w + x, frames `points_frame_pitch` FLOATS apart (0: ONE source view seen by
+ * every camera; else >= 3 h w).  valid: null or uint8 [frames or 1][h][w] with a row pitch (>= w) and a frame pitch (0: one map for every
+ * frame; else >= (h - 1) * row pitch + w) in bytes.  radius 0 .. P3D_VIEW_MAX_RADIUS.  zbuf int64 [frames][H][W], contiguous, 8-byte aligned, which the
+ * caller filled with P3D_VIEW_EMPTY (or with the keys of earlier splats).  For every point that is not dropped, key = zkey * 2^32 + i and
+ *     zbuf[f][ty][tx] = min(zbuf[f][ty][tx], key)       for every in-image (tx, ty) with |tx - sx| <= radius and |ty - sy| <= radius
+ * (a signed 64-bit atomic minimum: the smallest (zkey, i) wins whatever the order of arrival).  One launch.                              */
+int p3d_view_splat(const float* points, int64_t points_frame_pitch, const uint8_t* valid, int64_t valid_row_pitch, int64_t valid_frame_pitch,
+                   const float* cameras, int32_t frames, int32_t h, int32_t w, int32_t radius, int64_t* zbuf, int32_t H, int32_t W,
+                   p3d_stream_t stream);
+
+/* Resolve.  zbuf as p3d_view_splat left it.  src uint8 [frames or 1][h][w][channels], 1 <= channels <= P3D_VIEW_MAX_CHANNELS interleaved, rows `src_row_pitch`
+ * (>= w * channels) and frames `src_frame_pitch` bytes apart (0: one source for every frame; else >= (h - 1) * row pitch + w * channels);
+ * dst uint8 [frames][H][W][channels] with its own pitches (frame pitch not looked at for one frame), not overlapping src; fill (HOST memory,
+ * read during the call): `channels` bytes.  index: null or int32 [frames][H][W], contiguous; status uint8 [frames][H][W], contiguous;
+ * counts: null or int64 [5].  Per target pixel p = ty * W + tx, with key = zbuf[f][p], i = key & 0xffffffff, zk = key >> 32 (arithmetic):
+ *     i >= h * w (P3D_VIEW_EMPTY is such a key; src is never read outside):  dst[f][p][c] = fill[c], index = -1, status P3D_VIEW_HOLE
+ *     otherwise:  dst[f][p][c] = src[f or 0][i / w][i % w][c], index = i, and the status
+ *         target_points null:  P3D_VIEW_CONSISTENT
+ *         target_points float32 [frames][H * W][3], contiguous (the world points of the target view's own pixels), cameras as above and
+ *         0 <= tolerance <= P3D_VIEW_MAX_TOLERANCE in key units; zt = the zkey of target_points[f][p] under camera f:
+ *             P3D_VIEW_NO_TARGET   if that point is dropped (see above: the sx / sy range is not looked at here)
+ *             P3D_VIEW_CONSISTENT  if |zk - zt| <= tolerance
+ *             P3D_VIEW_BEHIND      if zk > zt
+ *             P3D_VIEW_IN_FRONT    otherwise.
+ * counts[s] += the pixels of status s.  One launch.                                                                                      */
+int p3d_view_resolve(const int64_t* zbuf, const uint8_t* src, int64_t src_row_pitch, int64_t src_frame_pitch, int32_t h, int32_t w,
+                     int32_t channels, const uint8_t fill[4], uint8_t* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch, int32_t* index,
+                     uint8_t* status, const float* target_points, const float* cameras, int64_t tolerance, int64_t* counts, int32_t frames,
+                     int32_t H, int32_t W, p3d_stream_t stream);
+
+/* Histogram of absolute differences.  a, b uint8 [frames][H][W][channels], 1 <= channels <= P3D_VIEW_MAX_CHANNELS, each with a row pitch (>= W * channels) and a
+ * frame pitch in bytes; where: null or uint8 [frames][H][W] with its pitches; 0 <= match <= 255; hist int64 [256].
+ *     hist[|a[f][p][c] - b[f][p][c]|] += 1     for every channel c of every pixel with where[f][p] == match (of every pixel: where null).
+ * One launch.                                                                                                                            */
+int p3d_view_difference_histogram(const uint8_t* a, int64_t a_row_pitch, int64_t a_frame_pitch, const uint8_t* b, int64_t b_row_pitch,
+                                  int64_t b_frame_pitch, const uint8_t* where, int64_t where_row_pitch, int64_t where_frame_pitch,
+                                  int32_t match, int32_t channels, int32_t frames, int32_t H, int32_t W, int64_t* hist, p3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
-
-/* The cross-view consistency kernels of the same library (csrc/regions/view_reproject.hip) are declared in a header of their own, which every
- * includer of this one sees: pix2pix3d_amd/regions.py binds the six prototypes above, pix2pix3d_amd/reproject.py the three of that header.  */
-#include "p3d_view_reproject.h"
 #endif

@@ -24,7 +24,8 @@ import torch
 from . import _lib, regions
 from .edit import MAX_SIZE
 
-MAX_LABELS, MAX_BINS, MAX_FRAMES = 32, 4096, 65536      # the bounds p3d_regions.h states in its comments
+_C = regions.HEADER.constants                           # p3d_regions.h states the bounds
+MAX_LABELS, MAX_BINS, MAX_FRAMES = _C['P3D_LABEL_MAX_LABELS'], _C['P3D_LABEL_MAX_BINS'], _C['P3D_LABEL_MAX_FRAMES']
 CLASS_AGNOSTIC = tuple(range(255))                      # the site set of "any boundary pixel" (255 is boundary()'s "none")
 BOUNDARY_LAUNCHES, INK_LAUNCHES = 8, 6                   # per frame, of libp3d_regions.so (per_class: 2 + 6 C)
 

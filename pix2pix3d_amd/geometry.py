@@ -14,35 +14,21 @@ lattice, an edit of the label map) moves the surface; this module says by how mu
 * ``mesh.simplify_to`` (in mesh.py) picks ``simplify``'s cell from a tolerance with ``compare``.
 
 The rules (validity of a face, the subdivision count, the order of the samples, the point-to-triangle distance operation by operation,
-the keys, the tree and why pruning is exact) are csrc/p3d_mesh_distance.h's; the CPU formulations below are the definition and the
+the keys, the tree and why pruning is exact) are include/p3d_hip.h's ("mesh distances"); the CPU formulations below are the definition and the
 kernels' bytes equal them.  Meshes are what ``mesh`` takes: vertices float32 [V, 3], faces int32 or int64 [T, 3], V and T below
 2^31 - 1.  Unlike ``mesh.clean`` and its kin nothing here rejects a bad face: a face with an index outside [0, V) or a non-finite
 corner contributes no sample and has distance +inf."""
 import math
-import os
 from typing import NamedTuple, Optional
 
 import torch
 
-from . import _lib, build, mesh, shape
+from . import _lib, mesh, shape
 
-HEADER = _lib.read_header(os.path.join(build.CSRC, 'p3d_mesh_distance.h'), base=_lib.HEADER)      # the five p3d_mesh_* prototypes of this module
-K_MAX_CAP = HEADER.constants['P3D_MESH_SAMPLE_KMAX']
-LEAF = HEADER.constants['P3D_MESH_BVH_LEAF']
-MAX_DEPTH = HEADER.constants['P3D_MESH_BVH_MAX_DEPTH']
+K_MAX_CAP = _lib.HEADER.constants['P3D_MESH_SAMPLE_KMAX']
+LEAF = _lib.HEADER.constants['P3D_MESH_BVH_LEAF']
+MAX_DEPTH = _lib.HEADER.constants['P3D_MESH_BVH_MAX_DEPTH']
 SORT_QUERIES_FROM = 1 << 14       # closest(sort_queries=None) sorts the query points by Morton key from this many points on
-_bound = False
-
-
-def _kernels():
-    """libp3d_hip.so with this module's prototypes bound onto it (once): the kernels are the product library's, their declarations
-    csrc/p3d_mesh_distance.h's."""
-    global _bound
-    handle = _lib.lib()
-    if not _bound:
-        HEADER.bind(handle._handle)
-        _bound = True
-    return handle
 
 
 # ---- operands ---------------------------------------------------------------------------------------------------------------
@@ -155,7 +141,7 @@ def _sample_points_cpu(vertices, faces32, k, offsets, n):
 
 def surface_samples(vertices, faces, spacing, k_max=64):
     """``Samples(points float32 [N, 3], face int64 [N], capped)``: every valid face f is cut into k_f^2 congruent sub-triangles and gives
-    their centroids, in a fixed order (csrc/p3d_mesh_distance.h), k_f being the smallest integer in [1, k_max] with
+    their centroids, in a fixed order (include/p3d_hip.h, "mesh distances"), k_f being the smallest integer in [1, k_max] with
     k_f * spacing >= the face's longest edge, decided on squared lengths in fp64 without a square root; a face that would need more
     gets k_max and is counted in ``capped`` (an int64 scalar on the device: no host copy until it is read).  A face with an index
     outside [0, V) or a non-finite corner gives nothing.  Device tensors run two launches with an int64 cumsum between them and copy
@@ -177,8 +163,8 @@ def surface_samples(vertices, faces, spacing, k_max=64):
         k, capped = _sample_counts_cpu(vertices, faces32, s2, k_max)
     else:
         k, capped = torch.empty([nf], dtype=torch.int32, device=dev), torch.empty([nf], dtype=torch.uint8, device=dev)
-        _lib.check(_kernels().p3d_mesh_sample_counts(_lib.ptr(vertices), nv, _lib.ptr(faces32), nf, s2, k_max, _lib.ptr(k), _lib.ptr(capped),
-                                                     _lib.stream_of(vertices)), 'mesh_sample_counts')
+        _lib.check(_lib.lib().p3d_mesh_sample_counts(_lib.ptr(vertices), nv, _lib.ptr(faces32), nf, s2, k_max, _lib.ptr(k), _lib.ptr(capped),
+                                                    _lib.stream_of(vertices)), 'mesh_sample_counts')
     offsets = torch.zeros([nf + 1], dtype=torch.int64, device=dev)
     offsets[1:] = torch.cumsum(k.long() ** 2, 0)
     n = int(offsets[-1])                                                   # the one device-to-host copy: sizes the output
@@ -189,8 +175,8 @@ def surface_samples(vertices, faces, spacing, k_max=64):
         points, face = _sample_points_cpu(vertices, faces32, k, offsets, n)
     else:
         points, face = torch.empty([n, 3], dtype=torch.float32, device=dev), torch.empty([n], dtype=torch.int32, device=dev)
-        _lib.check(_kernels().p3d_mesh_sample_points(_lib.ptr(vertices), nv, _lib.ptr(faces32), nf, _lib.ptr(k), _lib.ptr(offsets), n,
-                                                     _lib.ptr(points), _lib.ptr(face), _lib.stream_of(vertices)), 'mesh_sample_points')
+        _lib.check(_lib.lib().p3d_mesh_sample_points(_lib.ptr(vertices), nv, _lib.ptr(faces32), nf, _lib.ptr(k), _lib.ptr(offsets), n,
+                                                    _lib.ptr(points), _lib.ptr(face), _lib.stream_of(vertices)), 'mesh_sample_points')
     return Samples(points, face.long(), n_capped)
 
 
@@ -202,7 +188,7 @@ class Closest(NamedTuple):
 
 
 class Bvh(NamedTuple):
-    """``build_bvh``'s result: the hierarchy over one mesh's faces, on that mesh's device (csrc/p3d_mesh_distance.h)."""
+    """``build_bvh``'s result: the hierarchy over one mesh's faces, on that mesh's device (include/p3d_hip.h, "mesh distances")."""
     tris: torch.Tensor             # float32 [n_leaves * LEAF, 12]: the corners in sorted order, the face id in the first w
     nodes: torch.Tensor            # float32 [2 * n_pad - 1, 8]: the boxes in heap order
     box: torch.Tensor              # float32 [6]: (lo, hi) of the mesh's finite vertices (the frame of the Morton keys)
@@ -226,7 +212,7 @@ def _box_d2(p, lo, hi):
 
 
 def tri_d2(p, a, b, c):
-    """csrc/p3d_mesh_distance.h's tri_d2 on broadcastable float64 operands, each a tuple (x, y, z) of tensors: the squared distance
+    """include/p3d_hip.h's tri_d2 on broadcastable float64 operands, each a tuple (x, y, z) of tensors: the squared distance
     from p to the closed triangle a b c, one torch operation per rounding.  Total for finite inputs; never a NaN."""
     s = torch.minimum(torch.minimum(_seg_d2(p, a, b), _seg_d2(p, b, c)), _seg_d2(p, c, a))
     e1, e2 = _sub(b, a), _sub(c, a)
@@ -275,7 +261,7 @@ def _closest_cpu(points, vertices, faces32, pairs=1 << 20, face_chunk=4096):
 def build_bvh(vertices, faces):
     """The bounding-volume hierarchy ``closest`` walks for device tensors, reusable across queries of one mesh: a 63-bit Morton key per
     face, a stable sort, leaves of ``LEAF`` consecutive sorted faces and an implicit complete binary tree of fp32 boxes above them,
-    built one level per launch, bottom up (csrc/p3d_mesh_distance.h).  No host copy.  A uniform grid was considered and rejected: a
+    built one level per launch, bottom up (include/p3d_hip.h, "mesh distances").  No host copy.  A uniform grid was considered and rejected: a
     query far from the target walks O(r^3) empty cells, and two meshes that are compared need not overlap."""
     vertices, faces32 = _mesh('build_bvh', vertices, faces)
     if not vertices.is_cuda:
@@ -287,31 +273,31 @@ def build_bvh(vertices, faces):
         raise ValueError(f'build_bvh: {nf} faces need a tree deeper than {MAX_DEPTH}')
     box = _finite_box(vertices)
     key = torch.empty([nf], dtype=torch.int64, device=dev)
-    k = _kernels()
-    _lib.check(k.p3d_mesh_bvh_keys(_lib.ptr(vertices), nv, _lib.ptr(faces32), nf, _lib.ptr(box), _lib.ptr(key), _lib.stream_of(vertices)),
+    lib = _lib.lib()
+    _lib.check(lib.p3d_mesh_bvh_keys(_lib.ptr(vertices), nv, _lib.ptr(faces32), nf, _lib.ptr(box), _lib.ptr(key), _lib.stream_of(vertices)),
                'mesh_bvh_keys')
     order = torch.sort(key, stable=True).indices.to(torch.int32)
     tris = torch.empty([n_leaves * LEAF, 12], dtype=torch.float32, device=dev)
     nodes = torch.empty([2 * n_pad - 1, 8], dtype=torch.float32, device=dev)
-    _lib.check(k.p3d_mesh_bvh_build(_lib.ptr(vertices), nv, _lib.ptr(faces32), nf, _lib.ptr(order), n_pad, _lib.ptr(tris), _lib.ptr(nodes),
-                                    _lib.stream_of(vertices)), 'mesh_bvh_build')
+    _lib.check(lib.p3d_mesh_bvh_build(_lib.ptr(vertices), nv, _lib.ptr(faces32), nf, _lib.ptr(order), n_pad, _lib.ptr(tris), _lib.ptr(nodes),
+                                      _lib.stream_of(vertices)), 'mesh_bvh_build')
     return Bvh(tris, nodes, box, nf, n_pad)
 
 
 def _closest_device(points, bvh, sort_queries):
     n, dev = points.shape[0], points.device
-    k = _kernels()
+    lib = _lib.lib()
     order = None
     if n and (n >= SORT_QUERIES_FROM if sort_queries is None else sort_queries) and n < 2 ** 31 - 1:
         key = torch.empty([n], dtype=torch.int64, device=dev)              # neighbours in the wave walk the same nodes
-        _lib.check(k.p3d_mesh_bvh_keys(_lib.ptr(points), n, None, n, _lib.ptr(bvh.box), _lib.ptr(key), _lib.stream_of(points)), 'mesh_bvh_keys')
+        _lib.check(lib.p3d_mesh_bvh_keys(_lib.ptr(points), n, None, n, _lib.ptr(bvh.box), _lib.ptr(key), _lib.stream_of(points)), 'mesh_bvh_keys')
         order = torch.sort(key, stable=True).indices
         points = points[order].contiguous()
     d2 = torch.empty([n], dtype=torch.float64, device=dev)
     face = torch.empty([n], dtype=torch.int64, device=dev)
     status = torch.zeros([1], dtype=torch.int32, device=dev)
-    _lib.check(k.p3d_mesh_closest(_lib.ptr(points), n, _lib.ptr(bvh.tris), _lib.ptr(bvh.nodes), bvh.n_faces, bvh.n_pad, _lib.ptr(d2), _lib.ptr(face),
-                                  _lib.ptr(status), _lib.stream_of(points)), 'mesh_closest')
+    _lib.check(lib.p3d_mesh_closest(_lib.ptr(points), n, _lib.ptr(bvh.tris), _lib.ptr(bvh.nodes), bvh.n_faces, bvh.n_pad, _lib.ptr(d2), _lib.ptr(face),
+                                    _lib.ptr(status), _lib.stream_of(points)), 'mesh_closest')
     if n and int(status):                                                  # one device-to-host copy: the walk's own bound
         raise RuntimeError(f'mesh_closest: libp3d_hip error {_lib.P3D_ERR_LAUNCH}: a tree walk passed its iteration bound (the hierarchy is not one build_bvh made)')
     if order is None:
@@ -323,7 +309,7 @@ def _closest_device(points, bvh, sort_queries):
 
 def closest(points, vertices, faces, bvh=None, sort_queries=None):
     """``Closest(d2 float64 [N], face int64 [N])``: for every point the minimum over the mesh's valid faces of ``tri_d2`` (the squared
-    distance to the closed triangle, fp64 from the fp32 inputs, stated operation by operation in csrc/p3d_mesh_distance.h) and the
+    distance to the closed triangle, fp64 from the fp32 inputs, stated operation by operation in include/p3d_hip.h, "mesh distances") and the
     smallest face id that attains it.  A face with an index outside [0, V) or a non-finite corner has distance +inf; a non-finite
     point gets (+inf, -1), and so does every point when no face is valid.  The points' device picks the path and the mesh is moved
     there.  CPU tensors run THE DEFINITION: all N T pairs in chunks — meant for tests and small inputs, not for the 10^6 x 10^6 pairs

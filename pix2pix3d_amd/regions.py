@@ -12,7 +12,7 @@ and compositions of them in torch element-wise ops on the mask's device, none of
 ``select``, ``flood_fill``, ``grow``, ``shrink``, ``remove``, ``transform``.  Masks are uint8 [H, W] with contiguous pixels and any row pitch, 1 .. 4096 pixels a
 side (``edit._check_mask``); everything is written out of place.  ``EditSession.fill`` / ``grow`` / ``shrink`` / ``remove`` / ``move`` / ``scale`` / ``rotate`` /
 ``transform`` log these as undo steps (edit.py).  The library also carries the three counting kernels of the agreement metrics (evaluate.py calls them through
-``regions_lib()``) and the three kernels of the cross-view warp (reproject.py, which binds their own header onto the same library)."""
+``regions_lib()``) and the three kernels of the cross-view warp (reproject.py, likewise): ``HEADER`` declares all nine and ``regions_lib()`` binds them."""
 import ctypes
 import math
 
@@ -21,9 +21,10 @@ import torch
 from . import _lib
 from .edit import _check_mask
 
-MAX_LINEAR, MAX_TRANSLATION = 1 << 22, 1 << 40       # bounds of the six warp integers: c * 4095 stays far inside an int64
 _side = _lib.SideLibrary('regions')                  # libp3d_regions.so: loaded on the first call, device-guarded; launch_count() is its own counter
 REGIONS_LIB_PATH, HEADER = _side.path, _side.header
+# bounds of the six warp integers (2^22 and 2^40): c * 4095 stays far inside an int64
+MAX_LINEAR, MAX_TRANSLATION = 1 << HEADER.constants['P3D_LABEL_MAX_LINEAR_LOG2'], 1 << HEADER.constants['P3D_LABEL_MAX_TRANSLATION_LOG2']
 regions_lib, launch_count, _check = _side.lib, _side.launch_count, _side.check
 
 

@@ -3,7 +3,7 @@ needs no feature network.  The pixels of one view are lifted to world points alo
 pixel is kept, labels and colours are carried across and compared with what the generator actually rendered there.  The same forward warp is a cheap
 novel-view preview of a rendered frame (``warp``).  The reference has no code for any of this.
 
-Three primitives with fixed rules (csrc/regions/p3d_view_reproject.h, which p3d_regions.h includes, states them; the kernels live in libp3d_regions.so beside
+Three primitives with fixed rules (csrc/regions/p3d_regions.h states them; the kernels live in libp3d_regions.so beside
 the region tools and the agreement metrics and are called through ``regions.regions_lib()``), each with a torch formulation that CPU tensors take — the definition: fp64 element-wise ops in the
 header's order — and ONE device launch whose bytes equal it:
 
@@ -18,33 +18,22 @@ pairs), ``Consistency`` accumulates, ``video_consistency`` measures the frames o
 ``SketchSession.consistency`` the current frame against a second camera on the kept planes."""
 import ctypes
 import math
-import os
 
 import numpy as np
 import torch
 
-from . import _lib, build, evaluate, regions
+from . import _lib, evaluate, regions
 from .edit import MAX_SIZE
 
-EMPTY = (1 << 63) - 1                                       # P3D_VIEW_EMPTY: a z-buffer cell nothing landed on
-HOLE, CONSISTENT, BEHIND, IN_FRONT, NO_TARGET = range(5)    # the status of a target pixel (p3d_view_reproject.h)
+_C = regions.HEADER.constants                               # p3d_regions.h states every bound and code of the view functions
+EMPTY = _C['P3D_VIEW_EMPTY']                                # a z-buffer cell nothing landed on
+# the status of a target pixel
+HOLE, CONSISTENT, BEHIND, IN_FRONT, NO_TARGET = _C['P3D_VIEW_HOLE'], _C['P3D_VIEW_CONSISTENT'], _C['P3D_VIEW_BEHIND'], _C['P3D_VIEW_IN_FRONT'], _C['P3D_VIEW_NO_TARGET']
 STATUS_NAMES = ('hole', 'consistent', 'behind', 'in_front', 'no_target')
-KEY_SCALE, KEY_LIMIT, GUARD = 65536.0, 2147483648.0, 4      # zkey = floor(zc * 65536) < 2^31; a splat point may lie 4 pixels outside the image
-MAX_RADIUS, MAX_CHANNELS, MAX_FRAMES = 2, 4, evaluate.MAX_FRAMES
-MAX_TOLERANCE = (1 << 31) - 1
+KEY_SCALE, KEY_LIMIT, GUARD = 65536.0, 2147483648.0, _C['P3D_VIEW_GUARD']      # zkey = floor(zc * 65536) < 2^31; a splat point may lie GUARD pixels outside the image
+MAX_RADIUS, MAX_CHANNELS, MAX_FRAMES = _C['P3D_VIEW_MAX_RADIUS'], _C['P3D_VIEW_MAX_CHANNELS'], evaluate.MAX_FRAMES
+MAX_TOLERANCE = _C['P3D_VIEW_MAX_TOLERANCE']
 COUNT_LAUNCHES = {True: 5, False: 3}                         # consistency_counts: with labels / without
-HEADER = _lib.read_header(os.path.join(build.side_paths('regions').src_dir, 'p3d_view_reproject.h'), base=regions.HEADER)      # the three p3d_view_* prototypes
-_bound = []
-
-
-def _views_lib():
-    """``regions.regions_lib()`` with the three ``p3d_view_*`` signatures of ``HEADER`` bound onto it (once): the kernels live in the region tools' library, their
-    prototypes in a header of their own that ``p3d_regions.h`` includes."""
-    lib = regions.regions_lib()
-    if not _bound:
-        HEADER.bind(regions._side._raw)
-        _bound.append(True)
-    return lib
 
 
 # ---- argument checks ---------------------------------------------------------------------------------------------------------------
@@ -170,7 +159,7 @@ def _splat_torch(p, cameras, valid, radius, zbuf):
 
 def splat(points, cameras, size=None, radius=0, valid=None, out=None):
     """int64 [F, H, W]: the z-buffer of the world points ``points`` (float32 [F, h, w, 3]; [1, h, w, 3] or [h, w, 3]: ONE source view seen by all F cameras)
-    under ``cameras`` [F, 25] in views of ``size`` = (H, W) (default: the source's).  Every point i = y * w + x that is not dropped (p3d_view_reproject.h: ``valid``
+    under ``cameras`` [F, 25] in views of ``size`` = (H, W) (default: the source's).  Every point i = y * w + x that is not dropped (p3d_regions.h: ``valid``
     byte 0, non-finite, not in front of the camera, zc >= 2^15, more than 4 pixels outside the image) puts ``key = floor(zc * 65536) * 2^32 + i`` on the pixels
     within ``radius`` (0, 1, 2: a square of 1, 9, 25 pixels) of its own, where the smallest key stays: the nearest point, the smallest index among equals.  ``out``: a
     buffer to splat into (default: a fresh one filled with ``EMPTY``); several sources may share one.  ``valid``: uint8 / bool [F, h, w] (or [h, w], [1, h, w]: one map
@@ -195,8 +184,8 @@ def splat(points, cameras, size=None, radius=0, valid=None, out=None):
     if not out.is_cuda:
         return _splat_torch(p.reshape(p.shape[0], h * w, 3), cameras, None if v is None else v[..., 0], radius, out)
     with _lib.kernel_timer('view_splat', out):
-        code = _views_lib().p3d_view_splat(_lib.ptr(p), pitch, _lib.ptr(v), v_row or 0, v_frame or 0, _lib.ptr(cameras), f, h, w, radius,
-                                           _lib.ptr(out), big_h, big_w, _lib.stream_of(out))
+        code = regions.regions_lib().p3d_view_splat(_lib.ptr(p), pitch, _lib.ptr(v), v_row or 0, v_frame or 0, _lib.ptr(cameras), f, h, w, radius,
+                                                    _lib.ptr(out), big_h, big_w, _lib.stream_of(out))
     regions._check(code, 'view_splat')
     return out
 
@@ -279,10 +268,10 @@ def resolve(zbuf, source, fill=0, target_points=None, cameras=None, tolerance=No
         status = torch.empty([f, h, w], dtype=torch.uint8, device=dev)
         index = torch.empty([f, h, w], dtype=torch.int32, device=dev) if return_index else None
         with _lib.kernel_timer('view_resolve', status):
-            code = _views_lib().p3d_view_resolve(_lib.ptr(zbuf), _lib.ptr(src), s_row, s_frame, src.shape[1], src.shape[2], c, (ctypes.c_uint8 * 4)(*fill),
-                                                 _lib.ptr(warped), d_row, d_frame, _lib.ptr(index), _lib.ptr(status), _lib.ptr(target),
-                                                 _lib.ptr(cameras) if target is not None else None, tolerance or 0, _lib.ptr(counts), f, h, w,
-                                                 _lib.stream_of(status))
+            code = regions.regions_lib().p3d_view_resolve(_lib.ptr(zbuf), _lib.ptr(src), s_row, s_frame, src.shape[1], src.shape[2], c, (ctypes.c_uint8 * 4)(*fill),
+                                                          _lib.ptr(warped), d_row, d_frame, _lib.ptr(index), _lib.ptr(status), _lib.ptr(target),
+                                                          _lib.ptr(cameras) if target is not None else None, tolerance or 0, _lib.ptr(counts), f, h, w,
+                                                          _lib.stream_of(status))
         regions._check(code, 'view_resolve')
     warped = out if out is not None else (warped if had else warped[..., 0])      # ([h, w] is one frame of one channel: [F, H, W] comes back)
     return (warped, status, index) if return_index else (warped, status)
@@ -318,8 +307,8 @@ def difference_histogram(a, b, where=None, match=1, out=None):
         out += _difference_histogram_torch(va, vb, vw, match)
         return out
     with _lib.kernel_timer('view_difference_histogram', out):
-        code = _views_lib().p3d_view_difference_histogram(_lib.ptr(va), a_row, a_frame, _lib.ptr(vb), b_row, b_frame, _lib.ptr(vw), w_row, w_frame,
-                                                          match, c, f, h, w, _lib.ptr(out), _lib.stream_of(out))
+        code = regions.regions_lib().p3d_view_difference_histogram(_lib.ptr(va), a_row, a_frame, _lib.ptr(vb), b_row, b_frame, _lib.ptr(vw), w_row, w_frame,
+                                                                   match, c, f, h, w, _lib.ptr(out), _lib.stream_of(out))
     regions._check(code, 'view_difference_histogram')
     return out
 

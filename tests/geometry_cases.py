@@ -1,4 +1,4 @@
-"""Shared by tests/test_geometry_host.py and tests/test_geometry_gpu.py: plain-Python restatements of csrc/p3d_mesh_distance.h (one Python
+"""Shared by tests/test_geometry_host.py and tests/test_geometry_gpu.py: plain-Python restatements of the "mesh distances" section of include/p3d_hip.h (one Python
 float operation per rounding: Python floats are IEEE doubles), the exact distance in fractions.Fraction, and the meshes and point sets
 of the cases.  Nothing here calls pix2pix3d_amd.geometry's own formulations."""
 import functools
@@ -13,7 +13,7 @@ from test_mesh_cleanup_host import spheres_field
 INF = math.inf
 
 
-# ---- csrc/p3d_mesh_distance.h in Python floats ------------------------------------------------------------------------------------
+# ---- include/p3d_hip.h ("mesh distances") in Python floats ------------------------------------------------------------------------------------
 def dot(u, v):
     s = u[0] * v[0]
     s = s + u[1] * v[1]

@@ -241,11 +241,15 @@ def test_every_value_error():
 
 
 # ---- 3. the binding ------------------------------------------------------------------------------------------------------------------
-def test_the_three_new_names_follow_the_old_three_and_the_header_declares_functions_only():
+def test_the_headers_nine_names_are_in_order_and_its_constants_are_pinned():
     from pix2pix3d_amd import evaluate, regions
     names = list(regions.HEADER.functions)
-    assert names == ['p3d_label_components', 'p3d_label_nearest', 'p3d_label_warp', 'p3d_label_confusion', 'p3d_label_boundary', 'p3d_label_distance_histogram']
-    assert not regions.HEADER.constants and not regions.HEADER.structs
+    assert names == ['p3d_label_components', 'p3d_label_nearest', 'p3d_label_warp', 'p3d_label_confusion', 'p3d_label_boundary', 'p3d_label_distance_histogram',
+                     'p3d_view_splat', 'p3d_view_resolve', 'p3d_view_difference_histogram']
+    assert regions.HEADER.constants == {'P3D_LABEL_MAX_LINEAR_LOG2': 22, 'P3D_LABEL_MAX_TRANSLATION_LOG2': 40, 'P3D_LABEL_MAX_LABELS': 32, 'P3D_LABEL_MAX_BINS': 4096, 'P3D_LABEL_MAX_FRAMES': 65536, 'P3D_VIEW_MAX_RADIUS': 2,
+                                     'P3D_VIEW_MAX_CHANNELS': 4, 'P3D_VIEW_GUARD': 4, 'P3D_VIEW_MAX_TOLERANCE': (1 << 31) - 1, 'P3D_VIEW_EMPTY': (1 << 63) - 1, 'P3D_VIEW_HOLE': 0,
+                                     'P3D_VIEW_CONSISTENT': 1, 'P3D_VIEW_BEHIND': 2, 'P3D_VIEW_IN_FRONT': 3, 'P3D_VIEW_NO_TARGET': 4}
+    assert not regions.HEADER.structs
     assert (evaluate.MAX_LABELS, evaluate.MAX_BINS, evaluate.MAX_FRAMES) == (32, 4096, 65536)
     assert len(regions.HEADER.functions['p3d_label_confusion'][1]) == 15 and len(regions.HEADER.functions['p3d_label_distance_histogram'][1]) == 9
     L = regions.regions_lib()

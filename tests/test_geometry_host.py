@@ -297,16 +297,15 @@ def test_distance_colors_table_and_buckets():
 
 # ---- the C ABI ----------------------------------------------------------------------------------------------------------------------
 def test_entry_points_check_their_arguments_before_any_launch():
-    lib = geometry._kernels()._handle
-    assert sorted(geometry.HEADER.functions) == ['p3d_mesh_bvh_build', 'p3d_mesh_bvh_keys', 'p3d_mesh_closest', 'p3d_mesh_sample_counts',
-                                                 'p3d_mesh_sample_points']
-    assert not set(geometry.HEADER.functions) & set(_lib.HEADER.functions)
-    assert (geometry.K_MAX_CAP, geometry.LEAF, geometry.MAX_DEPTH, geometry.HEADER.constants['P3D_MESH_BVH_MARGIN_LOG2']) == (1024, 4, 31, 20)
+    lib = _lib.lib()
+    names = ['p3d_mesh_bvh_build', 'p3d_mesh_bvh_keys', 'p3d_mesh_closest', 'p3d_mesh_sample_counts', 'p3d_mesh_sample_points']
+    assert set(names) <= set(_lib.HEADER.functions)      # declared by the product header itself: bound when the library is loaded
+    assert (geometry.K_MAX_CAP, geometry.LEAF, geometry.MAX_DEPTH, _lib.HEADER.constants['P3D_MESH_BVH_MARGIN_LOG2']) == (1024, 4, 31, 20)
     n0 = _lib.launch_count()
-    for name, (restype, argtypes) in geometry.HEADER.functions.items():
-        fn = getattr(lib, name)
-        assert fn.argtypes == argtypes and ctypes.c_void_p in argtypes
-        code = fn(*[None if t is ctypes.c_void_p else t(1) for t in argtypes])      # one face, one point, spacing^2 = 1: only the pointers are wrong
+    for name in names:
+        restype, argtypes = _lib.HEADER.functions[name]
+        assert getattr(lib._handle, name).argtypes == argtypes and ctypes.c_void_p in argtypes
+        code = getattr(lib, name)(*[None if t is ctypes.c_void_p else t(1) for t in argtypes])      # one face, one point, spacing^2 = 1: only the pointers are wrong
         assert code == _lib.P3D_ERR_ARGUMENT, (name, code)
         assert b'null pointer' in lib.p3d_last_error(), (name, lib.p3d_last_error())
     spare = (ctypes.c_float * 64)()

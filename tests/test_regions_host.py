@@ -305,12 +305,19 @@ def test_kept_masks_are_bounded_and_older_entries_replay(loaded):
 
 
 # ---- 6. the binding -------------------------------------------------------------------------------------------------------------
-def test_regions_calls_its_three_entry_points_and_its_header_declares_functions_only():
-    """Declared, exported by its own library alone, bound: the regions row of tests/test_side_libraries.py."""
+def test_regions_calls_its_three_entry_points_and_its_header_pins_names_and_constants():
+    """Declared, exported by its own library alone, bound: the regions row of tests/test_side_libraries.py.  The header is the library's whole ABI: the
+    region tools, the agreement metrics and the cross-view functions, with every bound and code they share with Python."""
     from pix2pix3d_amd import regions
     called = set(re.findall(r'\bregions_lib\(\)\.(p3d_\w+)', (ROOT / 'pix2pix3d_amd' / 'regions.py').read_text()))
     assert {'p3d_label_components', 'p3d_label_nearest', 'p3d_label_warp'} <= called
-    assert not regions.HEADER.constants and not regions.HEADER.structs          # the header declares functions only
+    assert list(regions.HEADER.functions) == ['p3d_label_components', 'p3d_label_nearest', 'p3d_label_warp', 'p3d_label_confusion', 'p3d_label_boundary', 'p3d_label_distance_histogram',
+                                             'p3d_view_splat', 'p3d_view_resolve', 'p3d_view_difference_histogram']
+    assert regions.HEADER.constants == {'P3D_LABEL_MAX_LINEAR_LOG2': 22, 'P3D_LABEL_MAX_TRANSLATION_LOG2': 40, 'P3D_LABEL_MAX_LABELS': 32, 'P3D_LABEL_MAX_BINS': 4096, 'P3D_LABEL_MAX_FRAMES': 65536, 'P3D_VIEW_MAX_RADIUS': 2,
+                                     'P3D_VIEW_MAX_CHANNELS': 4, 'P3D_VIEW_GUARD': 4, 'P3D_VIEW_MAX_TOLERANCE': (1 << 31) - 1, 'P3D_VIEW_EMPTY': (1 << 63) - 1, 'P3D_VIEW_HOLE': 0,
+                                     'P3D_VIEW_CONSISTENT': 1, 'P3D_VIEW_BEHIND': 2, 'P3D_VIEW_IN_FRONT': 3, 'P3D_VIEW_NO_TARGET': 4}
+    assert not regions.HEADER.structs
+    assert (regions.MAX_LINEAR, regions.MAX_TRANSLATION) == (1 << 22, 1 << 40)
 
 
 def test_argument_errors_come_back_as_codes_without_a_gpu():

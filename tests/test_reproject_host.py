@@ -267,8 +267,7 @@ def test_argument_errors_of_the_python_surface(planted):
 
 def test_argument_errors_of_the_library_come_before_any_launch():
     from pix2pix3d_amd import _lib, regions
-    from pix2pix3d_amd import reproject
-    lib = reproject._views_lib()
+    lib = regions.regions_lib()
     n0 = regions.launch_count()
     p = ctypes.c_void_p(4096)                                                       # never read: every call below fails its argument check (or has no frames)
     fill = (ctypes.c_uint8 * 4)(1, 2, 3, 4)
@@ -295,19 +294,28 @@ def test_argument_errors_of_the_library_come_before_any_launch():
 
 
 def test_the_three_entry_points_live_in_the_regions_library_and_nowhere_else():
-    """Declared in a header of their own that p3d_regions.h includes, exported by libp3d_regions.so, bound onto ``regions.regions_lib()``, absent from the product ABI;
-    the header declares functions only (the status codes and EMPTY are comments there and constants here)."""
+    """Declared by p3d_regions.h after the six it had, exported by libp3d_regions.so, bound by ``regions.regions_lib()`` itself (no import of reproject needed),
+    absent from the product ABI; the status codes and EMPTY are the header's constants and reproject's names follow them."""
+    import json
     import pathlib
+    import subprocess
+    import sys
     from pix2pix3d_amd import _lib, build, regions, reproject
-    assert list(reproject.HEADER.functions) == ['p3d_view_splat', 'p3d_view_resolve', 'p3d_view_difference_histogram']
-    assert not reproject.HEADER.constants and not reproject.HEADER.structs and not set(reproject.HEADER.functions) & (set(regions.HEADER.functions) | set(_lib.HEADER.functions))
-    assert [len(reproject.HEADER.functions[n][1]) for n in reproject.HEADER.functions] == [14, 21, 16]
+    names = ['p3d_view_splat', 'p3d_view_resolve', 'p3d_view_difference_histogram']
+    assert list(regions.HEADER.functions)[-3:] == names and len(regions.HEADER.functions) == 9
+    assert not set(names) & set(_lib.HEADER.functions)
+    assert [len(regions.HEADER.functions[n][1]) for n in names] == [14, 21, 16]
     paths = build.side_paths('regions')
-    assert '#include "p3d_view_reproject.h"' in pathlib.Path(paths.header).read_text() and (pathlib.Path(paths.src_dir) / 'view_reproject.hip').is_file()
-    lib = reproject._views_lib()
-    assert lib is regions.regions_lib()
+    assert [h.name for h in pathlib.Path(paths.src_dir).glob('*.h')] == ['p3d_regions.h'] and (pathlib.Path(paths.src_dir) / 'view_reproject.hip').is_file()
+    assert '#include "p3d_' not in pathlib.Path(paths.header).read_text()
     side, product = ctypes.CDLL(paths.lib), ctypes.CDLL(_lib.LIB_PATH)
-    for name in reproject.HEADER.functions:
-        assert hasattr(side, name) and not hasattr(product, name) and getattr(regions._side._raw, name).argtypes is not None, name
+    for name in names:
+        assert hasattr(side, name) and not hasattr(product, name), name
+    child = ('import json; from pix2pix3d_amd import regions; raw = regions.regions_lib()._handle; '
+             'print(json.dumps([n for n in regions.HEADER.functions if getattr(raw, n).argtypes is None])); import sys; assert "pix2pix3d_amd.reproject" not in sys.modules')
+    r = subprocess.run([sys.executable, '-c', child], capture_output=True, text=True, cwd=pathlib.Path(_lib.LIB_PATH).parent.parent)
+    assert r.returncode == 0, r.stderr
+    assert json.loads(r.stdout.strip().splitlines()[-1]) == []
     assert (reproject.EMPTY, reproject.HOLE, reproject.CONSISTENT, reproject.BEHIND, reproject.IN_FRONT, reproject.NO_TARGET) == ((1 << 63) - 1, 0, 1, 2, 3, 4)
+    assert (reproject.GUARD, reproject.MAX_RADIUS, reproject.MAX_CHANNELS, reproject.MAX_FRAMES, reproject.MAX_TOLERANCE) == (4, 2, 4, 65536, (1 << 31) - 1)
     assert 'p3d_view' not in pathlib.Path(_lib.LIB_PATH).with_name('..').resolve().joinpath('include', 'p3d_hip.h').read_text()

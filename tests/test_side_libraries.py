@@ -1,6 +1,7 @@
-"""The kernel libraries beside libp3d_hip.so (``build.SIDE_LIBRARIES``), one row each: what the Python module calls is declared in the library's own
-header, the headers are disjoint, every library exports its own entry points and the product library none of them, ``SideLibrary.lib()`` binds every
-signature, and the library's own launch counter is wired.  No GPU is needed — the argument checks run before any device call — but the built libraries are."""
+"""The kernel libraries beside libp3d_hip.so (``build.SIDE_LIBRARIES``), one row each: what the Python modules call is declared in the library's own
+header, that header declares exactly what the library's sources define (the product's likewise), the headers are disjoint, every library exports its own
+entry points and the product library none of them, ``SideLibrary.lib()`` binds every signature, and the library's own launch counter is wired.  No GPU is
+needed — the argument checks run before any device call — but the built libraries are."""
 import ctypes
 import importlib
 import os
@@ -13,13 +14,15 @@ from pix2pix3d_amd import build
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 SERVICES = {'p3d_last_error', 'p3d_launch_count'}      # every side library links its own copy; their signatures come from the product header
-BOUND_BY = {'probes': ('diagnostics', 'probes'), 'regions': ('regions', 'regions_lib'), 'video': ('video', 'video_lib'),
-            'sketch': ('sketch', 'sketch_lib')}        # library -> (module of pix2pix3d_amd, the accessor its calls go through)
+# library -> (every module of pix2pix3d_amd that calls it, the one that holds the SideLibrary first; the accessor their calls go through).  A feature
+# that adds entry points to a library adds its module here and its prototypes to the library's one header: never a second header or a binding of its own.
+BOUND_BY = {'probes': (('diagnostics',), 'probes'), 'regions': (('regions', 'evaluate', 'reproject'), 'regions_lib'), 'video': (('video',), 'video_lib'),
+            'sketch': (('sketch',), 'sketch_lib')}
 NAMES = sorted(build.SIDE_LIBRARIES)
 
 
-def _module(name):
-    return importlib.import_module('pix2pix3d_amd.' + BOUND_BY[name][0])
+def _module(name, k=0):
+    return importlib.import_module('pix2pix3d_amd.' + BOUND_BY[name][0][k])
 
 
 def _exported(path, names):
@@ -31,9 +34,51 @@ def _exported(path, names):
 def test_calls_are_declared(name):
     module, accessor = _module(name), BOUND_BY[name][1]
     assert getattr(module, accessor) == module._side.lib and module.HEADER is module._side.header
-    called = set(re.findall(r'\b%s\(\)\.(p3d_\w+)' % accessor, pathlib.Path(module.__file__).read_text()))
     declared = set(module.HEADER.functions)
-    assert called - SERVICES and called - SERVICES <= declared, (name, sorted(called - SERVICES - declared))
+    for k in range(len(BOUND_BY[name][0])):
+        caller = _module(name, k)
+        called = set(re.findall(r'\b%s\(\)\.(p3d_\w+)' % accessor, pathlib.Path(caller.__file__).read_text()))
+        assert called - SERVICES and called - SERVICES <= declared, (name, caller.__name__, sorted(called - SERVICES - declared))
+
+
+def _defined(sources):
+    """The ``extern "C"`` p3d_* functions that .hip files define: ``extern "C" <type> p3d_x(`` and the definitions inside an ``extern "C" { }`` block
+    (taken to run to the last closing brace at the start of a line)."""
+    names = set()
+    for path in sources:
+        text = re.sub(r'/\*.*?\*/|//[^\n]*', '', pathlib.Path(path).read_text(), flags=re.S)
+        names |= set(re.findall(r'extern\s+"C"\s+[\w\s*]+?\b(p3d_\w+)\s*\(', text))
+        for block in re.findall(r'extern\s+"C"\s*\{(.*)^\}', text, flags=re.S | re.M):
+            names |= set(re.findall(r'^[\w \t*]+?\b(p3d_\w+)\s*\([^;{]*\)\s*\{', block, flags=re.M))
+    return names
+
+
+def _declared(header):
+    """As tests/test_abi.py scans include/*.h."""
+    return set(re.findall(r'\b(p3d_[a-z0-9_]+)\s*\(', re.sub(r'/\*.*?\*/', '', pathlib.Path(header).read_text(), flags=re.S)))
+
+
+@pytest.mark.parametrize('name', ['product'] + NAMES)
+def test_the_header_declares_exactly_what_the_sources_define(name):
+    """One header per library and nothing beside it: a function defined but not declared is bound by nobody (or by a second-hand binding), one declared but
+    not defined fails the load.  A scan of the sources: no GPU, no built library.  A side library also links the services of p3d_common.hip, which the
+    product header declares."""
+    from pix2pix3d_amd import _lib
+    services = _defined([os.path.join(build.CSRC, 'p3d_common.hip')])
+    assert SERVICES <= services <= set(_lib.HEADER.functions)
+    if name == 'product':
+        defined, header = _defined(build.sources()), ROOT / 'include' / 'p3d_hip.h'
+        assert len(defined) >= 100 and services <= defined
+    else:
+        paths = build.side_paths(name)
+        defined, header = _defined(pathlib.Path(paths.src_dir).glob('*.hip')), paths.header
+        assert defined and not defined & services
+    assert defined == _declared(header), (sorted(defined - _declared(header)), sorted(_declared(header) - defined))
+
+
+def test_only_the_five_headers_have_prototypes():
+    own = [ROOT / 'include' / 'p3d_hip.h'] + [pathlib.Path(build.side_paths(name).header) for name in NAMES]
+    assert [h for h in map(pathlib.Path, build.headers()) if h not in own and _declared(h)] == [] and all(_declared(h) for h in own)
 
 
 @pytest.mark.parametrize('name', NAMES)

@@ -59,8 +59,8 @@ def main():
     key = torch.empty([len(f32)], dtype=torch.int64, device=dev)
 
     def keys_and_sort():
-        _lib.check(geometry._kernels().p3d_mesh_bvh_keys(_lib.ptr(v32), len(v32), _lib.ptr(f32), len(f32), _lib.ptr(box), _lib.ptr(key),
-                                                         _lib.stream_of(v32)), 'mesh_bvh_keys')
+        _lib.check(_lib.lib().p3d_mesh_bvh_keys(_lib.ptr(v32), len(v32), _lib.ptr(f32), len(f32), _lib.ptr(box), _lib.ptr(key),
+                                                _lib.stream_of(v32)), 'mesh_bvh_keys')
         return torch.sort(key, stable=True).indices
     _, stage['keys_and_sort'] = timed(keys_and_sort)
     bvh, stage['build_bvh'] = timed(lambda: geometry.build_bvh(v, f))      # keys, sort and the level launches
