@@ -1,5 +1,6 @@
 /* libp3d_video.so — palette, dither and index frames for the GIF writer (pix2pix3d_amd/video.py) and, at the end, baseline JPEG
- * frames for the Motion-JPEG writer (section 2.1u) and the zlib streams of PNG and APNG files (section 2.1v).  A library of its
+ * frames for the Motion-JPEG writer (section 2.1u), the zlib streams of PNG and APNG files (section 2.1v) and what a setting of those writers
+ * costs in the picture: error sums, SSIM and a decoder's view of the JPEG coefficients (section 2.1x).  A library of its
  * own, like libp3d_regions.so: the product ABI (include/p3d_hip.h, libp3d_hip.so) exports none of this.  It carries its own copy of the
  * library services (p3d_last_error, p3d_launch_count).  Nothing here has a counterpart in the reference, which writes videos with imageio.
  *
@@ -145,6 +146,58 @@ int p3d_video_png_count(const uint8_t* filtered, int32_t n_frames, int32_t h, in
 int p3d_video_png_emit(const uint8_t* filtered, int32_t n_frames, int32_t h, int32_t row_bytes, int32_t segment_rows, const uint32_t* tables,
                        const uint32_t* headers, const int32_t* header_bits, const uint32_t* adler, const int64_t* offsets, uint8_t* data,
                        int64_t data_bytes, p3d_stream_t stream);
+
+/* ---- frame quality: error sums, SSIM and what a decoder shows for JPEG coefficients (video_quality.hip, video_jpeg_decode.hip) ----
+ * Two clips a and b, uint8 [n_frames][h][w][bpp], bpp = 1 .. 4, each with its own frame_pitch / row_pitch (>= w bpp) as above, are compared where they are.
+ * n_frames, h, w >= 0 and n_frames h w bpp < 2^31.  The results ACCUMULATE into int64 counters that the caller zeroed: calls add up, in any order (integer
+ * sums), and nothing waits for the host.  Integer arithmetic and a pure function of the inputs but for the three fp64 operations stated below: the
+ * formulations of pix2pix3d_amd/quality.py produce the same bytes.
+ *
+ * ERROR SUMS.  With d = a - b per sample, sums int64 [n_frames][bpp][4] gains, per frame and channel: sum |d|, sum d^2, max |d| (a 64-bit atomic max) and
+ * the number of samples with d != 0.  A clip with n_frames h w = 0 launches nothing.  ONE launch: registers, a wave reduction, LDS, then one atomic per
+ * slot per work-group.                                                                                                                                     */
+int p3d_video_error_sums(const uint8_t* a, int64_t a_frame_pitch, int64_t a_row_pitch, const uint8_t* b, int64_t b_frame_pitch, int64_t b_row_pitch,
+                         int32_t n_frames, int32_t h, int32_t w, int32_t bpp, int64_t* sums, p3d_stream_t stream);
+
+/* SSIM (Wang, Bovik, Sheikh, Simoncelli 2004): 11 x 11 Gaussian window of sigma 1.5, K1 = 0.01, K2 = 0.03, L = 255, the (h - 10) x (w - 10) windows that
+ * lie wholly inside the picture, every channel on its own.  The 1-D window is g[i] = round(1024 exp(-(i - 5)^2 / 4.5) / sum_j exp(-(j - 5)^2 / 4.5)), which
+ * sums to 1024; the 2-D weights are w[i][j] = g[i] g[j], their sum S = 2^20.  With x the samples of a and y those of b in a window, exact integers:
+ *     A = sum w x, B = sum w y (< 2^28);   Pxx = sum w x^2, Pyy = sum w y^2, Pxy = sum w x y (< 2^36)
+ * (the horizontal pass fits int32, the vertical one is int64 for the three products), and with C1 = round((0.01 255)^2 2^40), C2 = round((0.03 255)^2 2^40):
+ *     n1 = 2 A B + C1              n2 = 2 (S Pxy - A B) + C2
+ *     d1 = A^2 + B^2 + C1          d2 = S (Pxx + Pyy) - A^2 - B^2 + C2
+ * four int64 below 2^59 in magnitude; d1 >= C1 > 0 and, by Cauchy-Schwarz (S Pxx >= A^2), d2 >= C2 > 0.  Each is converted to fp64 (round to nearest even),
+ * q = (n1 n2) / (d1 d2) is three fp64 operations in that order, none contracted, and the window contributes the int64 round_half_even(q 2^32) (llrint).
+ * sums int64 [n_frames][bpp][2] gains the sum of the contributions and the number of windows; map, if non-null, float32 [n_frames][h - 10][w - 10][bpp],
+ * contiguous, receives (float) q.  h < 11 or w < 11 or n_frames = 0: no window, no launch.  ONE launch: a work-group per tile of
+ * P3D_VIDEO_SSIM_TILE_W x P3D_VIDEO_SSIM_TILE_H windows of one frame.                                                                                     */
+#define P3D_VIDEO_SSIM_WINDOW 1, 8, 37, 112, 218, 272, 218, 112, 37, 8, 1
+#define P3D_VIDEO_SSIM_TAPS 11
+#define P3D_VIDEO_SSIM_C1 7149574359613LL
+#define P3D_VIDEO_SSIM_C2 64346169236521LL
+#define P3D_VIDEO_SSIM_SHIFT 32         /* a window contributes round(q 2^32) */
+#define P3D_VIDEO_SSIM_TILE_W 32
+#define P3D_VIDEO_SSIM_TILE_H 16
+int p3d_video_ssim(const uint8_t* a, int64_t a_frame_pitch, int64_t a_row_pitch, const uint8_t* b, int64_t b_frame_pitch, int64_t b_row_pitch,
+                   int32_t n_frames, int32_t h, int32_t w, int32_t bpp, int64_t* sums, float* map, p3d_stream_t stream);
+
+/* What a decoder shows for coefficients as p3d_video_jpeg_blocks lays them out (no entropy decoding: a quality setting is judged where the frames are).
+ * DEQUANTISE: coefficient x table entry of its zigzag position (a 0 entry counts as 1), clamped to -32768 .. 32767.  INVERSE TRANSFORM with the table T of
+ * the forward pass, on the block c[v][u] in natural order: the column pass m[y][u] = (sum_v T[v][y] c[v][u] + 512) >> 10, then the row pass
+ * s[y][x] = (sum_u T[u][x] m[y][u] + 32768) >> 16 — 26 bits in all: T is 8192 x orthonormal, twice, and the quantiser's division by 8 Q has already taken
+ * the forward pass's factor 8 out, so c is the orthonormal DCT itself.  sum_v |T[v][y]| = 21641, so the first sum stays below 21641 x 32768 + 512 < 2^30
+ * in int32 and |m| <= 692513; the second, up to 21641 x 692513 > 2^31, is an int64 sum.  The sample is clamp(s + 128, 0, 255).  PLANES: Y of (mcus_y mcu) x (mcus_x mcu) samples, Cb and Cr the same (4:4:4) or half of it each way (4:2:0); scratch
+ * holds them, uint8, frame after frame, Y then Cb then Cr: scratch_bytes >= n_frames x (the Y plane + the two chroma planes).  UPSAMPLING at 4:2:0, on the
+ * chroma plane cropped to ceil(h / 2) x ceil(w / 2) with its edges replicated — the triangle filter: for the output row y, v[cx] = 3 near + far, near the
+ * chroma row y >> 1 and far the row above it for even y, below it for odd y; for the output column x, with cx = x >> 1, (3 v[cx] + v[cx - 1] + 8) >> 4 for
+ * even x and (3 v[cx] + v[cx + 1] + 7) >> 4 for odd x.  COLOUR, full-range JFIF in 16-bit fixed point (>> arithmetic), each clamped to 0 .. 255:
+ *     R = Y + ((91881 (Cr - 128) + 32768) >> 16)          B = Y + ((116130 (Cb - 128) + 32768) >> 16)
+ *     G = Y + ((-22554 (Cb - 128) - 46802 (Cr - 128) + 32768) >> 16)
+ * frames uint8 [n_frames][h][w][3] with frame_pitch / row_pitch (>= 3 w) receives the h x w crop; bytes between rows stay untouched.  n_frames h w = 0
+ * launches nothing.  TWO launches: a wave per block into the planes, then a thread per pixel.                                                             */
+int p3d_video_jpeg_decode(const int16_t* coefficients, int32_t n_frames, int32_t h, int32_t w, int32_t subsampling, const uint8_t* luma_q,
+                          const uint8_t* chroma_q, uint8_t* scratch, int64_t scratch_bytes, uint8_t* frames, int64_t frame_pitch, int64_t row_pitch,
+                          p3d_stream_t stream);
 
 #ifdef __cplusplus
 }

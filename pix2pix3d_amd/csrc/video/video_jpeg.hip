@@ -10,6 +10,10 @@
 //                        lanes).  The wave then reads the string 64 bytes at a time: a ballot of the 0xFF bytes gives every byte its place after
 //                        stuffing.  The first launch only counts the bytes, the second writes them: nothing of an interval's worst case (9948
 //                        bytes before stuffing) ever sits in device memory, and no interval shares a bit or a byte with another.
+// p3d_video_jpeg_decode  the way back without entropy decoding: a wave per block again — lane z dequantises the coefficient of
+//                        zigzag position z into its natural place in LDS, the column pass and the row pass of the inverse transform, and the block
+//                        leaves as 64 bytes of its component's plane in the caller's scratch; then a thread per pixel reads Y, filters the four chroma
+//                        samples around it (4:2:0) and stores three bytes.
 #include "../p3d_common.h"
 #include "p3d_video.h"
 
@@ -256,6 +260,89 @@ int layout(const char* what, int32_t n_frames, int32_t h, int32_t w, int32_t sub
     return P3D_OK;
 }
 
+// ---- the way back: what a decoder shows for the coefficients (p3d_video_jpeg_decode) -----------------------------------------------------------------
+struct DecodeArgs {
+    const int16_t* coefficients;
+    int H, W, subsampling;
+    Layout l;
+    int64_t blocks;                                 // of the clip
+    const uint8_t* luma_q; const uint8_t* chroma_q;
+    uint8_t* scratch;                               // per frame: Y [plane_h][plane_w], then Cb and Cr [chroma_h][chroma_w]
+    int plane_h, plane_w, chroma_h, chroma_w;
+    int64_t frame_bytes;                            // of a frame's three planes
+    uint8_t* frames; int64_t frame_pitch, row_pitch;
+};
+
+__global__ void __launch_bounds__(256) jpeg_planes_kernel(const DecodeArgs a)
+{
+    __shared__ int tile[4][2][64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & (kWave - 1);
+    const int64_t b = (int64_t)blockIdx.x * 4 + wave;
+    const bool valid = b < a.blocks;
+    const int64_t bc = valid ? b : a.blocks - 1;                               // waves past the clip redo its last block and store nothing
+    const int64_t per_frame = (int64_t)a.l.n_mcu * a.l.bpm;
+    const int64_t f = bc / per_frame;
+    const int rem = (int)(bc - f * per_frame);
+    const int mcu = rem / a.l.bpm, k = rem - mcu * a.l.bpm;
+    const int my = mcu / a.l.mcus_x, mx = mcu - my * a.l.mcus_x;
+    const bool luma = a.subsampling == 0 ? k == 0 : k < 4;
+    int (&in)[64] = tile[wave][0];
+    int (&mid)[64] = tile[wave][1];
+    const int q = max((int)(luma ? a.luma_q : a.chroma_q)[lane], 1);           // lane z: the coefficient of zigzag position z
+    in[kZigzag[lane]] = min(max((int)a.coefficients[bc * 64 + lane] * q, -32768), 32767);
+    __syncthreads();
+    const int y = lane >> 3, x = lane & 7;
+    int acc = 0;                                                              // lane (y, u = x): the column pass, |acc| <= 21641 x 32768
+#pragma unroll
+    for (int v = 0; v < 8; ++v) acc += kDct[v][y] * in[v * 8 + x];
+    mid[lane] = (acc + 512) >> 10;                                            // |mid| <= 692513
+    __syncthreads();
+    long long wide = 0;                                                       // lane (y, x): the row pass; 21641 x 692513 does not fit int32
+#pragma unroll
+    for (int u = 0; u < 8; ++u) wide += (long long)kDct[u][x] * mid[y * 8 + u];
+    const int s = (int)min(max(((wide + 32768) >> 16) + 128, 0ll), 255ll);
+    uint8_t* plane = a.scratch + f * a.frame_bytes;
+    int width, top, left;
+    if (a.subsampling == 0) {
+        plane += (int64_t)k * a.plane_h * a.plane_w; width = a.plane_w; top = my * 8; left = mx * 8;
+    } else if (k < 4) {
+        width = a.plane_w; top = my * 16 + (k >> 1) * 8; left = mx * 16 + (k & 1) * 8;
+    } else {
+        plane += (int64_t)a.plane_h * a.plane_w + (int64_t)(k - 4) * a.chroma_h * a.chroma_w; width = a.chroma_w; top = my * 8; left = mx * 8;
+    }
+    if (valid) plane[(int64_t)(top + y) * width + left + x] = (uint8_t)s;
+}
+
+__global__ void __launch_bounds__(256) jpeg_pixels_kernel(const DecodeArgs a, const int64_t pixels)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= pixels) return;
+    const int64_t hw = (int64_t)a.H * a.W;
+    const int64_t f = i / hw;
+    const int rem = (int)(i - f * hw);
+    const int y = rem / a.W, x = rem - y * a.W;
+    const uint8_t* const luma = a.scratch + f * a.frame_bytes;
+    const uint8_t* const cb_plane = luma + (int64_t)a.plane_h * a.plane_w;
+    const uint8_t* const cr_plane = cb_plane + (int64_t)a.chroma_h * a.chroma_w;
+    const int yy = luma[(int64_t)y * a.plane_w + x];
+    int cb, cr;
+    if (a.subsampling == 0) {
+        cb = cb_plane[(int64_t)y * a.plane_w + x]; cr = cr_plane[(int64_t)y * a.plane_w + x];
+    } else {
+        const int ch = (a.H + 1) >> 1, cw = (a.W + 1) >> 1;                    // the chroma plane that counts; its edges repeat
+        const int near = (y >> 1) * a.chroma_w, far = min(max((y >> 1) + ((y & 1) ? 1 : -1), 0), ch - 1) * a.chroma_w;
+        const int cx = x >> 1, ox = min(max(cx + ((x & 1) ? 1 : -1), 0), cw - 1);
+        const int bias = (x & 1) ? 7 : 8;
+        cb = (3 * (3 * cb_plane[near + cx] + cb_plane[far + cx]) + 3 * cb_plane[near + ox] + cb_plane[far + ox] + bias) >> 4;
+        cr = (3 * (3 * cr_plane[near + cx] + cr_plane[far + cx]) + 3 * cr_plane[near + ox] + cr_plane[far + ox] + bias) >> 4;
+    }
+    cb -= 128; cr -= 128;
+    uint8_t* const out = a.frames + f * a.frame_pitch + y * a.row_pitch + 3 * (int64_t)x;
+    out[0] = (uint8_t)min(max(yy + ((91881 * cr + 32768) >> 16), 0), 255);
+    out[1] = (uint8_t)min(max(yy + ((-22554 * cb - 46802 * cr + 32768) >> 16), 0), 255);
+    out[2] = (uint8_t)min(max(yy + ((116130 * cb + 32768) >> 16), 0), 255);
+}
+
 } // namespace
 
 extern "C" int p3d_video_jpeg_blocks(const uint8_t* frames, int64_t frame_pitch, int64_t row_pitch, int32_t n_frames, int32_t h, int32_t w,
@@ -301,4 +388,38 @@ extern "C" int p3d_video_jpeg_scan(const int16_t* coefficients, int32_t n_frames
     else      hipLaunchKernelGGL(jpeg_scan_kernel<false>, dim3((unsigned)groups), dim3(kWave), 0, (hipStream_t)stream, a);
     count_launch(FAM_AUX);
     return check_launch("video_jpeg_scan");
+}
+
+extern "C" int p3d_video_jpeg_decode(const int16_t* coefficients, int32_t n_frames, int32_t h, int32_t w, int32_t subsampling, const uint8_t* luma_q,
+                                     const uint8_t* chroma_q, uint8_t* scratch, int64_t scratch_bytes, uint8_t* frames, int64_t frame_pitch,
+                                     int64_t row_pitch, p3d_stream_t stream)
+{
+    using namespace p3d;
+    DecodeArgs a;
+    int64_t pixels = 0;
+    const int rc = layout("video_jpeg_decode", n_frames, h, w, subsampling, &a.l, &pixels);
+    if (rc != P3D_OK) return rc;
+    if (pixels == 0) return P3D_OK;
+    P3D_REQUIRE(coefficients && luma_q && chroma_q && scratch && frames, "video_jpeg_decode: coefficients, the two tables, scratch and frames must be non-null");
+    P3D_REQUIRE(((uintptr_t)coefficients & 1u) == 0, "video_jpeg_decode: coefficients must be 2-byte aligned");
+    P3D_REQUIRE(row_pitch >= 3 * (int64_t)w && frame_pitch >= 0, "video_jpeg_decode: the row pitch is shorter than the row, or the frame pitch negative");
+    const int mcu = 8 << subsampling;
+    a.plane_w = a.l.mcus_x * mcu; a.plane_h = (a.l.n_mcu / a.l.mcus_x) * mcu;
+    a.chroma_w = a.plane_w >> subsampling; a.chroma_h = a.plane_h >> subsampling;
+    a.frame_bytes = (int64_t)a.plane_h * a.plane_w + 2 * (int64_t)a.chroma_h * a.chroma_w;
+    P3D_REQUIRE(scratch_bytes >= a.frame_bytes * n_frames, "video_jpeg_decode: scratch holds %lld bytes, the planes of %d frames take %lld", (long long)scratch_bytes,
+                n_frames, (long long)(a.frame_bytes * n_frames));
+    a.coefficients = coefficients; a.H = h; a.W = w; a.subsampling = subsampling;
+    a.blocks = (int64_t)n_frames * a.l.n_mcu * a.l.bpm;
+    a.luma_q = luma_q; a.chroma_q = chroma_q; a.scratch = scratch;
+    a.frames = frames; a.frame_pitch = frame_pitch; a.row_pitch = row_pitch;
+    const int64_t groups = (a.blocks + 3) / 4;
+    P3D_REQUIRE(groups < (1ll << 31), "video_jpeg_decode: %lld blocks are too many for one launch", (long long)a.blocks);
+    hipLaunchKernelGGL(jpeg_planes_kernel, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, a);
+    count_launch(FAM_AUX);
+    int status = check_launch("video_jpeg_decode");
+    if (status != P3D_OK) return status;
+    hipLaunchKernelGGL(jpeg_pixels_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, pixels);
+    count_launch(FAM_AUX);
+    return check_launch("video_jpeg_decode");
 }

@@ -595,16 +595,19 @@ def render(G, ws, cameras, resolution=512, color='grey', palette=None, backgroun
 
 @torch.no_grad()
 def geometry_video(G, ws, cfg='seg2cat', n_frames=120, views_per_step=4, resolution=512, color='grey', path=None, fps=60, gif='pil', format='gif',
-                   **render_kwargs):
+                   psnr=None, ssim=None, **render_kwargs):
     """The geometry turntable of ``ws`` [1, num_ws, w_dim]: ``render`` over ``views.video_cameras(G, cfg, n_frames)``, ``views_per_step``
     cameras per cast launch, the backbone run once for all of them where the cast kernel serves.  uint8 [n_frames, R, R, 3] on ws's
     device; with ``path`` also written as a GIF: ``gif='pil'`` through ``mesh.save_gif``, ``gif='device'`` through ``video.save_gif`` (one palette for the
     clip, made and applied on the frames' device).  ``format='avi'``: a true-colour Motion-JPEG AVI through ``video.save_avi`` instead, encoded on the
-    frames' device (``gif`` plays no part); ``format='apng'``: a lossless animated PNG through ``video.save_apng``, likewise."""
+    frames' device (``gif`` plays no part) — with ``psnr`` or ``ssim`` (one of them) at the quality that ``video.jpeg_quality_for`` picks for that target;
+    ``format='apng'``: a lossless animated PNG through ``video.save_apng``, likewise."""
     if gif not in ('pil', 'device'):
         raise ValueError(f"geometry_video: gif must be 'pil' or 'device', got {gif!r}")
     if format not in ('gif', 'avi', 'apng'):
         raise ValueError(f"geometry_video: format must be 'gif', 'avi' or 'apng', got {format!r}")
+    if (psnr is not None or ssim is not None) and format != 'avi':
+        raise ValueError(f"geometry_video: psnr / ssim pick a JPEG quality and need format='avi', got {format!r}")
     step = int(views_per_step)
     if step < 1:
         raise ValueError(f'geometry_video: views_per_step must be >= 1, got {views_per_step}')
@@ -616,7 +619,7 @@ def geometry_video(G, ws, cfg='seg2cat', n_frames=120, views_per_step=4, resolut
     out = torch.cat(frames) if frames else torch.empty([0, int(resolution), int(resolution), 3], dtype=torch.uint8, device=ws.device)
     if path is not None and format == 'avi':
         from . import video
-        video.save_avi(path, out, fps=fps)
+        video.save_avi(path, out, fps=fps, psnr=psnr, ssim=ssim)
     elif path is not None and format == 'apng':
         from . import video
         video.save_apng(path, out, fps=fps)

@@ -24,7 +24,11 @@ rule holds: p3d_video.h states every step in integers, the formulation here is t
 Lossless needs no PIL either: ``encode_png`` makes every frame's zlib stream where the frames are (``png_filter``: the PNG row filters; ``png_counts``: the
 symbol counts of run-length deflate per segment; ``png_deflate``: one length-limited Huffman code a frame, made on the host, and the bytes), ``save_png`` /
 ``save_png_sequence`` write stills, ``save_apng`` an animated PNG, and ``png_chunks`` takes a file apart again; 1 .. 4 bytes a pixel, palette indices and
-16-bit grey (``depth16``) included."""
+16-bit grey (``depth16``) included.
+
+What a setting costs is measured where the frames are (``quality.py``): ``jpeg_decode`` / ``jpeg_reconstruct`` show what a viewer of
+the JPEGs sees without entropy decoding, ``jpeg_quality_for`` turns a PSNR or SSIM target into a quality (``encode_jpeg`` / ``save_avi`` take ``psnr=`` or
+``ssim=`` in place of one), and ``palette_quality`` measures the GIF knobs."""
 import numpy as np
 import torch
 
@@ -617,12 +621,18 @@ def jpeg_header(h, w, tables, subsampling='4:2:0'):
     return out + _segment(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
 
 
-def encode_jpeg(frames, quality=90, subsampling='4:2:0'):
+def encode_jpeg(frames, quality=90, subsampling='4:2:0', psnr=None, ssim=None):
     """A list of ``bytes``, one complete baseline JFIF per frame of uint8 [F, H, W, 3] (the module's frame contract; on the device or the host, or a numpy
     array): ``jpeg_header``, the frame's scan, EOI.  ``quality`` 1 .. 100 picks the tables (``jpeg_tables``).  From device frames: the two kernels' three
-    launches, ONE synchronisation with the host (the interval lengths) and ONE device -> host copy (the scans, a few percent of the frames' bytes)."""
+    launches, ONE synchronisation with the host (the interval lengths) and ONE device -> host copy (the scans, a few percent of the frames' bytes).
+    ``psnr`` or ``ssim`` (ONE of them): a target instead of a setting — ``jpeg_quality_for`` picks the quality, ``quality`` plays no part, and the tables in
+    the streams (``jpeg_tables`` of the choice) say what it was."""
     frames = torch.as_tensor(frames)
     f, h, w = _check_frames(frames)
+    if psnr is not None or ssim is not None:
+        _check_target(psnr, ssim, 'encode_jpeg')
+        if f * h * w:
+            quality = jpeg_quality_for(frames, psnr, ssim, subsampling)[0]
     sub, tables = _check_subsampling(subsampling), jpeg_tables(quality)
     if f == 0:
         return []
@@ -648,11 +658,12 @@ def _chunk(fourcc, payload):
     return fourcc + len(payload).to_bytes(4, 'little') + payload + b'\0' * (len(payload) & 1)
 
 
-def save_avi(path, frames, fps=60, quality=90, subsampling='4:2:0'):
+def save_avi(path, frames, fps=60, quality=90, subsampling='4:2:0', psnr=None, ssim=None):
     """The frames (``encode_jpeg``'s contract) as a Motion-JPEG AVI: a RIFF 'AVI ' file with the list 'hdrl' ('avih', and one 'strl' of 'strh' — 'vids' /
     'MJPG', the rate ``fps`` as dwRate / dwScale — and 'strf', a 40-byte BITMAPINFOHEADER of 24 bits), the list 'movi' of one '00dc' chunk per frame,
     padded to an even length, and 'idx1': per frame the key-frame flag, the chunk's offset from 'movi' and its length.  Every frame is a key frame.
-    ValueError for no frame and for a file that would reach 2^31 bytes (OpenDML is out of scope).  Returns the JPEG streams."""
+    ValueError for no frame and for a file that would reach 2^31 bytes (OpenDML is out of scope).  ``psnr`` / ``ssim``: ``encode_jpeg``'s target, which
+    then picks the quality.  Returns the JPEG streams."""
     import fractions
     import struct
     frames = torch.as_tensor(frames)
@@ -662,7 +673,7 @@ def save_avi(path, frames, fps=60, quality=90, subsampling='4:2:0'):
     rate = fractions.Fraction(fps).limit_denominator(1 << 16)
     if rate <= 0:
         raise ValueError(f'save_avi: fps must be > 0, got {fps!r}')
-    streams = encode_jpeg(frames, quality, subsampling)
+    streams = encode_jpeg(frames, quality, subsampling, psnr, ssim)
     movi, index = b'movi', b''
     chunks = [movi]
     at = 4                                                                        # of the next chunk, from the 'movi' word
@@ -718,6 +729,172 @@ def read_avi(path):
             raise ValueError(f'read_avi: the index entry at {entry} does not point at a 00dc chunk of {size} bytes')
         streams.append(data[at + 8:at + 8 + size])
     return streams, (rate // scale if rate % scale == 0 else rate / scale), (w, h)
+
+
+# ---- the way back: what a setting costs ------------------------------------------------------------------------------------------------------
+# A decoder's view of the coefficients without entropy decoding, so that ``quality.compare`` can judge a setting where the frames are, and the search
+# that turns a target into a setting.
+def jpeg_idct(coefficients):
+    """int64 [..., 8, 8] (y, x) of dequantised coefficients [..., 8, 8] (v, u) in natural order: the header's two integer passes, the column pass
+    m[y][u] = (sum_v T[v][y] c[v][u] + 512) >> 10, then the row pass s[y][x] = (sum_u T[u][x] m[y][u] + 32768) >> 16 — the level-shifted sample."""
+    t = jpeg_dct_table()
+    m = (torch.matmul(t.T, coefficients.to(torch.int64)) + 512) >> 10
+    return (torch.matmul(m, t) + 32768) >> 16
+
+
+def jpeg_dequantize(coefficients, tables, subsampling):
+    """int64 [F, n_mcu, blocks, 8, 8] (v, u): ``jpeg_coefficients``' int16 blocks times their table's entries (a 0 counts as 1), clamped to int16's range and
+    taken out of zigzag order."""
+    sub = _check_subsampling(subsampling)
+    luma_q, chroma_q = (torch.as_tensor(t).cpu().to(torch.int64).clamp(min=1) for t in tables)
+    n_luma = 4 if sub else 1
+    q = torch.stack([luma_q] * n_luma + [chroma_q] * 2)                            # [blocks, 64]
+    c = (coefficients.to(torch.int64) * q).clamp(-32768, 32767)
+    natural = torch.empty_like(c)
+    natural[..., jpeg_zigzag()] = c
+    return natural.reshape(*c.shape[:-1], 8, 8)
+
+
+def _jpeg_decode_torch(coefficients, tables, h, w, sub, out):
+    f = coefficients.shape[0]
+    mcu = 8 << sub
+    my, mx = -(-h // mcu), -(-w // mcu)
+    s = (jpeg_idct(jpeg_dequantize(coefficients, tables, sub)) + 128).clamp(0, 255).reshape(f, my, mx, -1, 8, 8)
+
+    def plane(blocks):                                                            # [F, my, mx, 8, 8] -> [F, 8 my, 8 mx]
+        return blocks.permute(0, 1, 3, 2, 4).reshape(f, my * 8, mx * 8)
+    if sub:
+        y = s[:, :, :, :4].reshape(f, my, mx, 2, 2, 8, 8).permute(0, 1, 3, 5, 2, 4, 6).reshape(f, my * 16, mx * 16)
+        ch, cw = (h + 1) // 2, (w + 1) // 2
+        rows, cols = torch.arange(h), torch.arange(w)
+        near, cx = rows >> 1, cols >> 1
+        far = (near + torch.where(rows & 1 == 1, 1, -1)).clamp(0, ch - 1)
+        ox = (cx + torch.where(cols & 1 == 1, 1, -1)).clamp(0, cw - 1)
+        bias = torch.where(cols & 1 == 1, 7, 8)
+        chroma = []
+        for k in (4, 5):
+            p = plane(s[:, :, :, k])[:, :ch, :cw]
+            v = 3 * p[:, near] + p[:, far]                                        # [F, h, cw]
+            chroma.append((3 * v[:, :, cx] + v[:, :, ox] + bias) >> 4)
+        cb, cr = chroma
+    else:
+        y, cb, cr = (plane(s[:, :, :, k]) for k in range(3))
+    y, cb, cr = y[:, :h, :w], cb[:, :h, :w] - 128, cr[:, :h, :w] - 128
+    rgb = torch.stack([y + ((91881 * cr + 32768) >> 16), y + ((-22554 * cb - 46802 * cr + 32768) >> 16), y + ((116130 * cb + 32768) >> 16)], dim=3)
+    out.copy_(rgb.clamp(0, 255).to(torch.uint8))
+    return out
+
+
+def jpeg_decode(coefficients, tables, h, w, subsampling='4:2:0', out=None):
+    """uint8 [F, h, w, 3]: what a decoder shows for ``coefficients`` (``jpeg_coefficients``' layout, for pictures of ``h`` x ``w``) under ``tables`` — no
+    entropy decoding, so a quality setting is judged where the frames are.  p3d_video.h states the rules: dequantise and clamp to int16, the inverse of
+    the integer DCT in two passes with 26 bits of rounding shifts, + 128 and clamp; at 4:2:0 the triangle filter on the chroma planes (3 : 1 vertically,
+    then 3 : 1 horizontally with the roundings 8 and 7, edges replicated); the fixed-point JFIF inverse colour transform; the crop.  Not bit-equal with any
+    libjpeg (their inverse DCTs differ by a level here and there), but the same picture.  ``out``: the caller's uint8 [F, h, w, 3] view with contiguous
+    pixels and any pitches.  Device tensors: TWO launches of ``p3d_video_jpeg_decode`` (blocks into planes in a scratch buffer, then pixels), no
+    synchronisation; CPU tensors: the torch formulation."""
+    sub = _check_subsampling(subsampling)
+    h, w = int(h), int(w)
+    _, n_mcu, bpm, _ = jpeg_layout(h, w, sub)
+    if not torch.is_tensor(coefficients) or coefficients.dtype != torch.int16 or coefficients.ndim != 4:
+        raise ValueError('jpeg_decode: coefficients must be an int16 [F, n_mcu, blocks, 64] tensor')
+    f = coefficients.shape[0]
+    if h < 0 or w < 0 or f * h * w >= MAX_PIXELS:
+        raise ValueError(f'jpeg_decode: {f} x {h} x {w} pixels are negative or reach 2^31')
+    luma_q, chroma_q = (torch.as_tensor(t) for t in tables)
+    for t in (luma_q, chroma_q):
+        if t.dtype != torch.uint8 or tuple(t.shape) != (64,):
+            raise ValueError('jpeg_decode: tables must be two uint8 [64] tensors')
+    if out is None:
+        out = torch.empty([f, h, w, 3], dtype=torch.uint8, device=coefficients.device)
+    elif not torch.is_tensor(out) or tuple(out.shape) != (f, h, w, 3) or out.device != coefficients.device:
+        raise ValueError(f'jpeg_decode: out must be uint8 [{f}, {h}, {w}, 3] on {coefficients.device}')
+    else:
+        _check_frames(out, 'jpeg_decode: out')
+        if f > 1 and h * w and out.stride(0) < h * out.stride(1):
+            raise ValueError(f'jpeg_decode: the frames of out overlap (strides {tuple(out.stride())})')
+    if f * h * w == 0:
+        return out
+    if tuple(coefficients.shape[1:]) != (n_mcu, bpm, 64):
+        raise ValueError(f'jpeg_decode: {h} x {w} at subsampling {subsampling!r} has [{n_mcu}, {bpm}, 64] coefficients a frame, got {list(coefficients.shape[1:])}')
+    if not coefficients.is_cuda:
+        return _jpeg_decode_torch(coefficients, (luma_q, chroma_q), h, w, sub, out)
+    coefficients = coefficients.contiguous()
+    luma_q, chroma_q = luma_q.to(coefficients.device).contiguous(), chroma_q.to(coefficients.device).contiguous()
+    mcu = 8 << sub
+    plane = (-(-h // mcu) * mcu) * (-(-w // mcu) * mcu)
+    scratch = torch.empty([f * (plane + 2 * (plane >> (2 * sub)))], dtype=torch.uint8, device=coefficients.device)
+    with _lib.kernel_timer('video_jpeg_decode', out):
+        code = video_lib().p3d_video_jpeg_decode(_lib.ptr(coefficients), f, h, w, sub, _lib.ptr(luma_q), _lib.ptr(chroma_q), _lib.ptr(scratch), scratch.shape[0],
+                                                 _lib.ptr(out), out.stride(0), out.stride(1), _lib.stream_of(out))
+    _check(code, 'video_jpeg_decode')
+    return out
+
+
+def jpeg_reconstruct(frames, quality=90, subsampling='4:2:0'):
+    """uint8 [F, H, W, 3] on the frames' device: what a viewer of ``encode_jpeg(frames, quality, subsampling)`` sees — ``jpeg_decode`` of ``jpeg_coefficients``,
+    three launches and no synchronisation from device frames."""
+    frames = torch.as_tensor(frames)
+    f, h, w = _check_frames(frames)
+    sub, tables = _check_subsampling(subsampling), jpeg_tables(quality)
+    if frames.is_cuda:
+        tables = _device_tables(('quantisation', _check_quality(quality)), frames.device, lambda: tables)
+    return jpeg_decode(jpeg_coefficients(frames, tables, sub), tables, h, w, sub)
+
+
+def _check_target(psnr, ssim, what):
+    """('psnr' or 'ssim', the target): exactly ONE of the two is given.  Both would need a rule for a quality that meets one and not the other; a caller who
+    wants both takes the larger of two searches."""
+    if (psnr is None) == (ssim is None):
+        raise ValueError(f'{what}: give psnr (dB) or ssim (0 .. 1), one of them, got psnr={psnr!r}, ssim={ssim!r}')
+    key, target = ('psnr', psnr) if ssim is None else ('ssim', ssim)
+    if isinstance(target, bool) or not isinstance(target, (int, float)) or target != target or (key == 'ssim' and not 0 <= target <= 1) or (key == 'psnr' and target < 0):
+        raise ValueError(f'{what}: {key} must be a number{" 0 .. 1" if key == "ssim" else " >= 0 (dB)"}, got {target!r}')
+    return key, float(target)
+
+
+def jpeg_quality_for(frames, psnr=None, ssim=None, subsampling='4:2:0', sample=8):
+    """``(quality, metrics, met)``: the JPEG quality that meets a target — ``psnr`` in dB or ``ssim`` in 0 .. 1, ONE of them (``_check_target``) — as
+    ``quality.compare`` measures ``jpeg_reconstruct`` against the frames, on at most ``sample`` evenly spaced frames of the clip (the first and the last among
+    them).  A bisection of 1 .. 100 in at most seven steps, each three launches for the reconstruction, two for the sums and ONE host read.  The measure
+    need not rise with the quality, so the promise is a post-condition, ``mesh.simplify_to``'s: the quality returned met the target as measured (``metrics``
+    is its ``compare`` dict), and the quality below it was tried and did not (unless it is 1); if 100 does not meet it, ``(100, its metrics, False)``.  A
+    clip without a sample — or, for ``ssim``, without a window — measures NaN, which meets nothing."""
+    from . import quality as Q
+    frames = torch.as_tensor(frames)
+    f, h, w = _check_frames(frames)
+    key, target = _check_target(psnr, ssim, 'jpeg_quality_for')
+    sub = _check_subsampling(subsampling)
+    if isinstance(sample, bool) or int(sample) != sample or int(sample) < 1:
+        raise ValueError(f'jpeg_quality_for: sample must be an integer >= 1, got {sample!r}')
+    n = int(sample)
+    if f > n:
+        frames = frames[[0] if n == 1 else [(i * (f - 1)) // (n - 1) for i in range(n)]]
+    measured = {}
+    low, high = 1, 101                                                            # the answer lies in low .. high; 101: none
+    while low < high:
+        mid = (low + high) // 2
+        measured[mid] = Q.compare(jpeg_reconstruct(frames, mid, sub), frames)
+        if measured[mid][key] >= target:
+            high = mid
+        else:
+            low = mid + 1
+    return (low, measured[low], True) if low <= 100 else (100, measured[100], False)
+
+
+def palette_quality(frames, indices, palette):
+    """``quality.compare`` of what a GIF shows, ``palette[indices]``, against the frames it was made from — what ``colors``, ``dither`` and ``palette`` of
+    ``palettize`` cost.  ``indices`` uint8 [F, H, W], ``palette`` uint8 [K, 3] or [F, K, 3], on the frames' device; one gather there, two launches, ONE host read."""
+    f, h, w = _check_frames(frames)
+    if not torch.is_tensor(indices) or indices.dtype != torch.uint8 or tuple(indices.shape) != (f, h, w) or indices.device != frames.device:
+        raise ValueError(f'palette_quality: indices must be uint8 [{f}, {h}, {w}] on {frames.device}')
+    if not torch.is_tensor(palette) or palette.dtype != torch.uint8 or palette.ndim not in (2, 3) or palette.shape[-1] != 3 or palette.device != frames.device \
+            or (palette.ndim == 3 and palette.shape[0] != f):
+        raise ValueError(f'palette_quality: palette must be uint8 [K, 3] or [{f}, K, 3] on {frames.device}')
+    from . import quality as Q
+    idx = indices.long().clamp(max=palette.shape[-2] - 1)                        # (an index past the palette shows its last row: no read out of bounds)
+    shown = palette[idx] if palette.ndim == 2 else torch.gather(palette, 1, idx.reshape(f, -1, 1).expand(-1, -1, 3)).reshape(f, h, w, 3)
+    return Q.compare(shown, frames)
 
 
 # ---- lossless frames: PNG and APNG -----------------------------------------------------------------------------------------------------------

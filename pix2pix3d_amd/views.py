@@ -327,7 +327,7 @@ def image_grid(frames, grid_size):
 
 
 @torch.no_grad()
-def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=120, fps=60, gif='pil', format='gif', **render_kwargs):
+def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=120, fps=60, gif='pil', format='gif', psnr=None, ssim=None, **render_kwargs):
     """generate_video.py after its inputs: the ``cfg`` cameras (``video_cameras``) at the script's ray resolution with ``noise_mode='const'``, rendered by
     ``render_views`` (its keyword arguments pass through); ``path`` / ``path_label`` receive the two GIFs the script writes with imageio at 60 fps.
     ``gif='pil'``: through ``mesh.save_gif``, PIL quantising every frame on the host.  ``gif='device'``: the image through ``video.save_gif`` (one palette for
@@ -335,11 +335,15 @@ def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=12
     palette, or the edge generators' grey frames with a grey ramp.  ``format='avi'``: both clips in true colour as Motion-JPEG AVIs through
     ``video.save_avi``, encoded where the frames are (``gif`` plays no part).  ``format='apng'``: both clips losslessly as animated PNGs through
     ``video.save_apng``, encoded where the frames are — the image as RGB, the label video as palette indices (``label_index`` with the frames' palette) or,
-    for the edge generators, as 8-bit grey.  Returns ``render_views``' dict."""
+    for the edge generators, as 8-bit grey.  ``psnr`` / ``ssim`` (``format='avi'`` only, one of them): a target for the image clip instead of the default
+    quality — ``video.jpeg_quality_for`` picks the setting where the frames are, the dict gains 'jpeg_quality': ``(quality, metrics, met)``, and the label
+    clip goes through ``video.save_avi`` with the same target.  Returns ``render_views``' dict."""
     if gif not in ('pil', 'device'):
         raise ValueError(f"generate_video: gif must be 'pil' or 'device', got {gif!r}")
     if format not in ('gif', 'avi', 'apng'):
         raise ValueError(f"generate_video: format must be 'gif', 'avi' or 'apng', got {format!r}")
+    if (psnr is not None or ssim is not None) and format != 'avi':
+        raise ValueError(f"generate_video: psnr / ssim pick a JPEG quality and need format='avi', got {format!r}")
     cams = video_cameras(G, cfg, n_frames).to(ws.device)
     render_kwargs.setdefault('noise_mode', 'const')
     render_kwargs.setdefault('neural_rendering_resolution', VIDEO_CFG[cfg]['neural_rendering_resolution'])
@@ -347,7 +351,11 @@ def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=12
     if path is not None:
         if format == 'avi':
             from . import video
-            video.save_avi(path, frames['image'], fps=fps)
+            if psnr is None and ssim is None:
+                video.save_avi(path, frames['image'], fps=fps)
+            else:
+                frames['jpeg_quality'] = video.jpeg_quality_for(frames['image'], psnr, ssim)
+                video.save_avi(path, frames['image'], fps=fps, quality=frames['jpeg_quality'][0])
         elif format == 'apng':
             from . import video
             video.save_apng(path, frames['image'], fps=fps)
@@ -362,7 +370,7 @@ def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=12
         if format == 'avi':
             from . import video
             label = frames['label']                                            # (the edge generators' frames are grey: [F, H, W])
-            video.save_avi(path_label, label if label.ndim == 4 else label[..., None].expand(-1, -1, -1, 3).contiguous(), fps=fps)
+            video.save_avi(path_label, label if label.ndim == 4 else label[..., None].expand(-1, -1, -1, 3).contiguous(), fps=fps, psnr=psnr, ssim=ssim)
         elif format == 'apng':
             from . import video
             if 'label_index' in frames:
