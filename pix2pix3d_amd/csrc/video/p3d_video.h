@@ -1,6 +1,7 @@
 /* libp3d_video.so — palette, dither and index frames for the GIF writer (pix2pix3d_amd/video.py) and, at the end, baseline JPEG
  * frames for the Motion-JPEG writer (section 2.1u), the zlib streams of PNG and APNG files (section 2.1v) and what a setting of those writers
- * costs in the picture: error sums, SSIM and a decoder's view of the JPEG coefficients (section 2.1x).  A library of its
+ * costs in the picture: error sums, SSIM and a decoder's view of the JPEG coefficients (section 2.1x) — and, after the JPEG coder, its inverse: the entropy
+ * decoder that reads such files, and libjpeg's, back (section 2.1y).  A library of its
  * own, like libp3d_regions.so: the product ABI (include/p3d_hip.h, libp3d_hip.so) exports none of this.  It carries its own copy of the
  * library services (p3d_last_error, p3d_launch_count).  Nothing here has a counterpart in the reference, which writes videos with imageio.
  *
@@ -86,6 +87,45 @@ int p3d_video_jpeg_blocks(const uint8_t* frames, int64_t frame_pitch, int64_t ro
  * block; the bits are ORed into LDS words and leave the work-group as plain byte stores.                                                           */
 int p3d_video_jpeg_scan(const int16_t* coefficients, int32_t n_frames, int32_t h, int32_t w, int32_t subsampling, const uint32_t* huffman,
                         int32_t* lengths, const int64_t* offsets, uint8_t* data, int64_t data_bytes, p3d_stream_t stream);
+
+/* The way back from a file: the inverse of p3d_video_jpeg_scan for ANY baseline stream in restart intervals — ours, or libjpeg's with its own tables and its
+ * own interval (video_jpeg_read.hip; the routine itself is jpeg_entropy.h, plain C++ that a host program runs as it stands).
+ * data uint8 [data_bytes] holds the scans of all frames; ranges int64 [n_frames][n_intervals][2] the first byte of every interval and the byte after its
+ * last, markers left out (clamped to 0 <= begin <= end <= data_bytes).  restart >= 1 MCUs an interval, n_intervals = ceil(n_mcu / restart), the last one
+ * possibly shorter; a stream without restart markers is ONE interval of n_mcu MCUs (restart = n_mcu).  components 3: every MCU codes all its blocks;
+ * components 1, with subsampling 0 only: a grey stream, whose MCU codes its Y block alone — the Cb and Cr blocks of the output stay zero.
+ * TABLES.  tables uint32 [n_sets][4][P3D_VIDEO_JPEG_TABLE_WORDS], per set DC luma, DC chroma, AC luma, AC chroma, each made from a DHT's BITS / HUFFVAL
+ * with the canonical codes of Annex C (code of the k-th value: they count up within a length, and a new length starts at twice the next code):
+ *     [0 .. 255]    per 8-bit prefix: length << 16 | symbol of the code of length 1 .. 8 that the prefix starts with, 0 where there is none;
+ *     [256 .. 271]  limit[l - 1], l = 1 .. 16: the last code of length l plus 1, 0 where no code has length l;
+ *     [272 .. 287]  offset[l - 1], int32: the index in HUFFVAL of the first code of length l minus that code;
+ *     [288 .. 351]  HUFFVAL, 256 bytes (zero-filled), byte i at bits 8 (i & 3) of word i >> 2.
+ * A symbol: if the entry of the next 8 bits has a length 1 .. 8, that is it.  Otherwise, for l = 9 .. 16 in turn, with c the next l bits: the first l
+ * with c < limit[l - 1] gives the symbol HUFFVAL[c + offset[l - 1]] if that index is 0 .. 255; no such l, or no such index: NO_CODE, and 16 bits count
+ * as read.  table_of_frame int32 [n_frames]: the set of every frame (clamped to 0 .. n_sets - 1).
+ * BITS.  An interval's bytes, most significant bit first; a 0x00 straight after a 0xFF inside the interval is dropped (any other byte after a 0xFF is
+ * data, as is the 0xFF).  Past the interval's end the bits are zeros, and reading one sets EXHAUSTED.
+ * BLOCKS, in the order p3d_video_jpeg_scan codes them, predictors 0 at the interval's start.  DC: a symbol `size` (> 11: SIZE), then `size` extra bits e:
+ * the difference is e if e >= 2^(size - 1), else e - 2^size + 1; the value is the predictor of the component plus the difference, clamped to int16's
+ * range, and becomes the predictor.  AC, from position z = 1 while z <= 63: a symbol run << 4 | size.  size = 0: run 0 ends the block, run 15 adds 16 to
+ * z (z > 63 then: RUN — a value must follow), any other run: SIZE.  size > 10: SIZE.  Otherwise z += run (z > 63: RUN), the value of the extra bits goes
+ * to position z, and z += 1.  After the last block, more than one whole data byte unread: LEFTOVER (up to 15 bits may pad an interval).
+ * STATUS.  After every symbol and after every run of extra bits the status is looked at: with a bit set the interval ends there, what it has stored stays,
+ * and the value in hand is not stored.  status int32 [n_frames][n_intervals] receives the bits; 0: the interval decoded cleanly.
+ * coefficients int16 [n_frames][n_mcu][blocks of an MCU][64] as p3d_video_jpeg_blocks lays them out, so that p3d_video_jpeg_decode takes them as they are.
+ * TWO launches: an asynchronous fill zeroes the coefficients (counted as one), then a lane per interval stores the non-zero values alone — a block's 128
+ * bytes would otherwise be a scattered store per lane.  The frame's four tables sit in LDS.  No read leaves [begin, end), no store the frame's blocks,
+ * and every loop is bounded, whatever the bytes and the tables hold.  n_frames h w = 0 launches nothing.                                                */
+#define P3D_VIDEO_JPEG_LOOKUP_BITS 8
+#define P3D_VIDEO_JPEG_TABLE_WORDS 352
+#define P3D_VIDEO_JPEG_STATUS_NO_CODE 1     /* no code within 16 bits */
+#define P3D_VIDEO_JPEG_STATUS_RUN 2         /* a run past position 63 */
+#define P3D_VIDEO_JPEG_STATUS_SIZE 4        /* a DC size > 11, an AC size > 10, or an end-of-band symbol of progressive scans */
+#define P3D_VIDEO_JPEG_STATUS_EXHAUSTED 8   /* bits read past the interval's end */
+#define P3D_VIDEO_JPEG_STATUS_LEFTOVER 16   /* more than one whole byte unread */
+int p3d_video_jpeg_unscan(const uint8_t* data, int64_t data_bytes, const int64_t* ranges, const uint32_t* tables, int32_t n_sets,
+                          const int32_t* table_of_frame, int32_t n_frames, int32_t h, int32_t w, int32_t subsampling, int32_t components, int32_t restart,
+                          int16_t* coefficients, int32_t* status, p3d_stream_t stream);
 
 /* ---- lossless frames: the zlib streams of PNG and APNG files (video_png.hip) ------------------------------------------------
  * Pixels are bpp = 1 .. 4 bytes; the kernels know only bpp, the colour type is the file header's business ('L' 1, 'LA' and 16-bit grey 2, 'RGB' 3,
