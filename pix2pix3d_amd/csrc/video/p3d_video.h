@@ -1,4 +1,4 @@
-/* libp3d_video.so — palette, dither and index frames for the GIF writer (pix2pix3d_amd/video.py) and, at the end, baseline JPEG
+/* libp3d_video.so — palette, dither and index frames for the GIF writer (pix2pix3d_amd/video/gif.py) and, at the end, baseline JPEG
  * frames for the Motion-JPEG writer (section 2.1u), the zlib streams of PNG and APNG files (section 2.1v) and what a setting of those writers
  * costs in the picture: error sums, SSIM and a decoder's view of the JPEG coefficients (section 2.1x) — and, after the JPEG coder, its inverse: the entropy
  * decoder that reads such files, and libjpeg's, back (section 2.1y).  A library of its
@@ -9,7 +9,7 @@
  * (>= 3 w) and frames `frame_pitch` bytes apart, so a strided selection of frames and a window of a larger canvas are read in place.
  * n_frames, h, w >= 0 and n_frames * h * w < 2^31; an empty clip launches nothing but the zeroing of the result.
  * A GROUP shares one histogram and one palette: the whole clip (per_frame = 0, n_groups = 1) or one frame (per_frame = 1, n_groups =
- * n_frames).  Everything is integer arithmetic and a pure function of the inputs: the torch formulations of pix2pix3d_amd/video.py produce
+ * n_frames).  Everything is integer arithmetic and a pure function of the inputs: the torch formulations of pix2pix3d_amd/video/gif.py produce
  * the same bytes.  All pointers are device memory.  Argument errors return P3D_ERR_ARGUMENT before any launch.                              */
 #ifndef P3D_VIDEO_H
 #define P3D_VIDEO_H
@@ -48,7 +48,7 @@ int p3d_video_quantize(const uint8_t* frames, int64_t frame_pitch, int64_t row_p
  * Frames as above.  subsampling 0 is 4:4:4: the minimum coded unit (MCU) covers 8 x 8 pixels and holds 3 blocks, Y Cb Cr; subsampling 1 is 4:2:0:
  * the MCU covers 16 x 16 pixels and holds 6 blocks, Y00 Y01 Y10 Y11 Cb Cr (Yyx: the 8 x 8 quarter at row y, column x of the MCU).
  * mcus_x = ceil(w / mcu), mcus_y = ceil(h / mcu), n_mcu = mcus_x mcus_y in raster order; a clip with n_frames h w = 0 has no MCU and launches nothing.
- * Everything is integer arithmetic and a pure function of the inputs; the formulations of pix2pix3d_amd/video.py produce the same bytes.             */
+ * Everything is integer arithmetic and a pure function of the inputs; the formulations of pix2pix3d_amd/video/jpeg.py produce the same bytes.        */
 #define P3D_VIDEO_JPEG_RESTART 8        /* MCUs of a restart interval: its 48 blocks are the lanes of ONE wave, their worst case 9948 bytes of LDS */
 #define P3D_VIDEO_JPEG_BLOCK_BITS 1658  /* the longest coded block: 9 + 11 bits of DC, 63 coefficients of 16 + 10 bits */
 /* T[u][x] = round(8192 a(u) cos((2 x + 1) u pi / 16)), a(0) = sqrt(1 / 8), a(u) = 1 / 2 otherwise: the rows of the integer DCT. */
@@ -131,7 +131,7 @@ int p3d_video_jpeg_unscan(const uint8_t* data, int64_t data_bytes, const int64_t
  * Pixels are bpp = 1 .. 4 bytes; the kernels know only bpp, the colour type is the file header's business ('L' 1, 'LA' and 16-bit grey 2, 'RGB' 3,
  * 'RGBA' 4, palette indices 1).  Frames uint8 [n_frames][h][w][bpp] with frame_pitch / row_pitch (>= w bpp) as above; n_frames h w bpp < 2^31 and
  * n_frames h (1 + w bpp) < 2^31; a clip with n_frames h w = 0 launches nothing.  Three stages, ONE launch each; integer arithmetic and a pure function
- * of the inputs throughout: the formulations of pix2pix3d_amd/video.py produce the same bytes.
+ * of the inputs throughout: the formulations of pix2pix3d_amd/video/png.py produce the same bytes.
  *
  * FILTER.  A row's filtered form is row_bytes = 1 + w bpp bytes: the filter type, then per byte x the residual (x - predictor) mod 256, with a the byte
  * bpp to the left (0 for the first pixel), b the byte above (0 in a frame's first row: every frame is filtered on its own) and c the byte above a.

@@ -1,5 +1,5 @@
-// Baseline JPEG frames for the MJPEG writer (p3d_video.h; pix2pix3d_amd/video.py).  Integer rules throughout: every byte is
-// defined by the header, and the formulations of video.py produce the same bytes.
+// Baseline JPEG frames for the MJPEG writer (p3d_video.h; pix2pix3d_amd/video/jpeg.py).  Integer rules throughout: every byte is
+// defined by the header, and the formulations of video/jpeg.py produce the same bytes.
 //
 // p3d_video_jpeg_blocks  a wave owns one 8 x 8 block, a lane one sample: colour transform (and the 2 x 2 chroma mean at 4:2:0) on the way in, the row
 //                        pass and the column pass of the integer DCT through 2 x 64 ints of LDS, then lane z quantises the coefficient of zigzag

@@ -1,4 +1,4 @@
-// Entropy decoding of baseline JPEG scans (p3d_video.h, "the way back from a file"; pix2pix3d_amd/video.py).
+// Entropy decoding of baseline JPEG scans (p3d_video.h, "the way back from a file"; pix2pix3d_amd/video/jpeg_read.py).
 //
 // p3d_video_jpeg_unscan  a lane owns one restart interval: Huffman decoding is a chain of data-dependent shifts, so the parallel unit is the interval,
 //                        which is byte-aligned, starts with predictors 0 and shares no bit with its neighbours.  The routine is jpeg_entropy.h, the text

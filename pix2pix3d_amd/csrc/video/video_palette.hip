@@ -1,5 +1,5 @@
-// Palette, dither and index frames for the GIF writer (p3d_video.h; pix2pix3d_amd/video.py).  Integer rules throughout:
-// every result is defined by the header, and the torch formulations of video.py produce the same bytes.
+// Palette, dither and index frames for the GIF writer (p3d_video.h; pix2pix3d_amd/video/gif.py).  Integer rules throughout:
+// every result is defined by the header, and the torch formulations of video/gif.py produce the same bytes.
 //
 // p3d_video_histogram    a work-group of 1024 threads owns a share of one frame's pixels and the whole 32768-bin histogram in LDS (128 KB: one
 //                        work-group per CU).  A wave takes 64 consecutive pixels; lanes whose bin equals their left neighbour's form a run, and

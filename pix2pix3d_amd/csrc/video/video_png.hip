@@ -1,5 +1,5 @@
-// Lossless frames: the zlib streams of PNG and APNG files (p3d_video.h; pix2pix3d_amd/video.py).  Integer rules throughout: every
-// byte is defined by the header, and the formulations of video.py produce the same bytes.
+// Lossless frames: the zlib streams of PNG and APNG files (p3d_video.h; pix2pix3d_amd/video/png.py).  Integer rules throughout: every
+// byte is defined by the header, and the formulations of video/png.py produce the same bytes.
 //
 // p3d_video_png_filter  a wave owns one row: a first pass sums |residual| of the five filter types (adaptive only), a wave reduction picks the type, a
 //                       second pass stores the residuals.  Four rows a work-group; the row above is read again rather than kept.

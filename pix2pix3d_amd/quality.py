@@ -1,8 +1,8 @@
 """What a setting costs, measured where the frames are: the error sums behind MAE, MSE and PSNR, and SSIM, between two clips on their own device.
 
-The frame writers of ``video.py`` have knobs — ``colors`` / ``dither`` / ``palette`` of the GIFs, ``quality`` / ``subsampling`` of the JPEGs — and so has the
+The frame writers of ``video/`` have knobs — ``colors`` / ``dither`` / ``palette`` of the GIFs, ``quality`` / ``subsampling`` of the JPEGs — and so has the
 arithmetic (fp16 heads, bf16x3, ``exact_fp32``).  This module says what one of them does to the picture without a copy of the frames to the host
-(csrc/video/p3d_video.h states the rules; the kernels live in libp3d_video.so and are reached through ``video.video_lib()``):
+(csrc/video/p3d_video.h states the rules; the kernels live in libp3d_video.so and are reached through ``clips.video_lib()``):
 
     error_sums(a, b)                      int64 [F, bpp, 4]: per frame and channel sum |d|, sum d^2, max |d| and the number of samples with d != 0
     ssim_sums(a, b)                       int64 [F, bpp, 2]: the sum of round(q 2^32) over the 11 x 11 windows inside the picture, and their number
@@ -12,7 +12,7 @@ arithmetic (fp16 heads, bf16x3, ``exact_fp32``).  This module says what one of t
     difference_map(a, b)                  uint8 heat frames of |d|
 
 Clips are uint8 [F, H, W, bpp], bpp = 2 .. 4, or [F, H, W] (bpp = 1), of one shape on one device, with contiguous pixels and any row and frame pitch
-(``video._check_frames``): a strided selection of frames and a window of a larger canvas are read in place.  SSIM is Wang et al.'s — Gaussian window of
+(``clips.check_frames``): a strided selection of frames and a window of a larger canvas are read in place.  SSIM is Wang et al.'s — Gaussian window of
 sigma 1.5, K1 = 0.01, K2 = 0.03, L = 255, valid windows only, every channel on its own — stated in integers (the window as 10-bit weights, the moments
 exact, the two constants scaled by 2^40) up to three fp64 operations per window, so the torch formulation here, which CPU tensors take, is the definition
 and the device kernel's bytes equal it.  The sums ACCUMULATE into ``out`` when the caller passes one: integer sums, no order, no host synchronisation."""
@@ -21,9 +21,9 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, video
+from . import _lib, clips
 
-_C = video.HEADER.constants
+_C = clips.HEADER.constants
 TAPS, SHIFT, C1, C2 = _C['P3D_VIDEO_SSIM_TAPS'], _C['P3D_VIDEO_SSIM_SHIFT'], _C['P3D_VIDEO_SSIM_C1'], _C['P3D_VIDEO_SSIM_C2']
 HALO = TAPS - 1
 S_BITS = 20                                          # the 2-D weights sum to S = 2^20
@@ -37,8 +37,8 @@ def ssim_window():
 
 def _check_pair(a, b, what):
     """(F, H, W, bpp) of two clips of one shape on one device."""
-    f, h, w = video._check_frames(a, f'{what}: a', bpp=(1, 2, 3, 4))
-    video._check_frames(b, f'{what}: b', bpp=(1, 2, 3, 4))
+    f, h, w = clips.check_frames(a, f'{what}: a', bpp=(1, 2, 3, 4))
+    clips.check_frames(b, f'{what}: b', bpp=(1, 2, 3, 4))
     if a.shape != b.shape:
         raise ValueError(f'{what}: a is {tuple(a.shape)}, b is {tuple(b.shape)}')
     if a.device != b.device:
@@ -85,8 +85,8 @@ def error_sums(a, b, out=None):
     if not a.is_cuda:
         return _error_sums_torch(a, b, out)
     with _lib.kernel_timer('video_error_sums', out):
-        code = video.video_lib().p3d_video_error_sums(*_pair(a, b, bpp), _lib.ptr(out), _lib.stream_of(out))
-    video._check(code, 'video_error_sums')
+        code = clips.video_lib().p3d_video_error_sums(*_pair(a, b, bpp), _lib.ptr(out), _lib.stream_of(out))
+    clips.check(code, 'video_error_sums')
     return out
 
 
@@ -139,8 +139,8 @@ def ssim_sums(a, b, out=None, maps=False):
             heat = _ssim_torch(a, b, out, maps)
         else:
             with _lib.kernel_timer('video_ssim', out):
-                code = video.video_lib().p3d_video_ssim(*_pair(a, b, bpp), _lib.ptr(out), _lib.ptr(heat), _lib.stream_of(out))
-            video._check(code, 'video_ssim')
+                code = clips.video_lib().p3d_video_ssim(*_pair(a, b, bpp), _lib.ptr(out), _lib.ptr(heat), _lib.stream_of(out))
+            clips.check(code, 'video_ssim')
     return (out, heat) if maps else out
 
 

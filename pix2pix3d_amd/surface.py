@@ -602,12 +602,8 @@ def geometry_video(G, ws, cfg='seg2cat', n_frames=120, views_per_step=4, resolut
     clip, made and applied on the frames' device).  ``format='avi'``: a true-colour Motion-JPEG AVI through ``video.save_avi`` instead, encoded on the
     frames' device (``gif`` plays no part) — with ``psnr`` or ``ssim`` (one of them) at the quality that ``video.jpeg_quality_for`` picks for that target;
     ``format='apng'``: a lossless animated PNG through ``video.save_apng``, likewise."""
-    if gif not in ('pil', 'device'):
-        raise ValueError(f"geometry_video: gif must be 'pil' or 'device', got {gif!r}")
-    if format not in ('gif', 'avi', 'apng'):
-        raise ValueError(f"geometry_video: format must be 'gif', 'avi' or 'apng', got {format!r}")
-    if (psnr is not None or ssim is not None) and format != 'avi':
-        raise ValueError(f"geometry_video: psnr / ssim pick a JPEG quality and need format='avi', got {format!r}")
+    from .video.clip import check_clip_options, save_clip
+    check_clip_options('geometry_video', gif, format, psnr, ssim)
     step = int(views_per_step)
     if step < 1:
         raise ValueError(f'geometry_video: views_per_step must be >= 1, got {views_per_step}')
@@ -617,15 +613,6 @@ def geometry_video(G, ws, cfg='seg2cat', n_frames=120, views_per_step=4, resolut
         kw['planes'] = shape._planes(G, ws, noise_mode=kw.get('noise_mode', 'const'))
     frames = [render(G, ws, cameras[s:s + step], resolution, color=color, **kw) for s in range(0, cameras.shape[0], step)]
     out = torch.cat(frames) if frames else torch.empty([0, int(resolution), int(resolution), 3], dtype=torch.uint8, device=ws.device)
-    if path is not None and format == 'avi':
-        from . import video
-        video.save_avi(path, out, fps=fps, psnr=psnr, ssim=ssim)
-    elif path is not None and format == 'apng':
-        from . import video
-        video.save_apng(path, out, fps=fps)
-    elif path is not None and gif == 'device':
-        from . import video
-        video.save_gif(path, out, fps=fps)
-    elif path is not None:
-        mesh.save_gif(path, out.cpu().numpy(), fps=fps)
+    if path is not None:
+        save_clip(path, out, fps=fps, format=format, gif=gif, psnr=psnr, ssim=ssim, who='geometry_video')
     return out

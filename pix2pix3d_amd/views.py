@@ -338,55 +338,24 @@ def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=12
     for the edge generators, as 8-bit grey.  ``psnr`` / ``ssim`` (``format='avi'`` only, one of them): a target for the image clip instead of the default
     quality — ``video.jpeg_quality_for`` picks the setting where the frames are, the dict gains 'jpeg_quality': ``(quality, metrics, met)``, and the label
     clip goes through ``video.save_avi`` with the same target.  Returns ``render_views``' dict."""
-    if gif not in ('pil', 'device'):
-        raise ValueError(f"generate_video: gif must be 'pil' or 'device', got {gif!r}")
-    if format not in ('gif', 'avi', 'apng'):
-        raise ValueError(f"generate_video: format must be 'gif', 'avi' or 'apng', got {format!r}")
-    if (psnr is not None or ssim is not None) and format != 'avi':
-        raise ValueError(f"generate_video: psnr / ssim pick a JPEG quality and need format='avi', got {format!r}")
+    from .video.clip import check_clip_options, save_clip
+    check_clip_options('generate_video', gif, format, psnr, ssim)
     cams = video_cameras(G, cfg, n_frames).to(ws.device)
     render_kwargs.setdefault('noise_mode', 'const')
     render_kwargs.setdefault('neural_rendering_resolution', VIDEO_CFG[cfg]['neural_rendering_resolution'])
     frames = render_views(G, ws, cams, **render_kwargs)
+    how = dict(fps=fps, format=format, gif=gif, psnr=psnr, ssim=ssim, who='generate_video')
     if path is not None:
-        if format == 'avi':
-            from . import video
-            if psnr is None and ssim is None:
-                video.save_avi(path, frames['image'], fps=fps)
-            else:
-                frames['jpeg_quality'] = video.jpeg_quality_for(frames['image'], psnr, ssim)
-                video.save_avi(path, frames['image'], fps=fps, quality=frames['jpeg_quality'][0])
-        elif format == 'apng':
-            from . import video
-            video.save_apng(path, frames['image'], fps=fps)
-        elif gif == 'device':
-            from . import video
-            video.save_gif(path, frames['image'], fps=fps)
-        else:
-            mesh.save_gif(path, frames['image'], fps=fps)
+        chosen = save_clip(path, frames['image'], **how)
+        if chosen is not None:
+            frames['jpeg_quality'] = chosen
     if path_label is not None:
         if 'label' not in frames:
             raise ValueError(f'generate_video: {type(G).__name__} has no label output for path_label')
-        if format == 'avi':
-            from . import video
-            label = frames['label']                                            # (the edge generators' frames are grey: [F, H, W])
-            video.save_avi(path_label, label if label.ndim == 4 else label[..., None].expand(-1, -1, -1, 3).contiguous(), fps=fps, psnr=psnr, ssim=ssim)
-        elif format == 'apng':
-            from . import video
-            if 'label_index' in frames:
-                pal = render_kwargs.get('palette')
-                video.save_apng(path_label, frames['label_index'], fps=fps, mode='P', palette=mesh.default_palette(256) if pal is None else torch.as_tensor(pal))
-            else:
-                video.save_apng(path_label, frames['label'], fps=fps)
-        elif gif == 'device':
-            from . import video
-            if 'label_index' in frames:                                        # default_palette(c) is the first c rows of default_palette(256)
-                pal = render_kwargs.get('palette')
-                video.save_gif_indexed(path_label, frames['label_index'], mesh.default_palette(256) if pal is None else torch.as_tensor(pal), fps=fps)
-            else:
-                video.save_gif_indexed(path_label, frames['label'], torch.arange(256, dtype=torch.uint8)[:, None].expand(256, 3), fps=fps)
-        else:
-            mesh.save_gif(path_label, frames['label'], fps=fps)
+        indices, pal = frames.get('label_index'), render_kwargs.get('palette')  # (the edge generators' frames are grey, [F, H, W], and have no indices)
+        if indices is not None:                                                # default_palette(c) is the first c rows of default_palette(256)
+            pal = mesh.default_palette(256) if pal is None else torch.as_tensor(pal)
+        save_clip(path_label, frames['label'], indices=indices, palette=pal, **how)
     return frames
 
 

@@ -1,4 +1,4 @@
-"""Frame quality on the host (pix2pix3d_amd/quality.py, the decode side of video.py): the torch formulations — the definitions the
+"""Frame quality on the host (pix2pix3d_amd/quality.py, the decode side of video/jpeg.py): the torch formulations — the definitions the
 device kernels must equal — against first principles, the fixed-point SSIM window against the true Gaussian, the decoder against an fp64 inverse and
 against PIL, the post-condition of the quality search, and the argument checks of the library and of Python.  No GPU: the library's checks run before any
 device call."""
@@ -346,10 +346,11 @@ def test_python_refuses_bad_arguments():
 
 
 def test_what_quality_calls_is_declared():
-    """tests/test_side_libraries.py scans video.py for ``video_lib().p3d_*``; the same scan of the second module that calls libp3d_video.so."""
+    """tests/test_side_libraries.py scans every module that calls libp3d_video.so for ``video_lib().p3d_*``; the same scan of this one, and of the module
+    that holds ``jpeg_decode``."""
     Q, video = _q(), _video()
     called = set(re.findall(r'\bvideo_lib\(\)\.(p3d_\w+)', pathlib.Path(Q.__file__).read_text()))
     assert called == {'p3d_video_error_sums', 'p3d_video_ssim'} and called <= set(video.HEADER.functions)
     names = list(video.HEADER.functions)
     assert names[0] == 'p3d_video_histogram' and names[-3:] == ['p3d_video_error_sums', 'p3d_video_ssim', 'p3d_video_jpeg_decode']      # appended after the PNG ones
-    assert 'p3d_video_jpeg_decode' in set(re.findall(r'\bvideo_lib\(\)\.(p3d_\w+)', pathlib.Path(video.__file__).read_text()))
+    assert 'p3d_video_jpeg_decode' in set(re.findall(r'\bvideo_lib\(\)\.(p3d_\w+)', pathlib.Path(video.jpeg.__file__).read_text()))

@@ -14,15 +14,20 @@ from pix2pix3d_amd import build
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 SERVICES = {'p3d_last_error', 'p3d_launch_count'}      # every side library links its own copy; their signatures come from the product header
-# library -> (every module of pix2pix3d_amd that calls it, the one that holds the SideLibrary first; the accessor their calls go through).  A feature
-# that adds entry points to a library adds its module here and its prototypes to the library's one header: never a second header or a binding of its own.
-BOUND_BY = {'probes': (('diagnostics',), 'probes'), 'regions': (('regions', 'evaluate', 'reproject'), 'regions_lib'), 'video': (('video',), 'video_lib'),
-            'sketch': (('sketch',), 'sketch_lib')}
+# library -> (every module of pix2pix3d_amd that calls it; the accessor their calls go through; the module that holds the SideLibrary, where that is not the
+# first caller: ``clips`` holds the video library and calls nothing itself).  A feature that adds entry points to a library adds its module here and its
+# prototypes to the library's one header: never a second header or a binding of its own.
+BOUND_BY = {'probes': (('diagnostics',), 'probes'), 'regions': (('regions', 'evaluate', 'reproject'), 'regions_lib'),
+            'video': (('video.gif', 'video.jpeg', 'video.jpeg_read', 'video.png', 'quality'), 'video_lib', 'clips'), 'sketch': (('sketch',), 'sketch_lib')}
 NAMES = sorted(build.SIDE_LIBRARIES)
 
 
 def _module(name, k=0):
     return importlib.import_module('pix2pix3d_amd.' + BOUND_BY[name][0][k])
+
+
+def _holder(name):
+    return importlib.import_module('pix2pix3d_amd.' + BOUND_BY[name][2]) if len(BOUND_BY[name]) > 2 else _module(name)
 
 
 def _exported(path, names):
@@ -32,13 +37,19 @@ def _exported(path, names):
 
 @pytest.mark.parametrize('name', NAMES)
 def test_calls_are_declared(name):
-    module, accessor = _module(name), BOUND_BY[name][1]
+    module, accessor = _holder(name), BOUND_BY[name][1]
     assert getattr(module, accessor) == module._side.lib and module.HEADER is module._side.header
     declared = set(module.HEADER.functions)
+    called_by_all = set()
     for k in range(len(BOUND_BY[name][0])):
         caller = _module(name, k)
         called = set(re.findall(r'\b%s\(\)\.(p3d_\w+)' % accessor, pathlib.Path(caller.__file__).read_text()))
         assert called - SERVICES and called - SERVICES <= declared, (name, caller.__name__, sorted(called - SERVICES - declared))
+        called_by_all |= called - SERVICES
+    if name == 'video':                                                          # every entry point has a caller among the modules of the row
+        from pix2pix3d_amd import video
+        assert called_by_all == declared, sorted(declared - called_by_all)
+        assert video._side is module._side and video.HEADER is module.HEADER and video.video_lib == module.video_lib
 
 
 def _defined(sources):
@@ -84,17 +95,17 @@ def test_only_the_five_headers_have_prototypes():
 @pytest.mark.parametrize('name', NAMES)
 def test_headers_are_disjoint(name):
     from pix2pix3d_amd import _lib
-    declared = set(_module(name).HEADER.functions)
+    declared = set(_holder(name).HEADER.functions)
     assert declared and not declared & set(_lib.HEADER.functions)
     for other in NAMES:
         if other != name:
-            assert not declared & set(_module(other).HEADER.functions), (name, other)
+            assert not declared & set(_holder(other).HEADER.functions), (name, other)
 
 
 @pytest.mark.parametrize('name', NAMES)
 def test_exports_are_right(name):
     from pix2pix3d_amd import _lib
-    module = _module(name)
+    module = _holder(name)
     declared = set(module.HEADER.functions)
     assert module._side.path == build.side_paths(name).lib
     assert _exported(module._side.path, declared | SERVICES) == declared | SERVICES
@@ -103,7 +114,7 @@ def test_exports_are_right(name):
 
 @pytest.mark.parametrize('name', NAMES)
 def test_binding_is_complete(name):
-    side = _module(name)._side
+    side = _holder(name)._side
     side.lib()
     assert [n for n in sorted(set(side.header.functions) | SERVICES) if getattr(side._raw, n).argtypes is None] == []
 
@@ -112,7 +123,7 @@ def test_binding_is_complete(name):
 def test_the_launch_counter_is_wired(name):
     """The first declared entry point with null pointers (1 for every integer: one frame, one pixel): its null check comes before any device call."""
     from pix2pix3d_amd import _lib
-    side = _module(name)._side
+    side = _holder(name)._side
     n0 = side.launch_count()
     assert type(n0) is int
     fn_name, (_, argtypes) = next(iter(side.header.functions.items()))

@@ -1,7 +1,6 @@
 """pix2pix3d_amd.video's baseline JPEG and Motion-JPEG AVI on the host: the tables against their formulas and against the files PIL writes, the integer DCT
 against fp64, the vectorised entropy coder against a bit-by-bit one on crafted blocks, byte stuffing, every stream decoded by PIL and its PSNR held
 against PIL's own encoder with the same tables, the AVI container's structure, and the default path of the video writers unchanged."""
-import os
 import re
 import struct
 
@@ -12,6 +11,7 @@ import torch
 from jpeg_cases import (PICTURES, SUBSAMPLINGS, canonical_codes, decode, frames_of, pil_jpeg, psnr, random_coefficients, reference_scan, split_jpeg,
                         tables_of)
 from model_cases import build_generator
+from pix2pix3d_amd import build
 from video_cases import gradient_frames, noise_frames
 
 
@@ -33,7 +33,7 @@ def test_the_dct_table_equals_its_formula_and_the_header_literals():
     want = np.round(8192 * np.where(u == 0, np.sqrt(1 / 8), 0.5) * np.cos((2 * x + 1) * u * np.pi / 16)).astype(np.int64)
     assert np.array_equal(t.numpy(), want)
     assert t[0].tolist() == [2896] * 8 and t[1, :4].tolist() == [4017, 3406, 2276, 799]
-    with open(os.path.join(os.path.dirname(video.__file__), 'csrc', 'video', 'p3d_video.h')) as fh:
+    with open(build.side_paths('video').header) as fh:
         rows = re.findall(r'#define P3D_VIDEO_JPEG_DCT_ROW(\d) (.*)', fh.read())
     assert [int(i) for i, _ in rows] == list(range(8))
     assert [[int(v) for v in row.split(',')] for _, row in rows] == want.tolist()
@@ -285,7 +285,7 @@ def test_an_avi_needs_a_frame_and_stays_below_2_gib(tmp_path, monkeypatch):
     video = _video()
     with pytest.raises(ValueError):
         video.save_avi(tmp_path / 'none.avi', torch.empty([0, 8, 8, 3], dtype=torch.uint8))
-    monkeypatch.setattr(video, 'MAX_AVI_BYTES', 2000)
+    monkeypatch.setattr(video.avi, 'MAX_AVI_BYTES', 2000)
     with pytest.raises(ValueError):
         video.save_avi(tmp_path / 'large.avi', noise_frames(2, 24, 40), quality=100)
     assert not (tmp_path / 'none.avi').exists() and not (tmp_path / 'large.avi').exists()
