@@ -187,6 +187,65 @@ int p3d_video_png_emit(const uint8_t* filtered, int32_t n_frames, int32_t h, int
                        const uint32_t* headers, const int32_t* header_bits, const uint32_t* adler, const int64_t* offsets, uint8_t* data,
                        int64_t data_bytes, p3d_stream_t stream);
 
+/* ---- the way back from a lossless file: RFC 1951 inflate and the inverse of FILTER (video_png_read.hip, png_inflate.h) ----------
+ * data uint8 [data_bytes]: raw deflate bytes — the zlib streams of all frames without their two header bytes and their four Adler bytes.  The bytes
+ * need not come from us; the Python formulation of pix2pix3d_amd/video/png_read.py is the definition, the device result equals it.
+ * PARTS.  parts int64 [n_parts][5]: in_begin, in_end, out_begin, out_end, final.  A part is a run of whole deflate blocks that begins on the first bit
+ * of the byte in_begin; it is decoded on its own into out[out_begin, out_end).  in_begin / in_end are clamped to 0 .. data_bytes, out_begin / out_end
+ * to 0 .. out_bytes, each end to no less than its begin.  A foreign stream is ONE part with final = 1; a stream whose segment boundaries are known is a
+ * part a segment, the last alone with final = 1.  The out ranges of different parts must not overlap (where they do, any of their bytes may stand).
+ * BITS.  A part's bytes, least significant bit first.  Past in_end the bits are zeros, and reading one sets EXHAUSTED.
+ * BLOCKS.  BFINAL (1 bit), BTYPE (2 bits).  BTYPE 3: BLOCK_TYPE.  BFINAL = 1 in a part that is not final: BOUNDARY.
+ *   Stored (0): the bits up to the next byte are skipped, then LEN and NLEN, 16 bits each; LEN != ~NLEN: STORED.  LEN bytes are copied; a byte at or
+ *   past in_end: EXHAUSTED, else a byte for out_end or beyond: OVERFLOW.
+ *   Fixed (1): the codes of RFC 1951 section 3.2.6 — literal/length lengths 8 (0 .. 143), 9 (.. 255), 7 (.. 279), 8 (.. 287), 32 distance codes of 5.
+ *   Dynamic (2): HLIT + 257 (5 bits), HDIST + 1 (5), HCLEN + 4 (4); more than 286 literal/length or 30 distance codes: CODE_LENGTHS.  HCLEN lengths of
+ *   3 bits for the code-length code in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15, the rest 0.  Then HLIT + HDIST lengths under that
+ *   code: 0 .. 15 a length; 16 the length before it 3 + (2 bits) times (nothing before it: CODE_LENGTHS); 17 zero 3 + (3 bits) times; 18 zero
+ *   11 + (7 bits) times; a repeat past HLIT + HDIST: CODE_LENGTHS.  An over-subscribed code (sum of 2^-length over its used symbols above 1), of any
+ *   of the three kinds: CODE_LENGTHS.  An incomplete code is accepted.
+ * SYMBOLS.  Codes are canonical (RFC 1951 section 3.2.2), read from their most significant bit: the first length l = 1 .. 15 at which the bits so far
+ * are a code of that length gives the symbol and l bits count as read; none: NO_CODE, and 15 bits count as read.  Literal/length 0 .. 255: the byte
+ * (at or past out_end: OVERFLOW, and it is not written); 256 ends the block; 286 and 287: NO_CODE; else with k = symbol - 257 the length 3 + k
+ * (k < 8), 258 (k = 28), else 3 + ((4 + (k & 3)) << e) + (e extra bits), e = (k - 4) >> 2.  Then a distance symbol d (30, 31: NO_CODE): 1 + d (d < 4),
+ * else 1 + ((2 + (d & 1)) << e) + (e extra bits), e = (d >> 1) - 1.  A distance above the bytes the part has written: DISTANCE, and nothing is copied.
+ * The match is copied byte by byte in order (an overlapping match repeats itself); a byte for out_end or beyond: OVERFLOW, the bytes before it stay.
+ * THE END.  A final part ends after the block with BFINAL = 1: one or more whole bytes unread before in_end: LEFTOVER.  A part that is not final ends
+ * after the first block that ends on the bit 8 in_end exactly.  Either kind that ends with fewer than out_end - out_begin bytes written: SHORT.
+ * STATUS.  After every block header, every symbol and every run of extra bits the status is looked at: with a bit set the part ends there, what it wrote
+ * stays, the rest of its range stays zero, and no other part is touched.  status int32 [n_parts] receives the bits; 0: the part decoded cleanly.
+ * TWO launches: an asynchronous fill zeroes out (counted as one), then a lane per part, P3D_VIDEO_PNG_INFLATE_LANES lanes a work-group, the decode
+ * tables of every lane in LDS.  No read leaves [in_begin, in_end), no store [out_begin, out_end), a match reads only inside [out_begin, out_end), and
+ * every loop is bounded, whatever the bytes hold.  n_parts = 0 launches nothing.
+ * WHY PARTS ARE SOUND.  If the parts of a stream tile its bytes and its output and every one reports 0, the bytes equal a serial decode: part 0 began
+ * on a true block boundary and ended on its in_end after a whole block, so part 1 began on one, and so on; every count was exact; no match looked
+ * outside its part.  A wrong list of parts shows as a status, never as a wrong picture.                                                                 */
+#define P3D_VIDEO_PNG_INFLATE_LANES 32
+#define P3D_VIDEO_PNG_STATUS_BLOCK_TYPE 1       /* BTYPE 3 */
+#define P3D_VIDEO_PNG_STATUS_STORED 2           /* LEN != ~NLEN */
+#define P3D_VIDEO_PNG_STATUS_CODE_LENGTHS 4     /* a dynamic header that describes no code */
+#define P3D_VIDEO_PNG_STATUS_NO_CODE 8          /* no code within 15 bits, or a symbol that stands for nothing */
+#define P3D_VIDEO_PNG_STATUS_DISTANCE 16        /* a match that reaches before the part's out_begin */
+#define P3D_VIDEO_PNG_STATUS_OVERFLOW 32        /* a byte for out_end or beyond */
+#define P3D_VIDEO_PNG_STATUS_EXHAUSTED 64       /* bits read past in_end */
+#define P3D_VIDEO_PNG_STATUS_LEFTOVER 128       /* whole bytes unread after the final block */
+#define P3D_VIDEO_PNG_STATUS_BOUNDARY 256       /* BFINAL = 1 in a part that is not final */
+#define P3D_VIDEO_PNG_STATUS_SHORT 512          /* fewer bytes written than the part's range holds */
+#define P3D_VIDEO_PNG_STATUS_FILTER 1024        /* a frame: a filter type above 4 (p3d_video_png_unfilter) */
+#define P3D_VIDEO_PNG_STATUS_ADLER 2048         /* a frame: the Adler-32 of the inflated bytes is not the stream's (set by png_read.py) */
+int p3d_video_png_inflate(const uint8_t* data, int64_t data_bytes, const int64_t* parts, int32_t n_parts, uint8_t* out, int64_t out_bytes,
+                          int32_t* status, p3d_stream_t stream);
+
+/* UNFILTER: the exact inverse of FILTER above.  filtered uint8 [n_frames][h][1 + w bpp], contiguous, as p3d_video_png_filter writes it, bpp = 1 .. 8
+ * (6 and 8: 16-bit colour, which the file reader refuses but the rule does not).  Per byte x = (residual + predictor) mod 256, the predictor of the
+ * row's type from the RECONSTRUCTED a (bpp bytes to the left, 0 for the first pixel), b (above, 0 in a frame's first row: every frame on its own) and
+ * c (above a).  A type byte above 4 sets the frame's FILTER bit, and the row is taken as type 0.  frames uint8 [n_frames][h][w][bpp] with
+ * frame_pitch / row_pitch (>= w bpp); bytes between rows stay untouched; it must not overlap filtered.  status int32 [n_frames]: 0 or FILTER.
+ * n_frames h (1 + w bpp) < 2^31; n_frames h w = 0 launches nothing.  ONE launch: a wave a frame, a lane a row of a band of 64 rows, each lane one
+ * pixel behind the lane above it.                                                                                                                       */
+int p3d_video_png_unfilter(const uint8_t* filtered, int32_t n_frames, int32_t h, int32_t w, int32_t bpp, uint8_t* frames, int64_t frame_pitch,
+                           int64_t row_pitch, int32_t* status, p3d_stream_t stream);
+
 /* ---- frame quality: error sums, SSIM and what a decoder shows for JPEG coefficients (video_quality.hip, video_jpeg_decode.hip) ----
  * Two clips a and b, uint8 [n_frames][h][w][bpp], bpp = 1 .. 4, each with its own frame_pitch / row_pitch (>= w bpp) as above, are compared where they are.
  * n_frames, h, w >= 0 and n_frames h w bpp < 2^31.  The results ACCUMULATE into int64 counters that the caller zeroed: calls add up, in any order (integer

@@ -651,3 +651,13 @@ class EditSession(_StageSession):
         Image.fromarray(mask.numpy()).save(os.path.join(directory, 'mask.png'))
         Image.fromarray(self.palette.cpu()[mask.long()].numpy()).save(os.path.join(directory, 'mask_color.png'))
         Image.fromarray(self.render()['image'].cpu().numpy()).save(os.path.join(directory, 'output.png'))
+
+
+def load_mask(path, device=None):
+    """uint8 [H, W] on ``device``: the label map that ``EditSession.save`` wrote as mask.png (or any 8-bit grey PNG), read and decoded where it will be
+    used — ``video.load_png``: no PIL, no numpy array, no second upload.  ValueError for a file that is not 8-bit grey."""
+    from . import video
+    mask, info = video.load_png(path, device)
+    if info.mode != 'L':
+        raise ValueError(f'load_mask: {path} is mode {info.mode!r}: a label map is 8-bit grey (L)')
+    return mask

@@ -499,6 +499,16 @@ class SketchSession(edit._StageSession):
         Image.fromarray(self.render()['image'].cpu().numpy()).save(os.path.join(directory, 'output.png'))
 
 
+def load_canvas(path, device=None):
+    """uint8 [H, W] on ``device``: the ink that ``SketchSession.save`` wrote as canvas.png (or any 8-bit grey PNG), read and decoded where it will be used
+    — ``video.load_png``.  ValueError for a file that is not 8-bit grey."""
+    from . import video
+    canvas, info = video.load_png(path, device)
+    if info.mode != 'L':
+        raise ValueError(f'load_canvas: {path} is mode {info.mode!r}: a canvas is 8-bit grey (L)')
+    return canvas
+
+
 if __name__ == '__main__':
     with open(THIN_TABLE_PATH, 'w') as f:
         f.write(thin_table_header())

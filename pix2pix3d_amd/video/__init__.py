@@ -6,6 +6,8 @@
     jpeg_read      the way back from a file: ``jpeg_parse``, ``jpeg_unscan``, ``decode_jpeg``, ``load_jpeg`` (section 2.1y)
     avi            Motion-JPEG AVI: ``save_avi``, ``read_avi``, ``decode_avi``, ``check_avi``
     png            lossless PNG and APNG: ``encode_png``, ``save_png``, ``save_png_sequence``, ``save_apng``, ``png_chunks`` (section 2.1v)
+    png_read       the way back from a lossless file: ``png_parse``, ``png_inflate``, ``png_unfilter``, ``decode_png``, ``load_png``, ``decode_apng``,
+                   ``check_png``, ``png_rgb`` (section 2.1z)
     clip           ``save_clip``: the one choice among these writers that ``views.generate_video`` and ``surface.geometry_video`` offer
 
 Everywhere the same rule: csrc/video/p3d_video.h states every step in integers, the torch / numpy formulation that CPU tensors take is the definition, and
@@ -21,4 +23,6 @@ from .avi import MAX_AVI_BYTES, check_avi, decode_avi, read_avi, save_avi
 from .png import (PNG_ADAPTIVE, PNG_FILTERS, PNG_HEADER_WORDS, PNG_MAX_MATCH, PNG_MODES, PNG_SEGMENT_BYTES, PNG_STATS, PNG_SYMBOLS, depth16, encode_png,
                   png_block_header, png_canonical_codes, png_chunks, png_code_lengths, png_counts, png_deflate, png_filter, png_header, png_segment_rows, save_apng,
                   save_png, save_png_sequence)
+from .png_read import (PNG_INFLATE_LANES, PNG_STATUS, PngInfo, check_png, decode_apng, decode_png, load_png, png_inflate, png_parse, png_rgb, png_status_names,
+                       png_unfilter)
 from .clip import check_clip_options, save_clip

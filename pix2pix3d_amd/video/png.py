@@ -329,10 +329,15 @@ def png_deflate(filtered, segment_rows):
     on a byte), then the Adler-32.  Device tensors: ``p3d_video_png_count``, the copy of the counts to the host — the ONLY synchronisation —, there one code, one
     block header and the exact byte length of every segment a frame, their upload in one pinned buffer, and ``p3d_video_png_emit``.  CPU tensors: the numpy
     formulation.  No pixel (F H = 0, or rows of the type byte only): no stream, ``offsets`` all 0."""
+    return _png_deflate(filtered, segment_rows)[:2]
+
+
+def _png_deflate(filtered, segment_rows):
+    """``png_deflate`` and, third, int64 numpy [F, S]: the bytes every segment takes in its frame's stream (what the segment index is made from)."""
     f, h, r = _check_filtered(filtered, 'png_deflate')
     rows = min(_check_segment_rows(segment_rows), max(h, 1))
     if f * h == 0 or r <= 1:
-        return torch.zeros([0], dtype=torch.uint8, device=filtered.device), torch.zeros([f + 1], dtype=torch.int64)
+        return torch.zeros([0], dtype=torch.uint8, device=filtered.device), torch.zeros([f + 1], dtype=torch.int64), np.zeros([f, 0], dtype=np.int64)
     filtered = filtered.contiguous()
     stats = png_counts(filtered, rows)
     host = stats.cpu().numpy().astype(np.int64)
@@ -353,7 +358,7 @@ def png_deflate(filtered, segment_rows):
                 part = slice(s * rows * r, s * rows * r + int(sizes[s]))
                 out[starts[i, s]:starts[i, s] + lengths[i, s]] = _png_segment_numpy(b[part], literals[part], match[part], plan, s == n_seg - 1, int(lengths[i, s]))
             out[offsets[i + 1] - 4:offsets[i + 1]] = list(plan.adler.to_bytes(4, 'big'))
-        return torch.from_numpy(out), torch.from_numpy(offsets.astype(np.int64))
+        return torch.from_numpy(out), torch.from_numpy(offsets.astype(np.int64)), lengths
     parts = [starts.astype(np.int64).reshape(-1), np.stack([p.table for p in plans]).reshape(-1), np.concatenate([p.header_words() for p in plans]),
              np.array([p.header_bits for p in plans], dtype=np.int32), np.array([p.adler for p in plans], dtype=np.uint32)]
     at = np.concatenate([[0], np.cumsum([p.nbytes for p in parts])])                 # the int64 part first: every part stays aligned
@@ -368,7 +373,7 @@ def png_deflate(filtered, segment_rows):
         code = video_lib().p3d_video_png_emit(_lib.ptr(filtered), f, h, r, rows, where[1], where[2], where[3], where[4], where[0], _lib.ptr(data), data.shape[0],
                                               _lib.stream_of(data))
     check(code, 'video_png_emit')
-    return data, torch.from_numpy(offsets.astype(np.int64))
+    return data, torch.from_numpy(offsets.astype(np.int64)), lengths
 
 
 def _png_chunk(kind, payload):
@@ -397,8 +402,15 @@ def png_header(h, w, mode, palette=None):
     return out + (_png_chunk(b'PLTE', _palette_bytes(palette)) if mode == 'P' else b'')
 
 
-def _png_streams(frames, mode, palette, filter, what):
-    """(frames' F, H, W, the mode, the zlib stream of every frame as bytes)."""
+def _segment_index(segment_rows, lengths):
+    """The seGM chunk of ONE frame whose segments take ``lengths`` bytes: big-endian uint32 ``segment_rows``, then for every segment but the first the offset
+    of its first byte in the frame's zlib stream.  An ancillary, private, unsafe-to-copy chunk: a reader that does not know it skips it, an editor drops it."""
+    firsts = 2 + np.cumsum(lengths)[:-1]
+    return _png_chunk(b'seGM', b''.join(int(v).to_bytes(4, 'big') for v in [segment_rows, *firsts.tolist()]))
+
+
+def _png_streams(frames, mode, palette, filter, what, index=False):
+    """(frames' F, H, W, the mode, the zlib stream of every frame as bytes, the seGM chunk of every frame: empty without ``index``)."""
     frames = torch.as_tensor(frames)
     if mode is None:
         if not torch.is_tensor(frames) or frames.ndim not in (3, 4) or (frames.ndim == 4 and frames.shape[3] not in (2, 3, 4)):
@@ -413,51 +425,54 @@ def _png_streams(frames, mode, palette, filter, what):
     if f and (h == 0 or w == 0):
         raise ValueError(f'{what}: a PNG has at least one pixel, got {h} x {w}')
     if f == 0:
-        return (f, h, w), mode, []
+        return (f, h, w), mode, [], []
     filtered = png_filter(frames, (0 if mode == 'P' else PNG_ADAPTIVE) if filter is None else filter)
-    data, offsets = png_deflate(filtered, png_segment_rows(w, bpp))
+    rows = png_segment_rows(w, bpp)
+    data, offsets, lengths = _png_deflate(filtered, rows)
     data, offsets = data.cpu().numpy().tobytes(), offsets.tolist()
-    return (f, h, w), mode, [data[offsets[i]:offsets[i + 1]] for i in range(f)]
+    return (f, h, w), mode, [data[offsets[i]:offsets[i + 1]] for i in range(f)], [_segment_index(rows, lengths[i]) if index else b'' for i in range(f)]
 
 
-def encode_png(frames, mode=None, palette=None, filter=None):
+def encode_png(frames, mode=None, palette=None, filter=None, index=False):
     """A list of ``bytes``, one complete PNG file per frame: ``png_header``, one IDAT with the frame's zlib stream, IEND.  Frames uint8, on the device or the host
     (or a numpy array), read in place whatever their pitches: [F, H, W] is 'L', [F, H, W, 2] 'LA', [F, H, W, 3] 'RGB', [F, H, W, 4] 'RGBA' when ``mode`` is None;
     ``mode='P'`` takes [F, H, W] indices with ``palette`` uint8 [n <= 256, 3] (every index below n: not checked, it would take a synchronisation), and
     ``mode='I;16'`` takes [F, H, W, 2] big-endian byte pairs (``depth16``).  ``filter``: see ``png_filter``; None is 'none' for 'P', as the specification
     recommends, and 'adaptive' otherwise.  Lossless: a decoder returns the frames' bytes.  From device frames: three launches (filter, count, emit), ONE
     synchronisation with the host (the segments' counts come down, one code a frame goes up) and ONE device -> host copy, of the compressed bytes.  The
-    chunks' CRC-32 is ``zlib.crc32`` on the host over those bytes."""
-    (f, h, w), mode, streams = _png_streams(frames, mode, palette, filter, 'encode_png')
+    chunks' CRC-32 is ``zlib.crc32`` on the host over those bytes.  ``index=True`` writes the segment index, a private ancillary chunk seGM before the
+    frame's data: ``png_read.decode_png`` then inflates every segment as a part of its own (a 512 x 512 RGB picture: 24 lanes, not one); any other
+    reader skips the chunk.  The default writes the bytes it always wrote."""
+    (f, h, w), mode, streams, indices = _png_streams(frames, mode, palette, filter, 'encode_png', index)
     if not streams:
         return []
     header, end = png_header(h, w, mode, palette), _png_chunk(b'IEND', b'')
-    return [header + _png_chunk(b'IDAT', s) + end for s in streams]
+    return [header + segments + _png_chunk(b'IDAT', s) + end for s, segments in zip(streams, indices)]
 
 
-def save_png(path, frame, mode=None, palette=None, filter=None):
+def save_png(path, frame, mode=None, palette=None, filter=None, index=False):
     """One frame — uint8 [H, W] or [H, W, bpp], on the device or the host — as a PNG file (``encode_png``).  Returns its bytes."""
     frame = torch.as_tensor(frame)
     if frame.ndim not in (2, 3):
         raise ValueError(f'save_png: frame must be uint8 [H, W] or [H, W, bpp], got {tuple(frame.shape)}')
-    stream, = encode_png(frame[None], mode, palette, filter)
+    stream, = encode_png(frame[None], mode, palette, filter, index)
     with open(path, 'wb') as fh:
         fh.write(stream)
     return stream
 
 
-def save_png_sequence(pattern, frames, mode=None, palette=None, filter=None):
+def save_png_sequence(pattern, frames, mode=None, palette=None, filter=None, index=False):
     """Every frame as a PNG file of its own, frame i at ``pattern.format(i)`` (say 'frame_{:04d}.png'), all encoded in one pass of ``encode_png``.  Returns
     the paths."""
     paths = []
-    for i, stream in enumerate(encode_png(frames, mode, palette, filter)):
+    for i, stream in enumerate(encode_png(frames, mode, palette, filter, index)):
         paths.append(str(pattern).format(i))
         with open(paths[-1], 'wb') as fh:
             fh.write(stream)
     return paths
 
 
-def save_apng(path, frames, fps=60, loops=0, mode=None, palette=None, filter=None):
+def save_apng(path, frames, fps=60, loops=0, mode=None, palette=None, filter=None, index=False):
     """The frames (``encode_png``'s contract) as an animated PNG: IHDR (and PLTE), acTL (the number of frames; ``loops`` plays, 0 for ever), then per frame fcTL —
     the whole canvas, the delay 1 / ``fps`` as a fraction of 16-bit terms, dispose 0 (none), blend 0 (source) — and its zlib stream, as IDAT for frame 0 (a
     viewer without APNG shows it) and as fdAT after that, fcTL and fdAT sharing one running sequence number.  Every frame is coded whole: bit-exact and
@@ -471,7 +486,7 @@ def save_apng(path, frames, fps=60, loops=0, mode=None, palette=None, filter=Non
         raise ValueError(f'save_apng: a frame of {float(1 / rate)} s does not fit the 16-bit delay')
     if isinstance(loops, bool) or int(loops) != loops or not 0 <= int(loops) < 1 << 31:
         raise ValueError(f'save_apng: loops must be an integer >= 0, got {loops!r}')
-    (f, h, w), mode, streams = _png_streams(frames, mode, palette, filter, 'save_apng')
+    (f, h, w), mode, streams, indices = _png_streams(frames, mode, palette, filter, 'save_apng', index)
     if f == 0:
         raise ValueError('save_apng: an APNG needs at least one frame')
     out, sequence = [png_header(h, w, mode, palette), _png_chunk(b'acTL', f.to_bytes(4, 'big') + int(loops).to_bytes(4, 'big'))], 0
@@ -479,6 +494,7 @@ def save_apng(path, frames, fps=60, loops=0, mode=None, palette=None, filter=Non
         control = w.to_bytes(4, 'big') + h.to_bytes(4, 'big') + bytes(8) + delay.numerator.to_bytes(2, 'big') + delay.denominator.to_bytes(2, 'big') + bytes(2)
         out.append(_png_chunk(b'fcTL', sequence.to_bytes(4, 'big') + control))
         sequence += 1
+        out.append(indices[i])                                                      # (seGM, or nothing: it describes the data chunk that follows)
         if i == 0:
             out.append(_png_chunk(b'IDAT', s))
         else:
@@ -525,3 +541,22 @@ def depth16(depth, lo, hi):
     v = torch.floor((depth.to(torch.float64) - float(lo)) / (float(hi) - float(lo)) * 65535 + 0.5)
     v = torch.nan_to_num(v, nan=0.0).clamp(0, 65535).to(torch.int64)
     return torch.stack([v >> 8, v & 255], dim=-1).to(torch.uint8)
+
+
+# The two launches of the way back (png_read.py), beside the other calls into the library: every entry point of the PNG stages is
+# called from this module.
+def _inflate_launch(data, parts, out, status):
+    """``p3d_video_png_inflate`` on device tensors: the fill of ``out`` and a lane per row of ``parts``; no synchronisation."""
+    with _lib.kernel_timer('video_png_inflate', out):
+        code = video_lib().p3d_video_png_inflate(_lib.ptr(data), data.shape[0], _lib.ptr(parts), parts.shape[0], _lib.ptr(out), out.shape[0], _lib.ptr(status),
+                                                 _lib.stream_of(out))
+    check(code, 'video_png_inflate')
+
+
+def _unfilter_launch(filtered, bpp, frames, status):
+    """``p3d_video_png_unfilter`` on device tensors: ``filtered`` [F, H, 1 + W bpp] contiguous into the clip ``frames``, whatever its pitches."""
+    f, h, r = filtered.shape
+    with _lib.kernel_timer('video_png_unfilter', frames):
+        code = video_lib().p3d_video_png_unfilter(_lib.ptr(filtered), f, h, (r - 1) // bpp, bpp, _lib.ptr(frames), frames.stride(0), frames.stride(1),
+                                                  _lib.ptr(status), _lib.stream_of(frames))
+    check(code, 'video_png_unfilter')
