@@ -400,15 +400,15 @@ def atlas_views(G, ws, vertices, faces, cfg='seg2cat', size=2048, n_views=24, ji
 
 @torch.no_grad()
 def atlas_mesh(G, ws, cfg='seg2cat', size=2048, resolution=512, threshold=50., n_frames=120, image_size=512, keep=None, min_faces=1,
-               cell=None, n_views=24, jitter='frozen', path=None, bake_kwargs=None, render_kwargs=None, smooth=0, tolerance=None, **synthesis_kwargs):
+               cell=None, n_views=24, jitter='frozen', path=None, bake_kwargs=None, render_kwargs=None, smooth=0, tolerance=None, target_faces=None, **synthesis_kwargs):
     """``texture.textured_mesh`` with a texture image instead of vertex colours: the clean-up geometry of ``mesh.extract_mesh``
-    (``resolution`` .. ``cell``, or ``tolerance`` in its place; decimate with either so that the faces fit the atlas with cells worth having), ``orient_faces``,
+    (``resolution`` .. ``cell``, or ``tolerance`` or ``target_faces`` in its place; decimate with either so that the faces fit the atlas with cells worth having), ``orient_faces``,
     vertex normals, a ``size``^2 texture baked from ``n_views`` views (``atlas_views``; ``bake_kwargs`` go to the bake, ``render_kwargs``,
     on top of ``synthesis_kwargs``, to ``views.render_views``), the script's
     turntable rendered with it, and, with ``path``, the OBJ with its MTL and PNG.  ``smooth`` Taubin iterations (``mesh.smooth`` at its
     defaults) move the vertices right after the clean-up, before anything is oriented or baked.  Returns (vertices, faces, layout,
     texture uint8 [size, size, 3], seen int32 [K], frames uint8 [n_frames, image_size, image_size, 3])."""
-    vertices, faces = mesh._clean_geometry(G, ws, resolution, threshold, keep, min_faces, cell, tolerance, **synthesis_kwargs)
+    vertices, faces = mesh._clean_geometry(G, ws, resolution, threshold, keep, min_faces, cell, tolerance, target_faces, **synthesis_kwargs)
     if smooth and len(vertices):
         vertices = mesh.smooth(vertices, faces, smooth)
     faces = orient_faces(vertices, faces)

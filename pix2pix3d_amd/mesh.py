@@ -16,7 +16,8 @@
   (``trimesh.smoothing.filter_taubin``): neighbour lists and boundary flags from sorts, Taubin smoothing of positions or of any
   per-vertex attribute, majority voting of labels, and smooth shading through ``shade(..., normals=)`` (csrc/mesh_filter.hip on device
   tensors; the CPU formulation is the definition and the bytes are the same).
-* ``simplify_to``: ``simplify`` with the cell picked from a tolerance, measured by ``geometry.compare`` (geometry.py).
+* ``simplify_to``: ``simplify`` with the cell picked from a tolerance, measured by ``geometry.compare`` (geometry.py).  Quadric-error
+  decimation to a face count, which keeps what clustering rounds off, is ``decimate.decimate`` (decimate.py; ``target_faces=`` below).
 * ``extract_mesh``: shape.extract_geometry, the optional clean-up and filters, the labels and the turntable in one call.
 """
 import functools
@@ -1011,14 +1012,20 @@ def vertex_labels(G, ws, vertices, palette=None, max_batch=10_000_000):
     return labels.to(vertices.device), pal.to(vertices.device)[labels.to(vertices.device)]
 
 
-def _clean_geometry(G, ws, resolution, threshold, keep, min_faces, cell, tolerance=None, **synthesis_kwargs):
+def _clean_geometry(G, ws, resolution, threshold, keep, min_faces, cell, tolerance=None, target_faces=None, **synthesis_kwargs):
     """extract_mesh's geometry: shape.extract_geometry and the optional clean-up (see ``extract_mesh``).  ``tolerance`` (world units)
-    decimates through ``simplify_to`` instead of a given ``cell``; the two exclude each other."""
+    decimates through ``simplify_to`` instead of a given ``cell``, ``target_faces`` through ``decimate.decimate``; the three exclude
+    each other."""
     if cell is not None and tolerance is not None:
         raise ValueError('cell= and tolerance= exclude each other: give the cell, or the tolerance that picks it')
+    if target_faces is not None and (cell is not None or tolerance is not None):
+        raise ValueError('target_faces= excludes cell= and tolerance=: quadric-error decimation to a face count, or vertex clustering')
     vertices, faces = shape.extract_geometry(G, ws, resolution, threshold, **synthesis_kwargs)
     if keep is not None or min_faces > 1:
         vertices, faces, _ = clean(vertices, faces, keep, min_faces)
+    if target_faces is not None:
+        from . import decimate                                             # (decimate imports this module)
+        return decimate.decimate(vertices, faces, target_faces)[:2]        # collapses detach nothing: ``keep`` is not applied again
     if tolerance is not None and len(faces):
         vertices, faces, cell, _ = simplify_to(vertices, faces, tolerance)
     elif cell is not None:
@@ -1053,21 +1060,21 @@ def script_turntable(G, n_frames=120):
 
 @torch.no_grad()
 def extract_mesh(G, ws, resolution=512, threshold=50., n_frames=120, image_size=512, palette=None, keep=None, min_faces=1, cell=None,
-                 smooth=0, smooth_labels=0, smooth_shading=False, lam=0.5, mu=-0.53, tolerance=None, **synthesis_kwargs):
+                 smooth=0, smooth_labels=0, smooth_shading=False, lam=0.5, mu=-0.53, tolerance=None, target_faces=None, **synthesis_kwargs):
     """applications/extract_mesh.py after its inputs: shape.extract_geometry, per-vertex label colours unless G is an edge-map
     generator (data_type 'edge') or has no label channels, and the script's turntable — orthographic xmag = ymag = 0.3 at radius 1 (edge2car: 0.6 at 1.2) about
     G.rendering_kwargs['avg_camera_pivot'], image_size^2 pixels.  Returns (vertices, faces, vertex_colors or None, frames uint8
     [n_frames, image_size, image_size, 3]).  Clean-up, off by default, runs on the bare geometry before the labels and the
     turntable: ``clean(keep, min_faces)`` when ``keep`` is given or ``min_faces`` exceeds 1, then ``simplify(cell)`` when ``cell``
     (world units) is given, or ``simplify_to(tolerance)`` when ``tolerance`` (world units: the sampled Hausdorff distance the
-    decimation may cost) is given instead; both together are a ValueError.  Clustering can pinch a thin neck into an edge, which no face carries, and so detach a crumb (and leaves
+    decimation may cost) is given instead, or ``decimate.decimate(target_faces)`` (quadric-error edge collapses down to that many faces, which keep ridges and necks and detach nothing) when ``target_faces`` is; any two together are a ValueError.  Clustering can pinch a thin neck into an edge, which no face carries, and so detach a crumb (and leaves
     the vertices of cells whose faces all collapsed): with both ``keep`` and ``cell`` the component count asked for is applied to the
     simplified mesh once more, so that keep=1 hands over one component.  Filtering, off by default too, follows the clean-up and
     leaves the faces alone: the labels are read at the unsmoothed vertices (the decoder's own level set), ``smooth_labels`` voting
     steps (``mesh.smooth_labels``) go over them before they become colours, ``smooth`` Taubin iterations with ``lam`` and ``mu``
     (``mesh.smooth``, boundary pinned) then move the vertices that are returned and rendered, and ``smooth_shading`` renders with
     ``texture.vertex_normals`` of that mesh instead of face normals."""
-    vertices, faces = _clean_geometry(G, ws, resolution, threshold, keep, min_faces, cell, tolerance, **synthesis_kwargs)
+    vertices, faces = _clean_geometry(G, ws, resolution, threshold, keep, min_faces, cell, tolerance, target_faces, **synthesis_kwargs)
     edge = getattr(G, 'data_type', None) == 'edge'                      # the script's edge2car branch; every other generator is seg-like
     labelled = not edge and int(getattr(G, 'semantic_channels', 0) or 0) > 1
     adj = adjacency(faces, len(vertices)) if (smooth or smooth_labels) and len(vertices) else None

@@ -335,14 +335,14 @@ def bake_views(G, ws, vertices, faces, cfg='seg2cat', n_views=24, jitter='frozen
 
 @torch.no_grad()
 def textured_mesh(G, ws, cfg='seg2cat', resolution=512, threshold=50., n_frames=120, image_size=512, keep=None, min_faces=1, cell=None,
-                  n_views=24, jitter='frozen', path=None, bake_kwargs=None, smooth=0, tolerance=None, **synthesis_kwargs):
-    """``mesh.extract_mesh`` with the generator's appearance: its geometry and clean-up arguments (``resolution`` .. ``cell``, or ``tolerance`` in its place), colours
+                  n_views=24, jitter='frozen', path=None, bake_kwargs=None, smooth=0, tolerance=None, target_faces=None, **synthesis_kwargs):
+    """``mesh.extract_mesh`` with the generator's appearance: its geometry and clean-up arguments (``resolution`` .. ``cell``, or ``tolerance`` or ``target_faces`` in its place), colours
     baked from ``n_views`` views (``bake_views``; ``bake_kwargs`` go to ``bake_colors``), the script's turntable rendered with them,
     and, with ``path``, the PLY with colours and vertex normals.  ``smooth`` Taubin iterations (``mesh.smooth`` at its defaults) move
     the vertices right after the clean-up: the bake, the normals, the turntable and the file are the smoothed mesh's.  Works for every
     generator, label channels or not.  Returns
     (vertices, faces, colors uint8 [V, 3], seen int32 [V], frames uint8 [n_frames, image_size, image_size, 3])."""
-    vertices, faces = mesh._clean_geometry(G, ws, resolution, threshold, keep, min_faces, cell, tolerance, **synthesis_kwargs)
+    vertices, faces = mesh._clean_geometry(G, ws, resolution, threshold, keep, min_faces, cell, tolerance, target_faces, **synthesis_kwargs)
     if smooth and len(vertices):
         vertices = mesh.smooth(vertices, faces, smooth)
     render_kwargs = dict(synthesis_kwargs)
