@@ -152,6 +152,73 @@ int p3d_mesh_edge_select(const int32_t* rank, const int32_t* edges, int32_t n_ed
 int p3d_mesh_collapse(float* vertices, double* quadrics, int32_t* parent, int32_t n_vertices, int32_t* faces, int32_t n_faces,
                       const int32_t* edges, const uint8_t* apply, const float* target, int32_t n_edges, uint8_t* dead, p3d_stream_t stream);
 
+/* ---- frame resampling (csrc/sketch/frame_resample.hip; pix2pix3d_amd/resample.py) -------------------------------------
+ * Pillow's Image.resize on 8-bit clips, bit for bit: for 8-bit samples it is integer arithmetic on fixed-point coefficient tables.  The tables
+ * are made on the host (resample.py, Python floats); the three entry points below are the passes.  Why here: as for the mesh decimation above.
+ *
+ * A CLIP is uint8 [frames][h][w][bpp], 1 <= bpp <= 4: pixels contiguous, rows `*_row_pitch` bytes apart (>= w bpp), frames `*_frame_pitch` bytes
+ * apart (>= 0; for a destination of more than one frame, at least the bytes of a frame).  1 <= h, w and every output size <= P3D_RESAMPLE_MAX_SIZE;
+ * frames >= 0, and frames == 0 is a success that launches nothing.  All offsets are 64-bit.  Results are written out of place: the bytes the
+ * destination spans must not meet the source's.  The channels of a pixel are resampled independently (PIL's L, RGB, RGBX; its LA / RGBA path
+ * premultiplies alpha and is not this).
+ *
+ * Coefficients of one axis of in_size pixels resampled to out_size from the source interval [in0, in1) (default [0, in_size)).  Every float step
+ * is IEEE double with one rounding per operator, in exactly this order.  A filter is a function f and a support S:
+ *     box       f(x) = 1 if -0.5 < x <= 0.5, else 0                                                                        S = 0.5
+ *     bilinear  f(x) = 1 - |x| if |x| < 1, else 0                                                                          S = 1
+ *     hamming   f(x) = 1 if x == 0; 0 if |x| >= 1; otherwise with t = pi |x|: sin(t) / t * (0.54 + 0.46 cos(t))            S = 1
+ *     bicubic   a = -0.5; |x| < 1: ((a + 2) |x| - (a + 3)) |x| |x| + 1;  |x| < 2: (((|x| - 5) |x| + 8) |x| - 4) a;  else 0  S = 2
+ *     lanczos   sinc(x) sinc(x / 3) for -3 <= x < 3, else 0; sinc(0) = 1, otherwise with t = pi x: sin(t) / t              S = 3
+ *   1. scale = (in1 - in0) / out_size, fs = max(scale, 1.0), support = S fs, ksize = int(ceil(support)) * 2 + 1.
+ *   2. For the output xx: center = in0 + (xx + 0.5) scale.
+ *   3. xmin = max(int(center - support + 0.5), 0).
+ *   4. count = min(int(center + support + 0.5), in_size) - xmin.
+ *   5. w[i] = f((i + xmin - center + 0.5) (1.0 / fs)) for i < count.
+ *   6. ww = the sum of w[i] accumulated from 0.0 in index order; if ww != 0, w[i] = w[i] / ww.
+ *   7. k[i] = int(-0.5 + w[i] 2^22) if w[i] < 0, else int(0.5 + w[i] 2^22); int truncates toward zero.
+ *   8. Entries beyond count are 0.
+ * The tables: bounds int32 [out_size][2] = (xmin, count) and weights int32 [out_size][ksize], with 255 sum |k| + 2^21 < 2^31 for every output
+ * (resample.py checks it), so that the int32 accumulators never wrap.
+ *
+ * ONE PASS.  Each byte is out = min(max((2^21 + sum_i k[i] src[xmin + i]) >> 22, 0), 255): an arithmetic shift on int32, the sum per byte lane.
+ * TWO AXES: the horizontal pass first, into a uint8 intermediate, then the vertical pass on it; the rounding to uint8 between the passes is part
+ * of the definition.  The caller hands the horizontal pass only the source rows the vertical pass reads (a view: any row pitch will do).
+ *
+ * NEAREST: index tables int32 [ow] and [oh], made on the host by ACCUMULATION: s = in_size / out_size; xo = s 0.5; for each output
+ * idx = min(int(xo), in_size - 1), then xo += s.  (The closed form int((x + 0.5) in_size / out_size) differs from it at some sizes.)
+ *
+ * Every kernel clamps what it reads from a table into the axis before use: xmin to [0, in_size], count to [0, min(ksize, in_size - xmin)], a
+ * nearest index to [0, in_size - 1].  No load leaves a source row and no store leaves the output, whatever the tables hold.
+ * Null pointers, sizes out of range, bpp outside 1 .. 4, ksize < 1 and pitches below the rows return P3D_ERR_ARGUMENT before any launch.      */
+#define P3D_RESAMPLE_MAX_SIZE 32768       /* every side of a source or a result */
+#define P3D_RESAMPLE_TILE_W 64            /* the work-group tile of the passes (tests straddle it): output pixels of the horizontal pass and of the */
+#define P3D_RESAMPLE_TILE_H 16            /* gather, DWORDS of a row (4 P3D_RESAMPLE_TILE_W bytes) of the vertical pass; rows of all three */
+#define P3D_RESAMPLE_LDS_ROW_BYTES 1024   /* the horizontal pass stages a tile's source span in LDS while it is at most this long a row ... */
+#define P3D_RESAMPLE_LDS_TAPS 64          /* ... and ksize is at most this; a longer span or tap list is read from global memory directly */
+
+/* The horizontal pass: dst[f][y][xx][c] from src[f][y][xmin(xx) + i][c]; dst is [frames][h][ow][bpp].  A work-group owns P3D_RESAMPLE_TILE_W output
+ * pixels of P3D_RESAMPLE_TILE_H rows: it reads the bounds and the weights of its columns once (into LDS) and stages the source span those outputs
+ * read, [the smallest xmin, the largest xmin + count) of every row of the tile, into LDS once — unless the span is longer than
+ * P3D_RESAMPLE_LDS_ROW_BYTES or ksize exceeds P3D_RESAMPLE_LDS_TAPS (a 512 -> 1 Lanczos has 3073 taps), when every tap is read from global
+ * memory.  One launch.                                                                                                                  */
+int p3d_frame_resample_rows(const uint8_t* src, int64_t src_frame_pitch, int64_t src_row_pitch, int32_t frames, int32_t h, int32_t w, int32_t bpp,
+                            uint8_t* dst, int64_t dst_frame_pitch, int64_t dst_row_pitch, int32_t ow, const int32_t* bounds, const int32_t* weights,
+                            int32_t ksize, p3d_stream_t stream);
+
+/* The vertical pass, channel-agnostic: a row is w bpp bytes and output byte j of row yy is the weighted sum of byte j over count(yy) source rows;
+ * dst is [frames][oh][w][bpp].  A lane owns four consecutive bytes: a dword load where the source row's address allows and a dword store where
+ * the output row's does, single bytes everywhere else (rows that start at an odd byte, the row's tail).  A wave owns one output row at a time,
+ * so its bounds and weights are wave-uniform.  One launch.                                                                              */
+int p3d_frame_resample_columns(const uint8_t* src, int64_t src_frame_pitch, int64_t src_row_pitch, int32_t frames, int32_t h, int32_t w, int32_t bpp,
+                               uint8_t* dst, int64_t dst_frame_pitch, int64_t dst_row_pitch, int32_t oh, const int32_t* bounds,
+                               const int32_t* weights, int32_t ksize, p3d_stream_t stream);
+
+/* The gather: dst[f][yy][xx] = src[f][y_index[yy]][x_index[xx]], all bpp bytes; dst is [frames][oh][ow][bpp], x_index int32 [ow], y_index int32
+ * [oh].  One launch.                                                                                                                    */
+int p3d_frame_resample_nearest(const uint8_t* src, int64_t src_frame_pitch, int64_t src_row_pitch, int32_t frames, int32_t h, int32_t w, int32_t bpp,
+                               uint8_t* dst, int64_t dst_frame_pitch, int64_t dst_row_pitch, int32_t oh, int32_t ow, const int32_t* x_index,
+                               const int32_t* y_index, p3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -653,11 +653,15 @@ class EditSession(_StageSession):
         Image.fromarray(self.render()['image'].cpu().numpy()).save(os.path.join(directory, 'output.png'))
 
 
-def load_mask(path, device=None):
+def load_mask(path, device=None, size=None):
     """uint8 [H, W] on ``device``: the label map that ``EditSession.save`` wrote as mask.png (or any 8-bit grey PNG), read and decoded where it will be
-    used — ``video.load_png``: no PIL, no numpy array, no second upload.  ValueError for a file that is not 8-bit grey."""
+    used — ``video.load_png``: no PIL, no numpy array, no second upload.  ``size`` ((width, height) or an int): resized to it where it is with
+    ``resample.resize(..., 'nearest')`` — a label is never blended — so that a map of any size enters a session.  ValueError for a file that is not 8-bit grey."""
     from . import video
     mask, info = video.load_png(path, device)
     if info.mode != 'L':
         raise ValueError(f'load_mask: {path} is mode {info.mode!r}: a label map is 8-bit grey (L)')
+    if size is not None:
+        from .resample import resize
+        mask = resize(mask[None], size, 'nearest')[0]
     return mask

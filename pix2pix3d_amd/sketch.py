@@ -19,7 +19,8 @@ take — the definition — and device kernels whose bytes equal it:
 A tap that leaves the image reads the REFLECTED index (``_reflect``: i < 0 -> -i, then i >= n -> 2 n - 2 - i, then clamped to [0, n - 1]; reflect-101, defined
 for n = 1 and 2).  Images are uint8 with contiguous pixels and any row pitch, 1 .. 4096 pixels a side; zero-size images return empty results and launch nothing.
 ``blur3`` alone has no kernel of its own (``condition`` fuses it): it is the torch formulation on the tensor's device.  The library also houses the four
-kernels of the quadric-error mesh decimation (decimate.py calls them through ``sketch_lib()``; the header says why they live here).
+kernels of the quadric-error mesh decimation (decimate.py calls them through ``sketch_lib()``; the header says why they live here) and the three of
+frame resampling (resample.py, likewise).
 
 ``SketchSession`` is the edge counterpart of ``edit.EditSession`` on the same stages below the canvas (``edit._StageSession``):
 
@@ -500,13 +501,17 @@ class SketchSession(edit._StageSession):
         Image.fromarray(self.render()['image'].cpu().numpy()).save(os.path.join(directory, 'output.png'))
 
 
-def load_canvas(path, device=None):
+def load_canvas(path, device=None, size=None, filter='box'):
     """uint8 [H, W] on ``device``: the ink that ``SketchSession.save`` wrote as canvas.png (or any 8-bit grey PNG), read and decoded where it will be used
-    — ``video.load_png``.  ValueError for a file that is not 8-bit grey."""
+    — ``video.load_png``.  ``size`` ((width, height) or an int): resized to it where it is with ``resample.resize(..., filter)`` (the box filter
+    keeps the ink a canvas loses to a nearest lookup).  ValueError for a file that is not 8-bit grey."""
     from . import video
     canvas, info = video.load_png(path, device)
     if info.mode != 'L':
         raise ValueError(f'load_canvas: {path} is mode {info.mode!r}: a canvas is 8-bit grey (L)')
+    if size is not None:
+        from .resample import resize
+        canvas = resize(canvas[None], size, filter)[0]
     return canvas
 
 

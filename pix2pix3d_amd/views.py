@@ -316,9 +316,35 @@ def render_views(G, ws, cameras, views_per_step=4, jitter='random', neural_rende
 
 
 # ---- the scripts ------------------------------------------------------------------------------------------------------------
-def image_grid(frames, grid_size):
-    """Contact sheet: frames [N, H, W, C] or [N, H, W] -> [gh * H, gw * W(, C)] for ``grid_size = (gw, gh)``, row-major (training_loop.py:74-89)."""
+def _check_resample(who, size, resample):
+    """The ``size=`` / ``resample=`` pair of the scripts, checked before anything is rendered."""
+    from . import resample as rs
+    if resample not in rs.FILTERS:
+        raise ValueError(f'{who}: resample must be one of {rs.FILTERS}, got {resample!r}')
+    if size is not None:
+        rs._check_size(size, who)
+
+
+def resize_clips(frames, size, resample='lanczos'):
+    """The uint8 clips of a frames dict at ``size`` ((width, height) or an int), where they are (``resample.resize``): 'image' through the filter
+    ``resample``; 'label' and 'label_index' ALWAYS through 'nearest' — a label is never blended; anything else in the dict ('depth', 'float') keeps its size.
+    ``size=None``: the dict as it is."""
+    if size is None:
+        return frames
+    from .resample import resize
+    for key, how in (('image', resample), ('label', 'nearest'), ('label_index', 'nearest')):
+        if key in frames:
+            frames[key] = resize(frames[key], size, how)
+    return frames
+
+
+def image_grid(frames, grid_size, cell=None):
+    """Contact sheet: frames [N, H, W, C] or [N, H, W] -> [gh * H, gw * W(, C)] for ``grid_size = (gw, gh)``, row-major (training_loop.py:74-89).
+    ``cell`` ((width, height) or an int): every frame is resized to it first (``resample.thumbnails``: Lanczos, on the frames' device) — a thumbnail sheet."""
     gw, gh = grid_size
+    if cell is not None:
+        from .resample import thumbnails
+        frames = thumbnails(frames, cell)
     n, h, w = frames.shape[:3]
     if gw * gh != n:
         raise ValueError(f'image_grid: {n} frames do not fill a {gw} x {gh} grid')
@@ -327,7 +353,8 @@ def image_grid(frames, grid_size):
 
 
 @torch.no_grad()
-def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=120, fps=60, gif='pil', format='gif', psnr=None, ssim=None, **render_kwargs):
+def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=120, fps=60, gif='pil', format='gif', psnr=None, ssim=None, size=None,
+                   resample='lanczos', **render_kwargs):
     """generate_video.py after its inputs: the ``cfg`` cameras (``video_cameras``) at the script's ray resolution with ``noise_mode='const'``, rendered by
     ``render_views`` (its keyword arguments pass through); ``path`` / ``path_label`` receive the two GIFs the script writes with imageio at 60 fps.
     ``gif='pil'``: through ``mesh.save_gif``, PIL quantising every frame on the host.  ``gif='device'``: the image through ``video.save_gif`` (one palette for
@@ -337,13 +364,16 @@ def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=12
     ``video.save_apng``, encoded where the frames are — the image as RGB, the label video as palette indices (``label_index`` with the frames' palette) or,
     for the edge generators, as 8-bit grey.  ``psnr`` / ``ssim`` (``format='avi'`` only, one of them): a target for the image clip instead of the default
     quality — ``video.jpeg_quality_for`` picks the setting where the frames are, the dict gains 'jpeg_quality': ``(quality, metrics, met)``, and the label
-    clip goes through ``video.save_avi`` with the same target.  Returns ``render_views``' dict."""
+    clip goes through ``video.save_avi`` with the same target.  ``size`` ((width, height) or an int): the clips are resized where they are before the
+    writer and before any quality search (``resize_clips``: the image through the filter ``resample``, label and index frames through 'nearest'), and the
+    dict holds them at that size; ``size=None`` writes the same bytes as ever.  Returns ``render_views``' dict."""
     from .video.clip import check_clip_options, save_clip
     check_clip_options('generate_video', gif, format, psnr, ssim)
+    _check_resample('generate_video', size, resample)
     cams = video_cameras(G, cfg, n_frames).to(ws.device)
     render_kwargs.setdefault('noise_mode', 'const')
     render_kwargs.setdefault('neural_rendering_resolution', VIDEO_CFG[cfg]['neural_rendering_resolution'])
-    frames = render_views(G, ws, cams, **render_kwargs)
+    frames = resize_clips(render_views(G, ws, cams, **render_kwargs), size, resample)
     how = dict(fps=fps, format=format, gif=gif, psnr=psnr, ssim=ssim, who='generate_video')
     if path is not None:
         chosen = save_clip(path, frames['image'], **how)
@@ -364,14 +394,17 @@ def generate_sample(G, ws, camera, path_color=None, path_label=None, palette=Non
     """generate_samples.py:108-120 after its inputs: one ``G.synthesis(ws, camera, noise_mode='const')`` finished by ``finish_frames``; the image and the
     label map go to ``path_color`` / ``path_label`` through PIL.  ``png='device'``: through ``video.save_png`` instead, encoded where the frames are — the
     image as RGB, the label map as palette indices where ``label_index`` exists (the same pixels, a smaller file).  ``camera`` is a [25] or [N, 25] label.
-    Returns ``finish_frames``' dict."""
+    ``size=None, resample='lanczos'`` (keywords, taken out of ``synthesis_kwargs``: the positional parameters stay as they were): as for ``generate_video``
+    (``resize_clips`` before the files are written).  Returns ``finish_frames``' dict."""
     from PIL import Image
     if png not in ('pil', 'device'):
         raise ValueError(f"generate_sample: png must be 'pil' or 'device', got {png!r}")
+    size, resample = synthesis_kwargs.pop('size', None), synthesis_kwargs.pop('resample', 'lanczos')
+    _check_resample('generate_sample', size, resample)
     camera = torch.as_tensor(camera, dtype=torch.float32).to(ws.device).reshape(-1, 25)
     synthesis_kwargs.setdefault('noise_mode', 'const')
     out = G.synthesis(ws, camera, **synthesis_kwargs)
-    frames = finish_frames(out, palette=palette, label_mode='grey' if getattr(G, 'data_type', None) == 'edge' else 'auto')
+    frames = resize_clips(finish_frames(out, palette=palette, label_mode='grey' if getattr(G, 'data_type', None) == 'edge' else 'auto'), size, resample)
     for p, key in ((path_color, 'image'), (path_label, 'label')):
         if p is not None and png == 'device':
             from . import video
