@@ -24,7 +24,7 @@ CXXFLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-Wall', '-W
 SIDE_LIBRARIES = {'probes': ('-DP3D_BUILD_PROBES',),      # hardware probes the tests and the kernel studies use (diagnostics.py)
                   'regions': (),                         # region tools of the edit session, agreement metrics, cross-view reprojection (regions.py, evaluate.py, reproject.py)
                   'video': (),                           # frame encoders of the video writers: GIF, JPEG / MJPEG AVI, PNG / APNG (video/)
-                  'sketch': ()}                          # edge-map canvas of the sketch session (sketch.py); quadric-error mesh decimation (decimate.py)
+                  'sketch': ()}                          # edge-map canvas of the sketch session (sketch.py); quadric-error mesh decimation (decimate.py); frame resampling (resample.py); MS-SSIM (multiscale.py)
 SidePaths = collections.namedtuple('SidePaths', 'src_dir header lib obj_dir')
 
 

@@ -152,6 +152,55 @@ int p3d_mesh_edge_select(const int32_t* rank, const int32_t* edges, int32_t n_ed
 int p3d_mesh_collapse(float* vertices, double* quadrics, int32_t* parent, int32_t n_vertices, int32_t* faces, int32_t n_faces,
                       const int32_t* edges, const uint8_t* apply, const float* target, int32_t n_edges, uint8_t* dead, p3d_stream_t stream);
 
+/* ---- multi-scale frame quality (csrc/sketch/frame_multiscale.hip; pix2pix3d_amd/multiscale.py) ------------------------
+ * MS-SSIM (Wang, Simoncelli, Bovik 2003) between two clips over a pyramid made on the device, in the integers of p3d_video.h's SSIM.  Why
+ * here: as for the mesh decimation above — the video header's prototype list and the callers of its library are pinned by tests.
+ *
+ * A CLIP is uint8 [frames][h][w][bpp], 1 <= bpp <= 4, as in "frame resampling" below: pixels contiguous, any row and frame pitch, read in place.
+ *
+ * PYRAMID.  Level 0 is the clip.  Level k + 1 is floor(h / 2) x floor(w / 2); its sample (y, x, c) is
+ *     (s[2y][2x][c] + s[2y][2x + 1][c] + s[2y + 1][2x][c] + s[2y + 1][2x + 1][c] + 2) >> 2
+ * of level k: every channel on its own, one rounding, an odd last row or column dropped.  (NOT the 'box' filter of the resampling below, which
+ * rounds once per pass.)
+ *
+ * PER LEVEL, for clips a (x) and b (y) of one size: the 11 x 11 window P3D_VIDEO_SSIM_WINDOW, the exact moments A, B, Pxx, Pyy, Pxy and the four
+ * int64 factors n1, n2, d1, d2 of p3d_video_ssim (p3d_video.h states them; the constants are that header's), every window that lies inside the
+ * picture, every channel on its own.  In fp64, every operator rounded once and none contracted:
+ *     q  = ((double)n1 * (double)n2) / ((double)d1 * (double)d2)          (p3d_video_ssim's value)
+ *     cs = (double)n2 / (double)d2                                        (contrast x structure; may be negative)
+ * and the window contributes llrint(q 2^32) and llrint(cs 2^32) (round half to even).
+ *
+ * SUMS: int64 [3] per frame and channel = (sum of the q contributions, sum of the cs contributions, the number of windows).  The entry point ADDS
+ * to them: integer sums, so neither the order of the work-groups nor that of the calls shows, and no call synchronises.
+ *
+ * ms_ssim = prod_{k < L - 1} max(cs_k, 0)^(w_k) * max(q_(L-1), 0)^(w_(L-1)) of the per-level means is fp64 work of the host (multiscale.py).   */
+#define P3D_MSSSIM_MAX_LEVELS 5
+#define P3D_MSSSIM_TILE_W 32              /* the work-group tile of p3d_frame_msssim_level, in PIXELS (tests straddle it); both are even, so */
+#define P3D_MSSSIM_TILE_H 16              /* that no 2 x 2 block of the next level straddles two work-groups */
+
+/* One clip to its next level: dst is [frames][h / 2][w / 2][bpp] with pitches of its own, apart from src.  A lane owns 4 consecutive output bytes
+ * (12 at bpp 3: four pixels), which come from 8 (24) consecutive source bytes of two rows: dword loads and ONE dword store (three) where the two
+ * source rows and the output row start on a dword, single bytes everywhere else and at a row's tail.  frames (h / 2) (w / 2) == 0 is a success
+ * that launches nothing.  One launch.                                                                                                     */
+int p3d_frame_halve(const uint8_t* src, int64_t src_frame_pitch, int64_t src_row_pitch, int32_t frames, int32_t h, int32_t w, int32_t bpp,
+                    uint8_t* dst, int64_t dst_frame_pitch, int64_t dst_row_pitch, p3d_stream_t stream);
+
+/* One level of a pair of clips: adds the level's three sums of frame f and channel c to sums[(f * bpp + c) * sums_pitch .. + 3) (sums_pitch in
+ * int64 elements, >= 3: the caller's [frames][bpp][levels][3] has sums_pitch = 3 levels and passes the level's own address) and, with next_a
+ * and next_b non-null (both or neither), writes the NEXT level of both clips, contiguous uint8 [frames][h / 2][w / 2][bpp] each, from the
+ * samples it has staged.  h >= 11 and w >= 11: a level without a window is an error, never skipped.
+ *
+ * A work-group owns the P3D_MSSSIM_TILE_W x P3D_MSSSIM_TILE_H PIXELS at an even origin of one frame, all channels: the windows whose first
+ * sample lies in the tile (their 42 x 26 samples go to LDS once, dwords where the addresses allow, no load past the frame) and the 16 x 8
+ * samples of the next level under the tile.  The grid covers pixel tiles, ceil(w / 32) x ceil(h / 16) a frame: a work-group at the right or
+ * bottom edge that owns no window still writes its share of the next level.  Per channel the moments run as in p3d_video_ssim (a horizontal
+ * pass into LDS, a vertical pass a lane a window), the contributions meet in a wave reduction and the work-group issues ONE atomic per slot.
+ * Every store is checked against the next level's sizes.  frames h w == 0 is a success that launches nothing; null a, b or sums (with
+ * anything to do) returns P3D_ERR_ARGUMENT before any device call.  One launch.                                                          */
+int p3d_frame_msssim_level(const uint8_t* a, int64_t a_frame_pitch, int64_t a_row_pitch, const uint8_t* b, int64_t b_frame_pitch,
+                           int64_t b_row_pitch, int32_t frames, int32_t h, int32_t w, int32_t bpp, int64_t* sums, int64_t sums_pitch,
+                           uint8_t* next_a, uint8_t* next_b, p3d_stream_t stream);
+
 /* ---- frame resampling (csrc/sketch/frame_resample.hip; pix2pix3d_amd/resample.py) -------------------------------------
  * Pillow's Image.resize on 8-bit clips, bit for bit: for 8-bit samples it is integer arithmetic on fixed-point coefficient tables.  The tables
  * are made on the host (resample.py, Python floats); the three entry points below are the passes.  Why here: as for the mesh decimation above.

@@ -19,8 +19,8 @@ take — the definition — and device kernels whose bytes equal it:
 A tap that leaves the image reads the REFLECTED index (``_reflect``: i < 0 -> -i, then i >= n -> 2 n - 2 - i, then clamped to [0, n - 1]; reflect-101, defined
 for n = 1 and 2).  Images are uint8 with contiguous pixels and any row pitch, 1 .. 4096 pixels a side; zero-size images return empty results and launch nothing.
 ``blur3`` alone has no kernel of its own (``condition`` fuses it): it is the torch formulation on the tensor's device.  The library also houses the four
-kernels of the quadric-error mesh decimation (decimate.py calls them through ``sketch_lib()``; the header says why they live here) and the three of
-frame resampling (resample.py, likewise).
+kernels of the quadric-error mesh decimation (decimate.py calls them through ``sketch_lib()``; the header says why they live here), the three of
+frame resampling (resample.py, likewise) and the two of multi-scale frame quality (multiscale.py, likewise).
 
 ``SketchSession`` is the edge counterpart of ``edit.EditSession`` on the same stages below the canvas (``edit._StageSession``):
 

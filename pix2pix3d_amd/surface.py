@@ -595,16 +595,16 @@ def render(G, ws, cameras, resolution=512, color='grey', palette=None, backgroun
 
 @torch.no_grad()
 def geometry_video(G, ws, cfg='seg2cat', n_frames=120, views_per_step=4, resolution=512, color='grey', path=None, fps=60, gif='pil', format='gif',
-                   psnr=None, ssim=None, size=None, resample='lanczos', **render_kwargs):
+                   psnr=None, ssim=None, size=None, resample='lanczos', ms_ssim=None, **render_kwargs):
     """The geometry turntable of ``ws`` [1, num_ws, w_dim]: ``render`` over ``views.video_cameras(G, cfg, n_frames)``, ``views_per_step``
     cameras per cast launch, the backbone run once for all of them where the cast kernel serves.  uint8 [n_frames, R, R, 3] on ws's
     device; with ``path`` also written as a GIF: ``gif='pil'`` through ``mesh.save_gif``, ``gif='device'`` through ``video.save_gif`` (one palette for the
     clip, made and applied on the frames' device).  ``format='avi'``: a true-colour Motion-JPEG AVI through ``video.save_avi`` instead, encoded on the
-    frames' device (``gif`` plays no part) — with ``psnr`` or ``ssim`` (one of them) at the quality that ``video.jpeg_quality_for`` picks for that target;
+    frames' device (``gif`` plays no part) — with ``psnr``, ``ssim`` or ``ms_ssim`` (one of them) at the quality that ``video.jpeg_quality_for`` picks for that target;
     ``format='apng'``: a lossless animated PNG through ``video.save_apng``, likewise.  ``size`` ((width, height) or an int): the frames are resized on their
     device first (``resample.resize`` with the filter ``resample``), before the writer and any quality search, and come back at that size."""
     from .video.clip import check_clip_options, save_clip
-    check_clip_options('geometry_video', gif, format, psnr, ssim)
+    check_clip_options('geometry_video', gif, format, psnr, ssim, ms_ssim)
     views._check_resample('geometry_video', size, resample)
     step = int(views_per_step)
     if step < 1:
@@ -619,5 +619,5 @@ def geometry_video(G, ws, cfg='seg2cat', n_frames=120, views_per_step=4, resolut
         from .resample import resize
         out = resize(out, size, resample)
     if path is not None:
-        save_clip(path, out, fps=fps, format=format, gif=gif, psnr=psnr, ssim=ssim, who='geometry_video')
+        save_clip(path, out, fps=fps, format=format, gif=gif, psnr=psnr, ssim=ssim, ms_ssim=ms_ssim, who='geometry_video')
     return out

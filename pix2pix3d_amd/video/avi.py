@@ -16,12 +16,12 @@ def _chunk(fourcc, payload):
     return fourcc + len(payload).to_bytes(4, 'little') + payload + b'\0' * (len(payload) & 1)
 
 
-def save_avi(path, frames, fps=60, quality=90, subsampling='4:2:0', psnr=None, ssim=None):
+def save_avi(path, frames, fps=60, quality=90, subsampling='4:2:0', psnr=None, ssim=None, ms_ssim=None):
     """The frames (``encode_jpeg``'s contract) as a Motion-JPEG AVI: a RIFF 'AVI ' file with the list 'hdrl' ('avih', and one 'strl' of 'strh' — 'vids' /
     'MJPG', the rate ``fps`` as dwRate / dwScale — and 'strf', a 40-byte BITMAPINFOHEADER of 24 bits), the list 'movi' of one '00dc' chunk per frame,
     padded to an even length, and 'idx1': per frame the key-frame flag, the chunk's offset from 'movi' and its length.  Every frame is a key frame.
-    ValueError for no frame and for a file that would reach 2^31 bytes (OpenDML is out of scope).  ``psnr`` / ``ssim``: ``encode_jpeg``'s target, which
-    then picks the quality.  Returns the JPEG streams."""
+    ValueError for no frame and for a file that would reach 2^31 bytes (OpenDML is out of scope).  ``psnr`` / ``ssim`` / ``ms_ssim``:
+    ``encode_jpeg``'s target, which then picks the quality.  Returns the JPEG streams."""
     import fractions
     import struct
     frames = torch.as_tensor(frames)
@@ -31,7 +31,7 @@ def save_avi(path, frames, fps=60, quality=90, subsampling='4:2:0', psnr=None, s
     rate = fractions.Fraction(fps).limit_denominator(1 << 16)
     if rate <= 0:
         raise ValueError(f'save_avi: fps must be > 0, got {fps!r}')
-    streams = encode_jpeg(frames, quality, subsampling, psnr, ssim)
+    streams = encode_jpeg(frames, quality, subsampling, psnr, ssim, ms_ssim)
     movi, index = b'movi', b''
     chunks = [movi]
     at = 4                                                                        # of the next chunk, from the 'movi' word

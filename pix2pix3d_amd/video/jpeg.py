@@ -6,8 +6,8 @@ Every frame is a baseline JFIF of its own, made without a codec library.  csrc/v
 those rules operation by operation — the definition — and the kernels' bytes equal them.
 
 What a setting costs is measured where the frames are (``quality.py``): ``jpeg_decode`` / ``jpeg_reconstruct`` show what a viewer of
-the JPEGs sees without entropy decoding, and ``jpeg_quality_for`` turns a PSNR or SSIM target into a quality (``encode_jpeg`` takes ``psnr=`` or ``ssim=`` in
-place of one)."""
+the JPEGs sees without entropy decoding, and ``jpeg_quality_for`` turns a PSNR, SSIM or MS-SSIM (``multiscale.py``; section 2.1ac) target into a quality (``encode_jpeg`` takes ``psnr=``, ``ssim=`` or
+``ms_ssim=`` in place of one)."""
 import numpy as np
 import torch
 
@@ -305,18 +305,18 @@ def jpeg_header(h, w, tables, subsampling='4:2:0'):
     return out + _segment(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
 
 
-def encode_jpeg(frames, quality=90, subsampling='4:2:0', psnr=None, ssim=None):
+def encode_jpeg(frames, quality=90, subsampling='4:2:0', psnr=None, ssim=None, ms_ssim=None):
     """A list of ``bytes``, one complete baseline JFIF per frame of uint8 [F, H, W, 3] (the module's frame contract; on the device or the host, or a numpy
     array): ``jpeg_header``, the frame's scan, EOI.  ``quality`` 1 .. 100 picks the tables (``jpeg_tables``).  From device frames: the two kernels' three
     launches, ONE synchronisation with the host (the interval lengths) and ONE device -> host copy (the scans, a few percent of the frames' bytes).
-    ``psnr`` or ``ssim`` (ONE of them): a target instead of a setting — ``jpeg_quality_for`` picks the quality, ``quality`` plays no part, and the tables in
-    the streams (``jpeg_tables`` of the choice) say what it was."""
+    ``psnr``, ``ssim`` or ``ms_ssim`` (ONE of them): a target instead of a setting — ``jpeg_quality_for`` picks the quality, ``quality`` plays no part, and
+    the tables in the streams (``jpeg_tables`` of the choice) say what it was."""
     frames = torch.as_tensor(frames)
     f, h, w = check_frames(frames)
-    if psnr is not None or ssim is not None:
-        _check_target(psnr, ssim, 'encode_jpeg')
+    if psnr is not None or ssim is not None or ms_ssim is not None:
+        _check_target(psnr, ssim, 'encode_jpeg', ms_ssim)
         if f * h * w:
-            quality = jpeg_quality_for(frames, psnr, ssim, subsampling)[0]
+            quality = jpeg_quality_for(frames, psnr, ssim, subsampling, ms_ssim=ms_ssim)[0]
     sub, tables = _check_subsampling(subsampling), jpeg_tables(quality)
     if f == 0:
         return []
@@ -449,28 +449,36 @@ def jpeg_reconstruct(frames, quality=90, subsampling='4:2:0'):
     return jpeg_decode(jpeg_coefficients(frames, tables, sub), tables, h, w, sub)
 
 
-def _check_target(psnr, ssim, what):
-    """('psnr' or 'ssim', the target): exactly ONE of the two is given.  Both would need a rule for a quality that meets one and not the other; a caller who
-    wants both takes the larger of two searches."""
-    if (psnr is None) == (ssim is None):
-        raise ValueError(f'{what}: give psnr (dB) or ssim (0 .. 1), one of them, got psnr={psnr!r}, ssim={ssim!r}')
-    key, target = ('psnr', psnr) if ssim is None else ('ssim', ssim)
-    if isinstance(target, bool) or not isinstance(target, (int, float)) or target != target or (key == 'ssim' and not 0 <= target <= 1) or (key == 'psnr' and target < 0):
-        raise ValueError(f'{what}: {key} must be a number{" 0 .. 1" if key == "ssim" else " >= 0 (dB)"}, got {target!r}')
+def _check_target(psnr, ssim, what, ms_ssim=None):
+    """('psnr', 'ssim' or 'ms_ssim', the target): exactly ONE of the three is given.  Two would need a rule for a quality that meets one and not the other; a
+    caller who wants several takes the largest of their searches."""
+    given = [(k, v) for k, v in (('psnr', psnr), ('ssim', ssim), ('ms_ssim', ms_ssim)) if v is not None]
+    if len(given) != 1:
+        raise ValueError(f'{what}: give psnr (dB), ssim (0 .. 1) or ms_ssim (0 .. 1), one of them, got psnr={psnr!r}, ssim={ssim!r}, ms_ssim={ms_ssim!r}')
+    key, target = given[0]
+    if isinstance(target, bool) or not isinstance(target, (int, float)) or target != target or (key != 'psnr' and not 0 <= target <= 1) or (key == 'psnr' and target < 0):
+        raise ValueError(f'{what}: {key} must be a number{" 0 .. 1" if key != "psnr" else " >= 0 (dB)"}, got {target!r}')
     return key, float(target)
 
 
-def jpeg_quality_for(frames, psnr=None, ssim=None, subsampling='4:2:0', sample=8):
-    """``(quality, metrics, met)``: the JPEG quality that meets a target — ``psnr`` in dB or ``ssim`` in 0 .. 1, ONE of them (``_check_target``) — as
-    ``quality.compare`` measures ``jpeg_reconstruct`` against the frames, on at most ``sample`` evenly spaced frames of the clip (the first and the last among
-    them).  A bisection of 1 .. 100 in at most seven steps, each three launches for the reconstruction, two for the sums and ONE host read.  The measure
-    need not rise with the quality, so the promise is a post-condition, ``mesh.simplify_to``'s: the quality returned met the target as measured (``metrics``
-    is its ``compare`` dict), and the quality below it was tried and did not (unless it is 1); if 100 does not meet it, ``(100, its metrics, False)``.  A
-    clip without a sample — or, for ``ssim``, without a window — measures NaN, which meets nothing."""
+def jpeg_quality_for(frames, psnr=None, ssim=None, subsampling='4:2:0', sample=8, ms_ssim=None):
+    """``(quality, metrics, met)``: the JPEG quality that meets a target — ``psnr`` in dB, ``ssim`` or ``ms_ssim`` in 0 .. 1, ONE of them (``_check_target``)
+    — as ``quality.compare`` (for ``ms_ssim``: ``multiscale.ms_ssim`` at five levels, whose dict ``metrics`` then is; both sides at least 176 pixels)
+    measures ``jpeg_reconstruct`` against the frames, on at most ``sample`` evenly spaced frames of the clip (the first and the last among them).  A
+    bisection of 1 .. 100 in at most seven steps, each three launches for the reconstruction, two for the sums (five for ``ms_ssim``) and ONE host read.
+    The measure need not rise with the quality, so the promise is a post-condition, ``mesh.simplify_to``'s: the quality returned met the target as measured
+    (``metrics`` is its ``compare`` dict), and the quality below it was tried and did not (unless it is 1); if 100 does not meet it,
+    ``(100, its metrics, False)``.  A clip without a sample — or, for ``ssim``, without a window — measures NaN, which meets nothing; for ``ms_ssim`` a
+    clip under 176 pixels a side is a ValueError."""
     frames = torch.as_tensor(frames)
     f, h, w = check_frames(frames)
-    key, target = _check_target(psnr, ssim, 'jpeg_quality_for')
+    key, target = _check_target(psnr, ssim, 'jpeg_quality_for', ms_ssim)
     sub = _check_subsampling(subsampling)
+    if key == 'ms_ssim':
+        from .. import multiscale                                                 # (here: multiscale -> sketch -> views -> this package)
+        measure = multiscale.ms_ssim
+    else:
+        measure = Q.compare
     if isinstance(sample, bool) or int(sample) != sample or int(sample) < 1:
         raise ValueError(f'jpeg_quality_for: sample must be an integer >= 1, got {sample!r}')
     n = int(sample)
@@ -480,7 +488,7 @@ def jpeg_quality_for(frames, psnr=None, ssim=None, subsampling='4:2:0', sample=8
     low, high = 1, 101                                                            # the answer lies in low .. high; 101: none
     while low < high:
         mid = (low + high) // 2
-        measured[mid] = Q.compare(jpeg_reconstruct(frames, mid, sub), frames)
+        measured[mid] = measure(jpeg_reconstruct(frames, mid, sub), frames)
         if measured[mid][key] >= target:
             high = mid
         else:

@@ -354,7 +354,7 @@ def image_grid(frames, grid_size, cell=None):
 
 @torch.no_grad()
 def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=120, fps=60, gif='pil', format='gif', psnr=None, ssim=None, size=None,
-                   resample='lanczos', **render_kwargs):
+                   resample='lanczos', ms_ssim=None, **render_kwargs):
     """generate_video.py after its inputs: the ``cfg`` cameras (``video_cameras``) at the script's ray resolution with ``noise_mode='const'``, rendered by
     ``render_views`` (its keyword arguments pass through); ``path`` / ``path_label`` receive the two GIFs the script writes with imageio at 60 fps.
     ``gif='pil'``: through ``mesh.save_gif``, PIL quantising every frame on the host.  ``gif='device'``: the image through ``video.save_gif`` (one palette for
@@ -362,19 +362,19 @@ def generate_video(G, ws, cfg='seg2cat', path=None, path_label=None, n_frames=12
     palette, or the edge generators' grey frames with a grey ramp.  ``format='avi'``: both clips in true colour as Motion-JPEG AVIs through
     ``video.save_avi``, encoded where the frames are (``gif`` plays no part).  ``format='apng'``: both clips losslessly as animated PNGs through
     ``video.save_apng``, encoded where the frames are — the image as RGB, the label video as palette indices (``label_index`` with the frames' palette) or,
-    for the edge generators, as 8-bit grey.  ``psnr`` / ``ssim`` (``format='avi'`` only, one of them): a target for the image clip instead of the default
+    for the edge generators, as 8-bit grey.  ``psnr`` / ``ssim`` / ``ms_ssim`` (``format='avi'`` only, one of them): a target for the image clip instead of the default
     quality — ``video.jpeg_quality_for`` picks the setting where the frames are, the dict gains 'jpeg_quality': ``(quality, metrics, met)``, and the label
     clip goes through ``video.save_avi`` with the same target.  ``size`` ((width, height) or an int): the clips are resized where they are before the
     writer and before any quality search (``resize_clips``: the image through the filter ``resample``, label and index frames through 'nearest'), and the
     dict holds them at that size; ``size=None`` writes the same bytes as ever.  Returns ``render_views``' dict."""
     from .video.clip import check_clip_options, save_clip
-    check_clip_options('generate_video', gif, format, psnr, ssim)
+    check_clip_options('generate_video', gif, format, psnr, ssim, ms_ssim)
     _check_resample('generate_video', size, resample)
     cams = video_cameras(G, cfg, n_frames).to(ws.device)
     render_kwargs.setdefault('noise_mode', 'const')
     render_kwargs.setdefault('neural_rendering_resolution', VIDEO_CFG[cfg]['neural_rendering_resolution'])
     frames = resize_clips(render_views(G, ws, cams, **render_kwargs), size, resample)
-    how = dict(fps=fps, format=format, gif=gif, psnr=psnr, ssim=ssim, who='generate_video')
+    how = dict(fps=fps, format=format, gif=gif, psnr=psnr, ssim=ssim, ms_ssim=ms_ssim, who='generate_video')
     if path is not None:
         chosen = save_clip(path, frames['image'], **how)
         if chosen is not None:
