@@ -23,8 +23,9 @@ CXXFLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-Wall', '-W
 # The libraries beside libp3d_hip.so, name -> extra compile flags.  Everything else about one follows from its name (side_paths).
 SIDE_LIBRARIES = {'probes': ('-DP3D_BUILD_PROBES',),      # hardware probes the tests and the kernel studies use (diagnostics.py)
                   'regions': (),                         # region tools of the edit session, agreement metrics, cross-view reprojection (regions.py, evaluate.py, reproject.py)
-                  'video': (),                           # frame encoders of the video writers: GIF, JPEG / MJPEG AVI, PNG / APNG (video/)
-                  'sketch': ()}                          # edge-map canvas of the sketch session (sketch.py); quadric-error mesh decimation (decimate.py); frame resampling (resample.py); MS-SSIM (multiscale.py)
+                  'video': (),                           # everything on uint8 clips, held by clips.py: the frame writers and readers (video/), frame quality (quality.py, multiscale.py), resampling (resample.py)
+                  'sketch': (),                          # edge-map canvas of the sketch session (sketch.py)
+                  'mesh': ()}                            # quadric-error mesh decimation (decimate.py)
 SidePaths = collections.namedtuple('SidePaths', 'src_dir header lib obj_dir')
 
 

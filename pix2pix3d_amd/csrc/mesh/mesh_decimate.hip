@@ -1,4 +1,4 @@
-// Quadric-error decimation for gfx950: the four kernels of a round of edge collapses (p3d_sketch.h, "mesh decimation";
+// Quadric-error decimation for gfx950: the four kernels of a round of edge collapses (p3d_mesh.h;
 // pix2pix3d_amd/decimate.py).  The rules are the header's; the torch formulation of decimate.py produces the same bytes.
 //
 // Every kernel is one thread per item, 256 threads a work-group, plain vector loads and stores, no float atomics, and every list walk is
@@ -16,7 +16,7 @@
 //                        the lower one (applied edges share no vertex, so the in-place update is race free); then a thread per face remaps
 //                        its corners through `parent` and flags the faces with two equal corners.
 #include "../p3d_common.h"
-#include "p3d_sketch.h"
+#include "p3d_mesh.h"
 #include <math.h>
 
 namespace {

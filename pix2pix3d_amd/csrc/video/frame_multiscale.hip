@@ -1,5 +1,5 @@
-// Multi-scale frame quality for gfx950 (p3d_sketch.h, "multi-scale frame quality"; pix2pix3d_amd/multiscale.py): the 2 x 2
-// pyramid of a clip and, per level, the sums behind MS-SSIM in the integers of p3d_video.h's SSIM.  The rules are the headers'; the torch
+// Multi-scale frame quality for gfx950 (p3d_video.h, "multi-scale frame quality"; pix2pix3d_amd/multiscale.py): the 2 x 2
+// pyramid of a clip and, per level, the sums behind MS-SSIM in the integers of the header's SSIM.  The rules are the header's; the torch
 // formulation of multiscale.py produces the same bytes.
 //
 // p3d_frame_halve          256 threads: 64 lanes along a row by 4 waves, a wave every fourth of the tile's 16 output rows, frames on grid.z (strided
@@ -10,19 +10,20 @@
 //                          16 x 8 samples of the next level under it.  The 42 x 26 samples of both clips that lie inside the frame go to LDS once,
 //                          as dwords where the global address allows (the LDS copy keeps the address's low two bits, so that an aligned dword stays
 //                          aligned); the next level of both clips is written from them straight away, 4 bytes a lane; then per channel the
-//                          horizontal pass writes the five int32 row sums of every (input row, window column) to LDS, a barrier, and the vertical
-//                          pass — a lane a window, two windows a lane — reads them down its own column.  q and cs meet in wave reductions and the
+//                          passes of ssim_window.h, which p3d_video_ssim runs too — the horizontal one into LDS, a barrier, the vertical one a
+//                          lane a window, two windows a lane.  q and cs meet in wave reductions and the
 //                          work-group issues ONE atomic per slot and channel.  A tile at the right or bottom edge without a window of its own
 //                          skips the passes (the condition is the same for the whole work-group) and still writes its samples of the next level.
 #include "../p3d_common.h"
-#include "../video/p3d_video.h"
-#include "p3d_sketch.h"
+#include "clip_checks.h"
+#include "p3d_video.h"
+#include "ssim_window.h"
 
 namespace {
 
 using namespace p3d;
+using namespace p3d::ssim;                                                      // kThreads, kWaves, the window's tile: one work-group shape for both kernels
 
-constexpr int kThreads = 256, kWaves = kThreads / kWave;
 constexpr int kMaxGridZ = 65535;
 
 // ---- the pyramid step -------------------------------------------------------------------------------------------------------------------------
@@ -76,14 +77,9 @@ __global__ void __launch_bounds__(kThreads) halve_kernel(const Halve g)
 }
 
 // ---- one level ----------------------------------------------------------------------------------------------------------------------------
-constexpr int kTaps = P3D_VIDEO_SSIM_TAPS, kHalo = kTaps - 1;
-constexpr int kTileW = P3D_MSSSIM_TILE_W, kTileH = P3D_MSSSIM_TILE_H;
-constexpr int kInW = kTileW + kHalo, kInH = kTileH + kHalo;                     // the samples under a tile's windows: 42 x 26
 constexpr int kRowWords = (kInW * 4 + 3 + 3) / 4;                               // dwords of a staged row: 168 bytes behind a shift of up to 3; 43, odd
-constexpr long long kC1 = P3D_VIDEO_SSIM_C1, kC2 = P3D_VIDEO_SSIM_C2;
-static_assert(kTileW * kTileH == 2 * kThreads && kTileW == 32, "two windows a lane, a row of windows half a wave");
+static_assert(kTileW == P3D_MSSSIM_TILE_W && kTileH == P3D_MSSSIM_TILE_H, "the pixel tile is the window tile of ssim_window.h");
 static_assert(kTileW % 2 == 0 && kTileH % 2 == 0, "no 2 x 2 block of the next level straddles two tiles");
-static_assert(P3D_VIDEO_SSIM_SHIFT == 32, "a window contributes llrint(value 2^32)");
 
 struct Level {
     const uint8_t* a; int64_t a_frame_pitch, a_row_pitch;
@@ -93,13 +89,6 @@ struct Level {
     unsigned long long* sums; int64_t sums_pitch;
     uint8_t* next_a; uint8_t* next_b;
 };
-
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_down(v, d);
-    return v;                                                                   // lane 0 holds the sum
-}
 
 // Dword d of a staged row: the row's bytes [0, span) stand at LDS bytes [shift, shift + span), shift = the global address's low two bits.
 __device__ __forceinline__ uint32_t staged_word(const uint8_t* row, int shift, int d, int span)
@@ -115,27 +104,12 @@ __device__ __forceinline__ uint32_t staged_word(const uint8_t* row, int shift, i
     return v;
 }
 
-// One window's two values from its five moments: the header's four factors, then fp64 with one rounding per operator.
-__device__ __forceinline__ void values_of(long long A, long long B, long long Pxx, long long Pyy, long long Pxy, double& q, double& cs)
-{
-#pragma clang fp contract(off)
-    const long long ab = A * B, aa_bb = A * A + B * B;
-    const long long n1 = 2 * ab + kC1, n2 = 2 * ((Pxy << 20) - ab) + kC2;
-    const long long d1 = aa_bb + kC1, d2 = ((Pxx + Pyy) << 20) - aa_bb + kC2;
-    const double fn2 = (double)n2, fd2 = (double)d2;
-    const double num = (double)n1 * fn2;
-    const double den = (double)d1 * fd2;
-    q = num / den;
-    cs = fn2 / fd2;
-}
-
 template <int BPP>
 __global__ void __launch_bounds__(kThreads) msssim_level_kernel(const Level p)
 {
     __shared__ uint32_t ta[kInH * kRowWords], tb[kInH * kRowWords];             // 2 x 4472 bytes
-    __shared__ int hb[5][kInH][kTileW];                                         // 16640 bytes: A, B, Pxx, Pyy, Pxy of (input row, window column)
+    __shared__ RowSums hb;
     __shared__ long long part[2][kWaves];
-    constexpr int g[kTaps] = {P3D_VIDEO_SSIM_WINDOW};
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & (kWave - 1);
     const int f = blockIdx.x / (unsigned)p.per_frame;
     const int tile = blockIdx.x - f * p.per_frame;
@@ -195,14 +169,10 @@ __global__ void __launch_bounds__(kThreads) msssim_level_kernel(const Level p)
             if (x < tw) {
                 const uint8_t* const ra = sa + r * (kRowWords * 4) + ((a_base + r * a_step) & 3) + x * BPP + c;
                 const uint8_t* const rb = sb + r * (kRowWords * 4) + ((b_base + r * b_step) & 3) + x * BPP + c;
-                int s_a = 0, s_b = 0, sxx = 0, syy = 0, sxy = 0;                // <= 1024 x 255^2 < 2^26
+                int s[5] = {};
 #pragma unroll
-                for (int k = 0; k < kTaps; ++k) {
-                    const int xa = ra[k * BPP], xb = rb[k * BPP];
-                    s_a += g[k] * xa; s_b += g[k] * xb;
-                    sxx += g[k] * xa * xa; syy += g[k] * xb * xb; sxy += g[k] * xa * xb;
-                }
-                hb[0][r][x] = s_a; hb[1][r][x] = s_b; hb[2][r][x] = sxx; hb[3][r][x] = syy; hb[4][r][x] = sxy;
+                for (int k = 0; k < kTaps; ++k) row_tap(s, ra[k * BPP], rb[k * BPP], k);
+                put_row_sums(hb, r, x, s);
             }
         }
         __syncthreads();
@@ -211,17 +181,13 @@ __global__ void __launch_bounds__(kThreads) msssim_level_kernel(const Level p)
         for (int j = 0; j < 2; ++j) {                                           // the vertical pass: window (x, y) of the tile
             const int o = tid + j * kThreads, y = o >> 5, x = o & (kTileW - 1);
             if (y < th && x < tw) {
-                int A = 0, B = 0;                                               // < 2^28
-                long long Pxx = 0, Pyy = 0, Pxy = 0;                            // < 2^36
+                Moments m{0, 0, 0, 0, 0};
 #pragma unroll
-                for (int k = 0; k < kTaps; ++k) {
-                    A += g[k] * hb[0][y + k][x]; B += g[k] * hb[1][y + k][x];
-                    Pxx += (long long)g[k] * hb[2][y + k][x]; Pyy += (long long)g[k] * hb[3][y + k][x]; Pxy += (long long)g[k] * hb[4][y + k][x];
-                }
-                double q, cs;
-                values_of(A, B, Pxx, Pyy, Pxy, q, cs);
-                mine_q += llrint(q * 4294967296.0);
-                mine_cs += llrint(cs * 4294967296.0);
+                for (int k = 0; k < kTaps; ++k) column_tap(m, hb, y, x, k);
+                double cs;
+                const double q = window_values<true>(m, &cs);
+                mine_q += contribution(q);
+                mine_cs += contribution(cs);
             }
         }
         mine_q = wave_sum(mine_q);
@@ -241,17 +207,6 @@ __global__ void __launch_bounds__(kThreads) msssim_level_kernel(const Level p)
     }
 }
 
-// What both entry points ask of a source clip; *pixels = frames h w.
-int check_clip(const char* who, int32_t frames, int32_t h, int32_t w, int32_t bpp, int64_t* pixels)
-{
-    P3D_REQUIRE(frames >= 0 && h >= 0 && w >= 0, "%s: frames, h and w must be >= 0 (got %d, %d, %d)", who, frames, h, w);
-    P3D_REQUIRE(bpp >= 1 && bpp <= 4, "%s: bpp must be 1 .. 4 (got %d)", who, bpp);
-    const int64_t hw = (int64_t)h * w;
-    P3D_REQUIRE(hw < (1ll << 31) && hw * frames * bpp < (1ll << 31), "%s: %d x %d x %d pixels of %d bytes reach 2^31", who, frames, h, w, bpp);
-    *pixels = hw * frames;
-    return P3D_OK;
-}
-
 } // namespace
 
 extern "C" int p3d_frame_halve(const uint8_t* src, int64_t src_frame_pitch, int64_t src_row_pitch, int32_t frames, int32_t h, int32_t w, int32_t bpp,
@@ -259,7 +214,7 @@ extern "C" int p3d_frame_halve(const uint8_t* src, int64_t src_frame_pitch, int6
 {
     using namespace p3d;
     int64_t pixels = 0;
-    if (int code = check_clip("frame_halve", frames, h, w, bpp, &pixels)) return code;
+    if (int code = check_clip_sizes("frame_halve", frames, h, w, bpp, &pixels)) return code;
     const int nh = h / 2, nw = w / 2;
     if ((int64_t)frames * nh * nw == 0) return P3D_OK;
     P3D_REQUIRE(src && dst, "frame_halve: a clip pointer is null");
@@ -291,14 +246,10 @@ extern "C" int p3d_frame_msssim_level(const uint8_t* a, int64_t a_frame_pitch, i
 {
     using namespace p3d;
     int64_t pixels = 0;
-    if (int code = check_clip("frame_msssim_level", frames, h, w, bpp, &pixels)) return code;
-    if (pixels == 0) return P3D_OK;
-    P3D_REQUIRE(a && b && sums, "frame_msssim_level: a, b and sums must be non-null");
+    const int rc = check_pair("frame_msssim_level", a, a_frame_pitch, a_row_pitch, b, b_frame_pitch, b_row_pitch, frames, h, w, bpp, sums, &pixels);
+    if (rc != P3D_OK || pixels == 0) return rc;
     P3D_REQUIRE(h >= kTaps && w >= kTaps, "frame_msssim_level: a level of %d x %d has no %d x %d window", w, h, kTaps, kTaps);
-    P3D_REQUIRE(((uintptr_t)sums & 7u) == 0 && sums_pitch >= 3, "frame_msssim_level: sums must be 8-byte aligned and sums_pitch at least 3 (got %lld)",
-                (long long)sums_pitch);
-    P3D_REQUIRE(a_row_pitch >= (int64_t)w * bpp && b_row_pitch >= (int64_t)w * bpp && a_frame_pitch >= 0 && b_frame_pitch >= 0,
-                "frame_msssim_level: a row pitch is shorter than the row, or a frame pitch negative");
+    P3D_REQUIRE(sums_pitch >= 3, "frame_msssim_level: sums_pitch must be at least 3 (got %lld)", (long long)sums_pitch);
     P3D_REQUIRE((next_a == nullptr) == (next_b == nullptr), "frame_msssim_level: next_a and next_b are both given or both null");
     P3D_REQUIRE(next_a == nullptr || next_a != next_b, "frame_msssim_level: next_a and next_b must be two buffers");
     Level p{a, a_frame_pitch, a_row_pitch, b, b_frame_pitch, b_row_pitch, h, w, 0, 0, (unsigned long long*)sums, sums_pitch, next_a, next_b};

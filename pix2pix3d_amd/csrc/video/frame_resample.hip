@@ -1,4 +1,4 @@
-// Frame resampling for gfx950: the two passes of Pillow's Image.resize on 8-bit clips and the nearest gather (p3d_sketch.h, "frame resampling";
+// Frame resampling for gfx950: the two passes of Pillow's Image.resize on 8-bit clips and the nearest gather (p3d_video.h, "frame resampling";
 // pix2pix3d_amd/resample.py).  The rules are the header's; the torch formulation of resample.py produces the same bytes.
 //
 // All three kernels are 256 threads a work-group — 64 lanes along a row by 4 waves, a wave taking every fourth row of the tile's
@@ -16,7 +16,7 @@
 //                              does not allow a dword.  No LDS: the rows neighbouring outputs share are re-read from L2.
 // p3d_frame_resample_nearest   a lane owns one output pixel of four rows; both index tables are read per lane / per wave.
 #include "../p3d_common.h"
-#include "p3d_sketch.h"
+#include "p3d_video.h"
 
 namespace {
 

@@ -1,13 +1,16 @@
-/* libp3d_video.so — palette, dither and index frames for the GIF writer (pix2pix3d_amd/video/gif.py) and, at the end, baseline JPEG
- * frames for the Motion-JPEG writer (section 2.1u), the zlib streams of PNG and APNG files (section 2.1v) and what a setting of those writers
- * costs in the picture: error sums, SSIM and a decoder's view of the JPEG coefficients (section 2.1x) — and, after the JPEG coder, its inverse: the entropy
- * decoder that reads such files, and libjpeg's, back (section 2.1y).  A library of its
- * own, like libp3d_regions.so: the product ABI (include/p3d_hip.h, libp3d_hip.so) exports none of this.  It carries its own copy of the
- * library services (p3d_last_error, p3d_launch_count).  Nothing here has a counterpart in the reference, which writes videos with imageio.
+/* libp3d_video.so — everything that works on uint8 clips.  For the writers: palette, dither and index frames of the GIFs (pix2pix3d_amd/video/gif.py; DESIGN.md
+ * section 2.1q), baseline JPEG frames of the Motion-JPEG AVIs (section 2.1u), the zlib streams of PNG and APNG files (section 2.1v).  The way back from such
+ * files: the JPEG entropy decoder (section 2.1y), inflate and un-filter (section 2.1z).  What a setting costs in the picture: error sums, SSIM and a decoder's
+ * view of the JPEG coefficients (section 2.1x), MS-SSIM over a pyramid made on the device (section 2.1ac).  And the frames at another size: Pillow's resize
+ * filters (section 2.1ab).  A library of its own, like libp3d_regions.so: the product ABI (include/p3d_hip.h, libp3d_hip.so) exports none of this.  It
+ * carries its own copy of the library services (p3d_last_error, p3d_launch_count).  Nothing here has a counterpart in the reference, which writes videos
+ * with imageio.
  *
- * Frames are uint8 [n_frames][h][w][3]: the three bytes of a pixel and the pixels of a row are contiguous, rows are `row_pitch` bytes apart
- * (>= 3 w) and frames `frame_pitch` bytes apart, so a strided selection of frames and a window of a larger canvas are read in place.
- * n_frames, h, w >= 0 and n_frames * h * w < 2^31; an empty clip launches nothing but the zeroing of the result.
+ * A CLIP ("frames") is uint8 [n_frames][h][w][bpp]: the bpp bytes of a pixel and the pixels of a row are contiguous, rows are `row_pitch` bytes apart
+ * (>= w bpp) and frames `frame_pitch` bytes apart (>= 0), so a strided selection of frames and a window of a larger canvas are read in place.  bpp is 3
+ * for the GIF and JPEG stages, which take no such argument, and 1 .. 4 wherever an entry point takes it.  n_frames, h, w >= 0 and n_frames h w bpp < 2^31
+ * (n_frames h w < 2^31 for the GIF and JPEG stages); an empty clip launches nothing but the zeroing of a result.  This is the one statement of the
+ * contract: the sections below say only what they add to it.
  * A GROUP shares one histogram and one palette: the whole clip (per_frame = 0, n_groups = 1) or one frame (per_frame = 1, n_groups =
  * n_frames).  Everything is integer arithmetic and a pure function of the inputs: the torch formulations of pix2pix3d_amd/video/gif.py produce
  * the same bytes.  All pointers are device memory.  Argument errors return P3D_ERR_ARGUMENT before any launch.                              */
@@ -297,6 +300,118 @@ int p3d_video_ssim(const uint8_t* a, int64_t a_frame_pitch, int64_t a_row_pitch,
 int p3d_video_jpeg_decode(const int16_t* coefficients, int32_t n_frames, int32_t h, int32_t w, int32_t subsampling, const uint8_t* luma_q,
                           const uint8_t* chroma_q, uint8_t* scratch, int64_t scratch_bytes, uint8_t* frames, int64_t frame_pitch, int64_t row_pitch,
                           p3d_stream_t stream);
+
+/* ---- multi-scale frame quality (frame_multiscale.hip, ssim_window.h; pix2pix3d_amd/multiscale.py) ------------------------
+ * MS-SSIM (Wang, Simoncelli, Bovik 2003) between two clips over a pyramid made on the device, in the integers of the SSIM above.
+ *
+ * PYRAMID.  Level 0 is the clip.  Level k + 1 is floor(h / 2) x floor(w / 2); its sample (y, x, c) is
+ *     (s[2y][2x][c] + s[2y][2x + 1][c] + s[2y + 1][2x][c] + s[2y + 1][2x + 1][c] + 2) >> 2
+ * of level k: every channel on its own, one rounding, an odd last row or column dropped.  (NOT the 'box' filter of the resampling below, which
+ * rounds once per pass.)
+ *
+ * PER LEVEL, for clips a (x) and b (y) of one size: the 11 x 11 window P3D_VIDEO_SSIM_WINDOW, the exact moments A, B, Pxx, Pyy, Pxy and the four
+ * int64 factors n1, n2, d1, d2 of p3d_video_ssim above, every window that lies inside the
+ * picture, every channel on its own.  In fp64, every operator rounded once and none contracted:
+ *     q  = ((double)n1 * (double)n2) / ((double)d1 * (double)d2)          (p3d_video_ssim's value)
+ *     cs = (double)n2 / (double)d2                                        (contrast x structure; may be negative)
+ * and the window contributes llrint(q 2^32) and llrint(cs 2^32) (round half to even).
+ *
+ * SUMS: int64 [3] per frame and channel = (sum of the q contributions, sum of the cs contributions, the number of windows).  The entry point ADDS
+ * to them: integer sums, so neither the order of the work-groups nor that of the calls shows, and no call synchronises.
+ *
+ * ms_ssim = prod_{k < L - 1} max(cs_k, 0)^(w_k) * max(q_(L-1), 0)^(w_(L-1)) of the per-level means is fp64 work of the host (multiscale.py).   */
+#define P3D_MSSSIM_MAX_LEVELS 5
+#define P3D_MSSSIM_TILE_W 32              /* the work-group tile of p3d_frame_msssim_level, in PIXELS (tests straddle it); both are even, so */
+#define P3D_MSSSIM_TILE_H 16              /* that no 2 x 2 block of the next level straddles two work-groups */
+
+/* One clip to its next level: dst is [frames][h / 2][w / 2][bpp] with pitches of its own, apart from src.  A lane owns 4 consecutive output bytes
+ * (12 at bpp 3: four pixels), which come from 8 (24) consecutive source bytes of two rows: dword loads and ONE dword store (three) where the two
+ * source rows and the output row start on a dword, single bytes everywhere else and at a row's tail.  frames (h / 2) (w / 2) == 0 is a success
+ * that launches nothing.  One launch.                                                                                                     */
+int p3d_frame_halve(const uint8_t* src, int64_t src_frame_pitch, int64_t src_row_pitch, int32_t frames, int32_t h, int32_t w, int32_t bpp,
+                    uint8_t* dst, int64_t dst_frame_pitch, int64_t dst_row_pitch, p3d_stream_t stream);
+
+/* One level of a pair of clips: adds the level's three sums of frame f and channel c to sums[(f * bpp + c) * sums_pitch .. + 3) (sums_pitch in
+ * int64 elements, >= 3: the caller's [frames][bpp][levels][3] has sums_pitch = 3 levels and passes the level's own address) and, with next_a
+ * and next_b non-null (both or neither), writes the NEXT level of both clips, contiguous uint8 [frames][h / 2][w / 2][bpp] each, from the
+ * samples it has staged.  h >= 11 and w >= 11: a level without a window is an error, never skipped.
+ *
+ * A work-group owns the P3D_MSSSIM_TILE_W x P3D_MSSSIM_TILE_H PIXELS at an even origin of one frame, all channels: the windows whose first
+ * sample lies in the tile (their 42 x 26 samples go to LDS once, dwords where the addresses allow, no load past the frame) and the 16 x 8
+ * samples of the next level under the tile.  The grid covers pixel tiles, ceil(w / 32) x ceil(h / 16) a frame: a work-group at the right or
+ * bottom edge that owns no window still writes its share of the next level.  Per channel the moments run as in p3d_video_ssim (a horizontal
+ * pass into LDS, a vertical pass a lane a window), the contributions meet in a wave reduction and the work-group issues ONE atomic per slot.
+ * Every store is checked against the next level's sizes.  frames h w == 0 is a success that launches nothing; null a, b or sums (with
+ * anything to do) returns P3D_ERR_ARGUMENT before any device call.  One launch.                                                          */
+int p3d_frame_msssim_level(const uint8_t* a, int64_t a_frame_pitch, int64_t a_row_pitch, const uint8_t* b, int64_t b_frame_pitch,
+                           int64_t b_row_pitch, int32_t frames, int32_t h, int32_t w, int32_t bpp, int64_t* sums, int64_t sums_pitch,
+                           uint8_t* next_a, uint8_t* next_b, p3d_stream_t stream);
+
+/* ---- frame resampling (frame_resample.hip; pix2pix3d_amd/resample.py) -------------------------------------
+ * Pillow's Image.resize on 8-bit clips, bit for bit: for 8-bit samples it is integer arithmetic on fixed-point coefficient tables.  The tables
+ * are made on the host (resample.py, Python floats); the three entry points below are the passes.
+ *
+ * Source and destination are clips, each with its own pitches; a destination of more than one frame has a frame pitch of at least the bytes of a
+ * frame.  1 <= h, w and every output size <= P3D_RESAMPLE_MAX_SIZE; frames == 0 is a success that launches nothing.  All offsets are 64-bit.
+ * Results are written out of place: the bytes the destination spans must not meet the source's.  The channels of a pixel are resampled
+ * independently (PIL's L, RGB, RGBX; its LA / RGBA path premultiplies alpha and is not this).
+ *
+ * Coefficients of one axis of in_size pixels resampled to out_size from the source interval [in0, in1) (default [0, in_size)).  Every float step
+ * is IEEE double with one rounding per operator, in exactly this order.  A filter is a function f and a support S:
+ *     box       f(x) = 1 if -0.5 < x <= 0.5, else 0                                                                        S = 0.5
+ *     bilinear  f(x) = 1 - |x| if |x| < 1, else 0                                                                          S = 1
+ *     hamming   f(x) = 1 if x == 0; 0 if |x| >= 1; otherwise with t = pi |x|: sin(t) / t * (0.54 + 0.46 cos(t))            S = 1
+ *     bicubic   a = -0.5; |x| < 1: ((a + 2) |x| - (a + 3)) |x| |x| + 1;  |x| < 2: (((|x| - 5) |x| + 8) |x| - 4) a;  else 0  S = 2
+ *     lanczos   sinc(x) sinc(x / 3) for -3 <= x < 3, else 0; sinc(0) = 1, otherwise with t = pi x: sin(t) / t              S = 3
+ *   1. scale = (in1 - in0) / out_size, fs = max(scale, 1.0), support = S fs, ksize = int(ceil(support)) * 2 + 1.
+ *   2. For the output xx: center = in0 + (xx + 0.5) scale.
+ *   3. xmin = max(int(center - support + 0.5), 0).
+ *   4. count = min(int(center + support + 0.5), in_size) - xmin.
+ *   5. w[i] = f((i + xmin - center + 0.5) (1.0 / fs)) for i < count.
+ *   6. ww = the sum of w[i] accumulated from 0.0 in index order; if ww != 0, w[i] = w[i] / ww.
+ *   7. k[i] = int(-0.5 + w[i] 2^22) if w[i] < 0, else int(0.5 + w[i] 2^22); int truncates toward zero.
+ *   8. Entries beyond count are 0.
+ * The tables: bounds int32 [out_size][2] = (xmin, count) and weights int32 [out_size][ksize], with 255 sum |k| + 2^21 < 2^31 for every output
+ * (resample.py checks it), so that the int32 accumulators never wrap.
+ *
+ * ONE PASS.  Each byte is out = min(max((2^21 + sum_i k[i] src[xmin + i]) >> 22, 0), 255): an arithmetic shift on int32, the sum per byte lane.
+ * TWO AXES: the horizontal pass first, into a uint8 intermediate, then the vertical pass on it; the rounding to uint8 between the passes is part
+ * of the definition.  The caller hands the horizontal pass only the source rows the vertical pass reads (a view: any row pitch will do).
+ *
+ * NEAREST: index tables int32 [ow] and [oh], made on the host by ACCUMULATION: s = in_size / out_size; xo = s 0.5; for each output
+ * idx = min(int(xo), in_size - 1), then xo += s.  (The closed form int((x + 0.5) in_size / out_size) differs from it at some sizes.)
+ *
+ * Every kernel clamps what it reads from a table into the axis before use: xmin to [0, in_size], count to [0, min(ksize, in_size - xmin)], a
+ * nearest index to [0, in_size - 1].  No load leaves a source row and no store leaves the output, whatever the tables hold.
+ * Null pointers, sizes out of range, bpp outside 1 .. 4, ksize < 1 and pitches below the rows return P3D_ERR_ARGUMENT before any launch.      */
+#define P3D_RESAMPLE_MAX_SIZE 32768       /* every side of a source or a result */
+#define P3D_RESAMPLE_TILE_W 64            /* the work-group tile of the passes (tests straddle it): output pixels of the horizontal pass and of the */
+#define P3D_RESAMPLE_TILE_H 16            /* gather, DWORDS of a row (4 P3D_RESAMPLE_TILE_W bytes) of the vertical pass; rows of all three */
+#define P3D_RESAMPLE_LDS_ROW_BYTES 1024   /* the horizontal pass stages a tile's source span in LDS while it is at most this long a row ... */
+#define P3D_RESAMPLE_LDS_TAPS 64          /* ... and ksize is at most this; a longer span or tap list is read from global memory directly */
+
+/* The horizontal pass: dst[f][y][xx][c] from src[f][y][xmin(xx) + i][c]; dst is [frames][h][ow][bpp].  A work-group owns P3D_RESAMPLE_TILE_W output
+ * pixels of P3D_RESAMPLE_TILE_H rows: it reads the bounds and the weights of its columns once (into LDS) and stages the source span those outputs
+ * read, [the smallest xmin, the largest xmin + count) of every row of the tile, into LDS once — unless the span is longer than
+ * P3D_RESAMPLE_LDS_ROW_BYTES or ksize exceeds P3D_RESAMPLE_LDS_TAPS (a 512 -> 1 Lanczos has 3073 taps), when every tap is read from global
+ * memory.  One launch.                                                                                                                  */
+int p3d_frame_resample_rows(const uint8_t* src, int64_t src_frame_pitch, int64_t src_row_pitch, int32_t frames, int32_t h, int32_t w, int32_t bpp,
+                            uint8_t* dst, int64_t dst_frame_pitch, int64_t dst_row_pitch, int32_t ow, const int32_t* bounds, const int32_t* weights,
+                            int32_t ksize, p3d_stream_t stream);
+
+/* The vertical pass, channel-agnostic: a row is w bpp bytes and output byte j of row yy is the weighted sum of byte j over count(yy) source rows;
+ * dst is [frames][oh][w][bpp].  A lane owns four consecutive bytes: a dword load where the source row's address allows and a dword store where
+ * the output row's does, single bytes everywhere else (rows that start at an odd byte, the row's tail).  A wave owns one output row at a time,
+ * so its bounds and weights are wave-uniform.  One launch.                                                                              */
+int p3d_frame_resample_columns(const uint8_t* src, int64_t src_frame_pitch, int64_t src_row_pitch, int32_t frames, int32_t h, int32_t w, int32_t bpp,
+                               uint8_t* dst, int64_t dst_frame_pitch, int64_t dst_row_pitch, int32_t oh, const int32_t* bounds,
+                               const int32_t* weights, int32_t ksize, p3d_stream_t stream);
+
+/* The gather: dst[f][yy][xx] = src[f][y_index[yy]][x_index[xx]], all bpp bytes; dst is [frames][oh][ow][bpp], x_index int32 [ow], y_index int32
+ * [oh].  One launch.                                                                                                                    */
+int p3d_frame_resample_nearest(const uint8_t* src, int64_t src_frame_pitch, int64_t src_row_pitch, int32_t frames, int32_t h, int32_t w, int32_t bpp,
+                               uint8_t* dst, int64_t dst_frame_pitch, int64_t dst_row_pitch, int32_t oh, int32_t ow, const int32_t* x_index,
+                               const int32_t* y_index, p3d_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -4,18 +4,19 @@
 // p3d_video_error_sums  a work-group of four waves owns kErrPixels consecutive pixels of one frame, a lane every 256th of them, all channels of a pixel in
 //                       its own registers.  16 values leave a lane; a wave reduction, 4 x 16 words of LDS, and the first 4 bpp lanes issue ONE atomic each.
 // p3d_video_ssim        a work-group owns a tile of 32 x 16 windows of one frame, all channels.  The 42 x 26 samples under it, of both clips, go to LDS once
-//                       (as bytes, channels interleaved as in memory); then per channel the horizontal pass writes the five int32 row sums of every
-//                       (input row, window column) to LDS, a barrier, and the vertical pass — a lane a window, two windows a lane — reads them down its own
-//                       column: consecutive lanes, consecutive words, no bank conflict.  The contributions meet in a wave reduction and ONE atomic a
+//                       (as bytes, channels interleaved as in memory); then per channel the passes of ssim_window.h — the horizontal one into LDS, a
+//                       barrier, the vertical one a lane a window, two windows a lane.  The contributions meet in a wave reduction and ONE atomic a
 //                       channel and work-group.
 #include "../p3d_common.h"
+#include "clip_checks.h"
 #include "p3d_video.h"
+#include "ssim_window.h"
 
 namespace {
 
 using namespace p3d;
+using namespace p3d::ssim;                                                      // kThreads, kWaves, the tile and wave_sum: one work-group shape for both kernels
 
-constexpr int kThreads = 256, kWaves = kThreads / kWave;
 constexpr int kErrPixels = kThreads * 16;                                       // of a work-group of the error sums
 
 struct PairArgs {
@@ -27,13 +28,6 @@ struct PairArgs {
     unsigned long long* sums;
     float* map;
 };
-
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_down(v, d);
-    return v;                                                                   // lane 0 holds the sum
-}
 
 __device__ __forceinline__ long long wave_max(long long v)
 {
@@ -90,30 +84,11 @@ __global__ void __launch_bounds__(kThreads) error_sums_kernel(const PairArgs p)
     }
 }
 
-constexpr int kTaps = P3D_VIDEO_SSIM_TAPS, kHalo = kTaps - 1;
-constexpr int kTileW = P3D_VIDEO_SSIM_TILE_W, kTileH = P3D_VIDEO_SSIM_TILE_H;
-constexpr int kInW = kTileW + kHalo, kInH = kTileH + kHalo;                     // the samples under a tile: 42 x 26
-constexpr long long kC1 = P3D_VIDEO_SSIM_C1, kC2 = P3D_VIDEO_SSIM_C2;
-static_assert(kTileW * kTileH == 2 * kThreads && kTileW == 32, "two windows a lane, a row of windows half a wave");
-
-// One window's value from its five moments: the header's four factors and three fp64 operations.
-__device__ __forceinline__ double ssim_of(long long A, long long B, long long Pxx, long long Pyy, long long Pxy)
-{
-#pragma clang fp contract(off)
-    const long long ab = A * B, aa_bb = A * A + B * B;
-    const long long n1 = 2 * ab + kC1, n2 = 2 * ((Pxy << 20) - ab) + kC2;
-    const long long d1 = aa_bb + kC1, d2 = ((Pxx + Pyy) << 20) - aa_bb + kC2;
-    const double num = (double)n1 * (double)n2;
-    const double den = (double)d1 * (double)d2;
-    return num / den;
-}
-
 __global__ void __launch_bounds__(kThreads) ssim_kernel(const PairArgs p)
 {
     __shared__ uint8_t ta[kInH][kInW * 4], tb[kInH][kInW * 4];                  // 2 x 4368 bytes
-    __shared__ int hb[5][kInH][kTileW];                                         // 16640 bytes: A, B, Pxx, Pyy, Pxy of (input row, window column)
+    __shared__ RowSums hb;
     __shared__ long long part[kWaves];
-    constexpr int g[kTaps] = {P3D_VIDEO_SSIM_WINDOW};
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & (kWave - 1);
     const int f = blockIdx.x / (unsigned)p.per_frame;
     const int tile = blockIdx.x - f * p.per_frame;
@@ -134,14 +109,10 @@ __global__ void __launch_bounds__(kThreads) ssim_kernel(const PairArgs p)
         for (int i = tid; i < ih * kTileW; i += kThreads) {                     // the horizontal pass
             const int r = i >> 5, x = i & (kTileW - 1);
             if (x < tw) {
-                int sa = 0, sb = 0, sxx = 0, syy = 0, sxy = 0;                  // <= 1024 x 255^2 < 2^26
+                int s[5] = {};
 #pragma unroll
-                for (int k = 0; k < kTaps; ++k) {
-                    const int xa = ta[r][(x + k) * p.bpp + c], xb = tb[r][(x + k) * p.bpp + c];
-                    sa += g[k] * xa; sb += g[k] * xb;
-                    sxx += g[k] * xa * xa; syy += g[k] * xb * xb; sxy += g[k] * xa * xb;
-                }
-                hb[0][r][x] = sa; hb[1][r][x] = sb; hb[2][r][x] = sxx; hb[3][r][x] = syy; hb[4][r][x] = sxy;
+                for (int k = 0; k < kTaps; ++k) row_tap(s, ta[r][(x + k) * p.bpp + c], tb[r][(x + k) * p.bpp + c], k);
+                put_row_sums(hb, r, x, s);
             }
         }
         __syncthreads();
@@ -150,15 +121,11 @@ __global__ void __launch_bounds__(kThreads) ssim_kernel(const PairArgs p)
         for (int j = 0; j < 2; ++j) {                                           // the vertical pass: window (x, y) of the tile
             const int o = tid + j * kThreads, y = o >> 5, x = o & (kTileW - 1);
             if (y < th && x < tw) {
-                int A = 0, B = 0;                                               // < 2^28
-                long long Pxx = 0, Pyy = 0, Pxy = 0;                            // < 2^36
+                Moments m{0, 0, 0, 0, 0};
 #pragma unroll
-                for (int k = 0; k < kTaps; ++k) {
-                    A += g[k] * hb[0][y + k][x]; B += g[k] * hb[1][y + k][x];
-                    Pxx += (long long)g[k] * hb[2][y + k][x]; Pyy += (long long)g[k] * hb[3][y + k][x]; Pxy += (long long)g[k] * hb[4][y + k][x];
-                }
-                const double q = ssim_of(A, B, Pxx, Pyy, Pxy);
-                mine += llrint(q * 4294967296.0);
+                for (int k = 0; k < kTaps; ++k) column_tap(m, hb, y, x, k);
+                const double q = window_values<false>(m);
+                mine += contribution(q);
                 if (p.map) p.map[(((int64_t)f * oh + y0 + y) * ow + x0 + x) * p.bpp + c] = (float)q;
             }
         }
@@ -175,23 +142,6 @@ __global__ void __launch_bounds__(kThreads) ssim_kernel(const PairArgs p)
         }
         __syncthreads();                                                        // part is free again
     }
-}
-
-// The checks both entry points share; *pixels = n_frames h w.
-int check_pair(const char* what, const uint8_t* a, int64_t a_frame_pitch, int64_t a_row_pitch, const uint8_t* b, int64_t b_frame_pitch, int64_t b_row_pitch,
-               int32_t n_frames, int32_t h, int32_t w, int32_t bpp, const int64_t* sums, int64_t* pixels)
-{
-    P3D_REQUIRE(n_frames >= 0 && h >= 0 && w >= 0, "%s: n_frames, h and w must be >= 0 (got %d, %d, %d)", what, n_frames, h, w);
-    P3D_REQUIRE(bpp >= 1 && bpp <= 4, "%s: bpp must be 1 .. 4 (got %d)", what, bpp);
-    const int64_t hw = (int64_t)h * w;
-    P3D_REQUIRE(hw < (1ll << 31) && hw * n_frames * bpp < (1ll << 31), "%s: %d x %d x %d pixels of %d bytes reach 2^31", what, n_frames, h, w, bpp);
-    *pixels = hw * n_frames;
-    if (*pixels == 0) return P3D_OK;
-    P3D_REQUIRE(a && b && sums, "%s: a, b and sums must be non-null", what);
-    P3D_REQUIRE(((uintptr_t)sums & 7u) == 0, "%s: sums must be 8-byte aligned", what);
-    P3D_REQUIRE(a_row_pitch >= (int64_t)w * bpp && b_row_pitch >= (int64_t)w * bpp && a_frame_pitch >= 0 && b_frame_pitch >= 0,
-                "%s: a row pitch is shorter than the row, or a frame pitch negative", what);
-    return P3D_OK;
 }
 
 } // namespace

@@ -5,25 +5,28 @@ carries the quadric of its input faces' planes (Garland & Heckbert 1997), an edg
 round collapses at once a set of cheap edges no two of which touch each other's 1-rings — so that the result is a pure function of the input, whatever
 order the hardware takes the edges in.  Only interior edges of a 2-manifold neighbourhood collapse (boundary and ``pinned`` vertices, fins and edges
 whose link condition fails are never touched), and a collapse that would turn a face over or into a spike is refused, so a closed manifold stays a
-closed manifold.  The rules are csrc/sketch/p3d_sketch.h's ("mesh decimation"); DESIGN.md section 2.1aa has the measurements.
+closed manifold.  The rules are csrc/mesh/p3d_mesh.h's; DESIGN.md section 2.1aa has the measurements.
 
     decimate(vertices, faces, target_faces, fraction, max_rounds, pinned)   -> Decimation
     decimate_to(vertices, faces, tolerance, spacing)                        -> (vertices', faces', target_faces or None, agreement)
 
-CPU tensors run the torch formulation below, which is the definition; device tensors run the kernels of csrc/sketch/mesh_decimate.hip through
-``sketch.sketch_lib()`` (libp3d_sketch.so: the one kernel library whose header may grow) with the same bytes.  The sorts and scans between the kernels (``mesh.adjacency``, the vertex -> face list, the ranks) are
-torch on the tensors' device for both."""
+CPU tensors run the torch formulation below, which is the definition; device tensors run the kernels of csrc/mesh/mesh_decimate.hip through
+``mesh_lib()`` (libp3d_mesh.so, a kernel library of its own beside libp3d_hip.so) with the same bytes.  The sorts and scans between the kernels
+(``mesh.adjacency``, the vertex -> face list, the ranks) are torch on the tensors' device for both."""
 import math
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
-from . import _lib, mesh, sketch
+from . import _lib, mesh
 
-NO_RANK = sketch.HEADER.constants['P3D_MESH_NO_RANK']
-QUADRIC = sketch.HEADER.constants['P3D_MESH_QUADRIC_DOUBLES']
-MAX_COUNT = sketch.HEADER.constants['P3D_MESH_DECIMATE_MAX']
+_side = _lib.SideLibrary('mesh')                     # libp3d_mesh.so: loaded on the first call, device-guarded; launch_count() is its own counter
+MESH_LIB_PATH, HEADER = _side.path, _side.header
+mesh_lib, launch_count, _check = _side.lib, _side.launch_count, _side.check
+NO_RANK = HEADER.constants['P3D_MESH_NO_RANK']
+QUADRIC = HEADER.constants['P3D_MESH_QUADRIC_DOUBLES']
+MAX_COUNT = HEADER.constants['P3D_MESH_DECIMATE_MAX']
 LAUNCHES_PER_ROUND = 6         # p3d_mesh_edge_costs 1, p3d_mesh_edge_select 3, p3d_mesh_collapse 2 (and p3d_mesh_quadrics once a call)
 DECIMATE_RUNGS = 40            # decimate_to's ladder of targets: T / 2^(i / 2), i = 1 .. 40, as long as they stay at 4 faces or more
 
@@ -71,7 +74,7 @@ def _sqrt(x):
 
 # ---- lists --------------------------------------------------------------------------------------------------------------------------
 def vertex_faces(faces, n_vertices):
-    """The vertex -> face list of p3d_sketch.h: (offsets int64 [V + 1], faces int32 [3 T]), a stable sort of the corners by their vertex."""
+    """The vertex -> face list of p3d_mesh.h: (offsets int64 [V + 1], faces int32 [3 T]), a stable sort of the corners by their vertex."""
     corner, order = torch.sort(faces.reshape(-1).long(), stable=True)
     offsets = torch.searchsorted(corner, torch.arange(n_vertices + 1, device=faces.device))
     return offsets, torch.div(order, 3, rounding_mode='floor').to(torch.int32)
@@ -139,7 +142,7 @@ def quadrics(vertices, faces32, vf_offsets, vf_faces):
     if not vertices.is_cuda:
         return _quadrics_torch(vertices, faces32, vf_offsets, vf_faces)
     q = torch.empty([vertices.shape[0], QUADRIC], dtype=torch.float64, device=vertices.device)
-    sketch._check(sketch.sketch_lib().p3d_mesh_quadrics(_lib.ptr(vertices), vertices.shape[0], _lib.ptr(faces32), faces32.shape[0], _lib.ptr(vf_offsets),
+    _check(mesh_lib().p3d_mesh_quadrics(_lib.ptr(vertices), vertices.shape[0], _lib.ptr(faces32), faces32.shape[0], _lib.ptr(vf_offsets),
                                                            _lib.ptr(vf_faces), _lib.ptr(q), _lib.stream_of(q)), 'mesh_quadrics')
     return q
 
@@ -248,7 +251,7 @@ def edge_costs(vertices, quads, faces32, lists, fixed):
     target = torch.empty([ne, 3], dtype=torch.float32, device=dev)
     cost = torch.empty([ne], dtype=torch.float64, device=dev)
     valid = torch.empty([ne], dtype=torch.uint8, device=dev)
-    sketch._check(sketch.sketch_lib().p3d_mesh_edge_costs(
+    _check(mesh_lib().p3d_mesh_edge_costs(
         _lib.ptr(vertices), _lib.ptr(quads), vertices.shape[0], _lib.ptr(faces32), faces32.shape[0], _lib.ptr(adj.offsets), _lib.ptr(adj.neighbours),
         adj.neighbours.shape[0], _lib.ptr(fixed), _lib.ptr(lists.vf_offsets), _lib.ptr(lists.vf_faces), _lib.ptr(lists.edges), ne, _lib.ptr(target),
         _lib.ptr(cost), _lib.ptr(valid), _lib.stream_of(target)), 'mesh_edge_costs')
@@ -299,7 +302,7 @@ def edge_select(rank, lists, n_vertices):
     adj, dev, ne = lists.adj, rank.device, rank.shape[0]
     m1, m2 = torch.empty([n_vertices], dtype=torch.int32, device=dev), torch.empty([n_vertices], dtype=torch.int32, device=dev)
     win = torch.empty([ne], dtype=torch.uint8, device=dev)
-    sketch._check(sketch.sketch_lib().p3d_mesh_edge_select(_lib.ptr(rank), _lib.ptr(lists.edges), ne, n_vertices, _lib.ptr(adj.offsets),
+    _check(mesh_lib().p3d_mesh_edge_select(_lib.ptr(rank), _lib.ptr(lists.edges), ne, n_vertices, _lib.ptr(adj.offsets),
                                                               _lib.ptr(adj.neighbours), _lib.ptr(lists.entry_edge), adj.neighbours.shape[0], _lib.ptr(m1),
                                                               _lib.ptr(m2), _lib.ptr(win), _lib.stream_of(win)), 'mesh_edge_select')
     return win
@@ -329,7 +332,7 @@ def collapse(vertices, quads, parent, faces32, edges, apply, target):
     if not vertices.is_cuda:
         return _collapse_torch(vertices, quads, parent, faces32, edges, apply, target)
     dead = torch.empty([faces32.shape[0]], dtype=torch.uint8, device=vertices.device)
-    sketch._check(sketch.sketch_lib().p3d_mesh_collapse(_lib.ptr(vertices), _lib.ptr(quads), _lib.ptr(parent), vertices.shape[0], _lib.ptr(faces32),
+    _check(mesh_lib().p3d_mesh_collapse(_lib.ptr(vertices), _lib.ptr(quads), _lib.ptr(parent), vertices.shape[0], _lib.ptr(faces32),
                                                            faces32.shape[0], _lib.ptr(edges), _lib.ptr(apply), _lib.ptr(target), edges.shape[0], _lib.ptr(dead),
                                                            _lib.stream_of(dead)), 'mesh_collapse')
     return dead

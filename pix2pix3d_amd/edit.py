@@ -37,6 +37,7 @@ import numpy as np
 import torch
 
 from . import _lib, mesh, views
+from .resample import resize
 
 MAX_SIZE, MAX_STROKES, MIN_COORD, MAX_COORD = _lib.P3D_PAINT_MAX_SIZE, _lib.P3D_PAINT_MAX_STROKES, _lib.P3D_PAINT_MIN_COORD, _lib.P3D_PAINT_MAX_COORD
 SLIDER_RANGE = dict(yaw=math.pi / 2, pitch=math.pi, roll=math.pi / 4)         # radians per 100 slider units (qt_demo_seg2cat.py:374-379)
@@ -662,6 +663,5 @@ def load_mask(path, device=None, size=None):
     if info.mode != 'L':
         raise ValueError(f'load_mask: {path} is mode {info.mode!r}: a label map is 8-bit grey (L)')
     if size is not None:
-        from .resample import resize
         mask = resize(mask[None], size, 'nearest')[0]
     return mask

@@ -3,8 +3,8 @@
 Single-scale SSIM (``quality.py``) at 512 x 512 is nearly blind to what separates this package's own variants — blur, ringing and low-frequency colour
 shifts of fp16 against fp32 heads, bf16x3 against ``exact_fp32``, 4:2:0 against 4:4:4, ``resample.resize(image_raw)`` against the SR heads — because those
 show only at coarser scales.  MS-SSIM weighs the contrast-structure term of four halvings and the full SSIM of the coarsest level, and needs no feature
-network (csrc/sketch/p3d_sketch.h, "multi-scale frame quality", states the rules; the kernels live in libp3d_sketch.so and are reached through
-``sketch.sketch_lib()``):
+network (csrc/video/p3d_video.h, "multi-scale frame quality", states the rules; the kernels live in libp3d_video.so and are reached through
+``clips.video_lib()``):
 
     halve(frames, out)                        uint8 [F, H // 2, W // 2(, bpp)]: (s00 + s01 + s10 + s11 + 2) >> 2 per channel, an odd last row or column dropped
     pyramid(frames, levels)                   the list of ``levels`` clips; level 0 is the input itself
@@ -16,7 +16,7 @@ network (csrc/sketch/p3d_sketch.h, "multi-scale frame quality", states the rules
 
 Clips are ``quality.py``'s: uint8 [F, H, W, bpp], bpp = 2 .. 4, or [F, H, W], of one shape on one device, contiguous pixels and any row and frame pitch
 (``clips.check_frames``), read in place.  Per level the window, the moments and the four int64 factors are ``quality.ssim_moments`` / ``ssim_factors``
-(p3d_video.h's constants): q = (n1 n2) / (d1 d2) as there, cs = n2 / d2 — two conversions and one fp64 division; it may be negative — and a window
+(on the device: the one window core both kernels run, csrc/video/ssim_window.h): q = (n1 n2) / (d1 d2) as there, cs = n2 / d2 — two conversions and one fp64 division; it may be negative — and a window
 contributes round_half_even(q 2^32) and round_half_even(cs 2^32).  So the torch formulation here, which CPU tensors take, is the definition, and the
 device kernels' bytes equal it.  A level with a side under 11 has no window: that is an error, never a level skipped.  The pyramid is deliberately NOT
 ``resample.resize(..., 'box')``, which rounds once per pass.  The sums ACCUMULATE into ``out``: integer sums, no order, no host synchronisation.
@@ -27,9 +27,9 @@ import math
 
 import torch
 
-from . import _lib, clips, quality, sketch
+from . import _lib, clips, quality
 
-_C = sketch.HEADER.constants
+_C = clips.HEADER.constants
 MAX_LEVELS, TILE_W, TILE_H = _C['P3D_MSSSIM_MAX_LEVELS'], _C['P3D_MSSSIM_TILE_W'], _C['P3D_MSSSIM_TILE_H']
 WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)   # Wang et al.'s exponents, finest level first
 SCALE = float(1 << quality.SHIFT)
@@ -72,10 +72,6 @@ def _check_weights(weights, levels, who):
     return w
 
 
-def _bpp(t):
-    return t.shape[3] if t.ndim == 4 else 1
-
-
 # ---- the pyramid ---------------------------------------------------------------------------------------------------------------------------
 def _halve_torch(frames):
     nh, nw = frames.shape[1] // 2, frames.shape[2] // 2
@@ -88,18 +84,17 @@ def halve(frames, out=None):
     own, an odd last row or column dropped; a side of 1 gives an empty level.  ``out``: a clip to write into, any row and frame pitch, apart from
     ``frames`` (``resample.resize``'s rules).  Device tensors: ONE ``p3d_frame_halve`` launch (none for an empty result), no synchronisation; CPU
     tensors: the torch formulation."""
-    from .resample import _check_out
     f, h, w = clips.check_frames(frames, 'halve: frames', bpp=(1, 2, 3, 4))
-    out = _check_out(out, [f, h // 2, w // 2] + list(frames.shape[3:]), frames, 'halve')
+    out = clips.check_out(out, [f, h // 2, w // 2] + list(frames.shape[3:]), frames, 'halve')
     if out.numel() == 0:
         return out
     if not frames.is_cuda:
         out.copy_(_halve_torch(frames))
         return out
     with _lib.kernel_timer('frame_halve', out):
-        code = sketch.sketch_lib().p3d_frame_halve(_lib.ptr(frames), frames.stride(0), frames.stride(1), f, h, w, _bpp(frames), _lib.ptr(out), out.stride(0),
-                                                   out.stride(1), _lib.stream_of(out))
-    sketch._check(code, 'frame_halve')
+        code = clips.video_lib().p3d_frame_halve(*clips.clip_args(frames), clips.bpp_of(frames), _lib.ptr(out), out.stride(0), out.stride(1),
+                                                 _lib.stream_of(out))
+    clips.check(code, 'frame_halve')
     return out
 
 
@@ -131,19 +126,17 @@ def _level_torch(a, b, out):
 
 def _level_device(a, b, sums, level, next_a=None, next_b=None):
     """One ``p3d_frame_msssim_level`` launch: the sums of ``level`` into ``sums`` [F, bpp, levels, 3], the next level into ``next_a`` / ``next_b``."""
-    f, h, w = a.shape[:3]
     with _lib.kernel_timer(f'frame_msssim_level{level}', sums):
-        code = sketch.sketch_lib().p3d_frame_msssim_level(_lib.ptr(a), a.stride(0), a.stride(1), _lib.ptr(b), b.stride(0), b.stride(1), f, h, w, _bpp(a),
-                                                          sums.data_ptr() + level * 3 * sums.element_size(), sums.shape[2] * 3, _lib.ptr(next_a),
-                                                          _lib.ptr(next_b), _lib.stream_of(sums))
-    sketch._check(code, 'frame_msssim_level')
+        code = clips.video_lib().p3d_frame_msssim_level(*clips.pair_args(a, b), sums.data_ptr() + level * 3 * sums.element_size(), sums.shape[2] * 3,
+                                                        _lib.ptr(next_a), _lib.ptr(next_b), _lib.stream_of(sums))
+    clips.check(code, 'frame_msssim_level')
 
 
 def level_sums(a, b, sums, level, next_a=None, next_b=None):
     """The entry point itself, for callers that bring their own buffers: adds the sums of clips ``a`` and ``b`` — one level — to ``sums[:, :, level]``
     of a contiguous int64 [F, bpp, levels, 3] and, with ``next_a`` and ``next_b`` (contiguous uint8 [F, H // 2, W // 2(, bpp)] on the device), writes the
     next level of both in the same launch.  Device tensors only."""
-    f, h, w, bpp = quality._check_pair(a, b, 'level_sums')
+    f, h, w, bpp = clips.check_pair(a, b, 'level_sums')
     if not a.is_cuda:
         raise ValueError('level_sums: the clips must be on a device (CPU tensors: msssim_sums)')
     if not torch.is_tensor(sums) or sums.dtype != torch.int64 or sums.ndim != 4 or tuple(sums.shape[:2]) != (f, bpp) or sums.shape[3] != 3 \
@@ -168,9 +161,9 @@ def msssim_sums(a, b, levels=MAX_LEVELS, out=None, fused=True):
     Device tensors, ``fused=True``: ``levels`` launches of ``p3d_frame_msssim_level``, each of which also writes the next level of both clips from the
     samples it has staged; ``fused=False``: ``p3d_frame_halve`` for each clip and level, and the level kernel only measures — 3 levels - 2 launches,
     the same bytes.  No synchronisation either way.  CPU tensors: the torch formulation."""
-    f, h, w, bpp = quality._check_pair(a, b, 'msssim_sums')
+    f, h, w, bpp = clips.check_pair(a, b, 'msssim_sums')
     _check_levels(levels, 'msssim_sums')
-    out = quality._check_out(out, [f, bpp, levels, 3], a.device, 'msssim_sums')
+    out = clips.check_sums(out, [f, bpp, levels, 3], a.device, 'msssim_sums')
     _check_size(h, w, levels, 'msssim_sums')
     if f == 0:
         return out
@@ -191,10 +184,6 @@ def msssim_sums(a, b, levels=MAX_LEVELS, out=None, fused=True):
 
 
 # ---- the host read ---------------------------------------------------------------------------------------------------------------------------
-def _mean(values):
-    return sum(values) / len(values) if values else float('nan')
-
-
 def _product(cs, q, weights):
     """prod_{k < L - 1} max(cs_k, 0)^(w_k) * max(q_(L-1), 0)^(w_(L-1)); NaN for a level without a window."""
     terms = list(cs[:-1]) + [q[-1]]
@@ -227,8 +216,8 @@ def metrics_from_msssim(sums, weights=None):
         return out
     per = [[_product(means([(i, c)], 1), means([(i, c)], 0), weights) for c in range(bpp)] for i in range(f)]
     everything = [(i, c) for i in range(f) for c in range(bpp)]
-    return {'ms_ssim': _mean([v for row in per for v in row]), 'frame_channel_ms_ssim': per, 'frame_ms_ssim': [_mean(row) for row in per],
-            'channel_ms_ssim': [_mean([per[i][c] for i in range(f)]) for c in range(bpp)],
+    return {'ms_ssim': quality.mean([v for row in per for v in row]), 'frame_channel_ms_ssim': per, 'frame_ms_ssim': [quality.mean(row) for row in per],
+            'channel_ms_ssim': [quality.mean([per[i][c] for i in range(f)]) for c in range(bpp)],
             'level_cs': means(everything, 1), 'level_q': means(everything, 0),
             'channel_level_cs': [means([(i, c) for i in range(f)], 1) for c in range(bpp)],
             'channel_level_q': [means([(i, c) for i in range(f)], 0) for c in range(bpp)],
@@ -257,7 +246,7 @@ class MultiScale:
         self.frames = 0
 
     def add(self, a, b):
-        f, _, _, bpp = quality._check_pair(a, b, 'MultiScale.add')
+        f, _, _, bpp = clips.check_pair(a, b, 'MultiScale.add')
         if bpp != self.bpp or a.device != self.device:
             raise ValueError(f'MultiScale.add: the clips have {bpp} bytes a pixel on {a.device}, the counters {self.bpp} on {self.device}')
         self.sums[0] += msssim_sums(a, b, self.levels).sum(dim=0)

@@ -35,38 +35,9 @@ def ssim_window():
     return torch.from_numpy(np.round(1024 * g / g.sum()).astype(np.int64))
 
 
-def _check_pair(a, b, what):
-    """(F, H, W, bpp) of two clips of one shape on one device."""
-    f, h, w = clips.check_frames(a, f'{what}: a', bpp=(1, 2, 3, 4))
-    clips.check_frames(b, f'{what}: b', bpp=(1, 2, 3, 4))
-    if a.shape != b.shape:
-        raise ValueError(f'{what}: a is {tuple(a.shape)}, b is {tuple(b.shape)}')
-    if a.device != b.device:
-        raise ValueError(f'{what}: a is on {a.device}, b on {b.device}')
-    return f, h, w, (a.shape[3] if a.ndim == 4 else 1)
-
-
-def _check_out(out, shape, device, what):
-    if out is None:
-        return torch.zeros(shape, dtype=torch.int64, device=device)
-    if not torch.is_tensor(out) or out.dtype != torch.int64 or tuple(out.shape) != tuple(shape) or out.device != device or not out.is_contiguous():
-        raise ValueError(f'{what}: out must be a contiguous int64 {list(shape)} tensor on {device}')
-    return out
-
-
-def _pair(a, b, bpp):
-    """The leading arguments of the two entry points: both clips with their pitches, then F, H, W, bpp."""
-    f, h, w = a.shape[:3]
-    return _lib.ptr(a), a.stride(0), a.stride(1), _lib.ptr(b), b.stride(0), b.stride(1), f, h, w, bpp
-
-
-def _channels(t):
-    return t if t.ndim == 4 else t[..., None]
-
-
 # ---- error sums ----------------------------------------------------------------------------------------------------------------------------
 def _error_sums_torch(a, b, out):
-    d = (_channels(a).to(torch.int64) - _channels(b).to(torch.int64)).abs()
+    d = (clips.channels(a).to(torch.int64) - clips.channels(b).to(torch.int64)).abs()
     out[..., 0] += d.sum(dim=(1, 2))
     out[..., 1] += (d * d).sum(dim=(1, 2))
     out[..., 2] = torch.maximum(out[..., 2], d.amax(dim=(1, 2)))
@@ -78,14 +49,14 @@ def error_sums(a, b, out=None):
     """int64 [F, bpp, 4]: per frame and channel, with d = a - b per sample, sum |d|, sum d^2, max |d| and the number of samples with d != 0.  ``out``: the
     caller's contiguous int64 [F, bpp, 4] on the clips' device, to which the call ADDS (the third slot by a maximum): zero it once, accumulate many calls,
     read once.  Device tensors: ONE ``p3d_video_error_sums`` launch, no synchronisation; CPU tensors: the torch formulation."""
-    f, h, w, bpp = _check_pair(a, b, 'error_sums')
-    out = _check_out(out, [f, bpp, 4], a.device, 'error_sums')
+    f, h, w, bpp = clips.check_pair(a, b, 'error_sums')
+    out = clips.check_sums(out, [f, bpp, 4], a.device, 'error_sums')
     if f * h * w == 0:
         return out
     if not a.is_cuda:
         return _error_sums_torch(a, b, out)
     with _lib.kernel_timer('video_error_sums', out):
-        code = clips.video_lib().p3d_video_error_sums(*_pair(a, b, bpp), _lib.ptr(out), _lib.stream_of(out))
+        code = clips.video_lib().p3d_video_error_sums(*clips.pair_args(a, b), _lib.ptr(out), _lib.stream_of(out))
     clips.check(code, 'video_error_sums')
     return out
 
@@ -95,7 +66,7 @@ def ssim_moments(a, b):
     """(A, B, Pxx, Pyy, Pxy): int64 [F, H - 10, W - 10, bpp] each, the exact weighted sums of x, y, x^2, y^2 and x y over every window (x from ``a``,
     y from ``b``), by a horizontal then a vertical pass of the 1-D window, as the kernel runs them.  Torch ops on the clips' device."""
     g = ssim_window().tolist()
-    x, y = _channels(a).to(torch.int64), _channels(b).to(torch.int64)
+    x, y = clips.channels(a).to(torch.int64), clips.channels(b).to(torch.int64)
     oh, ow = x.shape[1] - HALO, x.shape[2] - HALO
     out = []
     for q in (x, y, x * x, y * y, x * y):
@@ -130,8 +101,8 @@ def ssim_sums(a, b, out=None, maps=False):
     of windows; ``H < 11`` or ``W < 11`` has no window and adds nothing.  ``out`` accumulates as ``error_sums``' does.  With ``maps`` the call returns
     ``(sums, map)``, map float32 [F, H - 10, W - 10, bpp] (bpp = 1 included) holding (float) q of every window, for heat maps.  Device tensors: ONE
     ``p3d_video_ssim`` launch, no synchronisation; CPU tensors: the torch formulation (``ssim_moments``, ``ssim_factors``, ``ssim_values``)."""
-    f, h, w, bpp = _check_pair(a, b, 'ssim_sums')
-    out = _check_out(out, [f, bpp, 2], a.device, 'ssim_sums')
+    f, h, w, bpp = clips.check_pair(a, b, 'ssim_sums')
+    out = clips.check_sums(out, [f, bpp, 2], a.device, 'ssim_sums')
     oh, ow = max(h - HALO, 0), max(w - HALO, 0)
     heat = torch.empty([f, oh, ow, bpp], dtype=torch.float32, device=a.device) if maps else None
     if f * oh * ow:
@@ -139,7 +110,7 @@ def ssim_sums(a, b, out=None, maps=False):
             heat = _ssim_torch(a, b, out, maps)
         else:
             with _lib.kernel_timer('video_ssim', out):
-                code = clips.video_lib().p3d_video_ssim(*_pair(a, b, bpp), _lib.ptr(out), _lib.ptr(heat), _lib.stream_of(out))
+                code = clips.video_lib().p3d_video_ssim(*clips.pair_args(a, b), _lib.ptr(out), _lib.ptr(heat), _lib.stream_of(out))
             clips.check(code, 'video_ssim')
     return (out, heat) if maps else out
 
@@ -153,7 +124,8 @@ def _ratio(n, d):
     return float(n) / float(d) if d else float('nan')
 
 
-def _mean(values):
+def mean(values):
+    """The mean of a list of floats; NaN for an empty one."""
     return sum(values) / len(values) if values else float('nan')
 
 
@@ -185,7 +157,7 @@ def metrics_from_sums(error, ssim=None, samples=None):
         mse = _ratio(sum(e[i][c][1] for i, c in cells), total)
         per_channel = [_ratio(sum(s[i][c][0] for i in frames_of), sum(s[i][c][1] for i in frames_of) * scale) for c in channels_of]
         return {'mae': _ratio(sum(e[i][c][0] for i, c in cells), total), 'mse': mse, 'max': max([e[i][c][2] for i, c in cells], default=0),
-                'changed': _ratio(sum(e[i][c][3] for i, c in cells), total), 'psnr': _psnr(mse), 'ssim': _mean(per_channel)}
+                'changed': _ratio(sum(e[i][c][3] for i, c in cells), total), 'psnr': _psnr(mse), 'ssim': mean(per_channel)}
     out = block(range(f), range(bpp))
     per_channel, per_frame = [block(range(f), [c]) for c in range(bpp)], [block([i], range(bpp)) for i in range(f)]
     for key in ('mae', 'mse', 'max', 'changed', 'psnr', 'ssim'):
@@ -197,7 +169,7 @@ def metrics_from_sums(error, ssim=None, samples=None):
 
 def compare(a, b):
     """``metrics_from_sums`` of ``error_sums(a, b)`` and ``ssim_sums(a, b)``: two launches and ONE host read from device clips."""
-    f, h, w, _ = _check_pair(a, b, 'compare')
+    f, h, w, _ = clips.check_pair(a, b, 'compare')
     return metrics_from_sums(error_sums(a, b), ssim_sums(a, b), samples=h * w)
 
 
@@ -215,7 +187,7 @@ class Quality:
         self.frames = self.samples = 0                                          # host counts of what was added (samples: of one channel)
 
     def add(self, a, b):
-        f, h, w, bpp = _check_pair(a, b, 'Quality.add')
+        f, h, w, bpp = clips.check_pair(a, b, 'Quality.add')
         if bpp != self.bpp or a.device != self.device:
             raise ValueError(f'Quality.add: the clips have {bpp} bytes a pixel on {a.device}, the counters {self.bpp} on {self.device}')
         e, s = error_sums(a, b), ssim_sums(a, b)
@@ -235,9 +207,9 @@ class Quality:
 def difference_map(a, b, gain=1):
     """uint8 [F, H, W, 3] heat frames of the largest |a - b| over a pixel's channels, m = min(gain max_c |d|, 255): black through red (3 m), yellow (3 m - 255
     on green) to white (3 m - 510 on blue), each clamped to 0 .. 255.  Integer torch ops on the clips' device; no kernel of this package, no synchronisation."""
-    _check_pair(a, b, 'difference_map')
+    clips.check_pair(a, b, 'difference_map')
     if isinstance(gain, bool) or int(gain) != gain or int(gain) < 1:
         raise ValueError(f'difference_map: gain must be an integer >= 1, got {gain!r}')
-    m = ((_channels(a).to(torch.int16) - _channels(b).to(torch.int16)).abs().amax(dim=3).to(torch.int32) * int(gain)).clamp(max=255) if a.numel() else \
+    m = ((clips.channels(a).to(torch.int16) - clips.channels(b).to(torch.int16)).abs().amax(dim=3).to(torch.int32) * int(gain)).clamp(max=255) if a.numel() else \
         torch.zeros(a.shape[:3], dtype=torch.int32, device=a.device)
     return torch.stack([(3 * m).clamp(0, 255), (3 * m - 255).clamp(0, 255), (3 * m - 510).clamp(0, 255)], dim=3).to(torch.uint8)

@@ -1,7 +1,7 @@
 """Frame resampling: Pillow's ``Image.resize`` on uint8 clips, bit for bit — the one thing the frame stack could not do where the frames are.
 
 For 8-bit images PIL's resize is pure integer arithmetic on fixed-point coefficient tables, so "device bytes equal the CPU formulation" extends to "and
-equal PIL's bytes".  The rules are csrc/sketch/p3d_sketch.h's ("frame resampling"); DESIGN.md section 2.1ab has the measurements.
+equal PIL's bytes".  The rules are csrc/video/p3d_video.h's ("frame resampling"); DESIGN.md section 2.1ab has the measurements.
 
     FILTERS                                                 ('nearest', 'box', 'bilinear', 'hamming', 'bicubic', 'lanczos')
     coefficients(in_size, out_size, filter, interval)       (bounds int32 [out, 2] = (xmin, count), weights int32 [out, ksize]): 22-bit fixed point, CPU
@@ -13,8 +13,8 @@ Clips follow ``clips.check_frames``: uint8 [F, H, W, bpp] with bpp 2 .. 4, or [F
 The channels of a pixel are resampled independently.  That equals PIL for ``L``, ``RGB`` and ``RGBX``; it does NOT equal PIL's ``LA`` / ``RGBA`` path,
 which premultiplies alpha before it resamples — premultiplication is out of scope.  ``nearest`` takes no ``box``.
 
-CPU tensors run the integer torch formulation below, which is the definition; device tensors run the kernels of csrc/sketch/frame_resample.hip through
-``sketch.sketch_lib()`` (libp3d_sketch.so: the one kernel library whose header may grow) with the same bytes.  The tables are made on the host in Python
+CPU tensors run the integer torch formulation below, which is the definition; device tensors run the kernels of csrc/video/frame_resample.hip through
+``clips.video_lib()`` (libp3d_video.so: the library of everything on uint8 clips) with the same bytes.  The tables are made on the host in Python
 floats (IEEE double, one rounding per operator) and cached per (in, out, filter, interval, device): a repeated call uploads nothing and never
 synchronises."""
 import collections
@@ -23,11 +23,11 @@ import operator
 
 import torch
 
-from . import _lib, clips, sketch
+from . import _lib, clips
 
 FILTERS = ('nearest', 'box', 'bilinear', 'hamming', 'bicubic', 'lanczos')
 PRECISION_BITS = 22                                  # the fixed point of a weight: 32 - 8 - 2, PIL's
-MAX_SIZE, TILE_W, TILE_H = (sketch.HEADER.constants[k] for k in ('P3D_RESAMPLE_MAX_SIZE', 'P3D_RESAMPLE_TILE_W', 'P3D_RESAMPLE_TILE_H'))
+MAX_SIZE, TILE_W, TILE_H = (clips.HEADER.constants[k] for k in ('P3D_RESAMPLE_MAX_SIZE', 'P3D_RESAMPLE_TILE_W', 'P3D_RESAMPLE_TILE_H'))
 CACHE_ENTRIES = 64                                   # tables kept; the least recently used one leaves first
 
 
@@ -206,28 +206,19 @@ def _pass_torch(src, axis, bounds, weights):
     return (pass_sums(src, axis, bounds, weights) >> PRECISION_BITS).clamp(0, 255).to(torch.uint8)
 
 
-def _clip_args(t):
-    """A clip as the kernels take it: pointer, frame pitch, row pitch (bytes)."""
-    return _lib.ptr(t), t.stride(0), t.stride(1)
-
-
 def _pass_device(src, axis, bounds, weights, dst):
-    f, h, w = src.shape[:3]
-    bpp = src.shape[3] if src.ndim == 4 else 1
-    entry = sketch.sketch_lib().p3d_frame_resample_rows if axis == 2 else sketch.sketch_lib().p3d_frame_resample_columns
-    code = entry(*_clip_args(src), f, h, w, bpp, *_clip_args(dst), dst.shape[axis], _lib.ptr(bounds), _lib.ptr(weights), weights.shape[1],
+    entry = clips.video_lib().p3d_frame_resample_rows if axis == 2 else clips.video_lib().p3d_frame_resample_columns
+    code = entry(*clips.clip_args(src), clips.bpp_of(src), *clips.clip_args(dst)[:3], dst.shape[axis], _lib.ptr(bounds), _lib.ptr(weights), weights.shape[1],
                  _lib.stream_of(dst))
-    sketch._check(code, 'frame_resample_rows' if axis == 2 else 'frame_resample_columns')
+    clips.check(code, 'frame_resample_rows' if axis == 2 else 'frame_resample_columns')
 
 
 def _nearest(src, xidx, yidx, dst):
     if not src.is_cuda:
         dst.copy_(src.index_select(1, yidx.long()).index_select(2, xidx.long()))
         return
-    f, h, w = src.shape[:3]
-    bpp = src.shape[3] if src.ndim == 4 else 1
-    sketch._check(sketch.sketch_lib().p3d_frame_resample_nearest(*_clip_args(src), f, h, w, bpp, *_clip_args(dst), dst.shape[1], dst.shape[2],
-                                                                 _lib.ptr(xidx), _lib.ptr(yidx), _lib.stream_of(dst)), 'frame_resample_nearest')
+    clips.check(clips.video_lib().p3d_frame_resample_nearest(*clips.clip_args(src), clips.bpp_of(src), *clips.clip_args(dst)[:3], dst.shape[1], dst.shape[2],
+                                                             _lib.ptr(xidx), _lib.ptr(yidx), _lib.stream_of(dst)), 'frame_resample_nearest')
 
 
 # ---- resize ------------------------------------------------------------------------------------------------------------------------------
@@ -261,27 +252,6 @@ def _check_box(box, h, w, filter, who):
     return (None if (x0, x1) == (0.0, float(w)) else (x0, x1)), (None if (y0, y1) == (0.0, float(h)) else (y0, y1))
 
 
-def _byte_span(t):
-    first = t.data_ptr()
-    return first, first + sum((n - 1) * st for n, st in zip(t.shape, t.stride())) + 1
-
-
-def _check_out(out, shape, frames, who):
-    if out is None:
-        return torch.empty(shape, dtype=torch.uint8, device=frames.device)
-    if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or out.device != frames.device:
-        raise ValueError(f'{who}: out must be uint8 {tuple(shape)} on {frames.device}')
-    clips.check_frames(out, 'out', bpp=(1, 2, 3, 4))
-    if out.numel() and frames.numel():
-        if out.ndim > 1 and shape[0] > 1 and out.stride(0) < (shape[1] - 1) * out.stride(1) + shape[2] * (shape[3] if len(shape) == 4 else 1):
-            raise ValueError(f'{who}: the frames of out overlap each other (strides {tuple(out.stride())})')
-        lo, hi = _byte_span(out)
-        f_lo, f_hi = _byte_span(frames)
-        if lo < f_hi and f_lo < hi:
-            raise ValueError(f'{who} writes out of place: the bytes out spans must not meet the frames\'')
-    return out
-
-
 def resize(frames, size, filter='lanczos', box=None, out=None):
     """``PIL.Image.resize(size, filter, box)`` of every frame of a uint8 clip [F, H, W, bpp] (bpp 2 .. 4) or [F, H, W], where the clip is: uint8
     [F, oh, ow(, bpp)].  ``size``: (width, height) or an int for both; ``filter``: one of ``FILTERS``; ``box``: (x0, y0, x1, y1) floats, the source
@@ -297,7 +267,7 @@ def resize(frames, size, filter='lanczos', box=None, out=None):
     if f and not (1 <= h <= MAX_SIZE and 1 <= w <= MAX_SIZE):
         raise ValueError(f'resize: frames of {w} x {h} pixels: every side is 1 .. {MAX_SIZE}')
     box_x, box_y = _check_box(box, h, w, filter, 'resize')
-    out = _check_out(out, [f, oh, ow] + list(frames.shape[3:]), frames, 'resize')
+    out = clips.check_out(out, [f, oh, ow] + list(frames.shape[3:]), frames, 'resize')
     if f == 0:
         return out
     dev = frames.device

@@ -18,9 +18,7 @@ take — the definition — and device kernels whose bytes equal it:
 
 A tap that leaves the image reads the REFLECTED index (``_reflect``: i < 0 -> -i, then i >= n -> 2 n - 2 - i, then clamped to [0, n - 1]; reflect-101, defined
 for n = 1 and 2).  Images are uint8 with contiguous pixels and any row pitch, 1 .. 4096 pixels a side; zero-size images return empty results and launch nothing.
-``blur3`` alone has no kernel of its own (``condition`` fuses it): it is the torch formulation on the tensor's device.  The library also houses the four
-kernels of the quadric-error mesh decimation (decimate.py calls them through ``sketch_lib()``; the header says why they live here), the three of
-frame resampling (resample.py, likewise) and the two of multi-scale frame quality (multiscale.py, likewise).
+``blur3`` alone has no kernel of its own (``condition`` fuses it): it is the torch formulation on the tensor's device.
 
 ``SketchSession`` is the edge counterpart of ``edit.EditSession`` on the same stages below the canvas (``edit._StageSession``):
 
@@ -37,6 +35,7 @@ import torch
 
 from . import _lib, edit, views
 from .edit import _check_mask
+from .resample import resize
 
 _side = _lib.SideLibrary('sketch')                   # libp3d_sketch.so: loaded on the first call, device-guarded; launch_count() is its own counter
 SKETCH_LIB_PATH, HEADER = _side.path, _side.header
@@ -510,7 +509,6 @@ def load_canvas(path, device=None, size=None, filter='box'):
     if info.mode != 'L':
         raise ValueError(f'load_canvas: {path} is mode {info.mode!r}: a canvas is 8-bit grey (L)')
     if size is not None:
-        from .resample import resize
         canvas = resize(canvas[None], size, filter)[0]
     return canvas
 

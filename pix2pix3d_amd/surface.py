@@ -29,6 +29,7 @@ from typing import NamedTuple
 import torch
 
 from . import _lib, mesh, shape, texture, views
+from .resample import resize
 from .training.volumetric_rendering import renderer as _rmod
 
 GREY = mesh.GREY
@@ -616,7 +617,6 @@ def geometry_video(G, ws, cfg='seg2cat', n_frames=120, views_per_step=4, resolut
     frames = [render(G, ws, cameras[s:s + step], resolution, color=color, **kw) for s in range(0, cameras.shape[0], step)]
     out = torch.cat(frames) if frames else torch.empty([0, int(resolution), int(resolution), 3], dtype=torch.uint8, device=ws.device)
     if size is not None:
-        from .resample import resize
         out = resize(out, size, resample)
     if path is not None:
         save_clip(path, out, fps=fps, format=format, gif=gif, psnr=psnr, ssim=ssim, ms_ssim=ms_ssim, who='geometry_video')

@@ -11,7 +11,7 @@ the JPEGs sees without entropy decoding, and ``jpeg_quality_for`` turns a PSNR, 
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, multiscale
 from .. import quality as Q
 from ..clips import HEADER, MAX_PIXELS, check, check_frames, clip_args, video_lib
 
@@ -475,7 +475,6 @@ def jpeg_quality_for(frames, psnr=None, ssim=None, subsampling='4:2:0', sample=8
     key, target = _check_target(psnr, ssim, 'jpeg_quality_for', ms_ssim)
     sub = _check_subsampling(subsampling)
     if key == 'ms_ssim':
-        from .. import multiscale                                                 # (here: multiscale -> sketch -> views -> this package)
         measure = multiscale.ms_ssim
     else:
         measure = Q.compare

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib, mesh
+from . import resample as rs                       # (``resample`` is the name of the scripts' filter argument)
 from .training.volumetric_rendering import renderer as rmod
 
 SCALE, LABEL = _lib.P3D_FRAME_SCALE, _lib.P3D_FRAME_LABEL
@@ -318,7 +319,6 @@ def render_views(G, ws, cameras, views_per_step=4, jitter='random', neural_rende
 # ---- the scripts ------------------------------------------------------------------------------------------------------------
 def _check_resample(who, size, resample):
     """The ``size=`` / ``resample=`` pair of the scripts, checked before anything is rendered."""
-    from . import resample as rs
     if resample not in rs.FILTERS:
         raise ValueError(f'{who}: resample must be one of {rs.FILTERS}, got {resample!r}')
     if size is not None:
@@ -331,10 +331,9 @@ def resize_clips(frames, size, resample='lanczos'):
     ``size=None``: the dict as it is."""
     if size is None:
         return frames
-    from .resample import resize
     for key, how in (('image', resample), ('label', 'nearest'), ('label_index', 'nearest')):
         if key in frames:
-            frames[key] = resize(frames[key], size, how)
+            frames[key] = rs.resize(frames[key], size, how)
     return frames
 
 
@@ -343,8 +342,7 @@ def image_grid(frames, grid_size, cell=None):
     ``cell`` ((width, height) or an int): every frame is resized to it first (``resample.thumbnails``: Lanczos, on the frames' device) — a thumbnail sheet."""
     gw, gh = grid_size
     if cell is not None:
-        from .resample import thumbnails
-        frames = thumbnails(frames, cell)
+        frames = rs.thumbnails(frames, cell)
     n, h, w = frames.shape[:3]
     if gw * gh != n:
         raise ValueError(f'image_grid: {n} frames do not fill a {gw} x {gh} grid')

@@ -1,5 +1,5 @@
 """Shared by tests/test_mesh_decimate_host.py and tests/test_mesh_decimate_gpu.py: the meshes of the cases, built analytically, and a plain-Python loop
-that restates the "mesh decimation" rules of csrc/sketch/p3d_sketch.h (one Python float operation per rounding: Python floats are IEEE doubles; lists
+that restates the rules of csrc/mesh/p3d_mesh.h (one Python float operation per rounding: Python floats are IEEE doubles; lists
 and dicts instead of sorts).  Nothing here calls pix2pix3d_amd.decimate's own formulations."""
 import functools
 import math

@@ -1,4 +1,4 @@
-"""Shared by test_multiscale_host.py / test_multiscale_gpu.py: the pyramid rule and the per-level rules of p3d_sketch.h ("multi-scale frame quality") as
+"""Shared by test_multiscale_host.py / test_multiscale_gpu.py: the pyramid rule and the per-level rules of p3d_video.h ("multi-scale frame quality") as
 plain Python loops, the textbook MS-SSIM in float64 (exact Gaussian, unrounded 2 x 2 mean pooling), and the clips both files measure."""
 import functools
 
@@ -20,6 +20,34 @@ def halve_rule(a):
             block = a[:, 2 * y:2 * y + 2, 2 * x:2 * x + 2].astype(np.int64)
             out[:, y, x] = (block[:, 0, 0] + block[:, 0, 1] + block[:, 1, 0] + block[:, 1, 1] + 2) >> 2
     return out
+
+
+def odd_pitch_view(t):
+    """``t`` as a window of a larger canvas of other bytes whose row pitch is an ODD number of bytes (and whose first byte is off a dword): the same
+    values, and no two rows start at the same alignment."""
+    f, h, w = t.shape[:3]
+    bpp = t.shape[3] if t.ndim == 4 else 1
+    row = (w * bpp + 6) | 1
+    frame = (h + 2) * row
+    canvas = torch.full([f * frame + 8], 77, dtype=torch.uint8, device=t.device)
+    view = canvas.as_strided(tuple(t.shape), (frame, row, bpp, 1)[:t.ndim], 3)
+    view.copy_(t)
+    return view
+
+
+SINGLE_LEVEL_SIZES = ((1, 11, 11), (2, 27, 43))        # (F, H, W): one window; 17 x 33 windows, one past the 16 x 32 tile both ways
+
+
+def single_level_agrees(a, b):
+    """``ssim_sums`` equals the q sum and the window count of a one-level ``msssim_sums``, byte for byte, for the clips as they are and as windows of a
+    canvas with an odd row pitch — on the device the byte staging of one kernel against the dword staging of the other."""
+    from pix2pix3d_amd import multiscale, quality
+    for x, y in ((a, b), (odd_pitch_view(a), odd_pitch_view(b)), (a, odd_pitch_view(b))):
+        assert x.stride(1) % 2 == 1 or x is a
+        one, many = quality.ssim_sums(x, y), multiscale.msssim_sums(x, y, levels=1)
+        assert one.dtype == many.dtype == torch.int64 and one.device == many.device == a.device
+        assert torch.equal(one, many[:, :, 0, [0, 2]]), (tuple(a.shape), x.stride(), y.stride())
+    return one
 
 
 def msssim_loop(a, b, levels):

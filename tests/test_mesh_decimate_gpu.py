@@ -1,4 +1,4 @@
-"""pix2pix3d_amd.decimate on the device: the kernels of csrc/sketch/mesh_decimate.hip against the CPU formulation bit for bit — whole decimations of every
+"""pix2pix3d_amd.decimate on the device: the kernels of csrc/mesh/mesh_decimate.hip against the CPU formulation bit for bit — whole decimations of every
 case of decimate_cases.py (the subdivision-5 icosphere spans many work-groups and rounds), each entry point alone against its torch restatement,
 offset and non-contiguous operands, the library's launch counter, and ``extract_mesh(target_faces=)`` on a seeded generator."""
 import functools
@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import decimate_cases as dc
-from pix2pix3d_amd import decimate, mesh, sketch
+from pix2pix3d_amd import decimate, mesh
 from test_mesh_gpu import _median_mesh
 
 pytestmark = pytest.mark.gpu
@@ -45,12 +45,12 @@ def _assert_same(dev, cpu):
 def test_decimate_matches_cpu(hip_lib, name):
     v, f, target = _case(name)
     cpu = _cpu_result(name)
-    n0 = sketch.launch_count()
+    n0 = decimate.launch_count()
     dev = decimate.decimate(v.cuda(), f.cuda(), target)
     torch.cuda.synchronize()
     # the quadrics once, six launches per round that collapsed, and four (costs, select) for a last round in which no edge was valid
     stalled = not cpu.reached and cpu.rounds < decimate.default_max_rounds(len(f))
-    assert sketch.launch_count() - n0 == 1 + decimate.LAUNCHES_PER_ROUND * cpu.rounds + (4 if stalled else 0)
+    assert decimate.launch_count() - n0 == 1 + decimate.LAUNCHES_PER_ROUND * cpu.rounds + (4 if stalled else 0)
     _assert_same(dev, cpu)
     if name in LARGE_CASES:
         assert cpu.reached and cpu.rounds > 20 and dc.is_closed_manifold(cpu.faces)
@@ -78,26 +78,26 @@ def _cuda_lists(lists):
 
 def test_quadrics_alone(hip_lib):
     v, faces32, lists, _, quads = _round_operands()[:5]
-    n0 = sketch.launch_count()
+    n0 = decimate.launch_count()
     dev = decimate.quadrics(v.cuda(), faces32.cuda(), lists.vf_offsets.cuda(), lists.vf_faces.cuda())
-    assert sketch.launch_count() == n0 + 1
+    assert decimate.launch_count() == n0 + 1
     assert torch.equal(dev.cpu().view(torch.int64), quads.view(torch.int64)) and (quads[:, 9] > 0).all()
 
 
 def test_edge_costs_alone(hip_lib):
     v, faces32, lists, fixed, quads, target, cost, valid = _round_operands()[:8]
-    n0 = sketch.launch_count()
+    n0 = decimate.launch_count()
     dev = decimate.edge_costs(v.cuda(), quads.cuda(), faces32.cuda(), _cuda_lists(lists), fixed.cuda())
-    assert sketch.launch_count() == n0 + 1
+    assert decimate.launch_count() == n0 + 1
     assert torch.equal(dev[2].cpu(), valid) and 0 < int(valid.sum()) < len(valid)
     assert torch.equal(dev[1].cpu().view(torch.int64), cost.view(torch.int64)) and torch.equal(_bits(dev[0].cpu()), _bits(target))
 
 
 def test_edge_select_alone(hip_lib):
     v, _, lists, _, _, _, _, _, rank, win, _ = _round_operands()
-    n0 = sketch.launch_count()
+    n0 = decimate.launch_count()
     dev = decimate.edge_select(rank.cuda(), _cuda_lists(lists), len(v))
-    assert sketch.launch_count() == n0 + 3
+    assert decimate.launch_count() == n0 + 3
     assert torch.equal(dev.cpu(), win) and 1 < int(win.sum()) < int((rank != decimate.NO_RANK).sum())
 
 
@@ -107,9 +107,9 @@ def test_collapse_alone(hip_lib):
     state = [v.clone(), quads.clone(), torch.arange(len(v), dtype=torch.int32), faces32.clone()]
     dead = decimate.collapse(*state, lists.edges, apply, target)
     on_device = [t.cuda() for t in (v, quads, torch.arange(len(v), dtype=torch.int32), faces32)]
-    n0 = sketch.launch_count()
+    n0 = decimate.launch_count()
     dead_device = decimate.collapse(*on_device, lists.edges.cuda(), apply.cuda(), target.cuda())
-    assert sketch.launch_count() == n0 + 2
+    assert decimate.launch_count() == n0 + 2
     assert torch.equal(dead_device.cpu(), dead) and int(dead.sum()) == 2 * int(apply.sum())
     assert torch.equal(_bits(on_device[0].cpu()), _bits(state[0])) and torch.equal(on_device[1].cpu().view(torch.int64), state[1].view(torch.int64))
     assert torch.equal(on_device[2].cpu(), state[2]) and torch.equal(on_device[3].cpu(), state[3])
@@ -134,10 +134,10 @@ def test_extract_mesh_with_a_face_target(hip_lib):
     kw = dict(resolution=32, threshold=thr, n_frames=2, image_size=64, keep=1)
     v0, f0, _, _ = mesh.extract_mesh(G, ws, **kw)
     target = len(f0) // 4
-    n0 = sketch.launch_count()
+    n0 = decimate.launch_count()
     v, f, colors, frames = mesh.extract_mesh(G, ws, target_faces=target, **kw)
     torch.cuda.synchronize()
-    assert sketch.launch_count() > n0 and len(f0) > 400
+    assert decimate.launch_count() > n0 and len(f0) > 400
     cpu = decimate.decimate(v0.cpu(), f0.cpu(), target)
     assert torch.equal(f.cpu(), cpu.faces) and torch.equal(_bits(v.cpu()), _bits(cpu.vertices))
     assert target - 1 <= len(f) < len(f0) and tuple(colors.shape) == (len(v), 3) and tuple(frames.shape) == (2, 64, 64, 3)

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from multiscale_cases import pairs
+from multiscale_cases import SINGLE_LEVEL_SIZES, pairs, single_level_agrees
 from quality_cases import checkerboard, clip, disturbed, in_canvas
 
 pytestmark = pytest.mark.gpu
@@ -21,10 +21,10 @@ def _m():
 
 
 def _launches(fn):
-    from pix2pix3d_amd import sketch
-    n0 = sketch.launch_count()
+    from pix2pix3d_amd import clips
+    n0 = clips.launch_count()
     out = fn()
-    return sketch.launch_count() - n0, out
+    return clips.launch_count() - n0, out
 
 
 def _agrees(a, b, levels):
@@ -130,6 +130,16 @@ def test_halve_at_sizes_around_a_lane_and_a_tile(hip_lib, bpp):
         n, out = _launches(lambda: M.halve(a.cuda()))
         assert n == 0 and out.is_cuda and tuple(out.shape) == (2, h // 2, w // 2) + tuple(a.shape[3:])
     assert _launches(lambda: M.halve(clip(2, 6, 8, bpp, seed=171).cuda()))[0] == 1
+
+
+@pytest.mark.parametrize('bpp', [1, 2, 3, 4])
+def test_one_level_is_ssim_sums_on_the_device(hip_lib, bpp):
+    """The two kernels share one window core: their sums are the same bytes, and the CPU formulation's."""
+    from pix2pix3d_amd import quality
+    for n, (f, h, w) in enumerate(SINGLE_LEVEL_SIZES):
+        a = clip(f, h, w, bpp, seed=24 + n)
+        b = disturbed(a, seed=26 + n)
+        assert torch.equal(single_level_agrees(a.cuda(), b.cuda()).cpu(), quality.ssim_sums(a, b))
 
 
 def test_extremes_on_the_device(hip_lib):

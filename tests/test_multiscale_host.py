@@ -1,13 +1,13 @@
 """pix2pix3d_amd.multiscale without a GPU: the torch formulation — the definition — against a plain per-window Python loop, level by level against
 ``quality.ssim_sums`` on the pyramid, ``halve`` against its integer rule, the fixed points, every argument error, the distance to the textbook float
-formulation, where the prototypes stand, and the argument checks of the two entry points (which come before any device call)."""
+formulation, one level against ``quality.ssim_sums``, where the prototypes stand, and the argument checks of the two entry points (which come before any device call)."""
 import ctypes
 
 import numpy as np
 import pytest
 import torch
 
-from multiscale_cases import halve_rule, msssim_loop, msssim_true, pairs
+from multiscale_cases import SINGLE_LEVEL_SIZES, halve_rule, msssim_loop, msssim_true, pairs, single_level_agrees
 from quality_cases import checkerboard, clip, disturbed, in_canvas
 
 # The largest |ms_ssim - msssim_true| measured on the CPU over ``pairs()`` at five levels and the 'smooth' pair at one to four: 5.602e-4, on 'smooth' at two
@@ -47,6 +47,26 @@ def test_every_level_agrees_with_ssim_sums_on_the_pyramid(bpp):
     for k in range(5):
         assert torch.equal(sums[:, :, k, [0, 2]], quality.ssim_sums(pa[k], pb[k])), k
     assert int(sums[..., 1].min()) > 0 and not torch.equal(sums[..., 0], sums[..., 1])
+
+
+@pytest.mark.parametrize('bpp', [1, 2, 3, 4])
+def test_one_level_is_ssim_sums(bpp):
+    for n, (f, h, w) in enumerate(SINGLE_LEVEL_SIZES):
+        a = clip(f, h, w, bpp, seed=24 + n)
+        sums = single_level_agrees(a, disturbed(a, seed=26 + n))
+        assert sums[0, :, 1].tolist() == [(h - 10) * (w - 10)] * bpp
+
+
+@pytest.mark.parametrize('module', ['resample', 'multiscale', 'quality', 'decimate'])
+def test_the_import_pulls_in_no_session(module):
+    """The frame and mesh modules stand below the sessions: importing one leaves ``sketch``, ``views`` and ``edit`` unimported (a fresh interpreter each)."""
+    import pathlib
+    import subprocess
+    import sys
+    child = (f'import sys; import pix2pix3d_amd.{module}; '
+             'found = [m for m in ("sketch", "views", "edit") if "pix2pix3d_amd." + m in sys.modules]; assert not found, found')
+    r = subprocess.run([sys.executable, '-c', child], capture_output=True, text=True, cwd=pathlib.Path(__file__).resolve().parent.parent)
+    assert r.returncode == 0, r.stderr
 
 
 @pytest.mark.parametrize('bpp', [1, 2, 3, 4])
@@ -213,20 +233,20 @@ def test_the_target_reaches_the_writers(tmp_path):
 
 
 def test_where_the_prototypes_stand():
-    from pix2pix3d_amd import _lib, sketch
+    from pix2pix3d_amd import _lib, clips, decimate, regions, sketch
     M = _m()
-    names = list(sketch.HEADER.functions)
-    new = ['p3d_frame_halve', 'p3d_frame_msssim_level']
-    assert all(n in sketch.HEADER.functions for n in new) and not any(n in _lib.HEADER.functions for n in new)
-    assert names[-5:-3] == new and names[-3:] == ['p3d_frame_resample_rows', 'p3d_frame_resample_columns', 'p3d_frame_resample_nearest']
-    constants = sketch.HEADER.constants
+    new = ['p3d_frame_halve', 'p3d_frame_msssim_level']                             # declared by the video header and by no other
+    assert all(n in clips.HEADER.functions for n in new)
+    assert not any(n in header.functions for n in new for header in (_lib.HEADER, regions.HEADER, sketch.HEADER, decimate.HEADER))
+    assert [len(clips.HEADER.functions[n][1]) for n in new] == [11, 15]
+    constants = clips.HEADER.constants
     assert (M.TILE_W, M.TILE_H, M.MAX_LEVELS) == (constants['P3D_MSSSIM_TILE_W'], constants['P3D_MSSSIM_TILE_H'], constants['P3D_MSSSIM_MAX_LEVELS']) == (32, 16, 5)
     assert M.TILE_W % 2 == 0 and M.TILE_H % 2 == 0
 
 
 def test_the_library_refuses_bad_arguments_before_any_launch():
-    from pix2pix3d_amd import _lib, sketch
-    lib, n0 = sketch.sketch_lib(), sketch.launch_count()
+    from pix2pix3d_amd import _lib, clips
+    lib, n0 = clips.video_lib(), clips.launch_count()
     buffer = ctypes.create_string_buffer(4096)                                     # host memory: no call below may get as far as reading it
     p = ctypes.cast(buffer, ctypes.c_void_p)
     level = lambda a, b, f, h, w, bpp, sums=p, pitch=3, na=None, nb=None, row=48: lib.p3d_frame_msssim_level(a, 1024, row, b, 1024, 48, f, h, w, bpp, sums, pitch,
@@ -254,4 +274,4 @@ def test_the_library_refuses_bad_arguments_before_any_launch():
     assert halve(p, q, 2, 12, 12, 3, dframe=100) == _lib.P3D_ERR_ARGUMENT           # the destination's frames overlap
     assert halve(p, p, 1, 12, 12, 3) == _lib.P3D_ERR_ARGUMENT and b'out of place' in lib.p3d_last_error()
     assert halve(None, None, 0, 12, 12, 3) == _lib.P3D_OK and halve(None, None, 2, 1, 12, 3) == _lib.P3D_OK and halve(None, None, 2, 12, 1, 3) == _lib.P3D_OK
-    assert sketch.launch_count() == n0
+    assert clips.launch_count() == n0

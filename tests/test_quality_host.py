@@ -351,6 +351,8 @@ def test_what_quality_calls_is_declared():
     Q, video = _q(), _video()
     called = set(re.findall(r'\bvideo_lib\(\)\.(p3d_\w+)', pathlib.Path(Q.__file__).read_text()))
     assert called == {'p3d_video_error_sums', 'p3d_video_ssim'} and called <= set(video.HEADER.functions)
-    names = list(video.HEADER.functions)
-    assert names[0] == 'p3d_video_histogram' and names[-3:] == ['p3d_video_error_sums', 'p3d_video_ssim', 'p3d_video_jpeg_decode']      # appended after the PNG ones
+    from pix2pix3d_amd import _lib, decimate, regions, sketch
+    names = ['p3d_video_error_sums', 'p3d_video_ssim', 'p3d_video_jpeg_decode']      # declared by the video header and by no other
+    assert all(n in video.HEADER.functions for n in names)
+    assert not any(n in header.functions for n in names for header in (_lib.HEADER, regions.HEADER, sketch.HEADER, decimate.HEADER))
     assert 'p3d_video_jpeg_decode' in set(re.findall(r'\bvideo_lib\(\)\.(p3d_\w+)', pathlib.Path(video.jpeg.__file__).read_text()))

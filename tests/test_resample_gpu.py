@@ -84,13 +84,13 @@ def test_binary_noise_reaches_both_clamps(hip_lib):
 
 
 def test_launch_counts(hip_lib):
-    from pix2pix3d_amd import resample, sketch
+    from pix2pix3d_amd import clips, resample
     clip = uniform_clip(2, 20, 33, 3, seed=60).cuda()
 
     def launches(fn):
-        n0 = sketch.launch_count()
+        n0 = clips.launch_count()
         out = fn()
-        return sketch.launch_count() - n0, out
+        return clips.launch_count() - n0, out
     assert launches(lambda: _agrees(clip, (33, 9), 'lanczos', pitched=False))[0] == 1      # a single axis
     assert launches(lambda: _agrees(clip, (12, 20), 'lanczos', pitched=False))[0] == 1
     assert launches(lambda: _agrees(clip, (12, 9), 'lanczos', pitched=False))[0] == 2      # both

@@ -147,12 +147,12 @@ def test_the_table_cache_is_bounded_and_counts():
 
 # ---- contract ---------------------------------------------------------------------------------------------------------------------------------
 def test_every_argument_error_is_a_valueerror_before_the_library_is_touched(monkeypatch):
-    from pix2pix3d_amd import sketch
+    from pix2pix3d_amd import clips
 
     def touched():
         raise AssertionError('the library was touched')
-    monkeypatch.setattr(sketch, 'sketch_lib', touched)
-    monkeypatch.setattr(sketch._side, 'lib', touched)
+    monkeypatch.setattr(clips, 'video_lib', touched)
+    monkeypatch.setattr(clips._side, 'lib', touched)
     clip = uniform_clip(2, 20, 33, 3, seed=2)
     bad = [lambda: resample.resize(clip, (5, 5), 'cubic'),                                  # unknown filter
            lambda: resample.resize(clip, (5, 5), 'box', box=(4.0, 2.0, 4.0, 9.0)),          # empty box
@@ -178,13 +178,13 @@ def test_every_argument_error_is_a_valueerror_before_the_library_is_touched(monk
     assert resample.FILTERS == ('nearest', 'box', 'bilinear', 'hamming', 'bicubic', 'lanczos')
 
 
-def test_the_prototypes_are_the_headers_last_three_and_the_product_abi_gains_nothing():
-    from pix2pix3d_amd import _lib, sketch
-    names = list(sketch.HEADER.functions)
-    assert names[0] == 'p3d_sketch_condition'
-    assert names[-3:] == ['p3d_frame_resample_rows', 'p3d_frame_resample_columns', 'p3d_frame_resample_nearest']
-    assert not any(n in _lib.HEADER.functions for n in names[-3:])
-    assert (resample.TILE_W, resample.TILE_H) == (sketch.HEADER.constants['P3D_RESAMPLE_TILE_W'], sketch.HEADER.constants['P3D_RESAMPLE_TILE_H'])
+def test_the_prototypes_are_the_video_headers_alone_and_the_product_abi_gains_nothing():
+    from pix2pix3d_amd import _lib, clips, decimate, sketch
+    names = ['p3d_frame_resample_rows', 'p3d_frame_resample_columns', 'p3d_frame_resample_nearest']
+    assert all(n in clips.HEADER.functions for n in names)
+    assert not any(n in header.functions for n in names for header in (_lib.HEADER, sketch.HEADER, decimate.HEADER))
+    assert set(sketch.HEADER.functions) == {'p3d_sketch_condition', 'p3d_sketch_edge_classes', 'p3d_sketch_link', 'p3d_sketch_thin_step'}
+    assert (resample.TILE_W, resample.TILE_H) == (clips.HEADER.constants['P3D_RESAMPLE_TILE_W'], clips.HEADER.constants['P3D_RESAMPLE_TILE_H'])
 
 
 def test_the_new_keywords_at_their_defaults_change_no_byte(tmp_path):

@@ -18,7 +18,8 @@ SERVICES = {'p3d_last_error', 'p3d_launch_count'}      # every side library link
 # first caller: ``clips`` holds the video library and calls nothing itself).  A feature that adds entry points to a library adds its module here and its
 # prototypes to the library's one header: never a second header or a binding of its own.
 BOUND_BY = {'probes': (('diagnostics',), 'probes'), 'regions': (('regions', 'evaluate', 'reproject'), 'regions_lib'),
-            'video': (('video.gif', 'video.jpeg', 'video.jpeg_read', 'video.png', 'quality'), 'video_lib', 'clips'), 'sketch': (('sketch',), 'sketch_lib')}
+            'video': (('video.gif', 'video.jpeg', 'video.jpeg_read', 'video.png', 'quality', 'resample', 'multiscale'), 'video_lib', 'clips'),
+            'sketch': (('sketch',), 'sketch_lib'), 'mesh': (('decimate',), 'mesh_lib')}
 NAMES = sorted(build.SIDE_LIBRARIES)
 
 
@@ -46,9 +47,9 @@ def test_calls_are_declared(name):
         called = set(re.findall(r'\b%s\(\)\.(p3d_\w+)' % accessor, pathlib.Path(caller.__file__).read_text()))
         assert called - SERVICES and called - SERVICES <= declared, (name, caller.__name__, sorted(called - SERVICES - declared))
         called_by_all |= called - SERVICES
-    if name == 'video':                                                          # every entry point has a caller among the modules of the row
+    assert called_by_all == declared, sorted(declared - called_by_all)          # every entry point has a caller among the modules of the row
+    if name == 'video':
         from pix2pix3d_amd import video
-        assert called_by_all == declared, sorted(declared - called_by_all)
         assert video._side is module._side and video.HEADER is module.HEADER and video.video_lib == module.video_lib
 
 
@@ -87,7 +88,7 @@ def test_the_header_declares_exactly_what_the_sources_define(name):
     assert defined == _declared(header), (sorted(defined - _declared(header)), sorted(_declared(header) - defined))
 
 
-def test_only_the_five_headers_have_prototypes():
+def test_only_the_six_headers_have_prototypes():
     own = [ROOT / 'include' / 'p3d_hip.h'] + [pathlib.Path(build.side_paths(name).header) for name in NAMES]
     assert [h for h in map(pathlib.Path, build.headers()) if h not in own and _declared(h)] == [] and all(_declared(h) for h in own)
 

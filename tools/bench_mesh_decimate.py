@@ -1,4 +1,4 @@
-"""Time quadric-error decimation on the GPU (pix2pix3d_amd/decimate.py, csrc/sketch/mesh_decimate.hip) against vertex clustering, print ONE JSON line
+"""Time quadric-error decimation on the GPU (pix2pix3d_amd/decimate.py, csrc/mesh/mesh_decimate.hip) against vertex clustering, print ONE JSON line
 and write it to --out.
 
 The mesh of tools/time_mesh_cleanup.py: the seeded config-size seg2cat generator at the median of its density field on a --resolution^3 lattice

@@ -1,4 +1,4 @@
-"""Time frame resampling on the GPU (pix2pix3d_amd/resample.py, csrc/sketch/frame_resample.hip) against what a user does without it, print ONE JSON
+"""Time frame resampling on the GPU (pix2pix3d_amd/resample.py, csrc/video/frame_resample.hip) against what a user does without it, print ONE JSON
 line and write it to --out.
 
 The clip: --frames (120) frames of 512 x 512 RGB, the smooth gradients with three grey levels of noise of tests/video_cases.gradient_frames' formula,
